@@ -29,6 +29,8 @@ ADMM_L1, on the same batch), `f64` (the double-precision engine), `pnp` (configs
 bench_pnp.py, two child processes after this one has released the GPU), `parity` (three slices of
 the timed run against the NumPy oracle), `cpu_baseline` = the NumPy oracle (float64, np.fft,
 1 thread) on a bounded sample of the same slices.
+`--dump-outputs DIR` also writes x of the timed run as DIR/x.npy (a seeded sample of whole slices when
+large), so two builds given the same arguments -- hence the same inputs -- can be compared output for output.
 """
 import argparse
 import json
@@ -178,6 +180,23 @@ def launch_ranks(n, timeout_s, script=None):
         elif rc != 0 and text:                          # what a failed job's other ranks printed
             sys.stderr.write('--- stdout of rank %d ---\n%s\n' % (r, text))
     return rc
+
+
+DUMP_BYTES = 32 << 20                                              # --dump-outputs: at most this much of x (well under 64 MB in all)
+
+
+def dump_outputs(d, x):
+    """--dump-outputs DIR: x after the W + K iterations of the timed run (the reconstructions ADMM_CNC / ADMM_L1 hand back), in the
+    engine's own precision, as DIR/x.npy [n, H, W].  A batch larger than DUMP_BYTES is written as a fixed sample of whole slices
+    (seed 0, ascending order; DIR/x_slices.npy holds their indices as float64), so two builds run with the same arguments compare
+    slice for slice."""
+    import torch
+    B, H, W = x.shape
+    n = max(1, min(B, DUMP_BYTES // (H * W * x.element_size())))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, 'x.npy'), x[torch.as_tensor(idx, device=x.device)].cpu().numpy())
+    np.save(os.path.join(d, 'x_slices.npy'), idx.astype(np.float64))
 
 
 def claim_stdout():
@@ -367,6 +386,9 @@ def main():
                          'are counted); 0 = keep iterating the same state (it converges: data with many exact zeros)')
     ap.add_argument('--rehearse-gloo', action='store_true',
                     help='rehearsal of the N>1 launch path on a box with ONE GPU: gloo backend, all ranks on cuda:0')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, rank 0 writes x of the timed run (all ranks\' slices when N > 1) as DIR/x.npy, '
+                         'a fixed seeded sample of whole slices when it exceeds 32 MiB (indices in DIR/x_slices.npy)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -567,6 +589,8 @@ def main():
                                              'sustained_ms_per_step': [float(v) for v in per_rank[:, 3]] if sus else None}
     checksum = float(x_dev.double().sum())
     finite = bool(torch.isfinite(x_dev).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x_all if dist is not None else x_dev)
 
     # Checker legs (rank 0 of an N = 1 job, with the CPU baseline): the NumPy oracle runs the same W + K iterations on
     # three of the slices from the same measurements, so every line re-proves parity of what was timed; and the

@@ -304,8 +304,10 @@ def test_oracle_pnp_loop_with_the_trained_network_vs_the_unmodified_reference(go
     assert rel_l2(x, gold['trained_cnc_d_ffdnet_gray_it%d' % n_it]) <= 2e-6, rel_l2(x, gold['trained_cnc_d_ffdnet_gray_it%d' % n_it])
 
 
-def test_auto_backend_without_a_hip_device_is_torch():
-    """cnn_backend='auto' (the entry points' default): no HIP device here -> the PyTorch backend, with the reason; autocast modes likewise"""
+def test_auto_backend_without_a_hip_device_is_torch(monkeypatch):
+    """cnn_backend='auto' (the entry points' default): no HIP device -> the PyTorch backend, with the reason; autocast modes likewise.
+    The missing device is simulated, so the test holds on a machine with a GPU as well."""
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
     net, _, _ = D.build('ffdnet_gray')
     be, why = D.auto_backend(net)
     assert be == 'torch' and 'HIP' in why

@@ -500,7 +500,7 @@ def test_odd_batch_and_padding_slice(P, golden_inputs):
     assert rel_l2(x3[2], O.admm_l1(ys[2].astype(np.complex64).astype(np.complex128), masks[mid[2]], 20)) <= 1e-5
 
 
-def test_l1_single_state_form_is_bit_identical(P, golden_inputs):
+def test_l1_single_state_form_is_bit_identical(P, golden_inputs, tmp_path):
     """ADMM_L1's fused loop keeps only u = x + w between iterations (z = soft(u), w = u - z); the
     PNP_FUSED_L1_TWO_STATE=1 hook keeps z and w.  Same bits, and the state handed back is the
     genuine (z, w) pair."""
@@ -519,7 +519,7 @@ def test_l1_single_state_form_is_bit_identical(P, golden_inputs):
         "np.savez(sys.argv[1], x1=x1, z1=z1, w1=w1, x2=x2, z2=z2, w2=w2)\n" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     outs = []
     for flag in ('0', '1'):
-        path = '/tmp/l1_state_%s.npz' % flag
+        path = str(tmp_path / ('l1_state_%s.npz' % flag))
         subprocess.check_call([sys.executable, '-c', code, path], env=dict(os.environ, PNP_FUSED_L1_TWO_STATE=flag))
         outs.append(np.load(path))
     for k in ('x1', 'z1', 'w1', 'x2', 'z2', 'w2'):
@@ -601,7 +601,7 @@ def test_prox_edge_values(P, torch):
         assert np.abs(tz.cpu().numpy() - zr).max() <= 1e-6 and np.abs(tw.cpu().numpy() - wr).max() <= 1e-6
 
 
-def test_schedules_are_bit_identical(P):
+def test_schedules_are_bit_identical(P, tmp_path):
     """Two-launch path (PNP_SLICE=0; a batch of 131 would otherwise run slice-resident): the batch may be
     split over HIP queues (PNP_FUSED_STREAMS) and row/column workgroups of different halves may share one
     launch (PNP_FUSED_SCHED=1): scheduling only -- every slice sees the same arithmetic, so all schedules
@@ -621,7 +621,7 @@ def test_schedules_are_bit_identical(P):
         "np.savez(sys.argv[1], x=x, z=z, w=w, xl=xl)\n" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     outs = []
     for sched, streams, chunk in (('0', '1', '0'), ('1', '1', '0'), ('0', '2', '0'), ('1', '2', '0'), ('0', '3', '0'), ('0', '1', '48')):
-        path = '/tmp/sched_%s_%s_%s.npz' % (sched, streams, chunk)
+        path = str(tmp_path / ('sched_%s_%s_%s.npz' % (sched, streams, chunk)))
         subprocess.check_call([sys.executable, '-c', code, path],
                               env=dict(os.environ, PNP_SLICE='0', PNP_FUSED_SCHED=sched, PNP_FUSED_STREAMS=streams, PNP_FUSED_CHUNK=chunk))
         outs.append(np.load(path))

@@ -22,7 +22,7 @@ def _problem():
     return masks, y, mid
 
 
-def _worker(rank, world, port, q, precision='f32'):
+def _worker(rank, world, port, q, precision, results):
     import torch.distributed as dist
     import pnp_admm_cnc_mri_amd as P
     from pnp_admm_cnc_mri_amd import sharding
@@ -31,7 +31,7 @@ def _worker(rank, world, port, q, precision='f32'):
     dist.init_process_group('gloo', rank=rank, world_size=world)
     try:
         masks, y, mid = _problem()
-        solver = functools.partial(P.ADMM_CNC, device=0, results='/tmp/pnp_sharded_results_%d' % rank)
+        solver = functools.partial(P.ADMM_CNC, device=0, results=os.path.join(results, 'pnp_sharded_results_%d' % rank))
         x = sharding.solve_sharded(solver, masks, None, y=y, mask_id=mid, precision=precision, **P.PRESETS['ADMM_CNC'])
         if rank == 0:
             q.put(x)
@@ -41,7 +41,7 @@ def _worker(rank, world, port, q, precision='f32'):
 
 
 @pytest.mark.parametrize('precision', ['f32', 'f64'])
-def test_two_ranks_equal_one_process(precision):
+def test_two_ranks_equal_one_process(precision, tmp_path):
     import torch.multiprocessing as mp
     import pnp_admm_cnc_mri_amd as P
     s = socket.socket()
@@ -50,7 +50,7 @@ def test_two_ranks_equal_one_process(precision):
     s.close()
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q, precision)) for r in range(2)]
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, q, precision, str(tmp_path))) for r in range(2)]
     for p in procs:
         p.start()
     got = q.get(timeout=300)
@@ -58,7 +58,7 @@ def test_two_ranks_equal_one_process(precision):
         p.join(timeout=300)
         assert p.exitcode == 0
     masks, y, mid = _problem()
-    out = P.ADMM_CNC(masks, None, y=y, mask_id=mid, results='/tmp/pnp_sharded_results_ref', precision=precision, **P.PRESETS['ADMM_CNC'])
+    out = P.ADMM_CNC(masks, None, y=y, mask_id=mid, results=str(tmp_path / 'pnp_sharded_results_ref'), precision=precision, **P.PRESETS['ADMM_CNC'])
     real = np.float64 if precision == 'f64' else np.float32             # the gather keeps the solver's precision
     ref = np.stack([out[b].astype(real) for b in range(len(y))])
     assert got.dtype == real
@@ -92,7 +92,7 @@ def test_return_device_hands_back_the_reconstructions_as_one_device_tensor(tmp_p
     assert torch.is_tensor(dev) and np.array_equal(dev.cpu().numpy().astype(np.float64), np.stack([host[b] for b in range(7)]))
 
 
-def _worker_rccl(port, q):
+def _worker_rccl(port, q, results):
     """one rank on RCCL: the real backend's first contact with solve_sharded (a child process: the suite's own process must not keep
     a process group)"""
     import torch
@@ -111,10 +111,10 @@ def _worker_rccl(port, q):
             return real_gather(x_local, B_total, dst=dst, group=group)
         sharding.gather_slices = spy
         # the documented way for a bound solver: device in the partial, NOT in solve_sharded's keywords
-        bound = functools.partial(P.ADMM_CNC, device=0, results='/tmp/pnp_sharded_results_rccl')
+        bound = functools.partial(P.ADMM_CNC, device=0, results=results)
         x = sharding.solve_sharded(bound, masks, None, y=y, mask_id=mid, **P.PRESETS['ADMM_CNC'])
         # and the default: no device anywhere -> LOCAL_RANK under the process group
-        x_default = sharding.solve_sharded(functools.partial(P.ADMM_CNC, results='/tmp/pnp_sharded_results_rccl'), masks, None, y=y,
+        x_default = sharding.solve_sharded(functools.partial(P.ADMM_CNC, results=results), masks, None, y=y,
                                            mask_id=mid, **P.PRESETS['ADMM_CNC'])
         q.put((x, x_default, str(seen['device']), str(seen['dtype'])))
         dist.barrier()
@@ -122,7 +122,7 @@ def _worker_rccl(port, q):
         dist.destroy_process_group()
 
 
-def test_solve_sharded_through_rccl_with_one_rank():
+def test_solve_sharded_through_rccl_with_one_rank(tmp_path):
     """`solve_sharded` on the 'nccl' (= RCCL) backend, one rank, the solver's device bound with functools.partial: the gather is handed
     the tensor on the rank's own card and the result is bit-equal to the plain call."""
     import torch.multiprocessing as mp
@@ -133,13 +133,13 @@ def test_solve_sharded_through_rccl_with_one_rank():
     s.close()
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    p = ctx.Process(target=_worker_rccl, args=(port, q))
+    p = ctx.Process(target=_worker_rccl, args=(port, q, str(tmp_path / 'pnp_sharded_results_rccl')))
     p.start()
     x, x_default, dev, dt = q.get(timeout=300)
     p.join(timeout=300)
     assert p.exitcode == 0
     assert dev == 'cuda:0' and dt == 'torch.float32'
     masks, y, mid = _problem()
-    out = P.ADMM_CNC(masks, None, y=y, mask_id=mid, results='/tmp/pnp_sharded_results_ref', **P.PRESETS['ADMM_CNC'])
+    out = P.ADMM_CNC(masks, None, y=y, mask_id=mid, results=str(tmp_path / 'pnp_sharded_results_ref'), **P.PRESETS['ADMM_CNC'])
     ref = np.stack([out[b].astype(np.float32) for b in range(len(y))])
     assert np.array_equal(x, ref) and np.array_equal(x_default, ref)

@@ -56,7 +56,7 @@ def _worker(rank, world, port, B, q):
             q.put(x.numpy())
         else:
             assert x is None
-        dist.barrier()
+        dist.monitored_barrier()                      # gloo-only, CPU: dist.barrier() probes for an accelerator and opens the GPU
     finally:
         dist.destroy_process_group()
 
@@ -99,7 +99,7 @@ def _worker_solver(rank, world, port, q):
             q.put(x)
         else:
             assert x is None
-        dist.barrier()
+        dist.monitored_barrier()                      # gloo-only, CPU: dist.barrier() probes for an accelerator and opens the GPU
     finally:
         dist.destroy_process_group()
 
@@ -178,7 +178,7 @@ def _worker_noisy(rank, world, port, q):
             q.put(('all', x))
         if rank == 2:
             q.put(('sub', x2))
-        dist.barrier()
+        dist.monitored_barrier()                      # gloo-only, CPU: dist.barrier() probes for an accelerator and opens the GPU
     finally:
         dist.destroy_process_group()
 
@@ -241,7 +241,7 @@ def _worker8(rank, world, port, Bs, q):
             assert (x is not None) == (rank == 0)
             if rank == 0:
                 q.put((B, x))
-        dist.barrier()
+        dist.monitored_barrier()                      # gloo-only, CPU: dist.barrier() probes for an accelerator and opens the GPU
     finally:
         dist.destroy_process_group()
 

@@ -1,5 +1,5 @@
 // C ABI of libpnpmri.so (include/pnp_mri.h): context, problem upload, whole ADMM loops, step-wise
-// operators.  Host-side only; kernels live in kernels_generic.hip / kernels_fused256.hip.
+// operators, the denoisers' conv layers.  Host-side only; the kernels live in the kernels_*.hip files.
 #include "../../include/pnp_mri.h"
 #include "internal.h"
 
@@ -10,6 +10,7 @@
 #include <string.h>
 #include <dlfcn.h>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 using namespace pnp;
@@ -56,17 +57,43 @@ struct Range {
 };
 }  // namespace
 
+// The context's fast path, chosen at creation by shape, precision and PNP_FUSED_COLS, and beside it the slice-resident add-on of the
+// 256x256 float engine.  No engine (512x512 double, H != W): the generic kernels only.
+struct Engine {
+    enum Kind { none, fused256, split_f32, split_f64, fused512 } kind = none;
+    union {
+        Fused256* f256 = nullptr;     // 256 x 256 float: two launches per iteration
+        Fused256S<float>* s32;        // 256 x 256 "split chain" in float (PNP_FUSED_COLS=2) ...
+        Fused256S<double>* s64;       // ... and in double: the fast path of an fp64 context
+        Fused512* f512;               // 512 x 512 float
+    };
+    Slice256* slice = nullptr;        // fused256 only: whole loops slice-resident (pnp_dc_step stays on f256) ...
+    int slice_min_b = 0;              // ... for batches at least this large
+};
+
+// Which kernels run the loops (pnp_admm_*_run) of the uploaded problem.
+enum class Path { generic, slice, fused };
+
+// What the uploaded problem has of its tables: reset by every upload / synthesize (begin_problem, finish_problem).
+struct Problem {
+    Path path = Path::generic;        // the loops' path with the fast path on (loop_path)
+    bool fused_built = false;         // the engine's own tables (ensure_tables)
+    bool slice_built = false;         // the slice-resident tables
+};
+
 struct pnp_ctx {
     int device = 0, H = 0, W = 0, Bmax = 0;
     int B = 0, K = 0;                 // current problem (0 = none uploaded)
     size_t N = 0;                     // H*W
     hipStream_t stream = nullptr;
+    bool f64 = false;                 // fp64 validation context (pnp_ctx_create_f64): y, work, z, w, x hold doubles
     bool fast = true;
     bool have_x = false;
     bool have_state = false;         // z / w hold a defined state for the CURRENT problem: cleared by upload / synthesize, set by pnp_init_state or pnp_set_state(z, w)
-    float2* y = nullptr;              // [Bmax][H][W]
-    float2* work = nullptr;           // [Bmax][H][W] transform intermediate
-    float *z = nullptr, *w = nullptr, *x = nullptr;
+    bool state_sliced = false;       // z / w are in the slice-resident kernel's order (slice_layout.h, sl_state_index)
+    void* y = nullptr;                // [Bmax][H][W] complex, in the context's precision (bufs<R>)
+    void* work = nullptr;             // [Bmax][H][W] complex transform intermediate
+    void *z = nullptr, *w = nullptr, *x = nullptr;     // [Bmax][H][W] real
     uint8_t* mask_bank = nullptr;     // [Kcap][H][W]
     int Kcap = 0;
     int32_t* mask_id = nullptr;       // [Bmax]
@@ -76,25 +103,21 @@ struct pnp_ctx {
     void* stage = nullptr;            // staging for host inputs of synthesize
     size_t stage_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    Fused256* fused = nullptr;        // 256 x 256
-    Fused512* fused5 = nullptr;       // 512 x 512
-    Slice256* slice = nullptr;        // 256 x 256 slice-resident loops (whole runs; pnp_dc_step stays on `fused`)
-    bool slice_ready = false;        // the loops of the uploaded problem take the slice-resident path ...
-    bool slice_tabs = false;         // ... and its tables have been built (on the first such loop, or by pnp_prepare_loops)
-    bool state_sliced = false;       // c->z / c->w are in the slice-resident kernel's order (slice_layout.h, sl_state_index)
-    int slice_min_b = 0;              // batches at least this large run their loops slice-resident
-    bool slice_force = false;
-    Fused256S<float>* fs32 = nullptr;   // 256 x 256 "split chain" engine in float (PNP_FUSED_COLS=2) ...
-    Fused256S<double>* fs64 = nullptr;  // ... and in double: the fast path of an fp64 context
+    Engine eng;
+    Problem prob;
     FusedSchedule sched;              // defaults overridable by PNP_FUSED_* (read at creation) / pnp_set_schedule
-    bool fused_ready = false;         // tables prepared for the current problem
-    bool fused_tabs = false;          // 256x256 float: the two-launch tables themselves (built on first use when the slice-resident tables serve the loops)
-    // fp64 validation context (pnp_ctx_create_f64): same loop, generic kernels, double buffers
-    bool f64 = false;
-    double2* yd = nullptr;
-    double2* workd = nullptr;
-    double *zd = nullptr, *wd = nullptr, *xd = nullptr;
 };
+
+// The context's buffers as the element type of its precision (R = float | double).
+template <typename R> struct Bufs {
+    using C = typename CxOf<R>::type;
+    C *y, *work;
+    R *z, *w, *x;
+};
+template <typename R> static Bufs<R> bufs(const pnp_ctx* c) {
+    using C = typename CxOf<R>::type;
+    return {(C*)c->y, (C*)c->work, (R*)c->z, (R*)c->w, (R*)c->x};
+}
 
 static bool supported(int n) { return n == 256 || n == 512; }
 
@@ -140,36 +163,378 @@ static int read_knobs(Knobs* k, FusedSchedule* sch) {
     return PNP_OK;
 }
 
-static ProxParams make_prox_l1(double lambda1, double reo) {
-    ProxParams p{};
-    p.thr = (float)(reo * lambda1);
-    return p;
+// the z / w update's scalars (internal.h, ProxParamsT): combined in double, rounded once to R
+template <typename R> static ProxParamsT<R> prox_l1(double lambda1, double reo) { return {(R)(reo * lambda1)}; }
+template <typename R> static ProxParamsT<R> prox_cnc(double alpha, double lambda1, double reo, double b) {
+    return {(R)(alpha * reo * lambda1), (R)(1.0 - alpha), (R)alpha, (R)(alpha * reo * lambda1 * b), (R)(1.0 / b)};
 }
-static ProxParams make_prox_cnc(double alpha, double lambda1, double reo, double b) {
-    ProxParams p{};
-    p.thr = (float)(alpha * reo * lambda1);
-    p.c1 = (float)(1.0 - alpha);
-    p.c2 = (float)alpha;
-    p.c3 = (float)(alpha * reo * lambda1 * b);
-    p.ib = (float)(1.0 / b);
-    return p;
-}
-static float dc_coeff(double reo) { return (float)(1.0 / (1.0 + 1.0 / 2.0 / reo)); }
+template <typename R> static R dc_coeff(double reo) { return (R)(1.0 / (1.0 + 1.0 / 2.0 / reo)); }
 
-// The slice-resident loops keep z / w in their own order; everything else (the other kernel families, pnp_get_state /
-// pnp_set_state, pnp_init_state) sees natural [H][W].  One kernel converts when the need changes (into the slice path's own
-// padded arrays; in place with PNP_SLICE_PAD_KB=0).
-static int state_order(pnp_ctx* c, bool sliced) {
-    if (c->state_sliced == sliced) return PNP_OK;
-    if (c->B > 0) {
-        hipError_t e = slice256_state_order(c->slice, c->stream, c->z, c->w, c->B, sliced);
-        if (e != hipSuccess) return fail(PNP_E_HIP, "state order: %s", hipGetErrorString(e));
-    }
-    c->state_sliced = sliced;
+#define CTX(c) do { if (!(c)) return fail(PNP_E_ARG, "%s: ctx is null", __func__); HIPCHK(hipSetDevice((c)->device)); } while (0)
+#define NEED_PROBLEM(c) do { if ((c)->B <= 0) return fail(PNP_E_STATE, "%s: no problem uploaded", __func__); } while (0)
+#define NEED_STATE(c) do { if (!(c)->have_state) return undefined_state(__func__); } while (0)
+#define F32_ONLY(c) do { if ((c)->f64) return fail(PNP_E_STATE, "%s: not available on an fp64 validation context", __func__); } while (0)
+#define F64_ONLY(c) do { if (!(c)->f64) return fail(PNP_E_STATE, "%s: needs a context made by pnp_ctx_create_f64", __func__); } while (0)
+
+static int undefined_state(const char* who) {
+    return fail(PNP_E_STATE, "%s: z / w are undefined since the last upload / synthesize (call pnp_init_state or pnp_set_state with both z and w)", who);
+}
+
+static int copy_in(pnp_ctx* c, void* dst, const void* src, size_t bytes, int on_device) {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    if (!on_device) HIPCHK(hipStreamSynchronize(c->stream));   // caller may reuse its host buffer
+    return PNP_OK;
+}
+static int copy_out(pnp_ctx* c, void* dst, const void* src, size_t bytes, int on_device) {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    if (!on_device) HIPCHK(hipStreamSynchronize(c->stream));
     return PNP_OK;
 }
 
-static bool use_fused(pnp_ctx* c) { return c->fast && (c->fused || c->fused5 || c->fs32 || c->fs64) && c->fused_ready; }
+// ---- the problem lifecycle: begin_problem, y written, finish_problem ----
+
+// Drops the current problem and loads the masks of the next one.  A new problem invalidates the state (include/pnp_mri.h): z / w are
+// UNDEFINED until pnp_init_state or pnp_set_state(z, w).  The order flag goes with it -- a conversion under the new B would read the
+// slice path's padded arrays beyond the old batch.
+static int begin_problem(pnp_ctx* c, const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
+    c->B = 0;
+    c->prob = Problem{};
+    c->state_sliced = c->have_x = c->have_state = false;
+    if (!mask_bank) return fail(PNP_E_ARG, "mask_bank is null");
+    if (B < 1 || B > c->Bmax) return fail(PNP_E_ARG, "B=%d out of range [1,%d]", B, c->Bmax);
+    if (K < 1) return fail(PNP_E_ARG, "K must be >= 1");
+    if (K > c->Kcap) {
+        if (c->mask_bank) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->mask_bank)); c->mask_bank = nullptr; c->Kcap = 0; }
+        HIPCHK(hipMalloc((void**)&c->mask_bank, (size_t)K * c->N));
+        c->Kcap = K;
+    }
+    int rc = copy_in(c, c->mask_bank, mask_bank, (size_t)K * c->N, on_device);
+    if (rc) return rc;
+    if (mask_id) {
+        // ids index the mask bank inside the kernels: validate them for host AND device inputs
+        // (B int32 values; a device array is read back once -- problem upload is not the hot path)
+        std::vector<int32_t> tmp;
+        const int32_t* ids = mask_id;
+        if (on_device) {
+            tmp.resize((size_t)B);
+            HIPCHK(hipMemcpyAsync(tmp.data(), mask_id, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            ids = tmp.data();
+        }
+        for (int i = 0; i < B; ++i) if (ids[i] < 0 || ids[i] >= K) return fail(PNP_E_ARG, "mask_id[%d]=%d out of range [0,%d)", i, ids[i], K);
+        rc = copy_in(c, c->mask_id, mask_id, (size_t)B * sizeof(int32_t), on_device);
+        if (rc) return rc;
+    } else {
+        HIPCHK(hipMemsetAsync(c->mask_id, 0, (size_t)B * sizeof(int32_t), c->stream));
+    }
+    c->B = B; c->K = K;
+    return PNP_OK;
+}
+
+// One workgroup per slice, one workgroup per compute unit at a time: the batch runs in rounds of `cus` slices.
+// Measured on MI355X, ms per iteration, two-launch vs slice-resident (profiles/run_slice_sizes.sh, one box each):
+//   round 3 (profiles/slice_sizes_r03.txt):  B = 16: 0.0218 / 0.0289   32: 0.0253 / 0.0291   48: 0.0269 / 0.0302   56: 0.0290 / 0.0310
+//                                            64: 0.0340 / 0.0309   96: 0.0437 / 0.0319
+//   round 2:  B = 128: 0.0544 / 0.0405   256: 0.0954 / 0.0565   272: 0.1063 / 0.0904   320: 0.1224 / 0.0936   512: 0.1919 / 0.1075
+// A round costs the same full or not, and even a nearly empty second round (B = 272) beats the two-launch path:
+// the rule is simply "at least PNP_SLICE_MIN_B (64) slices" -- the crossover still sits between 56 and 64 with round 3's kernel.
+static bool slice_pays(const pnp_ctx* c) { return c->B >= c->eng.slice_min_b; }
+
+// The only place that builds per-problem tables, each set once per problem.  Path::fused: the engine's own tables -- built at upload,
+// unless the slice path serves the loops of a 256x256 float problem: then on first use (pnp_dc_step always runs on them).
+// Path::slice: the slice-resident tables (256 KiB per slice), built by the first slice loop or pnp_prepare_loops, so that the step-wise
+// PnP solvers -- which only ever call pnp_dc_step on such a context -- never pay for them.
+static int ensure_tables(pnp_ctx* c, Path path) {
+    const float2* y = (const float2*)c->y;
+    switch (path) {
+    case Path::generic:
+        return PNP_OK;
+    case Path::slice:
+        if (!c->prob.slice_built) HIPCHK(slice256_prepare(c->eng.slice, c->stream, y, c->mask_bank, c->mask_id, c->B));
+        c->prob.slice_built = true;
+        return PNP_OK;
+    case Path::fused:
+        if (c->prob.fused_built) return PNP_OK;
+        switch (c->eng.kind) {
+        case Engine::none:      return PNP_OK;
+        case Engine::fused256:  HIPCHK(fused256_prepare(c->eng.f256, c->stream, y, c->mask_bank, c->mask_id, c->B)); break;
+        case Engine::split_f32: HIPCHK(fused256s_prepare<float>(c->eng.s32, c->stream, c->y, c->mask_bank, c->mask_id, c->B)); break;
+        case Engine::split_f64: HIPCHK(fused256s_prepare<double>(c->eng.s64, c->stream, c->y, c->mask_bank, c->mask_id, c->B)); break;
+        case Engine::fused512:  HIPCHK(fused512_prepare(c->eng.f512, c->stream, y, c->mask_bank, c->mask_id, c->B)); break;
+        }
+        c->prob.fused_built = true;
+        return PNP_OK;
+    }
+    return PNP_OK;
+}
+
+// Ends every upload / synthesize: decides the loops' path of the new problem and builds the tables that must exist now.  Any failure --
+// rc from writing the problem, or a failed build -- leaves no problem behind: B = 0.
+static int finish_problem(pnp_ctx* c, int rc) {
+    if (rc == PNP_OK && c->eng.kind != Engine::none) {
+        c->prob.path = (c->eng.slice && slice_pays(c)) ? Path::slice : Path::fused;
+        if (c->prob.path == Path::fused) rc = ensure_tables(c, Path::fused);
+    }
+    if (rc != PNP_OK) { c->B = 0; c->prob = Problem{}; }
+    return rc;
+}
+
+// The loops' path now: pnp_set_fast_path may change it after the upload.
+static Path loop_path(const pnp_ctx* c) { return c->fast ? c->prob.path : Path::generic; }
+
+// The slice-resident loops keep z / w in their own order; everything else (the other kernel families, pnp_get_state /
+// pnp_set_state, pnp_init_state) sees natural [H][W].  One kernel converts when the need changes (into the slice path's own
+// padded arrays; in place with PNP_SLICE_PAD_KB=0).  The slice path is float only: a double state is always in natural order.
+template <typename R> static int state_order(pnp_ctx* c, bool sliced) {
+    if constexpr (std::is_same_v<R, double>) {
+        return PNP_OK;
+    } else {
+        if (c->state_sliced == sliced) return PNP_OK;
+        if (c->B > 0) {
+            hipError_t e = slice256_state_order(c->eng.slice, c->stream, (float*)c->z, (float*)c->w, c->B, sliced);
+            if (e != hipSuccess) return fail(PNP_E_HIP, "state order: %s", hipGetErrorString(e));
+        }
+        c->state_sliced = sliced;
+        return PNP_OK;
+    }
+}
+
+// ---- problem, state and loops: one body per precision, R = float | double ----
+
+template <typename R>
+static int upload_problem(pnp_ctx* c, const char* who, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, int B, int K,
+                          int on_device) {
+    if (!y) return fail(PNP_E_ARG, "%s: y is null", who);
+    int rc = begin_problem(c, mask_bank, mask_id, B, K, on_device);
+    if (rc == PNP_OK) rc = copy_in(c, c->y, y, (size_t)B * c->N * 2 * sizeof(R), on_device);
+    return finish_problem(c, rc);
+}
+
+// y = fft2(img) * mask + noise (S4:102).  In double the reference's first fft2 runs on the float32 image in complex64 (NumPy >= 2) and
+// is promoted by the float64 mask; here the float32 image is widened (exactly) and transformed in double, which is the nearer of the
+// two to the exact transform -- the two y differ by NumPy's own complex64 round-off, ~1e-7.
+template <typename R>
+static int synthesize_y(pnp_ctx* c, const float* img, const R* noise, int noise_per_slice, int B, int on_device) {
+    using C = typename CxOf<R>::type;
+    const Bufs<R> b = bufs<R>(c);
+    const size_t img_bytes = (size_t)B * c->N * sizeof(float);
+    const size_t noise_bytes = (noise_per_slice ? (size_t)B : 1) * c->N * sizeof(C);
+    const float* d_img = img;
+    const C* d_noise = (const C*)noise;
+    if (!on_device) {
+        if (noise_bytes + img_bytes > c->stage_bytes) {
+            if (c->stage) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->stage)); c->stage = nullptr; c->stage_bytes = 0; }
+            HIPCHK(hipMalloc(&c->stage, noise_bytes + img_bytes));
+            c->stage_bytes = noise_bytes + img_bytes;
+        }
+        d_noise = (const C*)c->stage;                                   // the complex noise first: alignment
+        d_img = (const float*)((const char*)c->stage + noise_bytes);
+        int rc = copy_in(c, (void*)d_noise, noise, noise_bytes, 0);
+        if (rc == PNP_OK) rc = copy_in(c, (void*)d_img, img, img_bytes, 0);
+        if (rc) return rc;
+    }
+    RowArgsT<R> ra{};
+    if constexpr (std::is_same_v<R, double>) {
+        HIPCHK(launch_widen(c->stream, d_img, b.x, (size_t)B * c->N));     // x is invalid until the next run anyway (have_x = false)
+        ra.rin0 = b.x;
+    } else {
+        ra.rin0 = d_img;
+    }
+    ra.cout = b.y; ra.scale = 1; ra.nrows = B * c->H;
+    HIPCHK(launch_rows<R>(c->stream, c->W, IN_REAL, false, EPI_COMPLEX, ra));
+    ColArgsT<R> ca{};
+    ca.in = b.y; ca.out = b.y; ca.y = d_noise; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id;
+    ca.y_per_slice = noise_per_slice; ca.B = B;
+    HIPCHK(launch_cols<R>(c->stream, c->H, c->W, true, MID_MASK_ADD, false, ca));
+    return PNP_OK;
+}
+
+template <typename R>
+static int synthesize_problem(pnp_ctx* c, const char* who, const float* img, const R* noise, int noise_per_slice,
+                              const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
+    if (!img || !noise) return fail(PNP_E_ARG, "%s: img/noise is null", who);
+    int rc = begin_problem(c, mask_bank, mask_id, B, K, on_device);
+    if (rc == PNP_OK) rc = synthesize_y<R>(c, img, noise, noise_per_slice, B, on_device);
+    return finish_problem(c, rc);
+}
+
+template <typename R> static int download_y(pnp_ctx* c, const char* who, R* y, int on_device) {
+    if (!y) return fail(PNP_E_ARG, "%s: null", who);
+    return copy_out(c, y, c->y, (size_t)c->B * c->N * 2 * sizeof(R), on_device);
+}
+
+template <typename R> static int download_x(pnp_ctx* c, const char* who, R* x, int on_device) {
+    if (!x) return fail(PNP_E_ARG, "%s: null", who);
+    if (!c->have_x) return fail(PNP_E_STATE, "%s: no iteration has been run since the state was set", who);
+    return copy_out(c, x, c->x, (size_t)c->B * c->N * sizeof(R), on_device);
+}
+
+// z = |ifft2(y)|, w = 0
+template <typename R> static int init_state(pnp_ctx* c) {
+    const Bufs<R> b = bufs<R>(c);
+    c->state_sliced = false;                           // both arrays are rewritten below, in natural order
+    ColArgsT<R> ca{};
+    ca.in = b.y; ca.out = b.work; ca.B = c->B;
+    HIPCHK(launch_cols<R>(c->stream, c->H, c->W, false, MID_NONE, true, ca));
+    RowArgsT<R> ra{};
+    ra.cin = b.work; ra.x_out = b.z; ra.scale = (R)1 / (R)c->N; ra.nrows = c->B * c->H;
+    HIPCHK(launch_rows<R>(c->stream, c->W, IN_COMPLEX, true, EPI_ABS_COMPLEX, ra));
+    HIPCHK(hipMemsetAsync(b.w, 0, (size_t)c->B * c->N * sizeof(R), c->stream));
+    c->have_x = false;
+    c->have_state = true;
+    return PNP_OK;
+}
+
+template <typename R> static int set_state(pnp_ctx* c, const char* who, const R* z, const R* w, int on_device) {
+    const size_t bytes = (size_t)c->B * c->N * sizeof(R);
+    int rc;
+    if (z && w) c->state_sliced = false;               // both replaced: nothing to convert
+    else if (!c->have_state) return undefined_state(who);                         // one of the two kept: it must be defined
+    else if ((rc = state_order<R>(c, false))) return rc;
+    if (z) { rc = copy_in(c, c->z, z, bytes, on_device); if (rc) return rc; }
+    if (w) { rc = copy_in(c, c->w, w, bytes, on_device); if (rc) return rc; }
+    c->have_x = false;
+    if (z && w) c->have_state = true;
+    return PNP_OK;
+}
+
+template <typename R> static int get_state(pnp_ctx* c, R* z, R* w, int on_device) {
+    const size_t bytes = (size_t)c->B * c->N * sizeof(R);
+    int rc;
+    if ((rc = state_order<R>(c, false))) return rc;
+    if (z) { rc = copy_out(c, z, c->z, bytes, on_device); if (rc) return rc; }
+    if (w) { rc = copy_out(c, w, c->w, bytes, on_device); if (rc) return rc; }
+    return PNP_OK;
+}
+
+// one generic iteration: rows fwd (z-w) -> cols fwd/blend/inv -> rows inv + prox + dual
+template <typename R>
+static int generic_iteration(pnp_ctx* c, const R* z_in, const R* w_in, RowEpi epi, const ProxParamsT<R>& pp, R cdc, R* x_out,
+                             R* z_io, R* w_io) {
+    const Bufs<R> b = bufs<R>(c);
+    RowArgsT<R> ra{};
+    ra.rin0 = z_in; ra.rin1 = w_in; ra.cout = b.work; ra.scale = 1; ra.nrows = c->B * c->H;
+    HIPCHK(launch_rows<R>(c->stream, c->W, IN_REAL_DIFF, false, EPI_COMPLEX, ra));
+    ColArgsT<R> ca{};
+    ca.in = b.work; ca.out = b.work; ca.y = b.y; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id;
+    ca.c = cdc; ca.B = c->B;
+    HIPCHK(launch_cols<R>(c->stream, c->H, c->W, true, MID_BLEND, true, ca));
+    RowArgsT<R> rb{};
+    rb.cin = b.work; rb.x_out = x_out; rb.z = z_io; rb.w = w_io; rb.scale = (R)1 / (R)c->N;
+    rb.prox = pp; rb.nrows = c->B * c->H;
+    HIPCHK(launch_rows<R>(c->stream, c->W, IN_COMPLEX, true, epi, rb));
+    return PNP_OK;
+}
+
+// The fast loops (Path::slice, Path::fused) on a float state ...
+static hipError_t fast_run(pnp_ctx* c, Path path, int iters, bool cnc, float cdc, const ProxParams& pp) {
+    const Bufs<float> b = bufs<float>(c);
+    if (path == Path::slice) return slice256_run(c->eng.slice, c->stream, b.z, b.w, b.x, c->B, iters, cnc, cdc, pp, c->sched);
+    switch (c->eng.kind) {
+    case Engine::fused256:  return fused256_run(c->eng.f256, c->stream, b.z, b.w, b.x, c->B, iters, cnc, cdc, pp, c->sched);
+    case Engine::split_f32: return fused256s_run<float>(c->eng.s32, c->stream, b.z, b.w, b.x, c->B, iters, cnc, cdc, pp, c->sched);
+    case Engine::fused512:  return fused512_run(c->eng.f512, c->stream, b.z, b.w, b.x, c->B, iters, cnc, cdc, pp, c->sched);
+    case Engine::none: case Engine::split_f64: break;
+    }
+    return hipErrorInvalidValue;
+}
+// ... and on a double state: the split chain is the one double engine (no slice path in double)
+static hipError_t fast_run(pnp_ctx* c, Path, int iters, bool cnc, double cdc, const ProxParamsT<double>& pp) {
+    const Bufs<double> b = bufs<double>(c);
+    return fused256s_run<double>(c->eng.s64, c->stream, b.z, b.w, b.x, c->B, iters, cnc, cdc, pp, c->sched);
+}
+
+template <typename R>
+static int run_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
+    const Bufs<R> b = bufs<R>(c);
+    const Path path = iters > 0 ? loop_path(c) : Path::generic;
+    if (int rc = ensure_tables(c, path)) return rc;
+    if (int rc = state_order<R>(c, path == Path::slice)) return rc;
+    const R cdc = dc_coeff<R>(reo);
+    switch (path) {
+    case Path::generic:
+        // iters == 0: the reference's loop body never runs and its x stays the initial x = |ifft2(y)| = z0 (S4:103, 107, 138)
+        if (iters == 0) HIPCHK(hipMemcpyAsync(b.x, b.z, (size_t)c->B * c->N * sizeof(R), hipMemcpyDeviceToDevice, c->stream));
+        for (int i = 0; i < iters; ++i) {
+            int rc = generic_iteration<R>(c, b.z, b.w, cnc ? EPI_CNC : EPI_L1, pp, cdc, (i == iters - 1) ? b.x : nullptr, b.z, b.w);
+            if (rc) return rc;
+        }
+        break;
+    case Path::slice:
+    case Path::fused:
+        HIPCHK(fast_run(c, path, iters, cnc, cdc, pp));
+        break;
+    }
+    c->have_x = true;
+    return PNP_OK;
+}
+
+// What the next loop call runs (pnp_get_plan): the schedule functions the engines themselves run by.
+struct LoopPlan { int queues, chunk, launches; };
+static LoopPlan loop_plan(const pnp_ctx* c) {
+    switch (loop_path(c)) {
+    case Path::generic: return {1, c->B, 3};          // rows, columns, rows
+    case Path::slice:   return {1, c->B, 0};          // one launch per RUN: the iterations are a loop inside it
+    case Path::fused:   break;
+    }
+    if (c->eng.kind == Engine::fused256) {
+        const Fused256Plan p = fused256_plan(c->B, c->sched);
+        return {p.queues, p.chunk, p.launches};
+    }
+    // the split-chain and 512x512 engines: chunked round-robin schedules, two launches per chunk
+    const ChunkPlan p = chunk_plan(c->B, c->sched, c->eng.kind == Engine::fused512, c->eng.kind == Engine::split_f64, c->sched.chunk_queues);
+    return {p.queues, p.chunk < c->B ? p.chunk : c->B, chunk_plan_launches(c->B, p)};
+}
+
+// the x (the caller's, or the ctx's own) and the ground truth (the caller's device array, or a copy of its host array) of a metric
+template <typename X>
+static int metric_inputs(pnp_ctx* c, const char* who, const X*& x, const uint8_t*& gt, int gt_on_device) {
+    if (!x) {
+        if (!c->have_x) return fail(PNP_E_STATE, "%s: x_dev is null and the ctx holds no x yet", who);
+        x = bufs<X>(c).x;
+    }
+    if (!gt_on_device) {
+        if (!c->gt) HIPCHK(hipMalloc((void**)&c->gt, (size_t)c->Bmax * c->N));
+        if (int rc = copy_in(c, c->gt, gt, (size_t)c->B * c->N, 0)) return rc;
+        gt = c->gt;
+    }
+    return PNP_OK;
+}
+
+template <typename X>
+static int metrics_any(pnp_ctx* c, const X* x, const uint8_t* gt, int gt_on_device, double* psnr, double* re) {
+    if (!gt || !psnr || !re) return fail(PNP_E_ARG, "pnp_metrics: null pointer");
+    if (int rc = metric_inputs(c, "pnp_metrics", x, gt, gt_on_device)) return rc;
+    HIPCHK(launch_metrics<X>(c->stream, x, gt, c->acc, c->B, (int)c->N));
+    std::vector<double> h((size_t)c->B * 2);
+    int rc = copy_out(c, h.data(), c->acc, h.size() * sizeof(double), 0);
+    if (rc) return rc;
+    for (int b = 0; b < c->B; ++b) {
+        const double mse = h[2 * b] / (double)c->N;
+        psnr[b] = (mse == 0.0) ? INFINITY : 20.0 * log10(255.0 / sqrt(mse));
+        re[b] = sqrt(h[2 * b]) / sqrt(h[2 * b + 1]);
+    }
+    return PNP_OK;
+}
+
+template <typename X>
+static int ssim_any(pnp_ctx* c, const X* x, const uint8_t* gt, int gt_on_device, double* ssim) {
+    if (!gt || !ssim) return fail(PNP_E_ARG, "pnp_ssim: null pointer");
+    if (int rc = metric_inputs(c, "pnp_ssim", x, gt, gt_on_device)) return rc;
+    const int tiles = ((c->W - 10 + 15) / 16) * ((c->H - 10 + 15) / 16);
+    if (!c->ssim_part) HIPCHK(hipMalloc((void**)&c->ssim_part, (size_t)c->Bmax * tiles * sizeof(double)));
+    HIPCHK(launch_ssim<X>(c->stream, x, gt, c->ssim_part, c->B, c->H, c->W));
+    std::vector<double> h((size_t)c->B * tiles);
+    int rc = copy_out(c, h.data(), c->ssim_part, h.size() * sizeof(double), 0);
+    if (rc) return rc;
+    const double npix = (double)(c->H - 10) * (double)(c->W - 10);
+    for (int b = 0; b < c->B; ++b) {
+        double s = 0.0;
+        for (int t = 0; t < tiles; ++t) s += h[(size_t)b * tiles + t];
+        ssim[b] = s / npix;
+    }
+    return PNP_OK;
+}
 
 extern "C" {
 
@@ -243,22 +608,11 @@ static int ctx_create_any(int device, int H, int W, int Bmax, pnp_ctx** out, boo
     if (!c) return fail(PNP_E_NOMEM, "pnp_ctx_create: host allocation failed");
     c->device = device; c->H = H; c->W = W; c->Bmax = Bmax; c->N = (size_t)H * W; c->f64 = f64;
     c->sched = sched0;
-    const size_t BN = (size_t)Bmax * c->N;
+    const size_t BN = (size_t)Bmax * c->N, real = f64 ? sizeof(double) : sizeof(float);
     hipError_t e = hipSuccess;
     auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-    if (f64) {
-        alloc((void**)&c->yd, BN * sizeof(double2));
-        alloc((void**)&c->workd, BN * sizeof(double2));
-        alloc((void**)&c->zd, BN * sizeof(double));
-        alloc((void**)&c->wd, BN * sizeof(double));
-        alloc((void**)&c->xd, BN * sizeof(double));
-    } else {
-        alloc((void**)&c->y, BN * sizeof(float2));
-        alloc((void**)&c->work, BN * sizeof(float2));
-        alloc((void**)&c->z, BN * sizeof(float));
-        alloc((void**)&c->w, BN * sizeof(float));
-        alloc((void**)&c->x, BN * sizeof(float));
-    }
+    for (void** p : {&c->y, &c->work}) alloc(p, BN * 2 * real);         // complex
+    for (void** p : {&c->z, &c->w, &c->x}) alloc(p, BN * real);
     alloc((void**)&c->mask_id, (size_t)Bmax * sizeof(int32_t));
     alloc((void**)&c->acc, (size_t)Bmax * 2 * sizeof(double));
     if (e == hipSuccess) e = hipEventCreate(&c->ev0);
@@ -269,34 +623,33 @@ static int ctx_create_any(int device, int H, int W, int Bmax, pnp_ctx** out, boo
         pnp_ctx_destroy(c);
         return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "pnp_ctx_create: %s", hipGetErrorString(e));
     }
-    if (H == W && (!f64 || H == 256)) {
-        hipError_t fe = hipSuccess;
-        if (f64)                                         c->fs64 = fused256s_create<double>(Bmax, &fe);
-        else if (H == 256 && kn.fused_cols == 2)         c->fs32 = fused256s_create<float>(Bmax, &fe);
-        else if (H == 256) {
-            c->fused = fused256_create(Bmax, &fe);
-            // Slice-resident loops: one workgroup (= one compute unit) per slice, so they pay off once the batch
-            // fills the chip; small batches stay on the two-launch path, which spreads a slice over many CUs.
-            // PNP_SLICE=0 never, =1 always, unset: batches of at least PNP_SLICE_MIN_B slices (slice_pays()).
-            const int mode = kn.slice;
-            c->slice_min_b = mode == 1 ? 1 : kn.slice_min_b;
-            c->slice_force = (mode == 1);
-            if (c->fused && mode != 0 && Bmax >= c->slice_min_b) {
-                hipError_t se = hipSuccess;
-                c->slice = slice256_create(Bmax, kn.slice_pad_kb, kn.slice_yh_pad_kb, &se);
-                // no room for the slice-resident tables (256 KiB per slice on top of the two-launch tables): the context
-                // degrades to the two-launch path (pnp_path_name says "fused") -- unless the caller forced PNP_SLICE=1
-                if (!c->slice) {
-                    (void)hipGetLastError();
-                    if (mode == 1) { fe = se; fused256_destroy(c->fused); c->fused = nullptr; }
-                }
-            }
+    Engine& g = c->eng;
+    if (H == 256 && W == 256) g.kind = f64 ? Engine::split_f64 : (kn.fused_cols == 2 ? Engine::split_f32 : Engine::fused256);
+    else if (H == 512 && W == 512 && !f64) g.kind = Engine::fused512;
+    hipError_t fe = hipSuccess;
+    bool made = true;
+    switch (g.kind) {
+    case Engine::none:      break;
+    case Engine::fused256:  made = (g.f256 = fused256_create(Bmax, &fe)) != nullptr; break;
+    case Engine::split_f32: made = (g.s32 = fused256s_create<float>(Bmax, &fe)) != nullptr; break;
+    case Engine::split_f64: made = (g.s64 = fused256s_create<double>(Bmax, &fe)) != nullptr; break;
+    case Engine::fused512:  made = (g.f512 = fused512_create(Bmax, &fe)) != nullptr; break;
+    }
+    // Slice-resident loops: one workgroup (= one compute unit) per slice, so they pay off once the batch fills the chip; small batches
+    // stay on the two-launch path, which spreads a slice over many CUs.  PNP_SLICE=0 never, =1 always, unset: batches of at least
+    // PNP_SLICE_MIN_B slices (slice_pays()).
+    if (made && g.kind == Engine::fused256 && kn.slice != 0) {
+        g.slice_min_b = kn.slice == 1 ? 1 : kn.slice_min_b;
+        if (Bmax >= g.slice_min_b) {
+            g.slice = slice256_create(Bmax, kn.slice_pad_kb, kn.slice_yh_pad_kb, &fe);
+            // no room for the slice-resident tables (256 KiB per slice on top of the two-launch tables): the context degrades to the
+            // two-launch path (pnp_path_name says "fused") -- unless the caller forced PNP_SLICE=1
+            if (!g.slice) { (void)hipGetLastError(); made = kn.slice != 1; }
         }
-        else                                             c->fused5 = fused512_create(Bmax, &fe);
-        if (!c->fused && !c->fused5 && !c->fs32 && !c->fs64) {
-            pnp_ctx_destroy(c);
-            return fail(PNP_E_HIP, "pnp_ctx_create: fused path: %s", hipGetErrorString(fe));
-        }
+    }
+    if (!made) {
+        pnp_ctx_destroy(c);
+        return fail(PNP_E_HIP, "pnp_ctx_create: fused path: %s", hipGetErrorString(fe));
     }
     *out = c;
     return PNP_OK;
@@ -308,25 +661,21 @@ int pnp_ctx_create_f64(int device, int H, int W, int Bmax, pnp_ctx** out) { retu
 int pnp_ctx_destroy(pnp_ctx* c) {
     if (!c) return PNP_OK;
     (void)hipSetDevice(c->device);
-    if (c->fused) fused256_destroy(c->fused);
-    if (c->fused5) fused512_destroy(c->fused5);
-    if (c->slice) slice256_destroy(c->slice);
-    if (c->fs32) fused256s_destroy(c->fs32);
-    if (c->fs64) fused256s_destroy(c->fs64);
-    void* ptrs[] = {c->y, c->work, c->z, c->w, c->x, c->mask_bank, c->mask_id, c->gt, c->acc, c->stage, c->ssim_part,
-                    c->yd, c->workd, c->zd, c->wd, c->xd};
+    switch (c->eng.kind) {
+    case Engine::none:      break;
+    case Engine::fused256:  fused256_destroy(c->eng.f256); break;
+    case Engine::split_f32: fused256s_destroy(c->eng.s32); break;
+    case Engine::split_f64: fused256s_destroy(c->eng.s64); break;
+    case Engine::fused512:  fused512_destroy(c->eng.f512); break;
+    }
+    slice256_destroy(c->eng.slice);
+    void* ptrs[] = {c->y, c->work, c->z, c->w, c->x, c->mask_bank, c->mask_id, c->gt, c->acc, c->stage, c->ssim_part};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     delete c;
     return PNP_OK;
 }
-
-#define CTX(c) do { if (!(c)) return fail(PNP_E_ARG, "%s: ctx is null", __func__); HIPCHK(hipSetDevice((c)->device)); } while (0)
-#define NEED_PROBLEM(c) do { if ((c)->B <= 0) return fail(PNP_E_STATE, "%s: no problem uploaded", __func__); } while (0)
-#define NEED_STATE(c) do { if (!(c)->have_state) return fail(PNP_E_STATE, "%s: z / w are undefined since the last upload / synthesize (call pnp_init_state or pnp_set_state with both z and w)", __func__); } while (0)
-#define F32_ONLY(c) do { if ((c)->f64) return fail(PNP_E_STATE, "%s: not available on an fp64 validation context", __func__); } while (0)
-#define F64_ONLY(c) do { if (!(c)->f64) return fail(PNP_E_STATE, "%s: needs a context made by pnp_ctx_create_f64", __func__); } while (0)
 
 int pnp_set_stream(pnp_ctx* c, void* s) { CTX(c); c->stream = (hipStream_t)s; return PNP_OK; }
 int pnp_sync(pnp_ctx* c) { CTX(c); HIPCHK(hipStreamSynchronize(c->stream)); return PNP_OK; }
@@ -345,291 +694,32 @@ int pnp_set_schedule(pnp_ctx* c, int queues, int mixed_launches, int chunk) {
     return PNP_OK;
 }
 
-static int copy_in(pnp_ctx* c, void* dst, const void* src, size_t bytes, int on_device) {
-    HIPCHK(hipMemcpyAsync(dst, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    if (!on_device) HIPCHK(hipStreamSynchronize(c->stream));   // caller may reuse its host buffer
-    return PNP_OK;
-}
-static int copy_out(pnp_ctx* c, void* dst, const void* src, size_t bytes, int on_device) {
-    HIPCHK(hipMemcpyAsync(dst, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    if (!on_device) HIPCHK(hipStreamSynchronize(c->stream));
-    return PNP_OK;
-}
-
-static int set_masks(pnp_ctx* c, const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
-    if (!mask_bank) return fail(PNP_E_ARG, "mask_bank is null");
-    if (B < 1 || B > c->Bmax) return fail(PNP_E_ARG, "B=%d out of range [1,%d]", B, c->Bmax);
-    if (K < 1) return fail(PNP_E_ARG, "K must be >= 1");
-    if (K > c->Kcap) {
-        if (c->mask_bank) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->mask_bank)); c->mask_bank = nullptr; c->Kcap = 0; }
-        HIPCHK(hipMalloc((void**)&c->mask_bank, (size_t)K * c->N));
-        c->Kcap = K;
-    }
-    int rc = copy_in(c, c->mask_bank, mask_bank, (size_t)K * c->N, on_device);
-    if (rc) return rc;
-    if (mask_id) {
-        // ids index the mask bank inside the kernels: validate them for host AND device inputs
-        // (B int32 values; a device array is read back once -- problem upload is not the hot path)
-        std::vector<int32_t> tmp;
-        const int32_t* ids = mask_id;
-        if (on_device) {
-            tmp.resize((size_t)B);
-            HIPCHK(hipMemcpyAsync(tmp.data(), mask_id, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            ids = tmp.data();
-        }
-        for (int i = 0; i < B; ++i) if (ids[i] < 0 || ids[i] >= K) return fail(PNP_E_ARG, "mask_id[%d]=%d out of range [0,%d)", i, ids[i], K);
-        rc = copy_in(c, c->mask_id, mask_id, (size_t)B * sizeof(int32_t), on_device);
-        if (rc) return rc;
-    } else {
-        HIPCHK(hipMemsetAsync(c->mask_id, 0, (size_t)B * sizeof(int32_t), c->stream));
-    }
-    c->B = B; c->K = K; c->have_x = false; c->fused_ready = false;
-    return PNP_OK;
-}
-
-// One workgroup per slice, one workgroup per compute unit at a time: the batch runs in rounds of `cus` slices.
-// Measured on MI355X, ms per iteration, two-launch vs slice-resident (profiles/run_slice_sizes.sh, one box each):
-//   round 3 (profiles/slice_sizes_r03.txt):  B = 16: 0.0218 / 0.0289   32: 0.0253 / 0.0291   48: 0.0269 / 0.0302   56: 0.0290 / 0.0310
-//                                            64: 0.0340 / 0.0309   96: 0.0437 / 0.0319
-//   round 2:  B = 128: 0.0544 / 0.0405   256: 0.0954 / 0.0565   272: 0.1063 / 0.0904   320: 0.1224 / 0.0936   512: 0.1919 / 0.1075
-// A round costs the same full or not, and even a nearly empty second round (B = 272) beats the two-launch path:
-// the rule is simply "at least PNP_SLICE_MIN_B (64) slices" -- the crossover still sits between 56 and 64 with round 3's kernel.
-static bool slice_pays(pnp_ctx* c) {
-    return c->slice_force || c->B >= c->slice_min_b;
-}
-
-static int prepare_fused_tables(pnp_ctx* c);
-// A failed prepare leaves no valid problem behind: B = 0, no table marked ready.
-static int prepare_fused(pnp_ctx* c) {
-    c->slice_ready = false;
-    c->slice_tabs = false;
-    c->fused_ready = false;
-    const int rc = prepare_fused_tables(c);
-    if (rc) { c->B = 0; c->slice_ready = false; c->fused_ready = false; }
-    return rc;
-}
-// the two-launch tables of a 256x256 float context: needed by pnp_dc_step and by loops that do not take the slice-resident path
-static int ensure_fused_tabs(pnp_ctx* c) {
-    if (c->fused && !c->fused_tabs) {
-        HIPCHK(fused256_prepare(c->fused, c->stream, c->y, c->mask_bank, c->mask_id, c->B));
-        c->fused_tabs = true;
-    }
-    return PNP_OK;
-}
-// the slice-resident tables (256 KiB per slice, two launches): built when the first loop takes that path, so that the step-wise
-// PnP solvers -- which only ever call pnp_dc_step on such a context -- never pay for them
-static int ensure_slice_tabs(pnp_ctx* c) {
-    if (c->slice && c->slice_ready && !c->slice_tabs) {
-        HIPCHK(slice256_prepare(c->slice, c->stream, c->y, c->mask_bank, c->mask_id, c->B));
-        c->slice_tabs = true;
-    }
-    return PNP_OK;
-}
-static int prepare_fused_tables(pnp_ctx* c) {
-    if (c->fused) {
-        c->fused_tabs = false;
-        c->slice_tabs = false;
-        if (c->slice && slice_pays(c)) {
-            c->slice_ready = true;                        // tables: ensure_slice_tabs / ensure_fused_tabs, on first use
-        } else {
-            const int rc = ensure_fused_tabs(c);
-            if (rc) return rc;
-        }
-        c->fused_ready = true;
-    } else if (c->fused5) {
-        HIPCHK(fused512_prepare(c->fused5, c->stream, c->y, c->mask_bank, c->mask_id, c->B));
-        c->fused_ready = true;
-    } else if (c->fs32) {
-        HIPCHK(fused256s_prepare<float>(c->fs32, c->stream, c->y, c->mask_bank, c->mask_id, c->B));
-        c->fused_ready = true;
-    } else if (c->fs64) {
-        HIPCHK(fused256s_prepare<double>(c->fs64, c->stream, c->yd, c->mask_bank, c->mask_id, c->B));
-        c->fused_ready = true;
-    }
-    return PNP_OK;
-}
-
 int pnp_upload_problem(pnp_ctx* c, const float* y, const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
-    CTX(c); F32_ONLY(c);
-    if (!y) return fail(PNP_E_ARG, "pnp_upload_problem: y is null");
-    // A new problem invalidates the state (include/pnp_mri.h): z / w are UNDEFINED until pnp_init_state or pnp_set_state(z, w).  The
-    // order flag is reset with it -- a conversion under the new B would read the slice path's padded arrays beyond the old batch.
-    c->state_sliced = false;
-    c->have_x = false;
-    c->have_state = false;
-    int rc = set_masks(c, mask_bank, mask_id, B, K, on_device);
-    if (rc) { c->B = 0; return rc; }
-    rc = copy_in(c, c->y, y, (size_t)B * c->N * sizeof(float2), on_device);
-    if (rc) { c->B = 0; return rc; }
-    return prepare_fused(c);
+    CTX(c); F32_ONLY(c); return upload_problem(c, __func__, y, mask_bank, mask_id, B, K, on_device);
+}
+int pnp_upload_problem_f64(pnp_ctx* c, const double* y, const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
+    CTX(c); F64_ONLY(c); return upload_problem(c, __func__, y, mask_bank, mask_id, B, K, on_device);
 }
 
 int pnp_synthesize_problem(pnp_ctx* c, const float* img, const float* noise, int noise_per_slice,
                            const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
-    CTX(c); F32_ONLY(c);
-    if (!img || !noise) return fail(PNP_E_ARG, "pnp_synthesize_problem: img/noise is null");
-    // A new problem invalidates the state (include/pnp_mri.h): z / w are UNDEFINED until pnp_init_state or pnp_set_state(z, w).  The
-    // order flag is reset with it -- a conversion under the new B would read the slice path's padded arrays beyond the old batch.
-    c->state_sliced = false;
-    c->have_x = false;
-    c->have_state = false;
-    int rc = set_masks(c, mask_bank, mask_id, B, K, on_device);
-    if (rc) { c->B = 0; return rc; }
-    const size_t img_bytes = (size_t)B * c->N * sizeof(float);
-    const size_t noise_bytes = (noise_per_slice ? (size_t)B : 1) * c->N * sizeof(float2);
-    const float* d_img = img;
-    const float2* d_noise = (const float2*)noise;
-    if (!on_device) {
-        const size_t need = img_bytes + noise_bytes;
-        if (need > c->stage_bytes) {
-            c->B = 0;                                   // no valid problem until y has been rebuilt
-            if (c->stage) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->stage)); c->stage = nullptr; c->stage_bytes = 0; }
-            HIPCHK(hipMalloc(&c->stage, need));
-            c->B = B;
-            c->stage_bytes = need;
-        }
-        rc = copy_in(c, c->stage, img, img_bytes, 0); if (rc) { c->B = 0; return rc; }
-        rc = copy_in(c, (char*)c->stage + img_bytes, noise, noise_bytes, 0); if (rc) { c->B = 0; return rc; }
-        d_img = (const float*)c->stage;
-        d_noise = (const float2*)((char*)c->stage + img_bytes);
-    }
-    RowArgs ra{};
-    ra.rin0 = d_img; ra.cout = c->y; ra.scale = 1.0f; ra.nrows = B * c->H;
-    HIPCHK(launch_rows(c->stream, c->W, IN_REAL, false, EPI_COMPLEX, ra));
-    ColArgs ca{};
-    ca.in = c->y; ca.out = c->y; ca.y = d_noise; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id;
-    ca.y_per_slice = noise_per_slice; ca.B = B;
-    HIPCHK(launch_cols(c->stream, c->H, c->W, true, MID_MASK_ADD, false, ca));
-    return prepare_fused(c);
+    CTX(c); F32_ONLY(c); return synthesize_problem(c, __func__, img, noise, noise_per_slice, mask_bank, mask_id, B, K, on_device);
+}
+int pnp_synthesize_problem_f64(pnp_ctx* c, const float* img, const double* noise, int noise_per_slice,
+                               const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
+    CTX(c); F64_ONLY(c); return synthesize_problem(c, __func__, img, noise, noise_per_slice, mask_bank, mask_id, B, K, on_device);
 }
 
-int pnp_download_y(pnp_ctx* c, float* y, int on_device) {
-    CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
-    if (!y) return fail(PNP_E_ARG, "pnp_download_y: null");
-    return copy_out(c, y, c->y, (size_t)c->B * c->N * sizeof(float2), on_device);
-}
+int pnp_download_y(pnp_ctx* c, float* y, int on_device) { CTX(c); F32_ONLY(c); NEED_PROBLEM(c); return download_y(c, __func__, y, on_device); }
+int pnp_download_y_f64(pnp_ctx* c, double* y, int on_device) { CTX(c); F64_ONLY(c); NEED_PROBLEM(c); return download_y(c, __func__, y, on_device); }
 
-int pnp_init_state(pnp_ctx* c) {
-    CTX(c); NEED_PROBLEM(c);
-    if (c->f64) {
-        ColArgsT<double> ca{};
-        ca.in = c->yd; ca.out = c->workd; ca.B = c->B;
-        HIPCHK(launch_cols<double>(c->stream, c->H, c->W, false, MID_NONE, true, ca));
-        RowArgsT<double> ra{};
-        ra.cin = c->workd; ra.x_out = c->zd; ra.scale = 1.0 / (double)c->N; ra.nrows = c->B * c->H;
-        HIPCHK(launch_rows<double>(c->stream, c->W, IN_COMPLEX, true, EPI_ABS_COMPLEX, ra));
-        HIPCHK(hipMemsetAsync(c->wd, 0, (size_t)c->B * c->N * sizeof(double), c->stream));
-        c->have_x = false;
-        c->have_state = true;
-        return PNP_OK;
-    }
-    c->state_sliced = false;                           // both arrays are rewritten below, in natural order
-    ColArgs ca{};
-    ca.in = c->y; ca.out = c->work; ca.B = c->B;
-    HIPCHK(launch_cols(c->stream, c->H, c->W, false, MID_NONE, true, ca));
-    RowArgs ra{};
-    ra.cin = c->work; ra.x_out = c->z; ra.scale = 1.0f / (float)c->N; ra.nrows = c->B * c->H;
-    HIPCHK(launch_rows(c->stream, c->W, IN_COMPLEX, true, EPI_ABS_COMPLEX, ra));
-    HIPCHK(hipMemsetAsync(c->w, 0, (size_t)c->B * c->N * sizeof(float), c->stream));
-    c->have_x = false;
-    c->have_state = true;
-    return PNP_OK;
-}
+int pnp_init_state(pnp_ctx* c) { CTX(c); NEED_PROBLEM(c); return c->f64 ? init_state<double>(c) : init_state<float>(c); }
 
-int pnp_set_state(pnp_ctx* c, const float* z, const float* w, int on_device) {
-    CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
-    const size_t bytes = (size_t)c->B * c->N * sizeof(float);
-    int rc;
-    if (z && w) c->state_sliced = false;               // both replaced: nothing to convert
-    else { NEED_STATE(c); if ((rc = state_order(c, false))) return rc; }      // one of the two kept: it must be defined
-    if (z) { rc = copy_in(c, c->z, z, bytes, on_device); if (rc) return rc; }
-    if (w) { rc = copy_in(c, c->w, w, bytes, on_device); if (rc) return rc; }
-    c->have_x = false;
-    if (z && w) c->have_state = true;
-    return PNP_OK;
-}
+int pnp_set_state(pnp_ctx* c, const float* z, const float* w, int on_device) { CTX(c); F32_ONLY(c); NEED_PROBLEM(c); return set_state(c, __func__, z, w, on_device); }
+int pnp_set_state_f64(pnp_ctx* c, const double* z, const double* w, int on_device) { CTX(c); F64_ONLY(c); NEED_PROBLEM(c); return set_state(c, __func__, z, w, on_device); }
 
-int pnp_get_state(pnp_ctx* c, float* z, float* w, int on_device) {
-    CTX(c); F32_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c);
-    const size_t bytes = (size_t)c->B * c->N * sizeof(float);
-    int rc;
-    if ((rc = state_order(c, false))) return rc;
-    if (z) { rc = copy_out(c, z, c->z, bytes, on_device); if (rc) return rc; }
-    if (w) { rc = copy_out(c, w, c->w, bytes, on_device); if (rc) return rc; }
-    return PNP_OK;
-}
-
-// one generic iteration: rows fwd (z-w) -> cols fwd/blend/inv -> rows inv + prox + dual
-static int generic_iteration(pnp_ctx* c, const float* z_in, const float* w_in, RowEpi epi, const ProxParams& pp,
-                             float cdc, float* x_out, float* z_io, float* w_io) {
-    RowArgs ra{};
-    ra.rin0 = z_in; ra.rin1 = w_in; ra.cout = c->work; ra.scale = 1.0f; ra.nrows = c->B * c->H;
-    HIPCHK(launch_rows(c->stream, c->W, IN_REAL_DIFF, false, EPI_COMPLEX, ra));
-    ColArgs ca{};
-    ca.in = c->work; ca.out = c->work; ca.y = c->y; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id;
-    ca.c = cdc; ca.B = c->B;
-    HIPCHK(launch_cols(c->stream, c->H, c->W, true, MID_BLEND, true, ca));
-    RowArgs rb{};
-    rb.cin = c->work; rb.x_out = x_out; rb.z = z_io; rb.w = w_io; rb.scale = 1.0f / (float)c->N;
-    rb.prox = pp; rb.nrows = c->B * c->H;
-    HIPCHK(launch_rows(c->stream, c->W, IN_COMPLEX, true, epi, rb));
-    return PNP_OK;
-}
-
-static int run_loop_f64(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<double>& pp, double reo) {
-    const double cdc = 1.0 / (1.0 + 1.0 / 2.0 / reo);
-    if (iters == 0) HIPCHK(hipMemcpyAsync(c->xd, c->zd, (size_t)c->B * c->N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    if (iters > 0 && use_fused(c)) {
-        HIPCHK(fused256s_run<double>(c->fs64, c->stream, c->zd, c->wd, c->xd, c->B, iters, cnc, cdc, pp, c->sched));
-        c->have_x = true;
-        return PNP_OK;
-    }
-    for (int i = 0; i < iters; ++i) {
-        RowArgsT<double> ra{};
-        ra.rin0 = c->zd; ra.rin1 = c->wd; ra.cout = c->workd; ra.scale = 1.0; ra.nrows = c->B * c->H;
-        HIPCHK(launch_rows<double>(c->stream, c->W, IN_REAL_DIFF, false, EPI_COMPLEX, ra));
-        ColArgsT<double> ca{};
-        ca.in = c->workd; ca.out = c->workd; ca.y = c->yd; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id;
-        ca.c = cdc; ca.B = c->B;
-        HIPCHK(launch_cols<double>(c->stream, c->H, c->W, true, MID_BLEND, true, ca));
-        RowArgsT<double> rb{};
-        rb.cin = c->workd; rb.x_out = (i == iters - 1) ? c->xd : nullptr; rb.z = c->zd; rb.w = c->wd;
-        rb.scale = 1.0 / (double)c->N; rb.prox = pp; rb.nrows = c->B * c->H;
-        HIPCHK(launch_rows<double>(c->stream, c->W, IN_COMPLEX, true, cnc ? EPI_CNC : EPI_L1, rb));
-    }
-    c->have_x = true;
-    return PNP_OK;
-}
-
-static int run_loop(pnp_ctx* c, int iters, bool cnc, const ProxParams& pp, double reo) {
-    if (iters < 0) return fail(PNP_E_ARG, "iters must be >= 0");
-    if (!(reo > 0.0)) return fail(PNP_E_ARG, "reo must be > 0");
-    const bool slice_loop = iters > 0 && use_fused(c) && c->slice && c->slice_ready;
-    if (slice_loop) { if (int rt = ensure_slice_tabs(c)) return rt; }
-    if (int rs = state_order(c, slice_loop)) return rs;
-    if (iters == 0) {
-        // the reference's loop body never runs and its x stays the initial x = |ifft2(y)| = z0 (S4:103, 107, 138)
-        HIPCHK(hipMemcpyAsync(c->x, c->z, (size_t)c->B * c->N * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        c->have_x = true;
-        return PNP_OK;
-    }
-    const float cdc = dc_coeff(reo);
-    if (use_fused(c)) {
-        if (c->slice && c->slice_ready) HIPCHK(slice256_run(c->slice, c->stream, c->z, c->w, c->x, c->B, iters, cnc, cdc, pp, c->sched));
-        else if (c->fused)  { const int rt = ensure_fused_tabs(c); if (rt) return rt; HIPCHK(fused256_run(c->fused, c->stream, c->z, c->w, c->x, c->B, iters, cnc, cdc, pp, c->sched)); }
-        else if (c->fs32)   HIPCHK(fused256s_run<float>(c->fs32, c->stream, c->z, c->w, c->x, c->B, iters, cnc, cdc, pp, c->sched));
-        else                HIPCHK(fused512_run(c->fused5, c->stream, c->z, c->w, c->x, c->B, iters, cnc, cdc, pp, c->sched));
-    } else {
-        for (int i = 0; i < iters; ++i) {
-            int rc = generic_iteration(c, c->z, c->w, cnc ? EPI_CNC : EPI_L1, pp, cdc,
-                                       (i == iters - 1) ? c->x : nullptr, c->z, c->w);
-            if (rc) return rc;
-        }
-    }
-    c->have_x = true;
-    return PNP_OK;
-}
+int pnp_get_state(pnp_ctx* c, float* z, float* w, int on_device) { CTX(c); F32_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c); return get_state(c, z, w, on_device); }
+int pnp_get_state_f64(pnp_ctx* c, double* z, double* w, int on_device) { CTX(c); F64_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c); return get_state(c, z, w, on_device); }
 
 // soft(a, thr) is evaluated as a - med3(a, -thr, thr) on the fast paths, which equals the reference's
 // fmax(|a| - thr, 0) * sign(a) (S1:18-19) for thr >= 0 only; the reference's own parameters are all positive.
@@ -643,48 +733,46 @@ static int check_thresholds(const char* who, double alpha, double lambda1, doubl
 int pnp_admm_l1_run(pnp_ctx* c, int iters, double lambda1, double reo) {
     CTX(c); NEED_PROBLEM(c); NEED_STATE(c);
     Range r("pnp_admm_l1_run");
-    if (int rv = check_thresholds("pnp_admm_l1_run", 0.0, lambda1, reo)) return rv;
-    if (c->f64) {
-        if (iters < 0 || !(reo > 0.0)) return fail(PNP_E_ARG, "pnp_admm_l1_run: iters >= 0 and reo > 0 required");
-        ProxParamsT<double> p{}; p.thr = reo * lambda1;
-        return run_loop_f64(c, iters, false, p, reo);
-    }
-    return run_loop(c, iters, false, make_prox_l1(lambda1, reo), reo);
+    if (int rv = check_thresholds(__func__, 0.0, lambda1, reo)) return rv;
+    if (iters < 0) return fail(PNP_E_ARG, "%s: iters must be >= 0", __func__);
+    return c->f64 ? run_loop(c, iters, false, prox_l1<double>(lambda1, reo), reo)
+                  : run_loop(c, iters, false, prox_l1<float>(lambda1, reo), reo);
 }
 
 int pnp_admm_cnc_run(pnp_ctx* c, int iters, double alpha, double lambda1, double reo, double b) {
     CTX(c); NEED_PROBLEM(c); NEED_STATE(c);
     Range r("pnp_admm_cnc_run");
     if (!(b > 0.0)) return fail(PNP_E_ARG, "pnp_admm_cnc_run: b must be > 0");
-    if (int rv = check_thresholds("pnp_admm_cnc_run", alpha, lambda1, reo)) return rv;
-    if (c->f64) {
-        if (iters < 0 || !(reo > 0.0)) return fail(PNP_E_ARG, "pnp_admm_cnc_run: iters >= 0 and reo > 0 required");
-        ProxParamsT<double> p{};
-        p.thr = alpha * reo * lambda1; p.c1 = 1.0 - alpha; p.c2 = alpha; p.c3 = alpha * reo * lambda1 * b; p.ib = 1.0 / b;
-        return run_loop_f64(c, iters, true, p, reo);
-    }
-    return run_loop(c, iters, true, make_prox_cnc(alpha, lambda1, reo, b), reo);
+    if (int rv = check_thresholds(__func__, alpha, lambda1, reo)) return rv;
+    if (iters < 0) return fail(PNP_E_ARG, "%s: iters must be >= 0", __func__);
+    return c->f64 ? run_loop(c, iters, true, prox_cnc<double>(alpha, lambda1, reo, b), reo)
+                  : run_loop(c, iters, true, prox_cnc<float>(alpha, lambda1, reo, b), reo);
 }
 
-int pnp_download_x(pnp_ctx* c, float* x, int on_device) {
-    CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
-    if (!x) return fail(PNP_E_ARG, "pnp_download_x: null");
-    if (!c->have_x) return fail(PNP_E_STATE, "pnp_download_x: no iteration has been run since the state was set");
-    return copy_out(c, x, c->x, (size_t)c->B * c->N * sizeof(float), on_device);
-}
+int pnp_download_x(pnp_ctx* c, float* x, int on_device) { CTX(c); F32_ONLY(c); NEED_PROBLEM(c); return download_x(c, __func__, x, on_device); }
+int pnp_download_x_f64(pnp_ctx* c, double* x, int on_device) { CTX(c); F64_ONLY(c); NEED_PROBLEM(c); return download_x(c, __func__, x, on_device); }
 
 int pnp_dc_step(pnp_ctx* c, const float* z, const float* w, float* x, double reo) {
     CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
     Range r("pnp_dc_step");
     if (!z || !w || !x) return fail(PNP_E_ARG, "pnp_dc_step: null pointer");
     if (!(reo > 0.0)) return fail(PNP_E_ARG, "pnp_dc_step: reo must be > 0");
-    if (use_fused(c)) {
-        if (c->fused)     { const int rt = ensure_fused_tabs(c); if (rt) return rt; HIPCHK(fused256_dc(c->fused, c->stream, z, w, x, c->B, dc_coeff(reo))); }
-        else if (c->fs32) HIPCHK(fused256s_dc<float>(c->fs32, c->stream, z, w, x, c->B, dc_coeff(reo)));
-        else              HIPCHK(fused512_dc(c->fused5, c->stream, z, w, x, c->B, dc_coeff(reo)));
-        return PNP_OK;
+    const float cdc = dc_coeff<float>(reo);
+    switch (loop_path(c)) {
+    case Path::generic:
+        return generic_iteration<float>(c, z, w, EPI_ABS_REAL, ProxParams{}, cdc, x, nullptr, nullptr);
+    case Path::slice:                                  // no single-step form: the step runs on the engine's own tables
+    case Path::fused:
+        break;
     }
-    return generic_iteration(c, z, w, EPI_ABS_REAL, ProxParams{}, dc_coeff(reo), x, nullptr, nullptr);
+    if (int rc = ensure_tables(c, Path::fused)) return rc;
+    switch (c->eng.kind) {
+    case Engine::fused256:  HIPCHK(fused256_dc(c->eng.f256, c->stream, z, w, x, c->B, cdc)); break;
+    case Engine::split_f32: HIPCHK(fused256s_dc<float>(c->eng.s32, c->stream, z, w, x, c->B, cdc)); break;
+    case Engine::fused512:  HIPCHK(fused512_dc(c->eng.f512, c->stream, z, w, x, c->B, cdc)); break;
+    case Engine::none: case Engine::split_f64: break;         // no fast path; a double context
+    }
+    return PNP_OK;
 }
 
 int pnp_prox_l1_dual(pnp_ctx* c, const float* x, float* z, float* w, double thr) {
@@ -701,7 +789,7 @@ int pnp_prox_cnc_dual(pnp_ctx* c, const float* x, float* z, float* w, double alp
     if (!x || !z || !w) return fail(PNP_E_ARG, "pnp_prox_cnc_dual: null pointer");
     if (!(b > 0.0)) return fail(PNP_E_ARG, "pnp_prox_cnc_dual: b must be > 0");
     if (int rv = check_thresholds("pnp_prox_cnc_dual", alpha, lambda1, reo)) return rv;
-    HIPCHK(launch_prox(c->stream, true, x, z, w, make_prox_cnc(alpha, lambda1, reo, b), (size_t)c->B * c->N));
+    HIPCHK(launch_prox(c->stream, true, x, z, w, prox_cnc<float>(alpha, lambda1, reo, b), (size_t)c->B * c->N));
     return PNP_OK;
 }
 
@@ -774,7 +862,7 @@ int pnp_Df(pnp_ctx* c, const float* x, float* out) {
     ra.rin0 = x; ra.cout = (float2*)out; ra.scale = 1.0f; ra.nrows = c->B * c->H;
     HIPCHK(launch_rows(c->stream, c->W, IN_REAL, false, EPI_COMPLEX, ra));
     ColArgs ca{};
-    ca.in = (const float2*)out; ca.out = (float2*)out; ca.y = c->y; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id; ca.B = c->B;
+    ca.in = (const float2*)out; ca.out = (float2*)out; ca.y = bufs<float>(c).y; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id; ca.B = c->B;
     HIPCHK(launch_cols(c->stream, c->H, c->W, true, MID_RESID, true, ca));
     RowArgs rb{};
     rb.cin = (const float2*)out; rb.cout = (float2*)out; rb.scale = 1.0f / (float)c->N; rb.nrows = c->B * c->H;
@@ -782,165 +870,21 @@ int pnp_Df(pnp_ctx* c, const float* x, float* out) {
     return PNP_OK;
 }
 
-}  // extern "C"  (templates have C++ linkage)
-
-template <typename X>
-static int metrics_any(pnp_ctx* c, const X* x, const X* own_x, const uint8_t* gt, int gt_on_device, double* psnr, double* re) {
-    if (!gt || !psnr || !re) return fail(PNP_E_ARG, "pnp_metrics: null pointer");
-    if (!x) {
-        if (!c->have_x) return fail(PNP_E_STATE, "pnp_metrics: x_dev is null and the ctx holds no x yet");
-        x = own_x;
-    }
-    const uint8_t* d_gt = gt;
-    if (!gt_on_device) {
-        if (!c->gt) HIPCHK(hipMalloc((void**)&c->gt, (size_t)c->Bmax * c->N));
-        int rc = copy_in(c, c->gt, gt, (size_t)c->B * c->N, 0);
-        if (rc) return rc;
-        d_gt = c->gt;
-    }
-    HIPCHK(launch_metrics<X>(c->stream, x, d_gt, c->acc, c->B, (int)c->N));
-    std::vector<double> h((size_t)c->B * 2);
-    int rc = copy_out(c, h.data(), c->acc, h.size() * sizeof(double), 0);
-    if (rc) return rc;
-    for (int b = 0; b < c->B; ++b) {
-        const double mse = h[2 * b] / (double)c->N;
-        psnr[b] = (mse == 0.0) ? INFINITY : 20.0 * log10(255.0 / sqrt(mse));
-        re[b] = sqrt(h[2 * b]) / sqrt(h[2 * b + 1]);
-    }
-    return PNP_OK;
-}
-
-template <typename X>
-static int ssim_any(pnp_ctx* c, const X* x, const X* own_x, const uint8_t* gt, int gt_on_device, double* ssim) {
-    if (!gt || !ssim) return fail(PNP_E_ARG, "pnp_ssim: null pointer");
-    if (!x) {
-        if (!c->have_x) return fail(PNP_E_STATE, "pnp_ssim: x_dev is null and the ctx holds no x yet");
-        x = own_x;
-    }
-    const uint8_t* d_gt = gt;
-    if (!gt_on_device) {
-        if (!c->gt) HIPCHK(hipMalloc((void**)&c->gt, (size_t)c->Bmax * c->N));
-        int rc = copy_in(c, c->gt, gt, (size_t)c->B * c->N, 0);
-        if (rc) return rc;
-        d_gt = c->gt;
-    }
-    const int tiles = ((c->W - 10 + 15) / 16) * ((c->H - 10 + 15) / 16);
-    if (!c->ssim_part) HIPCHK(hipMalloc((void**)&c->ssim_part, (size_t)c->Bmax * tiles * sizeof(double)));
-    HIPCHK(launch_ssim<X>(c->stream, x, d_gt, c->ssim_part, c->B, c->H, c->W));
-    std::vector<double> h((size_t)c->B * tiles);
-    int rc = copy_out(c, h.data(), c->ssim_part, h.size() * sizeof(double), 0);
-    if (rc) return rc;
-    const double npix = (double)(c->H - 10) * (double)(c->W - 10);
-    for (int b = 0; b < c->B; ++b) {
-        double s = 0.0;
-        for (int t = 0; t < tiles; ++t) s += h[(size_t)b * tiles + t];
-        ssim[b] = s / npix;
-    }
-    return PNP_OK;
-}
-
-extern "C" {
-
 int pnp_metrics(pnp_ctx* c, const float* x, const uint8_t* gt, int gt_on_device, double* psnr, double* re) {
     CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
-    return metrics_any<float>(c, x, c->x, gt, gt_on_device, psnr, re);
+    return metrics_any<float>(c, x, gt, gt_on_device, psnr, re);
 }
 int pnp_ssim(pnp_ctx* c, const float* x, const uint8_t* gt, int gt_on_device, double* ssim) {
     CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
-    return ssim_any<float>(c, x, c->x, gt, gt_on_device, ssim);
+    return ssim_any<float>(c, x, gt, gt_on_device, ssim);
 }
 int pnp_metrics_f64(pnp_ctx* c, const double* x, const uint8_t* gt, int gt_on_device, double* psnr, double* re) {
     CTX(c); F64_ONLY(c); NEED_PROBLEM(c);
-    return metrics_any<double>(c, x, c->xd, gt, gt_on_device, psnr, re);
+    return metrics_any<double>(c, x, gt, gt_on_device, psnr, re);
 }
 int pnp_ssim_f64(pnp_ctx* c, const double* x, const uint8_t* gt, int gt_on_device, double* ssim) {
     CTX(c); F64_ONLY(c); NEED_PROBLEM(c);
-    return ssim_any<double>(c, x, c->xd, gt, gt_on_device, ssim);
-}
-
-/* ---- fp64 validation context: problem / state / result in double ------------------------- */
-int pnp_upload_problem_f64(pnp_ctx* c, const double* y, const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
-    CTX(c); F64_ONLY(c);
-    if (!y) return fail(PNP_E_ARG, "pnp_upload_problem_f64: y is null");
-    c->have_x = false; c->have_state = false;           // a new problem: z / w undefined until pnp_init_state / pnp_set_state_f64(z, w)
-    int rc = set_masks(c, mask_bank, mask_id, B, K, on_device);
-    if (rc) { c->B = 0; return rc; }
-    rc = copy_in(c, c->yd, y, (size_t)B * c->N * sizeof(double2), on_device);
-    if (rc) { c->B = 0; return rc; }
-    return prepare_fused(c);
-}
-
-// y = fft2(img) * mask + noise in double (S4:102).  The reference's first fft2 runs on the float32 image in complex64
-// (NumPy >= 2) and is promoted by the float64 mask; here the float32 image is widened (exactly) and transformed in double,
-// which is the nearer of the two to the exact transform -- the two y differ by NumPy's own complex64 round-off, ~1e-7.
-int pnp_synthesize_problem_f64(pnp_ctx* c, const float* img, const double* noise, int noise_per_slice,
-                               const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
-    CTX(c); F64_ONLY(c);
-    if (!img || !noise) return fail(PNP_E_ARG, "pnp_synthesize_problem_f64: img/noise is null");
-    c->have_x = false; c->have_state = false;
-    int rc = set_masks(c, mask_bank, mask_id, B, K, on_device);
-    if (rc) { c->B = 0; return rc; }
-    const size_t img_bytes = (size_t)B * c->N * sizeof(float);
-    const size_t noise_bytes = (noise_per_slice ? (size_t)B : 1) * c->N * sizeof(double2);
-    const float* d_img = img;
-    const double2* d_noise = (const double2*)noise;
-    if (!on_device) {
-        const size_t need = img_bytes + noise_bytes;
-        if (need > c->stage_bytes) {
-            c->B = 0;                                   // no valid problem until y has been rebuilt
-            if (c->stage) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->stage)); c->stage = nullptr; c->stage_bytes = 0; }
-            HIPCHK(hipMalloc(&c->stage, need));
-            c->B = B;
-            c->stage_bytes = need;
-        }
-        rc = copy_in(c, (char*)c->stage, noise, noise_bytes, 0); if (rc) { c->B = 0; return rc; }      // doubles first: alignment
-        rc = copy_in(c, (char*)c->stage + noise_bytes, img, img_bytes, 0); if (rc) { c->B = 0; return rc; }
-        d_noise = (const double2*)c->stage;
-        d_img = (const float*)((char*)c->stage + noise_bytes);
-    }
-    HIPCHK(launch_widen(c->stream, d_img, c->xd, (size_t)B * c->N));     // x is invalid until the next run anyway (have_x = false)
-    RowArgsT<double> ra{};
-    ra.rin0 = c->xd; ra.cout = c->yd; ra.scale = 1.0; ra.nrows = B * c->H;
-    HIPCHK(launch_rows<double>(c->stream, c->W, IN_REAL, false, EPI_COMPLEX, ra));
-    ColArgsT<double> ca{};
-    ca.in = c->yd; ca.out = c->yd; ca.y = d_noise; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id;
-    ca.y_per_slice = noise_per_slice; ca.B = B;
-    HIPCHK(launch_cols<double>(c->stream, c->H, c->W, true, MID_MASK_ADD, false, ca));
-    return prepare_fused(c);
-}
-
-int pnp_download_y_f64(pnp_ctx* c, double* y, int on_device) {
-    CTX(c); F64_ONLY(c); NEED_PROBLEM(c);
-    if (!y) return fail(PNP_E_ARG, "pnp_download_y_f64: null");
-    return copy_out(c, y, c->yd, (size_t)c->B * c->N * sizeof(double2), on_device);
-}
-
-int pnp_set_state_f64(pnp_ctx* c, const double* z, const double* w, int on_device) {
-    CTX(c); F64_ONLY(c); NEED_PROBLEM(c);
-    const size_t bytes = (size_t)c->B * c->N * sizeof(double);
-    int rc;
-    if (!(z && w)) NEED_STATE(c);                          // one of the two kept: it must be defined
-    if (z) { rc = copy_in(c, c->zd, z, bytes, on_device); if (rc) return rc; }
-    if (w) { rc = copy_in(c, c->wd, w, bytes, on_device); if (rc) return rc; }
-    c->have_x = false;
-    if (z && w) c->have_state = true;
-    return PNP_OK;
-}
-
-int pnp_get_state_f64(pnp_ctx* c, double* z, double* w, int on_device) {
-    CTX(c); F64_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c);
-    const size_t bytes = (size_t)c->B * c->N * sizeof(double);
-    int rc;
-    if (z) { rc = copy_out(c, z, c->zd, bytes, on_device); if (rc) return rc; }
-    if (w) { rc = copy_out(c, w, c->wd, bytes, on_device); if (rc) return rc; }
-    return PNP_OK;
-}
-
-int pnp_download_x_f64(pnp_ctx* c, double* x, int on_device) {
-    CTX(c); F64_ONLY(c); NEED_PROBLEM(c);
-    if (!x) return fail(PNP_E_ARG, "pnp_download_x_f64: null");
-    if (!c->have_x) return fail(PNP_E_STATE, "pnp_download_x_f64: no iteration has been run since the state was set");
-    return copy_out(c, x, c->xd, (size_t)c->B * c->N * sizeof(double), on_device);
+    return ssim_any<double>(c, x, gt, gt_on_device, ssim);
 }
 
 int pnp_is_f64(pnp_ctx* c) { return (c && c->f64) ? 1 : 0; }
@@ -1091,45 +1035,27 @@ int pnp_timer_stop(pnp_ctx* c, float* ms) {
 // Build now whatever per-problem tables the loops (pnp_admm_*_run) of the uploaded problem will use; they are otherwise built
 // by the first loop call (256x256 float contexts only -- every other path prepares at upload).  Benchmarks call it so that a
 // timed region with no warm-up holds iterations only.
-int pnp_prepare_loops(pnp_ctx* c) {
-    CTX(c); NEED_PROBLEM(c);
-    if (!c->fused || !use_fused(c)) return PNP_OK;
-    if (c->slice && c->slice_ready) return ensure_slice_tabs(c);
-    return ensure_fused_tabs(c);
-}
+int pnp_prepare_loops(pnp_ctx* c) { CTX(c); NEED_PROBLEM(c); return ensure_tables(c, loop_path(c)); }
 
 int pnp_get_plan(pnp_ctx* c, int* queues, int* chunk, int* launches_per_iteration) {
     CTX(c);
-    int q = 1, ch = c->B;
-    if (use_fused(c) && !(c->slice && c->slice_ready)) {
-        if (c->fs32 || c->fs64 || c->fused5) {
-            const ChunkPlan p = chunk_plan(c->B, c->sched, c->fused5 != nullptr, c->fs64 != nullptr, c->sched.chunk_queues);
-            q = p.queues; ch = p.chunk < c->B ? p.chunk : c->B;
-        } else if (c->sched.chunk > 0) {
-            ch = c->sched.chunk < c->B ? c->sched.chunk : c->B;
-        } else if (c->sched.queues >= 2 && c->B >= 32 * c->sched.queues) {
-            q = c->sched.queues;
-        }
-    }
-    if (queues) *queues = q;
-    if (chunk) *chunk = ch;
-    if (launches_per_iteration) *launches_per_iteration = pnp_kernels_per_iteration(c);
+    const LoopPlan p = loop_plan(c);
+    if (queues) *queues = p.queues;
+    if (chunk) *chunk = p.chunk;
+    if (launches_per_iteration) *launches_per_iteration = p.launches;
     return PNP_OK;
 }
 
-int pnp_kernels_per_iteration(pnp_ctx* c) {
-    if (!c) return 0;
-    if (!use_fused(c)) return 3;                      // generic: rows, columns, rows
-    if (c->slice && c->slice_ready) return 0;         // one launch per RUN: the iterations are a loop inside it
-    if (c->fs32 || c->fs64 || c->fused5) {               // chunked round-robin schedules: two launches per chunk
-        return chunk_plan_launches(c->B, chunk_plan(c->B, c->sched, c->fused5 != nullptr, c->fs64 != nullptr, c->sched.chunk_queues));
-    }
-    const int q = (c->sched.chunk > 0 || c->sched.queues < 2 || c->B < 32 * c->sched.queues) ? 1 : c->sched.queues;
-    return 2 * q;                                     // two launches per queue and batched iteration
-}
+int pnp_kernels_per_iteration(pnp_ctx* c) { return c ? loop_plan(c).launches : 0; }
+
 const char* pnp_path_name(pnp_ctx* c) {
-    if (!c || !use_fused(c)) return "generic";
-    return (c->slice && c->slice_ready) ? "slice" : "fused";
+    if (!c) return "generic";
+    switch (loop_path(c)) {
+    case Path::generic: return "generic";
+    case Path::slice:   return "slice";
+    case Path::fused:   return "fused";
+    }
+    return "generic";
 }
 
 }  // extern "C"

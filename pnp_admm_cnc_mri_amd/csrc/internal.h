@@ -148,6 +148,15 @@ static inline ChunkPlan chunk_plan(int B, const FusedSchedule& sch, bool is512, 
 }
 static inline int chunk_plan_launches(int B, const ChunkPlan& p) { return 2 * ((B + p.chunk - 1) / p.chunk); }
 
+// The schedule fused256_run gives a batch of B slices -- the run follows it and pnp_get_plan reports it.
+struct Fused256Plan {
+    int queues;     // parts of the batch, one per HIP queue (1: the whole batch on the caller's queue)
+    int chunk;      // slices per sequential chunk (B: one chunk)
+    int launches;   // kernel launches per iteration
+    bool mixed;     // parts of at least 64 slices take the staggered mixed launches (k_fmixed)
+};
+Fused256Plan fused256_plan(int B, const FusedSchedule& sch);
+
 // fused 256x256 path (kernels_fused256.hip): state resident in the ctx, two slices packed into
 // one complex transform.  See DESIGN.md.
 struct Fused256;

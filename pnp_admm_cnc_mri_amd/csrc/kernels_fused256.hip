@@ -504,14 +504,24 @@ static hipError_t run_mixed(Fused256* f, hipStream_t s, float* z, float* w, floa
 // Slices are independent, so the K-iteration chains of different parts of the batch may run on
 // different queues, share launches (run_mixed) or run one chunk after another (chunk*(z,w,T,Yh)
 // <= the 256 MiB Infinity Cache keeps a chunk's working set on die; measured +-2 %).
+Fused256Plan fused256_plan(int B, const FusedSchedule& sch) {
+    const int queues = sch.queues < 1 ? 1 : (sch.queues > Fused256::MAXQ ? Fused256::MAXQ : sch.queues);
+    if (sch.chunk > 0) {                                                  // one queue, one chunk after another
+        const int chunk = (sch.chunk & ~1) < 2 ? 2 : (sch.chunk & ~1);
+        if (chunk < B) return {1, chunk, 2 * ((B + chunk - 1) / chunk), false};
+        return {1, B, 2, false};
+    }
+    if (queues >= 2 && B >= 32 * queues) return {queues, B, 2 * queues, sch.mixed != 0};
+    return {1, B, 2, queues == 1 && sch.mixed != 0};
+}
+
 hipError_t fused256_run(Fused256* f, hipStream_t s, float* z, float* w, float* x, int B, int iters, bool cnc,
                         float dc_c, ProxParams pp, const FusedSchedule& sch) {
     if (iters <= 0) return hipSuccess;
     const int prox = cnc ? 2 : (sch.l1_two_state ? 1 : 3);
-    int queues = sch.queues < 1 ? 1 : (sch.queues > Fused256::MAXQ ? Fused256::MAXQ : sch.queues);
-    if (sch.chunk > 0) queues = 1;
-    if (queues == 1 && sch.chunk <= 0 && sch.mixed && B >= 64) return run_mixed(f, s, z, w, x, 0, B, iters, prox, dc_c, pp);
-    if (queues >= 2 && B >= 32 * queues) {
+    const Fused256Plan plan = fused256_plan(B, sch);
+    if (plan.queues >= 2) {
+        const int queues = plan.queues;
         hipError_t e = hipSuccess;
         if (!f->ev_fork) e = hipEventCreateWithFlags(&f->ev_fork, hipEventDisableTiming);
         for (int q = 0; q < queues - 1 && e == hipSuccess; ++q) {
@@ -526,19 +536,18 @@ hipError_t fused256_run(Fused256* f, hipStream_t s, float* z, float* w, float* x
             const int Bq = (q == queues - 1) ? (B - c0) : (((B / queues) + 1) & ~1);     // even-sized parts
             hipStream_t sq = (q == 0) ? s : f->side[q - 1];
             if (q > 0) e = hipStreamWaitEvent(sq, f->ev_fork, 0);
-            if (e == hipSuccess) e = (sch.mixed && Bq >= 64) ? run_mixed(f, sq, z, w, x, c0, Bq, iters, prox, dc_c, pp)
-                                                              : run_chunk(f, sq, z, w, x, c0, Bq, iters, prox, dc_c, pp);
+            if (e == hipSuccess) e = (plan.mixed && Bq >= 64) ? run_mixed(f, sq, z, w, x, c0, Bq, iters, prox, dc_c, pp)
+                                                               : run_chunk(f, sq, z, w, x, c0, Bq, iters, prox, dc_c, pp);
             if (q > 0 && e == hipSuccess) e = hipEventRecord(f->ev_join[q - 1], sq);
             if (q > 0 && e == hipSuccess) e = hipStreamWaitEvent(s, f->ev_join[q - 1], 0);
             c0 += Bq;
         }
         return e;
     }
-    int chunk = sch.chunk > 0 ? (sch.chunk & ~1) : B;
-    if (chunk < 2) chunk = 2;
+    if (plan.mixed && B >= 64) return run_mixed(f, s, z, w, x, 0, B, iters, prox, dc_c, pp);
     hipError_t e = hipSuccess;
-    for (int c0 = 0; c0 < B && e == hipSuccess; c0 += chunk)
-        e = run_chunk(f, s, z, w, x, c0, (B - c0 < chunk) ? (B - c0) : chunk, iters, prox, dc_c, pp);
+    for (int c0 = 0; c0 < B && e == hipSuccess; c0 += plan.chunk)
+        e = run_chunk(f, s, z, w, x, c0, (B - c0 < plan.chunk) ? (B - c0) : plan.chunk, iters, prox, dc_c, pp);
     return e;
 }
 

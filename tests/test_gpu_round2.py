@@ -494,6 +494,8 @@ def test_plan_reports_what_the_loops_will_do(env):
         assert eng.path_name == 'slice' and eng.plan == {'queues': 1, 'chunk': 512, 'launches_per_iteration': 0}
         eng.upload(np.zeros((40, 256, 256), np.complex64), mask)
         assert eng.path_name == 'fused' and eng.plan['launches_per_iteration'] == 2 * eng.plan['queues']
+        eng.set_schedule(queues=1, mixed_launches=False, chunk=15)      # sequential chunks of 14 slices (even): 14 + 14 + 12
+        assert eng.plan == {'queues': 1, 'chunk': 14, 'launches_per_iteration': 6}
     with P.Engine(512, 512, Bmax=64) as eng:
         eng.upload(np.zeros((52, 512, 512), np.complex64), np.ones((512, 512), np.uint8))
         assert eng.plan == {'queues': 4, 'chunk': 16, 'launches_per_iteration': 8}

@@ -22,7 +22,10 @@
  *   - one ctx per device per host thread; a ctx is not re-entrant.
  *   - hyper-parameters (alpha, lambda1, reo, b, thresholds) are C doubles, as the Python floats of
  *     the reference are; derived coefficients are formed in double and rounded to float once.
- *   - H, W in {256, 512}.  B <= Bmax.
+ *   - H, W in {256, 512} (pnp_ctx_create[_f64]), or both in [128, 1024] (pnp_ctx_create_any[_f64], since ABI 12).
+ *     B <= Bmax.  256x256 and 512x512 keep their fast paths; every other shape of an any-size context runs the generic
+ *     three-launch iteration on the any-size FFT kernels: mixed-radix (2, 3, 4, 5, 7) Stockham transforms for 7-smooth
+ *     lengths, Bluestein (a power-of-two convolution of length <= 2048) for the rest (pnp_ctx_path, pnp_fft_plan).
  */
 #ifndef PNP_MRI_H
 #define PNP_MRI_H
@@ -39,7 +42,7 @@ extern "C" {
 #define PNP_E_STATE      -3   /* call order (e.g. run before upload)        */
 #define PNP_E_NOMEM      -4
 
-#define PNP_ABI_VERSION   11
+#define PNP_ABI_VERSION   12
 
 typedef struct pnp_ctx pnp_ctx;
 
@@ -181,6 +184,10 @@ int pnp_ssim(pnp_ctx* ctx, const float* x_dev, const uint8_t* gt, int gt_on_devi
  * ADMM_L1 / ADMM_CNC (precision='f64') run the reference's own arithmetic end to end; the step-wise / operator entry points
  * (PnP path: the reference itself switches to float32 there, S6:273-285) are float-only and return PNP_E_STATE on such a context. */
 int pnp_ctx_create_f64(int device, int H, int W, int Bmax, pnp_ctx** out);
+/* The same two creations for any H, W in [128, 1024] (since ABI 12); shapes in {256, 512}^2 get exactly the context the calls
+ * above make.  Outside the range: PNP_E_ARG. */
+int pnp_ctx_create_any(int device, int H, int W, int Bmax, pnp_ctx** out);
+int pnp_ctx_create_any_f64(int device, int H, int W, int Bmax, pnp_ctx** out);
 /* y: [B][H][W] complex128 (interleaved doubles); masks as pnp_upload_problem. */
 int pnp_upload_problem_f64(pnp_ctx* ctx, const double* y, const uint8_t* mask_bank,
                            const int32_t* mask_id, int B, int K, int on_device);
@@ -304,9 +311,15 @@ int pnp_timer_stop(pnp_ctx* ctx, float* elapsed_ms);    /* records, synchronises
  * loop inside ONE launch), and which kernel family the loops take for the uploaded problem:
  *   "slice"   256x256 float, batches of >= 64 slices: one workgroup keeps a slice in registers for the whole run
  *   "fused"   two launches per iteration (256x256 float / double, 512x512 float)
- *   "generic" three launches per iteration (any H, W in {256, 512}; pnp_set_fast_path(ctx, 0)) */
+ *   "generic" three launches per iteration (any H, W; pnp_set_fast_path(ctx, 0)) */
 int         pnp_kernels_per_iteration(pnp_ctx* ctx);
 const char* pnp_path_name(pnp_ctx* ctx);
+/* Which kernels a context runs on, fixed at creation: "anysize" (H, W not both in {256, 512}: the any-size FFT kernels,
+ * generic iteration) or, for the fixed-size kernels, pnp_path_name's answer. */
+const char* pnp_ctx_path(pnp_ctx* ctx);
+/* The transform plan of one axis (0 = rows, length W; 1 = columns, length H) as text, e.g. "stockham 320 = 4*4*4*5",
+ * "bluestein 218 -> 512 = 4*4*4*4*2", or "fixed 256" for the fixed-size kernels.  buf gets at most len bytes, NUL included. */
+int         pnp_fft_plan(pnp_ctx* ctx, int axis, char* buf, int len);
 
 #ifdef __cplusplus
 }

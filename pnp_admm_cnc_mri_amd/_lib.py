@@ -55,6 +55,8 @@ SIGNATURES = {
     'pnp_Df': (C.c_int, [ctx_p, _vp, _vp]),
     'pnp_metrics': (C.c_int, [ctx_p, _vp, _vp, C.c_int, c_double_p, c_double_p]),
     'pnp_ctx_create_f64': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ctx_p)]),
+    'pnp_ctx_create_any': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ctx_p)]),
+    'pnp_ctx_create_any_f64': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ctx_p)]),
     'pnp_upload_problem_f64': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
     'pnp_set_state_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
     'pnp_get_state_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
@@ -88,9 +90,11 @@ SIGNATURES = {
     'pnp_timer_stop': (C.c_int, [ctx_p, c_float_p]),
     'pnp_kernels_per_iteration': (C.c_int, [ctx_p]),
     'pnp_path_name': (C.c_char_p, [ctx_p]),
+    'pnp_ctx_path': (C.c_char_p, [ctx_p]),
+    'pnp_fft_plan': (C.c_int, [ctx_p, C.c_int, C.c_char_p, C.c_int]),
 }
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 _lib = None
 
 

@@ -58,7 +58,7 @@ struct Range {
 }  // namespace
 
 // The context's fast path, chosen at creation by shape, precision and PNP_FUSED_COLS, and beside it the slice-resident add-on of the
-// 256x256 float engine.  No engine (512x512 double, H != W): the generic kernels only.
+// 256x256 float engine.  No engine (512x512 double, H != W, any other size): the generic kernels only.
 struct Engine {
     enum Kind { none, fused256, split_f32, split_f64, fused512 } kind = none;
     union {
@@ -104,6 +104,7 @@ struct pnp_ctx {
     size_t stage_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     Engine eng;
+    AnySize* any = nullptr;           // H, W not both in {256, 512}: the row / column transforms run on the any-size kernels
     Problem prob;
     FusedSchedule sched;              // defaults overridable by PNP_FUSED_* (read at creation) / pnp_set_schedule
 };
@@ -120,6 +121,14 @@ template <typename R> static Bufs<R> bufs(const pnp_ctx* c) {
 }
 
 static bool supported(int n) { return n == 256 || n == 512; }
+
+// The row and column roles of the generic path: the fixed-size kernels for H, W in {256, 512}, the any-size kernels otherwise.
+template <typename R> static hipError_t rows(const pnp_ctx* c, RowIn in, bool inv, RowEpi epi, const RowArgsT<R>& a) {
+    return c->any ? anysize_rows<R>(c->any, c->stream, in, inv, epi, a) : launch_rows<R>(c->stream, c->W, in, inv, epi, a);
+}
+template <typename R> static hipError_t cols(const pnp_ctx* c, bool pre_fwd, ColMid mid, bool post_inv, const ColArgsT<R>& a) {
+    return c->any ? anysize_cols<R>(c->any, c->stream, pre_fwd, mid, post_inv, a) : launch_cols<R>(c->stream, c->H, c->W, pre_fwd, mid, post_inv, a);
+}
 
 // Environment knobs: read ONCE per context (pnp_ctx_create), whole-string integers, range-checked -- a stray or mistyped
 // variable fails the creation with PNP_E_ARG instead of silently changing which kernel a caller gets.
@@ -341,11 +350,11 @@ static int synthesize_y(pnp_ctx* c, const float* img, const R* noise, int noise_
         ra.rin0 = d_img;
     }
     ra.cout = b.y; ra.scale = 1; ra.nrows = B * c->H;
-    HIPCHK(launch_rows<R>(c->stream, c->W, IN_REAL, false, EPI_COMPLEX, ra));
+    HIPCHK(rows<R>(c, IN_REAL, false, EPI_COMPLEX, ra));
     ColArgsT<R> ca{};
     ca.in = b.y; ca.out = b.y; ca.y = d_noise; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id;
     ca.y_per_slice = noise_per_slice; ca.B = B;
-    HIPCHK(launch_cols<R>(c->stream, c->H, c->W, true, MID_MASK_ADD, false, ca));
+    HIPCHK(cols<R>(c, true, MID_MASK_ADD, false, ca));
     return PNP_OK;
 }
 
@@ -375,10 +384,10 @@ template <typename R> static int init_state(pnp_ctx* c) {
     c->state_sliced = false;                           // both arrays are rewritten below, in natural order
     ColArgsT<R> ca{};
     ca.in = b.y; ca.out = b.work; ca.B = c->B;
-    HIPCHK(launch_cols<R>(c->stream, c->H, c->W, false, MID_NONE, true, ca));
+    HIPCHK(cols<R>(c, false, MID_NONE, true, ca));
     RowArgsT<R> ra{};
     ra.cin = b.work; ra.x_out = b.z; ra.scale = (R)1 / (R)c->N; ra.nrows = c->B * c->H;
-    HIPCHK(launch_rows<R>(c->stream, c->W, IN_COMPLEX, true, EPI_ABS_COMPLEX, ra));
+    HIPCHK(rows<R>(c, IN_COMPLEX, true, EPI_ABS_COMPLEX, ra));
     HIPCHK(hipMemsetAsync(b.w, 0, (size_t)c->B * c->N * sizeof(R), c->stream));
     c->have_x = false;
     c->have_state = true;
@@ -414,15 +423,15 @@ static int generic_iteration(pnp_ctx* c, const R* z_in, const R* w_in, RowEpi ep
     const Bufs<R> b = bufs<R>(c);
     RowArgsT<R> ra{};
     ra.rin0 = z_in; ra.rin1 = w_in; ra.cout = b.work; ra.scale = 1; ra.nrows = c->B * c->H;
-    HIPCHK(launch_rows<R>(c->stream, c->W, IN_REAL_DIFF, false, EPI_COMPLEX, ra));
+    HIPCHK(rows<R>(c, IN_REAL_DIFF, false, EPI_COMPLEX, ra));
     ColArgsT<R> ca{};
     ca.in = b.work; ca.out = b.work; ca.y = b.y; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id;
     ca.c = cdc; ca.B = c->B;
-    HIPCHK(launch_cols<R>(c->stream, c->H, c->W, true, MID_BLEND, true, ca));
+    HIPCHK(cols<R>(c, true, MID_BLEND, true, ca));
     RowArgsT<R> rb{};
     rb.cin = b.work; rb.x_out = x_out; rb.z = z_io; rb.w = w_io; rb.scale = (R)1 / (R)c->N;
     rb.prox = pp; rb.nrows = c->B * c->H;
-    HIPCHK(launch_rows<R>(c->stream, c->W, IN_COMPLEX, true, epi, rb));
+    HIPCHK(rows<R>(c, IN_COMPLEX, true, epi, rb));
     return PNP_OK;
 }
 
@@ -595,10 +604,14 @@ int pnp_calibrate_stream(int device, int slices, double seconds, double* gbs) {
     return rc;
 }
 
-static int ctx_create_any(int device, int H, int W, int Bmax, pnp_ctx** out, bool f64) {
+// any_size: pnp_ctx_create_any[_f64] -- H, W in [128, 1024]; pnp_ctx_create[_f64] keep their contract of H, W in {256, 512}
+static int ctx_create_impl(int device, int H, int W, int Bmax, pnp_ctx** out, bool f64, bool any_size) {
     if (!out) return fail(PNP_E_ARG, "pnp_ctx_create: out is null");
     *out = nullptr;
-    if (!supported(H) || !supported(W)) return fail(PNP_E_ARG, "pnp_ctx_create: H, W must be 256 or 512 (got %dx%d)", H, W);
+    const bool fixed = supported(H) && supported(W);
+    if (!any_size && !fixed) return fail(PNP_E_ARG, "pnp_ctx_create: H, W must be 256 or 512 (got %dx%d; pnp_ctx_create_any takes 128..1024)", H, W);
+    if (!fixed && !(anysize_supported(H) && anysize_supported(W)))
+        return fail(PNP_E_ARG, "pnp_ctx_create_any: H, W must be 256 or 512, or both in [128, 1024] (got %dx%d)", H, W);
     if (Bmax < 1) return fail(PNP_E_ARG, "pnp_ctx_create: Bmax must be >= 1");
     Knobs kn;
     FusedSchedule sched0;
@@ -619,6 +632,7 @@ static int ctx_create_any(int device, int H, int W, int Bmax, pnp_ctx** out, boo
     if (e == hipSuccess) e = hipEventCreate(&c->ev1);
     if (e == hipSuccess) e = upload_twiddles();
     if (e == hipSuccess) e = upload_gauss();
+    if (e == hipSuccess && !fixed) c->any = anysize_create(H, W, f64, &e);
     if (e != hipSuccess) {
         pnp_ctx_destroy(c);
         return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "pnp_ctx_create: %s", hipGetErrorString(e));
@@ -655,8 +669,10 @@ static int ctx_create_any(int device, int H, int W, int Bmax, pnp_ctx** out, boo
     return PNP_OK;
 }
 
-int pnp_ctx_create(int device, int H, int W, int Bmax, pnp_ctx** out) { return ctx_create_any(device, H, W, Bmax, out, false); }
-int pnp_ctx_create_f64(int device, int H, int W, int Bmax, pnp_ctx** out) { return ctx_create_any(device, H, W, Bmax, out, true); }
+int pnp_ctx_create(int device, int H, int W, int Bmax, pnp_ctx** out) { return ctx_create_impl(device, H, W, Bmax, out, false, false); }
+int pnp_ctx_create_f64(int device, int H, int W, int Bmax, pnp_ctx** out) { return ctx_create_impl(device, H, W, Bmax, out, true, false); }
+int pnp_ctx_create_any(int device, int H, int W, int Bmax, pnp_ctx** out) { return ctx_create_impl(device, H, W, Bmax, out, false, true); }
+int pnp_ctx_create_any_f64(int device, int H, int W, int Bmax, pnp_ctx** out) { return ctx_create_impl(device, H, W, Bmax, out, true, true); }
 
 int pnp_ctx_destroy(pnp_ctx* c) {
     if (!c) return PNP_OK;
@@ -669,6 +685,7 @@ int pnp_ctx_destroy(pnp_ctx* c) {
     case Engine::fused512:  fused512_destroy(c->eng.f512); break;
     }
     slice256_destroy(c->eng.slice);
+    anysize_destroy(c->any);
     void* ptrs[] = {c->y, c->work, c->z, c->w, c->x, c->mask_bank, c->mask_id, c->gt, c->acc, c->stage, c->ssim_part};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -821,10 +838,10 @@ static int fft2_any(pnp_ctx* c, const float* in, float* out, int B, bool inv) {
     if (B < 1 || B > c->Bmax) return fail(PNP_E_ARG, "fft2: B=%d out of range [1,%d]", B, c->Bmax);
     RowArgs ra{};
     ra.cin = (const float2*)in; ra.cout = (float2*)out; ra.scale = inv ? 1.0f / (float)c->N : 1.0f; ra.nrows = B * c->H;
-    HIPCHK(launch_rows(c->stream, c->W, IN_COMPLEX, inv, EPI_COMPLEX, ra));
+    HIPCHK(rows<float>(c, IN_COMPLEX, inv, EPI_COMPLEX, ra));
     ColArgs ca{};
     ca.in = (const float2*)out; ca.out = (float2*)out; ca.B = B;
-    HIPCHK(launch_cols(c->stream, c->H, c->W, !inv, MID_NONE, inv, ca));
+    HIPCHK(cols<float>(c, !inv, MID_NONE, inv, ca));
     return PNP_OK;
 }
 
@@ -836,10 +853,10 @@ int pnp_A(pnp_ctx* c, const float* x, float* k) {
     if (!x || !k) return fail(PNP_E_ARG, "pnp_A: null pointer");
     RowArgs ra{};
     ra.rin0 = x; ra.cout = (float2*)k; ra.scale = 1.0f; ra.nrows = c->B * c->H;
-    HIPCHK(launch_rows(c->stream, c->W, IN_REAL, false, EPI_COMPLEX, ra));
+    HIPCHK(rows<float>(c, IN_REAL, false, EPI_COMPLEX, ra));
     ColArgs ca{};
     ca.in = (const float2*)k; ca.out = (float2*)k; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id; ca.B = c->B;
-    HIPCHK(launch_cols(c->stream, c->H, c->W, true, MID_MASK, false, ca));
+    HIPCHK(cols<float>(c, true, MID_MASK, false, ca));
     return PNP_OK;
 }
 
@@ -848,10 +865,10 @@ int pnp_AH(pnp_ctx* c, const float* k, float* out) {
     if (!k || !out) return fail(PNP_E_ARG, "pnp_AH: null pointer");
     ColArgs ca{};
     ca.in = (const float2*)k; ca.out = (float2*)out; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id; ca.B = c->B;
-    HIPCHK(launch_cols(c->stream, c->H, c->W, false, MID_MASK, true, ca));
+    HIPCHK(cols<float>(c, false, MID_MASK, true, ca));
     RowArgs ra{};
     ra.cin = (const float2*)out; ra.cout = (float2*)out; ra.scale = 1.0f / (float)c->N; ra.nrows = c->B * c->H;
-    HIPCHK(launch_rows(c->stream, c->W, IN_COMPLEX, true, EPI_COMPLEX, ra));
+    HIPCHK(rows<float>(c, IN_COMPLEX, true, EPI_COMPLEX, ra));
     return PNP_OK;
 }
 
@@ -860,13 +877,13 @@ int pnp_Df(pnp_ctx* c, const float* x, float* out) {
     if (!x || !out) return fail(PNP_E_ARG, "pnp_Df: null pointer");
     RowArgs ra{};
     ra.rin0 = x; ra.cout = (float2*)out; ra.scale = 1.0f; ra.nrows = c->B * c->H;
-    HIPCHK(launch_rows(c->stream, c->W, IN_REAL, false, EPI_COMPLEX, ra));
+    HIPCHK(rows<float>(c, IN_REAL, false, EPI_COMPLEX, ra));
     ColArgs ca{};
     ca.in = (const float2*)out; ca.out = (float2*)out; ca.y = bufs<float>(c).y; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id; ca.B = c->B;
-    HIPCHK(launch_cols(c->stream, c->H, c->W, true, MID_RESID, true, ca));
+    HIPCHK(cols<float>(c, true, MID_RESID, true, ca));
     RowArgs rb{};
     rb.cin = (const float2*)out; rb.cout = (float2*)out; rb.scale = 1.0f / (float)c->N; rb.nrows = c->B * c->H;
-    HIPCHK(launch_rows(c->stream, c->W, IN_COMPLEX, true, EPI_COMPLEX, rb));
+    HIPCHK(rows<float>(c, IN_COMPLEX, true, EPI_COMPLEX, rb));
     return PNP_OK;
 }
 
@@ -1047,6 +1064,18 @@ int pnp_get_plan(pnp_ctx* c, int* queues, int* chunk, int* launches_per_iteratio
 }
 
 int pnp_kernels_per_iteration(pnp_ctx* c) { return c ? loop_plan(c).launches : 0; }
+
+const char* pnp_ctx_path(pnp_ctx* c) {
+    if (c && c->any) return "anysize";
+    return pnp_path_name(c);
+}
+
+int pnp_fft_plan(pnp_ctx* c, int axis, char* buf, int len) {
+    if (!c || !buf || len < 1 || axis < 0 || axis > 1) return fail(PNP_E_ARG, "pnp_fft_plan: ctx / buf null, len < 1 or axis not 0 or 1");
+    if (c->any) { anysize_describe(c->any, axis, buf, len); return PNP_OK; }
+    snprintf(buf, (size_t)len, "fixed %d", axis == 0 ? c->W : c->H);
+    return PNP_OK;
+}
 
 const char* pnp_path_name(pnp_ctx* c) {
     if (!c) return "generic";

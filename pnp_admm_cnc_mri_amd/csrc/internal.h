@@ -62,6 +62,16 @@ template <typename R> hipError_t launch_rows(hipStream_t s, int W, RowIn in, boo
 template <typename R> hipError_t launch_cols(hipStream_t s, int H, int W, bool pre_fwd, ColMid mid, bool post_inv, const ColArgsT<R>& a);
 hipError_t upload_twiddles();       // fills the __device__ tables of the current device
 
+// any-size path (kernels_anysize.hip): H, W in [128, 1024], the same roles and epilogues as launch_rows / launch_cols; plan and
+// twiddle / chirp tables owned by the context (anysize_plan.h), in the context's precision
+struct AnySize;
+bool       anysize_supported(int n);
+AnySize*   anysize_create(int H, int W, bool f64, hipError_t* err);
+void       anysize_destroy(AnySize*);
+int        anysize_describe(const AnySize*, int axis /* 0 rows (W), 1 columns (H) */, char* buf, int len);
+template <typename R> hipError_t anysize_rows(const AnySize*, hipStream_t s, RowIn in, bool inv, RowEpi epi, const RowArgsT<R>& a);
+template <typename R> hipError_t anysize_cols(const AnySize*, hipStream_t s, bool pre_fwd, ColMid mid, bool post_inv, const ColArgsT<R>& a);
+
 // pointwise
 hipError_t launch_prox(hipStream_t s, bool cnc, const float* x, float* z, float* w, ProxParams p, size_t n);
 hipError_t launch_combine(hipStream_t s, const float* z, const float* x, const float* w, const float* sden,
@@ -71,7 +81,7 @@ hipError_t launch_dual_clamp(hipStream_t s, float* x, float* z, float* w, size_t
 template <typename X> hipError_t launch_metrics(hipStream_t s, const X* x, const uint8_t* gt, double* acc /*[B][2]*/, int B, int N);
 hipError_t upload_gauss();
 template <typename X> hipError_t launch_ssim(hipStream_t s, const X* x, const uint8_t* gt, double* partial /*[B][tiles]*/, int B, int H, int W);
-hipError_t launch_widen(hipStream_t s, const float* in, double* out, size_t n);      // float -> double, n % 4 == 0
+hipError_t launch_widen(hipStream_t s, const float* in, double* out, size_t n);      // float -> double
 
 // calibration (pnp_calibrate_stream): the slice-resident loop's access shape without its arithmetic, `passes` passes over `slices` slices of 256 KiB
 hipError_t launch_calibrate_stream(hipStream_t s, float* z, float* w, const float* y, int slices, int passes);

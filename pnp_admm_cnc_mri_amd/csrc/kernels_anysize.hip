@@ -1,0 +1,364 @@
+// Any-size c2c kernels of libpnpmri.so for gfx950: H, W in [128, 1024], float and double.
+//
+// The same row / column roles as launch_rows / launch_cols (kernels_generic.hip), with the same RowIn / RowEpi / ColMid
+// epilogues, for every slice shape outside {256, 512}^2: the generic loop body of api.hip drives them unchanged.  Plan,
+// tables and butterflies: anysize_plan.h (7-smooth lengths: mixed-radix Stockham; others: Bluestein over a power of two).
+//
+//   rows   : G rows per 256-thread workgroup, each row a line of LDS (pitch m + 1), both ping-pong buffers in LDS
+//   columns: a tile of G columns x H rows, transposed into LDS on load (pitch m + 1, odd: the transposing writes of
+//            consecutive columns fall in distinct banks); global accesses are G-element row segments
+// G is chosen per axis on the host so that a workgroup holds about 40 KiB of LDS (16 lines at most, 1 at least: a
+// Bluestein line of m = 2048 in double takes 64 KiB).  Every stage is one pass of all 256 threads over the G lines'
+// butterflies and ends in a workgroup barrier.  Twiddles, chirp and the Bluestein kernel spectrum are device tables owned by
+// the context (fp64-generated, rounded once to float for a float context), read through the caches.
+//
+// Not a fast path: the iteration runs the three launches of the generic loop (rows, columns, rows) at any size.
+#include "internal.h"
+#include "anysize_plan.h"
+#include "prox_ops.h"
+#include <string.h>
+#include <atomic>
+#include <vector>
+
+namespace pnp {
+
+using anysize::Plan;
+
+// one axis of a context, as the kernels see it
+template <typename R> struct AxisT {
+    using C = typename CxOf<R>::type;
+    Plan plan;
+    const C* tw;        // [m]  W_m^i
+    const C* chirp;     // [n]  w_j (Bluestein only)
+    const C* kern;      // [m]  FFT_m(conj chirp) / m (Bluestein only)
+    int lines;          // G: lines per workgroup
+    int pitch;          // LDS complex elements per line (m + 1)
+};
+
+struct AnySize {
+    bool f64 = false;
+    Plan plan[2];               // [0] rows (length W), [1] columns (length H)
+    void* table[2] = {};        // per axis: tw [m], chirp [n], kern [m] in the context's precision
+    int lines[2] = {};
+};
+
+constexpr int ANY_THREADS = 256;
+constexpr size_t ANY_LDS_TARGET = 40 * 1024;        // per workgroup: four workgroups per compute unit for the float lines
+constexpr size_t ANY_LDS_MAX = 96 * 1024;           // bounds what any configuration needs (the most: one double Bluestein line, 64 KiB + 32 B)
+
+template <typename R> static size_t any_lds(const AxisT<R>& t) { return 2 * sizeof(typename CxOf<R>::type) * (size_t)t.lines * t.pitch; }
+
+// ---- the line transform: G lines of LDS, unnormalised, forward or inverse ----
+
+template <bool INV, typename C>
+__device__ __forceinline__ C* stockham_lines(C* a, C* b, int G, int pitch, const Plan& pl, const C* tw) {
+    const int L = pl.m;
+    int Ns = 1;
+    for (int s = 0; s < pl.nstages; ++s) {
+        const int r = pl.radix[s], nb = L / r, total = G * nb;
+        for (int i = threadIdx.x; i < total; i += ANY_THREADS) {
+            const int g = i / nb, j = i - g * nb;
+            anysize::stockham_bfly_r<INV>(r, a + g * pitch, b + g * pitch, tw, L, Ns, j);
+        }
+        __syncthreads();
+        C* t = a; a = b; b = t;
+        Ns *= r;
+    }
+    return a;
+}
+
+// a: G lines holding n values each; b: scratch.  Returns the buffer holding the n results of every line.
+// Bluestein: chirp, forward m-point transform, times the kernel spectrum, inverse m-point transform, chirp.  The inverse
+// transform is conj(forward(conj(x))): the conjugations ride on the two chirp passes.
+template <bool INV, typename R>
+__device__ __forceinline__ typename CxOf<R>::type* line_fft(typename CxOf<R>::type* a, typename CxOf<R>::type* b, const AxisT<R>& t) {
+    using C = typename CxOf<R>::type;
+    using anysize::mkc;
+    const int G = t.lines, pitch = t.pitch, n = t.plan.n, m = t.plan.m;
+    if (!t.plan.bluestein) return stockham_lines<INV>(a, b, G, pitch, t.plan, t.tw);
+    for (int i = threadIdx.x; i < G * m; i += ANY_THREADS) {
+        const int g = i / m, j = i - g * m;
+        C v = mkc<C>(R(0), R(0));
+        if (j < n) {
+            v = a[g * pitch + j];
+            if (INV) v = anysize::cconj(v);
+            v = anysize::cmul(v, t.chirp[j]);
+        }
+        a[g * pitch + j] = v;
+    }
+    __syncthreads();
+    C* r = stockham_lines<false>(a, b, G, pitch, t.plan, t.tw);
+    C* o = (r == a) ? b : a;
+    for (int i = threadIdx.x; i < G * m; i += ANY_THREADS) {
+        const int g = i / m, j = i - g * m;
+        r[g * pitch + j] = anysize::cmul(r[g * pitch + j], t.kern[j]);
+    }
+    __syncthreads();
+    r = stockham_lines<true>(r, o, G, pitch, t.plan, t.tw);
+    for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) {
+        const int g = i / n, j = i - g * n;
+        C v = anysize::cmul(r[g * pitch + j], t.chirp[j]);
+        if (INV) v = anysize::cconj(v);
+        r[g * pitch + j] = v;
+    }
+    __syncthreads();
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------
+// rows: the epilogues of k_rows (kernels_generic.hip)
+// ------------------------------------------------------------------------------------------
+template <int IN, bool INV, int EPI, typename R>
+__global__ __launch_bounds__(ANY_THREADS) void k_any_rows(RowArgsT<R> p, AxisT<R> t) {
+    using C = typename CxOf<R>::type;
+    using anysize::mkc;
+    extern __shared__ __attribute__((aligned(16))) unsigned char any_smem[];
+    C* sA = reinterpret_cast<C*>(any_smem);
+    C* sB = sA + t.lines * t.pitch;
+    const int G = t.lines, n = t.plan.n, pitch = t.pitch;
+    const int row0 = blockIdx.x * G;
+    for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) {
+        const int g = i / n, k = i - g * n, row = row0 + g;
+        C v = mkc<C>(R(0), R(0));
+        if (row < p.nrows) {
+            const size_t e = (size_t)row * n + k;
+            if (IN == IN_COMPLEX) v = p.cin[e];
+            else if (IN == IN_REAL) v = mkc<C>(p.rin0[e], R(0));
+            else v = mkc<C>(p.rin0[e] - p.rin1[e], R(0));
+        }
+        sA[g * pitch + k] = v;
+    }
+    __syncthreads();
+    const C* r = line_fft<INV, R>(sA, sB, t);
+    for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) {
+        const int g = i / n, k = i - g * n, row = row0 + g;
+        if (row >= p.nrows) continue;
+        const size_t e = (size_t)row * n + k;
+        const C v = r[g * pitch + k];
+        if (EPI == EPI_COMPLEX) {
+            p.cout[e] = mkc<C>(v.x * p.scale, v.y * p.scale);
+        } else if (EPI == EPI_ABS_REAL) {
+            p.x_out[e] = fabs(v.x * p.scale);
+        } else if (EPI == EPI_ABS_COMPLEX) {
+            p.x_out[e] = sqrt(v.x * v.x + v.y * v.y) * p.scale;
+        } else {
+            const R x = fabs(v.x * p.scale);
+            R z = p.z[e], w = p.w[e];
+            if (EPI == EPI_L1) prox_l1(x, z, w, p.prox); else prox_cnc(x, z, w, p.prox);
+            p.z[e] = z;
+            p.w[e] = w;
+            if (p.x_out) p.x_out[e] = x;
+        }
+    }
+}
+
+// More than 64 KiB of dynamic LDS needs an opt-in per kernel and device.  Only a launch that needs it makes it (a double Bluestein line,
+// 64 KiB + 32 B), and the opt-in asks for ANY_LDS_MAX, the bound of every configuration: the attribute is a cap, not an allocation,
+// so one value serves every context on the device and a racing second opt-in writes the same value.
+static hipError_t lds_opt_in(const void* fn, std::atomic<bool>* done, size_t lds) {
+    if (lds <= 64 * 1024) return hipSuccess;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (done[dev].load(std::memory_order_acquire)) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ANY_LDS_MAX);
+    if (e == hipSuccess) done[dev].store(true, std::memory_order_release);
+    return e;
+}
+
+template <int IN, bool INV, int EPI, typename R>
+static hipError_t any_rows_t(hipStream_t s, const AxisT<R>& t, const RowArgsT<R>& a) {
+    static std::atomic<bool> done[64] = {};
+    if (hipError_t e = lds_opt_in((const void*)k_any_rows<IN, INV, EPI, R>, done, any_lds(t))) return e;
+    const unsigned grid = (unsigned)((a.nrows + t.lines - 1) / t.lines);
+    hipLaunchKernelGGL((k_any_rows<IN, INV, EPI, R>), dim3(grid), dim3(ANY_THREADS), any_lds(t), s, a, t);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// columns: [optional forward] -> pointwise k-space op -> [optional inverse], the pointwise pass of k_cols
+// ------------------------------------------------------------------------------------------
+template <bool PRE, int MID, bool POST, typename R>
+__global__ __launch_bounds__(ANY_THREADS) void k_any_cols(ColArgsT<R> p, AxisT<R> t, int W) {
+    using C = typename CxOf<R>::type;
+    using anysize::mkc;
+    extern __shared__ __attribute__((aligned(16))) unsigned char any_smem[];
+    C* sA = reinterpret_cast<C*>(any_smem);
+    C* sB = sA + t.lines * t.pitch;
+    const int G = t.lines, H = t.plan.n, pitch = t.pitch;
+    const int tiles = (W + G - 1) / G;
+    const int b = blockIdx.x / tiles;
+    const int k0 = (blockIdx.x % tiles) * G;
+    const int gc = min(G, W - k0);                     // columns of this tile inside the slice
+    const size_t sbase = (size_t)b * H * W;
+    for (int idx = threadIdx.x; idx < H * G; idx += ANY_THREADS) {
+        const int r = idx / G, c = idx - r * G;
+        sA[c * pitch + r] = c < gc ? p.in[sbase + (size_t)r * W + k0 + c] : mkc<C>(R(0), R(0));
+    }
+    __syncthreads();
+    C* cur = sA;
+    C* oth = sB;
+    if (PRE) {
+        C* r = line_fft<false, R>(sA, sB, t);
+        if (r != sA) { cur = sB; oth = sA; }
+    }
+    if (MID != MID_NONE) {
+        const int mid = p.mask_id ? p.mask_id[b] : 0;
+        const uint8_t* mask = p.mask_bank + (size_t)mid * H * W;
+        const C* yb = p.y + ((MID == MID_MASK_ADD && !p.y_per_slice) ? 0 : sbase);
+        for (int idx = threadIdx.x; idx < H * G; idx += ANY_THREADS) {
+            const int r = idx / G, c = idx - r * G;
+            if (c >= gc) continue;
+            const size_t g = (size_t)r * W + k0 + c;
+            C X = cur[c * pitch + r];
+            const bool m = mask[g] != 0;
+            // an unsampled measurement is SELECTED away, never multiplied: a NaN there cannot reach the result
+            if (MID == MID_BLEND) {
+                if (m) { const C yv = yb[g]; X.x = fma_r(yv.x - X.x, p.c, X.x); X.y = fma_r(yv.y - X.y, p.c, X.y); }
+            } else if (MID == MID_MASK) {
+                if (!m) X = mkc<C>(R(0), R(0));
+            } else if (MID == MID_RESID) {
+                if (m) { const C yv = yb[g]; X.x -= yv.x; X.y -= yv.y; } else X = mkc<C>(R(0), R(0));
+            } else if (MID == MID_MASK_ADD) {
+                const C nv = yb[g];
+                X = m ? anysize::cadd(X, nv) : nv;
+            }
+            cur[c * pitch + r] = X;
+        }
+        __syncthreads();
+    }
+    if (POST) {
+        C* r = line_fft<true, R>(cur, oth, t);
+        if (r != cur) { oth = cur; cur = r; }
+    }
+    for (int idx = threadIdx.x; idx < H * G; idx += ANY_THREADS) {
+        const int r = idx / G, c = idx - r * G;
+        if (c < gc) p.out[sbase + (size_t)r * W + k0 + c] = cur[c * pitch + r];
+    }
+}
+
+template <bool PRE, int MID, bool POST, typename R>
+static hipError_t any_cols_t(hipStream_t s, const AxisT<R>& t, int W, const ColArgsT<R>& a) {
+    static std::atomic<bool> done[64] = {};
+    if (hipError_t e = lds_opt_in((const void*)k_any_cols<PRE, MID, POST, R>, done, any_lds(t))) return e;
+    const unsigned grid = (unsigned)a.B * (unsigned)((W + t.lines - 1) / t.lines);
+    hipLaunchKernelGGL((k_any_cols<PRE, MID, POST, R>), dim3(grid), dim3(ANY_THREADS), any_lds(t), s, a, t, W);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// host: plan and tables per context
+// ------------------------------------------------------------------------------------------
+template <typename R> static AxisT<R> axis(const AnySize* A, int i) {
+    using C = typename CxOf<R>::type;
+    AxisT<R> t;
+    t.plan = A->plan[i];
+    t.tw = reinterpret_cast<const C*>(A->table[i]);
+    t.chirp = t.tw + t.plan.m;
+    t.kern = t.chirp + t.plan.n;
+    t.lines = A->lines[i];
+    t.pitch = t.plan.m + 1;
+    return t;
+}
+
+// lines per workgroup: about ANY_LDS_TARGET of LDS, 1..16, and no more than the lines there are across the axis
+static int lines_per_wg(const Plan& p, size_t cbytes, int across) {
+    const size_t per_line = 2 * cbytes * (size_t)(p.m + 1);
+    int g = (int)(ANY_LDS_TARGET / per_line);
+    if (g > 16) g = 16;
+    if (g > across) g = across;
+    return g < 1 ? 1 : g;
+}
+
+template <typename C>
+static hipError_t upload_axis(const Plan& p, void** out) {
+    std::vector<double> tre, tim, cre, cim;
+    anysize::twiddles(p.m, tre, tim);
+    std::vector<C> h((size_t)2 * p.m + p.n, anysize::mkc<C>(0.0, 0.0));
+    for (int i = 0; i < p.m; ++i) h[i] = anysize::mkc<C>(tre[i], tim[i]);
+    if (p.bluestein) {
+        anysize::chirp(p.n, cre, cim);
+        std::vector<double2> kd;
+        anysize::bluestein_kernel<double2>(p, cre, cim, kd);
+        for (int j = 0; j < p.n; ++j) h[p.m + j] = anysize::mkc<C>(cre[j], cim[j]);
+        for (int i = 0; i < p.m; ++i) h[p.m + p.n + i] = anysize::mkc<C>(kd[i].x, kd[i].y);
+    }
+    hipError_t e = hipMalloc(out, h.size() * sizeof(C));
+    if (e == hipSuccess) e = hipMemcpy(*out, h.data(), h.size() * sizeof(C), hipMemcpyHostToDevice);
+    return e;
+}
+
+bool anysize_supported(int n) { return n >= anysize::MIN_N && n <= anysize::MAX_N; }
+
+AnySize* anysize_create(int H, int W, bool f64, hipError_t* err) {
+    *err = hipSuccess;
+    if (!anysize_supported(H) || !anysize_supported(W)) { *err = hipErrorInvalidValue; return nullptr; }
+    AnySize* A = new (std::nothrow) AnySize();
+    if (!A) { *err = hipErrorOutOfMemory; return nullptr; }
+    A->f64 = f64;
+    const int len[2] = {W, H}, across[2] = {1 << 30, W};
+    const size_t cb = f64 ? sizeof(double2) : sizeof(float2);
+    for (int i = 0; i < 2 && *err == hipSuccess; ++i) {
+        A->plan[i] = anysize::make_plan(len[i]);
+        if (A->plan[i].nstages < 1 || A->plan[i].m > anysize::MAX_M) { *err = hipErrorInvalidValue; break; }
+        A->lines[i] = lines_per_wg(A->plan[i], cb, across[i]);
+        *err = f64 ? upload_axis<double2>(A->plan[i], &A->table[i]) : upload_axis<float2>(A->plan[i], &A->table[i]);
+    }
+    if (*err != hipSuccess) { anysize_destroy(A); return nullptr; }
+    return A;
+}
+
+void anysize_destroy(AnySize* A) {
+    if (!A) return;
+    for (void* p : A->table) if (p) (void)hipFree(p);
+    delete A;
+}
+
+int anysize_describe(const AnySize* A, int i, char* buf, int len) {
+    if (!A || i < 0 || i > 1 || !buf || len < 1) return -1;
+    const Plan& p = A->plan[i];
+    int o = p.bluestein ? snprintf(buf, (size_t)len, "bluestein %d -> %d =", p.n, p.m) : snprintf(buf, (size_t)len, "stockham %d =", p.n);
+    for (int s = 0; s < p.nstages && o >= 0 && o < len; ++s) o += snprintf(buf + o, (size_t)(len - o), s ? "*%d" : " %d", p.radix[s]);
+    return 0;
+}
+
+template <typename R>
+hipError_t anysize_rows(const AnySize* A, hipStream_t s, RowIn in, bool inv, RowEpi epi, const RowArgsT<R>& a) {
+    if (!A || A->f64 != std::is_same<R, double>::value) return hipErrorInvalidValue;
+    const AxisT<R> t = axis<R>(A, 0);
+    if (!inv && epi == EPI_COMPLEX) {
+        if (in == IN_COMPLEX)   return any_rows_t<IN_COMPLEX, false, EPI_COMPLEX>(s, t, a);
+        if (in == IN_REAL)      return any_rows_t<IN_REAL, false, EPI_COMPLEX>(s, t, a);
+        if (in == IN_REAL_DIFF) return any_rows_t<IN_REAL_DIFF, false, EPI_COMPLEX>(s, t, a);
+    }
+    if (inv && in == IN_COMPLEX) {
+        switch (epi) {
+            case EPI_COMPLEX:     return any_rows_t<IN_COMPLEX, true, EPI_COMPLEX>(s, t, a);
+            case EPI_ABS_REAL:    return any_rows_t<IN_COMPLEX, true, EPI_ABS_REAL>(s, t, a);
+            case EPI_ABS_COMPLEX: return any_rows_t<IN_COMPLEX, true, EPI_ABS_COMPLEX>(s, t, a);
+            case EPI_L1:          return any_rows_t<IN_COMPLEX, true, EPI_L1>(s, t, a);
+            case EPI_CNC:         return any_rows_t<IN_COMPLEX, true, EPI_CNC>(s, t, a);
+        }
+    }
+    return hipErrorInvalidValue;
+}
+template hipError_t anysize_rows<float>(const AnySize*, hipStream_t, RowIn, bool, RowEpi, const RowArgsT<float>&);
+template hipError_t anysize_rows<double>(const AnySize*, hipStream_t, RowIn, bool, RowEpi, const RowArgsT<double>&);
+
+template <typename R>
+hipError_t anysize_cols(const AnySize* A, hipStream_t s, bool pre, ColMid mid, bool post, const ColArgsT<R>& a) {
+    if (!A || A->f64 != std::is_same<R, double>::value) return hipErrorInvalidValue;
+    const AxisT<R> t = axis<R>(A, 1);
+    const int W = A->plan[0].n;
+    if (pre && !post && mid == MID_NONE)      return any_cols_t<true, MID_NONE, false>(s, t, W, a);
+    if (!pre && post && mid == MID_NONE)      return any_cols_t<false, MID_NONE, true>(s, t, W, a);
+    if (pre && post && mid == MID_BLEND)      return any_cols_t<true, MID_BLEND, true>(s, t, W, a);
+    if (pre && !post && mid == MID_MASK)      return any_cols_t<true, MID_MASK, false>(s, t, W, a);
+    if (!pre && post && mid == MID_MASK)      return any_cols_t<false, MID_MASK, true>(s, t, W, a);
+    if (pre && post && mid == MID_RESID)      return any_cols_t<true, MID_RESID, true>(s, t, W, a);
+    if (pre && !post && mid == MID_MASK_ADD)  return any_cols_t<true, MID_MASK_ADD, false>(s, t, W, a);
+    return hipErrorInvalidValue;
+}
+template hipError_t anysize_cols<float>(const AnySize*, hipStream_t, bool, ColMid, bool, const ColArgsT<float>&);
+template hipError_t anysize_cols<double>(const AnySize*, hipStream_t, bool, ColMid, bool, const ColArgsT<double>&);
+
+}  // namespace pnp

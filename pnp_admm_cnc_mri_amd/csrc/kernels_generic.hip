@@ -13,6 +13,7 @@
 //            segments; the LDS pitch N+1 keeps the transposing writes conflict-free.
 #include "internal.h"
 #include "fft16.h"
+#include "prox_ops.h"
 #include <math.h>
 
 namespace pnp {
@@ -47,9 +48,6 @@ template <> struct Tw<double> { __device__ static const double2* get(int N) { re
 
 __device__ __forceinline__ float2  mkc(float x, float y)   { return make_float2(x, y); }
 __device__ __forceinline__ double2 mkc(double x, double y) { return make_double2(x, y); }
-__device__ __forceinline__ float  fma_r(float a, float b, float c)    { return fmaf(a, b, c); }
-__device__ __forceinline__ double fma_r(double a, double b, double c) { return fma(a, b, c); }
-
 template <typename C> __device__ __forceinline__ C cmul(C a, C b) {
     return mkc(fma_r(a.x, b.x, -(a.y * b.y)), fma_r(a.x, b.y, a.y * b.x));
 }
@@ -114,24 +112,6 @@ __device__ __forceinline__ C* fft_lds(C* a, C* b, const C* tw, int t) {
         C* tmp = a; a = b; b = tmp;
     }
     return a;
-}
-
-template <typename R> __device__ __forceinline__ R soft(R a, R c) {
-    const R m = fabs(a) - c;
-    const R r = m > R(0) ? m : R(0);
-    return a < R(0) ? -r : r;
-}
-template <typename R> __device__ __forceinline__ void prox_l1(R x, R& z, R& w, const ProxParamsT<R>& p) {
-    const R u = x + w;
-    z = soft(u, p.thr);
-    w = u - z;
-}
-template <typename R> __device__ __forceinline__ void prox_cnc(R x, R& z, R& w, const ProxParamsT<R>& p) {
-    const R u = x + w;
-    const R clipz = z < -p.ib ? -p.ib : (z > p.ib ? p.ib : z);          // z - soft(z, 1/b)
-    const R t = fma_r(p.c1, z, fma_r(p.c2, u, p.c3 * clipz));
-    z = soft(t, p.thr);
-    w = u - z;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -650,14 +630,15 @@ template hipError_t launch_cols<float>(hipStream_t, int, int, bool, ColMid, bool
 template hipError_t launch_cols<double>(hipStream_t, int, int, bool, ColMid, bool, const ColArgsT<double>&);
 
 // ------------------------------------------------------------------------------------------
-// pointwise kernels on caller pointers (PnP path, S6:301-308): 4 floats per lane, grid-stride
+// pointwise kernels on caller pointers (PnP path, S6:301-308): 4 floats per lane, grid-stride; a scalar tail when n % 4 != 0
+// (any-size slices: B H W need not be a multiple of 4)
 // ------------------------------------------------------------------------------------------
 // torch's clamp_(0, 1) (S6:306-308): NaN in -> NaN out.  fminf / fmaxf alone are IEEE minNum / maxNum and return the OTHER operand for a
 // NaN -- a non-finite denoiser output would turn into 0 here and the loop would carry on with plausible numbers.
 __device__ __forceinline__ float clamp01(float v) { return v != v ? v : fminf(fmaxf(v, 0.0f), 1.0f); }
 
 template <bool CNC>
-__global__ __launch_bounds__(256) void k_prox(const float4* x, float4* z, float4* w, ProxParams p, size_t n4) {
+__global__ __launch_bounds__(256) void k_prox(const float4* x, float4* z, float4* w, ProxParams p, size_t n4, size_t n) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const float4 xv = x[i];
         float4 zv = z[i], wv = w[i];
@@ -665,10 +646,14 @@ __global__ __launch_bounds__(256) void k_prox(const float4* x, float4* z, float4
         else     { prox_l1(xv.x, zv.x, wv.x, p);  prox_l1(xv.y, zv.y, wv.y, p);  prox_l1(xv.z, zv.z, wv.z, p);  prox_l1(xv.w, zv.w, wv.w, p); }
         z[i] = zv; w[i] = wv;
     }
+    for (size_t i = 4 * n4 + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float* zs = (float*)z; float* ws = (float*)w;
+        if (CNC) prox_cnc(((const float*)x)[i], zs[i], ws[i], p); else prox_l1(((const float*)x)[i], zs[i], ws[i], p);
+    }
 }
 
 __global__ __launch_bounds__(256) void k_combine(const float4* z, const float4* x, const float4* w, const float4* sd,
-                                                 float4* t, float c1, float c2, float c3, size_t n4) {
+                                                 float4* t, float c1, float c2, float c3, size_t n4, size_t n) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const float4 zv = z[i], xv = x[i], wv = w[i], sv = sd[i];
         float4 o;
@@ -679,22 +664,34 @@ __global__ __launch_bounds__(256) void k_combine(const float4* z, const float4* 
         o.w = c1 * zv.w + c2 * (xv.w + wv.w) + c3 * (zv.w - sv.w);
         t[i] = o;
     }
+    for (size_t i = 4 * n4 + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float zv = ((const float*)z)[i], xv = ((const float*)x)[i], wv = ((const float*)w)[i], sv = ((const float*)sd)[i];
+        ((float*)t)[i] = c1 * zv + c2 * (xv + wv) + c3 * (zv - sv);
+    }
 }
 
-__global__ __launch_bounds__(256) void k_add(const float4* a, const float4* b, float4* o, size_t n4) {
+__global__ __launch_bounds__(256) void k_add(const float4* a, const float4* b, float4* o, size_t n4, size_t n) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const float4 av = a[i], bv = b[i];
         o[i] = make_float4(av.x + bv.x, av.y + bv.y, av.z + bv.z, av.w + bv.w);
     }
+    for (size_t i = 4 * n4 + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        ((float*)o)[i] = ((const float*)a)[i] + ((const float*)b)[i];
 }
 
-__global__ __launch_bounds__(256) void k_dual_clamp(float4* x, float4* z, float4* w, size_t n4) {
+__global__ __launch_bounds__(256) void k_dual_clamp(float4* x, float4* z, float4* w, size_t n4, size_t n) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         float4 xv = x[i], zv = z[i], wv = w[i];
         wv.x = wv.x + xv.x - zv.x; wv.y = wv.y + xv.y - zv.y; wv.z = wv.z + xv.z - zv.z; wv.w = wv.w + xv.w - zv.w;
         x[i] = make_float4(clamp01(xv.x), clamp01(xv.y), clamp01(xv.z), clamp01(xv.w));
         z[i] = make_float4(clamp01(zv.x), clamp01(zv.y), clamp01(zv.z), clamp01(zv.w));
         w[i] = make_float4(clamp01(wv.x), clamp01(wv.y), clamp01(wv.z), clamp01(wv.w));
+    }
+    for (size_t i = 4 * n4 + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float* xs = (float*)x; float* zs = (float*)z; float* ws = (float*)w;
+        const float xv = xs[i], zv = zs[i];
+        const float wv = ws[i] + xv - zv;
+        xs[i] = clamp01(xv); zs[i] = clamp01(zv); ws[i] = clamp01(wv);
     }
 }
 
@@ -705,25 +702,25 @@ static inline unsigned pw_grid(size_t n4) {
 
 hipError_t launch_prox(hipStream_t s, bool cnc, const float* x, float* z, float* w, ProxParams p, size_t n) {
     const size_t n4 = n / 4;
-    if (cnc) hipLaunchKernelGGL(k_prox<true>, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)x, (float4*)z, (float4*)w, p, n4);
-    else     hipLaunchKernelGGL(k_prox<false>, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)x, (float4*)z, (float4*)w, p, n4);
+    if (cnc) hipLaunchKernelGGL(k_prox<true>, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)x, (float4*)z, (float4*)w, p, n4, n);
+    else     hipLaunchKernelGGL(k_prox<false>, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)x, (float4*)z, (float4*)w, p, n4, n);
     return hipGetLastError();
 }
 hipError_t launch_combine(hipStream_t s, const float* z, const float* x, const float* w, const float* sd, float* t,
                           float c1, float c2, float c3, size_t n) {
     const size_t n4 = n / 4;
     hipLaunchKernelGGL(k_combine, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)z, (const float4*)x,
-                       (const float4*)w, (const float4*)sd, (float4*)t, c1, c2, c3, n4);
+                       (const float4*)w, (const float4*)sd, (float4*)t, c1, c2, c3, n4, n);
     return hipGetLastError();
 }
 hipError_t launch_add(hipStream_t s, const float* a, const float* b, float* o, size_t n) {
     const size_t n4 = n / 4;
-    hipLaunchKernelGGL(k_add, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)a, (const float4*)b, (float4*)o, n4);
+    hipLaunchKernelGGL(k_add, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)a, (const float4*)b, (float4*)o, n4, n);
     return hipGetLastError();
 }
 hipError_t launch_dual_clamp(hipStream_t s, float* x, float* z, float* w, size_t n) {
     const size_t n4 = n / 4;
-    hipLaunchKernelGGL(k_dual_clamp, dim3(pw_grid(n4)), dim3(256), 0, s, (float4*)x, (float4*)z, (float4*)w, n4);
+    hipLaunchKernelGGL(k_dual_clamp, dim3(pw_grid(n4)), dim3(256), 0, s, (float4*)x, (float4*)z, (float4*)w, n4, n);
     return hipGetLastError();
 }
 
@@ -831,15 +828,17 @@ template hipError_t launch_ssim<float>(hipStream_t, const float*, const uint8_t*
 template hipError_t launch_ssim<double>(hipStream_t, const double*, const uint8_t*, double*, int, int, int);
 
 // float -> double widening of the image handed to the double-precision synthesis (exact)
-__global__ __launch_bounds__(256) void k_widen(const float4* in, double4* out, size_t n4) {
+__global__ __launch_bounds__(256) void k_widen(const float4* in, double4* out, size_t n4, size_t n) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const float4 v = in[i];
         out[i] = make_double4((double)v.x, (double)v.y, (double)v.z, (double)v.w);
     }
+    for (size_t i = 4 * n4 + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        ((double*)out)[i] = (double)((const float*)in)[i];
 }
 hipError_t launch_widen(hipStream_t s, const float* in, double* out, size_t n) {
     const size_t n4 = n / 4;
-    hipLaunchKernelGGL(k_widen, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)in, (double4*)out, n4);
+    hipLaunchKernelGGL(k_widen, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)in, (double4*)out, n4, n);
     return hipGetLastError();
 }
 

@@ -753,14 +753,17 @@ def forward_flops(den, H, W, device, detail=False):
     return (2 * macs[0], 2 * macs[1]) if detail else 2 * macs[0]
 
 
-def auto_backend(model, device=None, bank=None, cnn_dtype=None):
+def auto_backend(model, device=None, bank=None, cnn_dtype=None, shape=None):
     """What `cnn_backend='auto'` (the entry points' default since round 6) resolves to: ('hip_f16x3' | 'torch', reason).
     'hip_f16x3' -- the split-half matrix-core kernels of libpnpmri.so, held to the same goldens and bars as the PyTorch / MIOpen backend at
     every run length (tests/test_gpu_pnp.py) -- when (a) the device is a gfx950 part, (b) EVERY convolution of the network is one the
     library takes (hip_covers_stack / UNetRes.hip_covers: otherwise part of the forward would still be MIOpen's), (c) every weight -- of
-    every model of an IRCNN bank -- is finite and inside the half range, (d) float32 arithmetic is asked for.  'torch' otherwise."""
+    every model of an IRCNN bank -- is finite and inside the half range, (d) float32 arithmetic is asked for, (e) the slices' shape (H, W),
+    if given, is a multiple of 8 on both sides (the shapes the split-half kernels are held to).  'torch' otherwise."""
     if cnn_dtype not in (None, 'fp32'):
         return 'torch', 'cnn_dtype=%s is a PyTorch autocast mode' % cnn_dtype
+    if shape is not None and (int(shape[0]) % 8 or int(shape[1]) % 8):
+        return 'torch', 'slices of %d x %d: H, W not multiples of 8' % (int(shape[0]), int(shape[1]))
     dev = torch.device(device if device is not None else 'cuda')
     if dev.type != 'cuda' or not torch.cuda.is_available():
         return 'torch', 'no HIP device'
@@ -788,13 +791,14 @@ class Denoiser:
     [B,1,H,W] float32 CUDA tensor to the denoised tensor for iteration i."""
 
     def __init__(self, model_name, model, noise_level_model, sigmas=None, noises=None, x8=False, bank=None,
-                 cnn_batch=None, channels_last=True, cnn_dtype=None, miopen_find='auto', backend='torch', graph=False):
+                 cnn_batch=None, channels_last=True, cnn_dtype=None, miopen_find='auto', backend='torch', graph=False, shape=None):
         """backend: 'torch' (default: the whole forward in PyTorch-ROCm / MIOpen, as the north star keeps it) or 'hip' (the
         64 -> 64 conv3x3 (+ ReLU) layers of DnCNN / FDnCNN / FFDNet / IRCNN (dilations 1..4) and DRUNet's 64-channel residual
         blocks on libpnpmri.so's fp32-MFMA kernel, the plain stacks' first and last layers on its direct kernels; float32 only)
         or 'hip_f16x3' (the same, with the 64 -> 64 layers in split-half arithmetic on the f16 matrix cores: float32 operands
         carried as two halves, three exact-product matrix instructions per product, float32 accumulation -- float32-level
-        results at several times the float32 matrix rate; operands must lie within the half range, |x| <= 65504)."""
+        results at several times the float32 matrix rate; operands must lie within the half range, |x| <= 65504).  shape: the slices' (H, W),
+        for backend='auto' (auto_backend)."""
         # graph=True: a forward of at most `cnn_batch` slices is captured once per input shape into a HIP graph (torch.cuda.CUDAGraph)
         # and replayed -- for the reference's own usage, ONE slice per call (S6:231), where a forward is a train of 17 .. 70 launches
         # of a few microseconds each.  Same kernels, same results; re-captured when a parameter changes (load_state_dict).
@@ -803,7 +807,7 @@ class Denoiser:
         self._sig_static = None
         self._in_graph = False
         if backend == 'auto':
-            backend, why = auto_backend(model, None, bank, cnn_dtype)
+            backend, why = auto_backend(model, None, bank, cnn_dtype, shape)
             logging.getLogger('pnp_admm_cnc_mri_amd').info('cnn_backend=auto -> %s (%s)', backend, why)
         if backend not in ('torch',) + HIP_BACKENDS:
             raise ValueError("backend must be 'auto', 'torch', 'hip' or 'hip_f16x3'")

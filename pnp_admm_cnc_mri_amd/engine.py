@@ -28,7 +28,7 @@ def _host(a, dtype):
 
 
 class Engine:
-    """One context per (device, H, W, Bmax).  Not thread-safe, not re-entrant (as the ABI says)."""
+    """One context per (device, H, W, Bmax), H, W in [128, 1024].  Not thread-safe, not re-entrant (as the ABI says)."""
 
     def __init__(self, H=256, W=256, Bmax=1, device=0, precision='f32'):
         """precision='f64': the reference's own arithmetic (S4:109) -- every buffer and step in double; problem
@@ -39,7 +39,7 @@ class Engine:
         self._L = _lib.lib()
         self._ctx = _lib.ctx_p()
         self.f64 = precision == 'f64'
-        create = self._L.pnp_ctx_create_f64 if self.f64 else self._L.pnp_ctx_create
+        create = self._L.pnp_ctx_create_any_f64 if self.f64 else self._L.pnp_ctx_create_any      # H, W in [128, 1024]
         _lib.check(create(int(device), int(H), int(W), int(Bmax), C.byref(self._ctx)))
         self.H, self.W, self.Bmax, self.device = int(H), int(W), int(Bmax), int(device)
         self.B = 0
@@ -94,6 +94,17 @@ class Engine:
     @property
     def path_name(self):
         return self._L.pnp_path_name(self._ctx).decode()
+
+    @property
+    def ctx_path(self):
+        """'anysize' (H, W not both in {256, 512}: the any-size FFT kernels) or, for the fixed-size kernels, path_name."""
+        return self._L.pnp_ctx_path(self._ctx).decode()
+
+    def fft_plan(self, axis):
+        """The transform plan of axis 0 (rows, length W) or 1 (columns, length H) as text (pnp_fft_plan)."""
+        buf = C.create_string_buffer(128)
+        _lib.check(self._L.pnp_fft_plan(self._ctx, int(axis), buf, len(buf)))
+        return buf.value.decode()
 
     @property
     def kernels_per_iteration(self):

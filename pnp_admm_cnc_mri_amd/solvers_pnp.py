@@ -63,8 +63,9 @@ PRESETS = {
 
 
 def _load_model(model_name, model, model_zoo, iter_num, noises, x8, cnn_batch, device, cnn_dtype=None, miopen_find='auto',
-                cnn_backend='auto', cnn_graph=False):
-    """The model-zoo switch of S6:129-217: build by name, load weights, eval, no grad, to device."""
+                cnn_backend='auto', cnn_graph=False, shape=None):
+    """The model-zoo switch of S6:129-217: build by name, load weights, eval, no grad, to device.  shape: the slices' (H, W), for
+    cnn_backend='auto'."""
     import torch
     net, nlm, scheduled = D.build(model_name)
     bank = None
@@ -90,7 +91,7 @@ def _load_model(model_name, model, model_zoo, iter_num, noises, x8, cnn_batch, d
                                  modelSigma2=nlm * 255., w=1.0)
         sigmas = torch.tensor(s)
     return D.Denoiser(model_name, net, nlm, sigmas=sigmas, noises=noises, x8=x8, bank=bank, cnn_batch=cnn_batch,
-                      cnn_dtype=cnn_dtype, miopen_find=miopen_find, backend=cnn_backend, graph=cnn_graph).to(device)
+                      cnn_dtype=cnn_dtype, miopen_find=miopen_find, backend=cnn_backend, graph=cnn_graph, shape=shape).to(device)
 
 
 def _device_state(torch, eng, B, H, W, dev):
@@ -136,7 +137,7 @@ def PNP_ADMM_CNC_D(model_name, mask, noises, images=None, y=None, mask_id=None, 
     dev = torch.device('cuda', device)
     job = _Job(mask, noises, model_name, 'PNP_ADMM_CNC_D', images, y, mask_id, testsets, testset_name, results,
                save_E, device)
-    den = _load_model(model_name, model, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph)   # x8 = False, S6:93
+    den = _load_model(model_name, model, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))   # x8 = False, S6:93
     with torch.cuda.device(dev), torch.no_grad(), job.open_engine(torch.cuda.current_stream(dev).cuda_stream) as eng:
         B, H, W = job.B, job.H, job.W
         x, z, w = _device_state(torch, eng, B, H, W, dev)
@@ -176,11 +177,11 @@ def PNP_ADMM_CNC_DnCNN(model_name1, model_name2, mask, noises, images=None, y=No
     dev = torch.device('cuda', device)
     job = _Job(mask, noises, model_name1 + '_' + model_name2, 'PNP_ADMM_CNC_DnCNN', images, y, mask_id, testsets,
                testset_name, results, save_E, device)
-    den1 = _load_model(model_name1, model, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph)
+    den1 = _load_model(model_name1, model, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))
     if faithful_model2_path and model2 is None:
-        den2 = _load_model(model_name1, model, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph)
+        den2 = _load_model(model_name1, model, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))
     else:
-        den2 = _load_model(model_name2, model2, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph)
+        den2 = _load_model(model_name2, model2, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))
     with torch.cuda.device(dev), torch.no_grad(), job.open_engine(torch.cuda.current_stream(dev).cuda_stream) as eng:
         B, H, W = job.B, job.H, job.W
         x, z, w = _device_state(torch, eng, B, H, W, dev)
@@ -211,7 +212,7 @@ def PNP_ADMM_L1_D(model_name, mask, noises, images=None, y=None, mask_id=None, t
     x8 = fam in ('drunet', 'ffdnet')                       # x8 = True (S3:87) survives only there (S3:130,142,181)
     job = _Job(mask, noises, model_name, '_' + model_name + '_PNP_ADMM_L1_D', images, y, mask_id, testsets,
                testset_name, results, save_E, device, psnr_fmt='{:.2f}')            # file name S3:308, PSNR format S3:320
-    den = _load_model(model_name, model, model_zoo, iter_num, noises, x8, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph)
+    den = _load_model(model_name, model, model_zoo, iter_num, noises, x8, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))
     with torch.cuda.device(dev), torch.no_grad(), job.open_engine(torch.cuda.current_stream(dev).cuda_stream) as eng:
         B, H, W = job.B, job.H, job.W
         x, z, w = _device_state(torch, eng, B, H, W, dev)

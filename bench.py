@@ -3,7 +3,15 @@
 (BASELINE.json configs[1]: ADMM_CNC, Q_Random30, S4:176 presets), synthetic inputs of
 SURVEY.md section 8(d).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W            # the headline figure alone
+    python bench.py --gpus N --steps K --warmup W --full     # and every other measurement and check below
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line.  Everything
+else it can measure or check (sustained, l1, f64, latency and pnp sub-records, parity against the oracle, CPU
+baselines) runs after the timed steps, only with --full, and fills keys that stay null in a plain line.  What runs
+before the timed steps is the same in both: the card's stream calibration
+(`roofline.calibration`, 0.6 s) stays in a plain run because the timed steps start from the clock and power state
+it leaves the card in.
 
 One "step" = one batched ADMM iteration (x-update in k-space, CNC z-update, dual update) over
 the 512 slices a GPU holds.  Slices are independent, so N GPUs hold N x 512 different slices
@@ -24,7 +32,7 @@ where no PMC figure exists) / HIP-event time per iteration on the kernels' own s
 physical fraction of the 8 TB/s peak, <= 1.  `roofline.frac_contract_57N` prices the same time
 against SURVEY.md 8(d)'s 57*N_pix*B bytes (the quantity rounds 1-3 printed under `frac`; it
 exceeds 1 because the kernels move fewer bytes than that formulation).
-Sub-records at N = 1: `sustained` (back-to-back 100-iteration solves), `l1` (configs[0]'s solver,
+Sub-records (--full) at N = 1: `sustained` (back-to-back 100-iteration solves), `l1` (configs[0]'s solver,
 ADMM_L1, on the same batch), `f64` (the double-precision engine), `pnp` (configs[2] through
 bench_pnp.py, two child processes after this one has released the GPU), `parity` (three slices of
 the timed run against the NumPy oracle), `cpu_baseline` = the NumPy oracle (float64, np.fft,
@@ -363,7 +371,11 @@ def main():
     ap.add_argument('--precision', choices=['f32', 'f64'], default='f32',
                     help="f64 = the double-precision engine (meets 1e-5 against the float64 reference at 100 CNC "
                          "iterations, DESIGN.md section 2); the headline stays f32")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run everything beyond the headline: sustained / l1 / f64 / latency / pnp sub-records, '
+                         'parity against the oracle, CPU baselines (the --no-*, --cpu-budget and --sustain-* options tune these and apply only with --full)')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='--full without the CPU legs: no parity, f64, latency or pnp record and no CPU baselines')
     ap.add_argument('--cpu-budget', type=float, default=20.0)
     ap.add_argument('--launch-timeout', type=float, default=float(os.environ.get('PNP_BENCH_TIMEOUT', 1500)),
                     help='--gpus N without torchrun: seconds after which hanging rank processes are killed (exit 124)')
@@ -453,7 +465,8 @@ def main():
     eng.prepare_loops()                                               # per-problem tables of the loop kernels: never inside a timed region
     # Attribution (round 6): which card, at which nominal clock, and what ITS memory system gives a plain streaming kernel with the slice
     # kernel's access shape today (pnp_calibrate_stream, >= 0.6 s, before anything is timed) -- boxes of the pool differ by several per cent
-    # with a byte-identical kernel (10 015 -> 9 552 it/s round over round)
+    # with a byte-identical kernel (10 015 -> 9 552 it/s round over round).  Not behind --full: the timed steps start from the
+    # clock and power state this leaves the card in.
     device_rec, calib = None, None
     try:
         import ctypes as C_
@@ -529,14 +542,14 @@ def main():
         return n_timed * ks, e.timer_stop()
 
     sus = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         sus_steps, sus_ms = sustained(eng, args.sustain_s, ev_ms / args.steps)
         sus = [float(sus_steps), float(sus_ms)]
 
     # `l1` sub-record (N = 1, headline configuration): ADMM_L1 -- the solver of BASELINE.json configs[0], S1:171 presets -- on the
     # same resident batch: a burst of K steps after W warm-up steps from a fresh state, then the sustained form (half the span).
     l1_rec = None
-    if (world == 1 and args.solver == 'cnc' and args.size == 256 and args.precision == 'f32' and not args.generic and not args.no_l1_record):
+    if (args.full and world == 1 and args.solver == 'cnc' and args.size == 256 and args.precision == 'f32' and not args.generic and not args.no_l1_record):
         def run_l1(e, n):
             e.admm_l1(n, 0.1, 0.015)
         eng.init_state()
@@ -597,7 +610,8 @@ def main():
     # double-precision engine -- the configuration that holds 1e-5 against the float64 reference at config 2's own
     # 100 CNC iterations -- is timed in the same process on the same batch.
     parity, f64_record = None, None
-    checker = rank == 0 and world == 1 and not args.no_cpu_baseline
+    cpu_legs = args.full and world == 1 and not args.no_cpu_baseline
+    checker = rank == 0 and cpu_legs
     if checker:
         from oracle import admm_oracle as O
         n_it = args.warmup + args.steps
@@ -709,7 +723,7 @@ def main():
             'value': value, 'unit': 'it/s (512-slice batches)',
             'n_gpus': world, 'steps': K, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': args.precision, 'data': 'synthetic',
+            'dtype': args.precision, 'data': 'synthetic', 'full': args.full,
             'config': {'workload': 'ADMM_%s, %d synthetic %dx%d complex64 slices per GPU, %s, %s presets'
                                    % (args.solver.upper(), B, H, W, 'Q_Random30' if H == 256 else 'seeded mask bank of 3',
                                       'S4:176' if args.solver == 'cnc' else 'S1:171'),
@@ -746,7 +760,7 @@ def main():
                                  '(slice-resident path: z, w and the Hermitian half-plane table only, the transposed field never '
                                  'leaves the compute unit; fused path: two real slices per complex FFT, Hermitian half plane).'},
         }
-        if world == 1 and not args.no_cpu_baseline and args.size == 256 and args.precision == 'f32' and not (args.no_pnp_record and args.no_latency_record):
+        if cpu_legs and args.size == 256 and args.precision == 'f32' and not (args.no_pnp_record and args.no_latency_record):
             # the sub-records get the whole card: this process lets go of its engine, its buffers and torch's cached blocks first
             eng.close()
             del x_dev
@@ -760,7 +774,7 @@ def main():
                 torch.cuda.empty_cache()
             if not args.no_pnp_record:
                 line['pnp'] = pnp_record()
-        if world == 1 and not args.no_cpu_baseline:
+        if cpu_legs:
             line['cpu_baseline'] = cpu_baseline(masks, mask_id, args.cpu_budget)
             try:
                 line['cpu_baseline_all_cores'] = cpu_baseline_all_cores(min(8.0, args.cpu_budget))

@@ -3,19 +3,19 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/bench_lines; mkdir -p $O
 export PNP_BENCH_CACHE=/tmp/pnp_bench_inputs
-python3 bench.py > $O/default_100.json 2>/dev/null                                         # full line incl. CPU baselines, parity and f64 records
-python3 bench.py --steps 20 --warmup 5 > $O/driver_shape_full.json 2>/dev/null                 # the driver's command line
-for i in 1 2 3; do python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/driver_shape_$i.json 2>/dev/null; done
-PNP_SLICE=0 python3 bench.py --no-cpu-baseline > $O/fused_100.json 2>/dev/null
-python3 bench.py --solver l1 --no-cpu-baseline > $O/l1_100.json 2>/dev/null
-python3 bench.py --precision f64 --steps 50 --warmup 5 --no-cpu-baseline > $O/f64_50.json 2>/dev/null
-python3 bench.py --size 512 --batch 256 --no-cpu-baseline > $O/size512_100.json 2>/dev/null
-python3 bench.py --size 512 --batch 256 --steps 20 --warmup 5 --no-cpu-baseline > $O/size512_driver_shape.json 2>/dev/null
-python3 bench.py --generic --no-cpu-baseline > $O/generic_100.json 2>/dev/null
+python3 bench.py --full > $O/default_100.json 2>/dev/null                                         # full line incl. CPU baselines, parity and f64 records
+python3 bench.py --full --steps 20 --warmup 5 > $O/driver_shape_full.json 2>/dev/null                 # the driver's command line
+for i in 1 2 3; do python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/driver_shape_$i.json 2>/dev/null; done
+PNP_SLICE=0 python3 bench.py --full --no-cpu-baseline > $O/fused_100.json 2>/dev/null
+python3 bench.py --full --solver l1 --no-cpu-baseline > $O/l1_100.json 2>/dev/null
+python3 bench.py --full --precision f64 --steps 50 --warmup 5 --no-cpu-baseline > $O/f64_50.json 2>/dev/null
+python3 bench.py --full --size 512 --batch 256 --no-cpu-baseline > $O/size512_100.json 2>/dev/null
+python3 bench.py --full --size 512 --batch 256 --steps 20 --warmup 5 --no-cpu-baseline > $O/size512_driver_shape.json 2>/dev/null
+python3 bench.py --full --generic --no-cpu-baseline > $O/generic_100.json 2>/dev/null
 # (the round-2 Stockham column kernel is an experiment-build knob since round 4: bash profiles/variants.sh knobs; PNP_MRI_LIB=build/variants/lib_knobs.so PNP_GENERIC_STOCKHAM=1 ...)
-python3 bench.py --gpus 2 --rehearse-gloo --steps 20 --warmup 5 > $O/gpus2_rehearsal.json 2>/dev/null
-PNP_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/rccl_one_rank.json 2>/dev/null
-python3 bench.py --batch 1024 --no-cpu-baseline > $O/batch1024_100.json 2>/dev/null
+python3 bench.py --full --gpus 2 --rehearse-gloo --steps 20 --warmup 5 > $O/gpus2_rehearsal.json 2>/dev/null
+PNP_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/rccl_one_rank.json 2>/dev/null
+python3 bench.py --full --batch 1024 --no-cpu-baseline > $O/batch1024_100.json 2>/dev/null
 python3 - $O <<'PY'
 import glob, json, os, sys
 for f in sorted(glob.glob(sys.argv[1] + '/*.json')):

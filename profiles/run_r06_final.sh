@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r06_final
 mkdir -p $O
 cd $R
-timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $O/driver_shape_full.json 2> $O/driver_shape_full.err; echo "bench rc $?"
+timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $O/driver_shape_full.json 2> $O/driver_shape_full.err; echo "bench rc $?"
 timeout -k 10 300 bash profiles/collect.sh r06_slice_cnc --sustain-s 0 --no-l1-record > $O/collect.log 2>&1; tail -1 $O/collect.log
 timeout -k 10 200 bash profiles/experiments/prof_pnp_kernels.sh ffdnet_gray hip_f16x3 4 --no-parity > $O/rocprof_r06_pnp_ffdnet_f16x3_kernels.txt 2>&1
 timeout -k 10 300 bash profiles/experiments/prof_pnp_kernels.sh drunet_gray hip_f16x3 2 --no-parity --mask Q_Cartesian30 > $O/rocprof_r06_pnp_drunet_f16x3_kernels.txt 2>&1

@@ -38,7 +38,7 @@ def test_bench_launches_its_own_ranks():
     JSON line and exits 0.  The N = 1 invocation keeps its shape."""
     env_ = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--rehearse-gloo', '--batch', '32', '--steps', '3',
-           '--warmup', '1', '--sustain-s', '0.2']
+           '--warmup', '1', '--full', '--sustain-s', '0.2']
     r = subprocess.run(cmd, env=env_, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith('{')]
@@ -59,6 +59,32 @@ def test_bench_launches_its_own_ranks():
     assert j1['sustained'] is None and j1['per_rank'] is None
     # same slices on rank 0 of both runs: the N = 2 job's rank 0 did exactly the N = 1 job's work
     assert j1['x_checksum'] == j['x_checksum']
+
+
+def test_plain_bench_run_is_the_headline_alone():
+    """Without --full the line carries the headline and nothing measured after the timed steps: no sustained / l1 / f64 /
+    latency / pnp record, no parity, no CPU baseline.  What comes before them is that of the --full run (the card's stream
+    calibration included), and so are the timed steps: the same slices, the same W + K iterations, the same x."""
+    env_ = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
+    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--batch', '64', '--steps', '3', '--warmup', '1']
+    lines = {}
+    for extra in ([], ['--full', '--cpu-budget', '0.3', '--sustain-s', '0.2', '--no-pnp-record', '--no-latency-record']):
+        r = subprocess.run(base + extra, env=env_, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        out = r.stdout.decode().strip().splitlines()
+        assert len(out) == 1, out[:3]
+        lines[bool(extra)] = json.loads(out[0])
+    j, jf = lines[False], lines[True]
+    assert j['full'] is False and jf['full'] is True
+    assert j['n_gpus'] == 1 and j['steps'] == 3 and j['warmup'] == 1 and j['dtype'] == 'f32' and j['higher_is_better'] is True
+    assert j['unit'] == jf['unit'] and j['metric'] == jf['metric'] and j['config']['path'] == 'slice' and j['x_finite']
+    assert abs(j['value'] - 3 / (j['ms_per_step'] * 3e-3) * 64 / 512) <= 1e-6 * j['value']
+    for k in ('sustained', 'l1', 'f64', 'parity', 'cpu_baseline'):
+        assert j[k] is None and jf[k] is not None, k
+    assert 'latency' not in j and 'pnp' not in j and 'cpu_baseline_all_cores' not in j
+    assert j['roofline']['calibration']['calibration_gbs'] > 0 and jf['roofline']['calibration']['calibration_gbs'] > 0
+    assert j['roofline']['frac'] > 0 and j['config']['device']['arch'].startswith('gfx950')
+    assert j['x_checksum'] == jf['x_checksum']
 
 
 # ----------------------------------------------------------------------------------------------
@@ -517,7 +543,7 @@ def test_bench_runs_its_collectives_on_rccl_with_one_rank():
     with socket.socket() as so:
         so.bind(('127.0.0.1', 0))
         port = so.getsockname()[1]
-    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--batch', '64', '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
+    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--batch', '64', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline',
             '--sustain-s', '0.2']
     r = subprocess.run(base, env=dict(env_, PNP_BENCH_FORCE_DIST='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port)),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
@@ -534,10 +560,10 @@ def test_bench_runs_its_collectives_on_rccl_with_one_rank():
 
 
 def test_bench_line_carries_parity_and_the_f64_record():
-    """With the CPU legs on, rank 0 of an N = 1 job re-proves parity of the timed run against the oracle (three slices,
+    """With --full and the CPU legs on, rank 0 of an N = 1 job re-proves parity of the timed run against the oracle (three slices,
     W + K iterations) and times the double-precision engine in the same process."""
     env_ = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--batch', '64', '--steps', '8', '--warmup', '2',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--batch', '64', '--steps', '8', '--warmup', '2', '--full',
                         '--cpu-budget', '1', '--sustain-s', '0.5', '--no-pnp-record'], env=env_, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     j = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith('{')][0])
@@ -614,7 +640,7 @@ def test_bench_line_at_512_with_its_cpu_legs():
     """`bench.py --size 512` (the shape of config 5) with the checker legs on: the metric string names the shape, the oracle
     comparison and both CPU baselines run on 512 x 512 data (they once built 256 x 256 phantoms for a 512 x 512 mask)."""
     env_ = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--size', '512', '--batch', '8', '--steps', '2', '--warmup', '1',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--size', '512', '--batch', '8', '--steps', '2', '--warmup', '1', '--full',
                         '--cpu-budget', '0.5', '--sustain-s', '0.2'], env=env_, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     j = json.loads(r.stdout.decode().strip())

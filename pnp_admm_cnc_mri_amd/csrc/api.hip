@@ -478,21 +478,22 @@ static int run_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, d
     return PNP_OK;
 }
 
-// What the next loop call runs (pnp_get_plan): the schedule functions the engines themselves run by.
-struct LoopPlan { int queues, chunk, launches; };
+// What the next loop call runs (pnp_get_plan): the plans the engines themselves run by (loop_schedule.h).
 static LoopPlan loop_plan(const pnp_ctx* c) {
     switch (loop_path(c)) {
-    case Path::generic: return {1, c->B, 3};          // rows, columns, rows
-    case Path::slice:   return {1, c->B, 0};          // one launch per RUN: the iterations are a loop inside it
-    case Path::fused:   break;
+    case Path::generic: break;
+    case Path::slice:   return plan_slice(c->B, c->sched);         // one launch per RUN: the iterations are a loop inside it
+    case Path::fused:
+        switch (c->eng.kind) {
+        case Engine::fused256:  return plan_fused256(c->B, c->sched);
+        case Engine::split_f32: return plan_chunked(c->B, c->sched, Chunked::split_f32);
+        case Engine::split_f64: return plan_chunked(c->B, c->sched, Chunked::split_f64);
+        case Engine::fused512:  return plan_chunked(c->B, c->sched, Chunked::fused512);
+        case Engine::none:      break;
+        }
+        break;
     }
-    if (c->eng.kind == Engine::fused256) {
-        const Fused256Plan p = fused256_plan(c->B, c->sched);
-        return {p.queues, p.chunk, p.launches};
-    }
-    // the split-chain and 512x512 engines: chunked round-robin schedules, two launches per chunk
-    const ChunkPlan p = chunk_plan(c->B, c->sched, c->eng.kind == Engine::fused512, c->eng.kind == Engine::split_f64, c->sched.chunk_queues);
-    return {p.queues, p.chunk < c->B ? p.chunk : c->B, chunk_plan_launches(c->B, p)};
+    return {1, c->B, 3, false, 1, c->B};                             // generic: rows, columns, rows
 }
 
 // the x (the caller's, or the ctx's own) and the ground truth (the caller's device array, or a copy of its host array) of a metric

@@ -11,6 +11,7 @@
 // so input and output have the same "stride-16" distribution, and a forward transform can feed
 // a pointwise stage and an inverse transform with no re-ordering in between.
 #pragma once
+#include "prox_params.h"
 
 #if defined(__HIPCC__)
 #define PNP_HD __host__ __device__ __forceinline__
@@ -256,10 +257,8 @@ PNP_HD void fft512_b2(c32 (&a)[16], const c32* twt) {                  // after 
 // ----------------------------------------------------------------------------------------------
 // z / w updates shared by all kernels (S1:123-126, S4:127-132)
 // ----------------------------------------------------------------------------------------------
-template <typename R>
-struct ProxCoefT {
-    R thr, c1, c2, c3, ib;
-};
+// the scalars are prox_params.h's ProxParamsT; the host emulations (tests/host) name it ProxCoefT
+template <typename R> using ProxCoefT = ProxParamsT<R>;
 using ProxCoef = ProxCoefT<float>;
 
 // clamp(a, -c, c), c >= 0; one v_med3_f32 in float device code
@@ -280,12 +279,12 @@ template <typename R> PNP_HD R soft_thr(R a, R c) {
     const R r = m > 0 ? m : (R)0;
     return a < 0 ? -r : r;
 }
-template <typename R> PNP_HD void prox_l1_pt(R x, R& z, R& w, const ProxCoefT<R>& p) {
+template <typename R> PNP_HD void prox_l1_pt(R x, R& z, R& w, const ProxParamsT<R>& p) {
     const R u = x + w;
     z = soft_thr(u, p.thr);
     w = u - z;
 }
-template <typename R> PNP_HD void prox_cnc_pt(R x, R& z, R& w, const ProxCoefT<R>& p) {
+template <typename R> PNP_HD void prox_cnc_pt(R x, R& z, R& w, const ProxParamsT<R>& p) {
     const R u = x + w;
     const R cz = clamp_sym(z, p.ib);                           // z - soft(z, 1/b)
     const R t = fma_(p.c1, z, fma_(p.c2, u, p.c3 * cz));

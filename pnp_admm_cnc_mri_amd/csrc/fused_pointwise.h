@@ -18,7 +18,7 @@ struct FRowArgsT {
     R* x_out;
     int B;
     R scale;            // 1 / (H W)
-    ProxCoefT<R> prox;
+    ProxParamsT<R> prox;
     int u_first;        // PROX 3: 1 while the w buffer still holds a genuine w
 };
 using FRowArgs = FRowArgsT<float>;

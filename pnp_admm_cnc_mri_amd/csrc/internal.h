@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include "loop_schedule.h"
+#include "prox_params.h"
 
 namespace pnp {
 
@@ -11,17 +13,6 @@ namespace pnp {
 template <typename R> struct CxOf;
 template <> struct CxOf<float>  { using type = float2; };
 template <> struct CxOf<double> { using type = double2; };
-
-// Scalars of the z/w update, pre-combined on the host in double and rounded once to R.
-template <typename R>
-struct ProxParamsT {
-    R thr;      // L1: reo*lambda1            CNC: alpha*reo*lambda1   (outer soft threshold)
-    R c1;       // CNC: 1-alpha
-    R c2;       // CNC: alpha
-    R c3;       // CNC: alpha*reo*lambda1*b
-    R ib;       // CNC: 1/b   (inner clip level: z - soft(z,1/b) == clip(z,-1/b,1/b))
-};
-using ProxParams = ProxParamsT<float>;
 
 enum RowIn  { IN_COMPLEX = 0, IN_REAL = 1, IN_REAL_DIFF = 2 };
 enum RowEpi { EPI_COMPLEX = 0, EPI_ABS_REAL = 1, EPI_ABS_COMPLEX = 2, EPI_L1 = 3, EPI_CNC = 4 };
@@ -114,58 +105,6 @@ hipError_t launch_conv3x3_head(hipStream_t s, const float* x_nchw, const float* 
                                int n, int cin, int H, int W, int relu);
 hipError_t launch_conv3x3_tail(hipStream_t s, const float* x_nhwc, const float* w_oihw, const float* bias, float* y_nchw,
                                int n, int cout, int H, int W);
-
-// How the fused loops are scheduled (scheduling only: results are bit-identical for every setting).
-struct FusedSchedule {
-    int queues = 2;         // HIP queues the batch is split over (1..4); kernel heads/tails overlap
-    int mixed = 0;          // 256x256: row workgroups of one half + column workgroups of the other per launch (k_fmixed)
-    int chunk = 0;          // >0: a queue finishes all iterations on `chunk` slices before its next chunk; 0: the path's default
-                            // (chunk_plan below); <0: off (whole batch / two halves)
-    int l1_two_state = 0;   // test hook: ADMM_L1 keeps z and w every iteration instead of u only
-    // Experiment knobs.  They stay at these defaults unless the library is built with -DPNP_EXPERIMENT_KNOBS (profiles/variants.sh
-    // does); such a build reads them from the environment ONCE, at pnp_ctx_create (api.hip, read_knobs), range-checked.
-    int chunk_queues = 0;   // >0: queues of the chunked schedules           (PNP_F512_QUEUES / PNP_F256S_QUEUES)
-    int slice_xor = 0;      // slice <-> workgroup permutation b ^ xor          (PNP_SLICE_XOR)
-    int slice_queues = 1;   // slice-resident run cut over HIP queues ...       (PNP_SLICE_QUEUES)
-    int slice_segment = 0;  // ... and into launches of this many iterations    (PNP_SLICE_SEGMENT)
-    int slice_flip = 1;     // every other multi-round call walks the batch backwards (PNP_SLICE_FLIP)
-};
-
-// Chunked schedules of the 512x512 loops and of the split-chain (double) 256x256 loops: a queue runs ALL iterations of a run on
-// `chunk` slices before its next chunk, and the chunks go round-robin to Q queues -- Q chunks in flight, whose working set
-// (Q * chunk * 4 MiB at 512x512, * 2.5 MiB in double) stays around the 256 MiB Infinity Cache and whose kernel tails overlap
-// each other's heads.  Measured on one box each (it/s; profiles/bench_r02):
-//   512x512, 256 slices: whole batch 1057-1171 (a slow mode on some boxes), 1 x 48: 1161-1172, 2 x 32: 1338, 3 x 24: 1360,
-//                        4 x 16: 1358, 4 x 24: 1361, 4 x 8: 1244
-//   double, 512 slices:  two halves on two queues 2186-2400, 1 x 96: 2423, 2 x 48: 2563, 3 x 32: 2570, 4 x 24: 2573, 4 x 64: 2436
-struct ChunkPlan {
-    int queues, chunk;      // chunk == B and queues == 1: the whole batch at once
-};
-static inline ChunkPlan chunk_plan(int B, const FusedSchedule& sch, bool is512, bool is_double, int env_queues /* <=0: none */) {
-    ChunkPlan p;
-    p.queues = env_queues > 0 ? env_queues : (sch.queues >= 2 ? 4 : 1);
-    if (p.queues > 4) p.queues = 4;
-    const int dflt = is512 ? (p.queues >= 2 ? 16 : 48) : (is_double ? (p.queues >= 2 ? 24 : 96) : 0);
-    p.chunk = sch.chunk != 0 ? sch.chunk : dflt;
-    if (p.chunk <= 0) {                                     // off
-        if (!is512 && sch.queues >= 2 && B >= 64) { p.queues = 2; p.chunk = ((B / 2) + 1) & ~1; }     // two halves (round 1)
-        else { p.queues = 1; p.chunk = B; }
-    }
-    p.chunk &= ~1;
-    if (p.chunk < 2) p.chunk = 2;
-    if (p.chunk >= B) { p.chunk = B > 2 ? ((B + 1) & ~1) : 2; p.queues = 1; }
-    return p;
-}
-static inline int chunk_plan_launches(int B, const ChunkPlan& p) { return 2 * ((B + p.chunk - 1) / p.chunk); }
-
-// The schedule fused256_run gives a batch of B slices -- the run follows it and pnp_get_plan reports it.
-struct Fused256Plan {
-    int queues;     // parts of the batch, one per HIP queue (1: the whole batch on the caller's queue)
-    int chunk;      // slices per sequential chunk (B: one chunk)
-    int launches;   // kernel launches per iteration
-    bool mixed;     // parts of at least 64 slices take the staggered mixed launches (k_fmixed)
-};
-Fused256Plan fused256_plan(int B, const FusedSchedule& sch);
 
 // fused 256x256 path (kernels_fused256.hip): state resident in the ctx, two slices packed into
 // one complex transform.  See DESIGN.md.

@@ -24,9 +24,8 @@
 // The W256 twiddle table is staged in LDS and read where used; keeping it in 32 VGPRs cost a wave
 // per SIMD.  Everything is compiled with -ffp-contract=off and explicit fmaf (fft16.h), so all
 // kernel variants and schedules round identically.
-#include "internal.h"
+#include "engine_host.h"
 #include "fused_layout.h"
-#include "fused_pointwise.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -37,26 +36,6 @@ __device__ c64 g_twd[256];
 template <typename R> __device__ __forceinline__ const cxT<R>* tw_table();
 template <> __device__ __forceinline__ const c32* tw_table<float>() { return g_twf; }
 template <> __device__ __forceinline__ const c64* tw_table<double>() { return g_twd; }
-
-struct Fused256 {
-    int Bmax = 0, np = 0;
-    c32* T = nullptr;
-    float4* Yh = nullptr;
-    unsigned long long* Mh = nullptr;
-    // extra queues: parts of the batch run their whole K-iteration chains concurrently, so the
-    // bandwidth-bound row kernel of one part fills the memory-idle phases of another part's
-    // column kernel (slices are independent; results do not depend on the split)
-    static constexpr int MAXQ = 4;
-    hipStream_t side[MAXQ - 1] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr;
-    hipEvent_t ev_join[MAXQ - 1] = {nullptr, nullptr, nullptr};
-};
-
-static inline ProxCoef to_coef(const ProxParams& p) {
-    ProxCoef c;
-    c.thr = p.thr; c.c1 = p.c1; c.c2 = p.c2; c.c3 = p.c3; c.ib = p.ib;
-    return c;
-}
 
 // ------------------------------------------------------------------------------------------
 // table preparation (once per uploaded problem)
@@ -349,6 +328,32 @@ __global__ __launch_bounds__(256) void k_fmixed(FRowArgs pr, FColArgs pc, int nR
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+template <typename R, typename K>
+static hipError_t launch_frows(K, hipStream_t s, int np, const FRowArgsT<R>& a) {
+    hipLaunchKernelGGL((k_frows<R, K::inv, K::prox, K::fwd, K::write_x>), dim3(np * 16), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+struct Fused256 {
+    static constexpr size_t N = 65536;
+    int Bmax = 0, np = 0;
+    c32* T = nullptr;
+    float4* Yh = nullptr;
+    unsigned long long* Mh = nullptr;
+    // extra queues: parts of the batch run their whole K-iteration chains concurrently, so the bandwidth-bound row kernel of one
+    // part fills the memory-idle phases of another part's column kernel (slices are independent; results do not depend on the split)
+    SideQueues queues;
+
+    FColArgs col_args(int pair0, float c) const {
+        return {T + (size_t)pair0 * 65536, Yh + (size_t)pair0 * YH_PAIR, Mh + (size_t)pair0 * MH_PAIR, c};
+    }
+    template <typename K> hipError_t rows(K k, hipStream_t s, int pairs, const FRowArgs& a) const { return launch_frows(k, s, pairs, a); }
+    hipError_t cols(hipStream_t s, int pair0, int pairs, float c) const {
+        hipLaunchKernelGGL(k_fcols, dim3(pairs * 9), dim3(256), 0, s, col_args(pair0, c));
+        return hipGetLastError();
+    }
+};
+
 Fused256* fused256_create(int Bmax, hipError_t* err) {
     Fused256* f = new Fused256();
     f->Bmax = Bmax;
@@ -356,14 +361,7 @@ Fused256* fused256_create(int Bmax, hipError_t* err) {
     hipError_t e = hipMalloc((void**)&f->T, (size_t)f->np * 65536 * sizeof(c32));
     if (e == hipSuccess) e = hipMalloc((void**)&f->Yh, (size_t)f->np * YH_PAIR * sizeof(float4));
     if (e == hipSuccess) e = hipMalloc((void**)&f->Mh, (size_t)f->np * MH_PAIR * sizeof(unsigned long long));
-    if (e == hipSuccess) {
-        static thread_local c32 h[256];
-        for (int m = 0; m < 256; ++m) {
-            const double a = -2.0 * M_PI * (double)m / 256.0;
-            h[m] = mk((float)cos(a), (float)sin(a));
-        }
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_twf), h, sizeof(h));
-    }
+    if (e == hipSuccess) e = upload_twiddle_table<float>(HIP_SYMBOL(g_twf), 256);
     if (e != hipSuccess) {
         fused256_destroy(f);
         *err = e;
@@ -378,11 +376,6 @@ void fused256_destroy(Fused256* f) {
     if (f->T) (void)hipFree(f->T);
     if (f->Yh) (void)hipFree(f->Yh);
     if (f->Mh) (void)hipFree(f->Mh);
-    for (int q = 0; q < Fused256::MAXQ - 1; ++q) {
-        if (f->side[q]) (void)hipStreamDestroy(f->side[q]);
-        if (f->ev_join[q]) (void)hipEventDestroy(f->ev_join[q]);
-    }
-    if (f->ev_fork) (void)hipEventDestroy(f->ev_fork);
     delete f;
 }
 
@@ -395,89 +388,6 @@ hipError_t fused256_prepare(Fused256* f, hipStream_t s, const float2* y, const u
     return hipGetLastError();
 }
 
-template <bool HAS_INV, int PROX, bool HAS_FWD, bool WRITE_X>
-static hipError_t launch_frows(hipStream_t s, int np, const FRowArgs& a) {
-    hipLaunchKernelGGL((k_frows<float, HAS_INV, PROX, HAS_FWD, WRITE_X>), dim3(np * 16), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-static FColArgs col_args(Fused256* f, int pair0, float c) {
-    FColArgs a;
-    a.T = f->T + (size_t)pair0 * 65536;
-    a.Yh = f->Yh + (size_t)pair0 * YH_PAIR;
-    a.Mh = f->Mh + (size_t)pair0 * MH_PAIR;
-    a.c = c;
-    return a;
-}
-
-static hipError_t launch_fcols(Fused256* f, hipStream_t s, int pair0, int np, float c) {
-    const FColArgs a = col_args(f, pair0, c);
-    hipLaunchKernelGGL(k_fcols, dim3(np * 9), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-// K iterations on slices [c0, c0+Bc) enqueued on stream s
-static hipError_t run_chunk(Fused256* f, hipStream_t s, float* z, float* w, float* x, int c0, int Bc, int iters,
-                            int prox, float dc_c, const ProxParams& pp) {
-    const int np = (Bc + 1) / 2, pair0 = c0 / 2;
-    const size_t so = (size_t)c0 * 65536;
-    FRowArgs a;
-    a.T = f->T + (size_t)pair0 * 65536;
-    a.z_in = z + so; a.w_in = w + so; a.z_out = z + so; a.w_out = w + so; a.x_out = x + so; a.B = Bc;
-    a.scale = 1.0f / 65536.0f; a.prox = to_coef(pp); a.u_first = 1;
-    hipError_t e = launch_frows<false, 0, true, false>(s, np, a);
-    for (int i = 0; i < iters && e == hipSuccess; ++i) {
-        e = launch_fcols(f, s, pair0, np, dc_c);
-        if (e != hipSuccess) break;
-        const bool last = (i == iters - 1);
-        a.u_first = (i == 0);
-        if (prox == 2)      e = last ? launch_frows<true, 2, false, true>(s, np, a) : launch_frows<true, 2, true, false>(s, np, a);
-        else if (prox == 1) e = last ? launch_frows<true, 1, false, true>(s, np, a) : launch_frows<true, 1, true, false>(s, np, a);
-        else                e = last ? launch_frows<true, 3, false, true>(s, np, a) : launch_frows<true, 3, true, false>(s, np, a);
-    }
-    return e;
-}
-
-static FRowArgs row_args(Fused256* f, float* z, float* w, float* x, int c0, int Bc, const ProxParams& pp) {
-    const size_t so = (size_t)c0 * 65536;
-    FRowArgs a;
-    a.T = f->T + (size_t)(c0 / 2) * 65536;
-    a.z_in = z + so; a.w_in = w + so; a.z_out = z + so; a.w_out = w + so; a.x_out = x + so; a.B = Bc;
-    a.scale = 1.0f / 65536.0f; a.prox = to_coef(pp); a.u_first = 1;
-    return a;
-}
-
-template <bool HAS_INV, int PROX, bool HAS_FWD, bool WRITE_X>
-static hipError_t launch_mixed_t(hipStream_t s, const FRowArgs& ra, int npR, const FColArgs& ca, int npC) {
-    const int nR = npR * 16, nC = npC * 9;
-    hipLaunchKernelGGL((k_fmixed<HAS_INV, PROX, HAS_FWD, WRITE_X>), dim3(nR + nC), dim3(256), 0, s, ra, ca, nR, nC);
-    return hipGetLastError();
-}
-
-// kind: 0 = first (forward only), 1 = mid, 2 = last;  prox: 1 L1 two-state, 2 CNC, 3 L1 single-state
-static hipError_t launch_mixed(hipStream_t s, int kind, int prox, const FRowArgs& ra, int npR, const FColArgs& ca, int npC) {
-    if (kind == 0) return launch_mixed_t<false, 0, true, false>(s, ra, npR, ca, npC);
-    if (kind == 1) {
-        if (prox == 2) return launch_mixed_t<true, 2, true, false>(s, ra, npR, ca, npC);
-        if (prox == 3) return launch_mixed_t<true, 3, true, false>(s, ra, npR, ca, npC);
-        return launch_mixed_t<true, 1, true, false>(s, ra, npR, ca, npC);
-    }
-    if (prox == 2) return launch_mixed_t<true, 2, false, true>(s, ra, npR, ca, npC);
-    if (prox == 3) return launch_mixed_t<true, 3, false, true>(s, ra, npR, ca, npC);
-    return launch_mixed_t<true, 1, false, true>(s, ra, npR, ca, npC);
-}
-static hipError_t launch_rows_kind(hipStream_t s, int kind, int prox, const FRowArgs& ra, int np) {
-    if (kind == 0) return launch_frows<false, 0, true, false>(s, np, ra);
-    if (kind == 1) {
-        if (prox == 2) return launch_frows<true, 2, true, false>(s, np, ra);
-        if (prox == 3) return launch_frows<true, 3, true, false>(s, np, ra);
-        return launch_frows<true, 1, true, false>(s, np, ra);
-    }
-    if (prox == 2) return launch_frows<true, 2, false, true>(s, np, ra);
-    if (prox == 3) return launch_frows<true, 3, false, true>(s, np, ra);
-    return launch_frows<true, 1, false, true>(s, np, ra);
-}
-
 // Staggered schedule over two halves A, B of the batch (slices are independent):
 //   F(A) | C0(A)+F(B) | R0(A)+C0(B) | C1(A)+R0(B) | ... | R_{K-1}(A)+C_{K-1}(B) | R_{K-1}(B)
 // every '+' is ONE mixed launch (k_fmixed): row workgroups of one half next to column workgroups
@@ -486,80 +396,45 @@ static hipError_t run_mixed(Fused256* f, hipStream_t s, float* z, float* w, floa
                             int prox, float dc_c, const ProxParams& pp) {
     const int BA = ((B / 2) + 1) & ~1, BB = B - BA;
     const int npA = BA / 2, npB = (BB + 1) / 2;
-    FRowArgs ra = row_args(f, z, w, x, c0, BA, pp), rb = row_args(f, z, w, x, c0 + BA, BB, pp);
-    const FColArgs ca = col_args(f, c0 / 2, dc_c), cb = col_args(f, c0 / 2 + npA, dc_c);
-    hipError_t e = launch_rows_kind(s, 0, prox, ra, npA);                         // F(A)
-    if (e == hipSuccess) e = launch_mixed(s, 0, prox, rb, npB, ca, npA);           // C0(A) + F(B)
+    FRowArgs ra = chain_row_args(f, z, w, z, w, x, c0, BA, pp), rb = chain_row_args(f, z, w, z, w, x, c0 + BA, BB, pp);
+    const FColArgs ca = f->col_args(c0 / 2, dc_c), cb = f->col_args(c0 / 2 + npA, dc_c);
+    auto rows = [&](Stage st, const FRowArgs& r, int np) {
+        return with_row_kind(st, prox, [&](auto k) { return launch_frows(k, s, np, r); });
+    };
+    auto mixed = [&](Stage st, const FRowArgs& r, int npR, const FColArgs& c, int npC) {
+        return with_row_kind<false>(st, prox, [&](auto k) {
+            using K = decltype(k);
+            hipLaunchKernelGGL((k_fmixed<K::inv, K::prox, K::fwd, K::write_x>), dim3(npR * 16 + npC * 9), dim3(256), 0, s,
+                               r, c, npR * 16, npC * 9);
+            return hipGetLastError();
+        });
+    };
+    hipError_t e = rows(Stage::first, ra, npA);                                     // F(A)
+    if (e == hipSuccess) e = mixed(Stage::first, rb, npB, ca, npA);                  // C0(A) + F(B)
     for (int i = 0; i < iters && e == hipSuccess; ++i) {
         const bool last = (i == iters - 1);
         ra.u_first = rb.u_first = (i == 0);
-        e = launch_mixed(s, last ? 2 : 1, prox, ra, npA, cb, npB);                 // R_i(A) + C_i(B)
+        e = mixed(last ? Stage::last : Stage::mid, ra, npA, cb, npB);              // R_i(A) + C_i(B)
         if (e != hipSuccess) break;
-        if (!last) e = launch_mixed(s, 1, prox, rb, npB, ca, npA);                 // C_{i+1}(A) + R_i(B)
-        else       e = launch_rows_kind(s, 2, prox, rb, npB);                      // R_{K-1}(B)
+        if (!last) e = mixed(Stage::mid, rb, npB, ca, npA);                        // C_{i+1}(A) + R_i(B)
+        else       e = rows(Stage::last, rb, npB);                                 // R_{K-1}(B)
     }
     return e;
-}
-
-// Slices are independent, so the K-iteration chains of different parts of the batch may run on
-// different queues, share launches (run_mixed) or run one chunk after another (chunk*(z,w,T,Yh)
-// <= the 256 MiB Infinity Cache keeps a chunk's working set on die; measured +-2 %).
-Fused256Plan fused256_plan(int B, const FusedSchedule& sch) {
-    const int queues = sch.queues < 1 ? 1 : (sch.queues > Fused256::MAXQ ? Fused256::MAXQ : sch.queues);
-    if (sch.chunk > 0) {                                                  // one queue, one chunk after another
-        const int chunk = (sch.chunk & ~1) < 2 ? 2 : (sch.chunk & ~1);
-        if (chunk < B) return {1, chunk, 2 * ((B + chunk - 1) / chunk), false};
-        return {1, B, 2, false};
-    }
-    if (queues >= 2 && B >= 32 * queues) return {queues, B, 2 * queues, sch.mixed != 0};
-    return {1, B, 2, queues == 1 && sch.mixed != 0};
 }
 
 hipError_t fused256_run(Fused256* f, hipStream_t s, float* z, float* w, float* x, int B, int iters, bool cnc,
                         float dc_c, ProxParams pp, const FusedSchedule& sch) {
     if (iters <= 0) return hipSuccess;
-    const int prox = cnc ? 2 : (sch.l1_two_state ? 1 : 3);
-    const Fused256Plan plan = fused256_plan(B, sch);
-    if (plan.queues >= 2) {
-        const int queues = plan.queues;
-        hipError_t e = hipSuccess;
-        if (!f->ev_fork) e = hipEventCreateWithFlags(&f->ev_fork, hipEventDisableTiming);
-        for (int q = 0; q < queues - 1 && e == hipSuccess; ++q) {
-            if (f->side[q]) continue;
-            e = hipStreamCreateWithFlags(&f->side[q], hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_join[q], hipEventDisableTiming);
-        }
-        if (e != hipSuccess) return e;
-        e = hipEventRecord(f->ev_fork, s);
-        int c0 = 0;
-        for (int q = 0; q < queues && e == hipSuccess; ++q) {
-            const int Bq = (q == queues - 1) ? (B - c0) : (((B / queues) + 1) & ~1);     // even-sized parts
-            hipStream_t sq = (q == 0) ? s : f->side[q - 1];
-            if (q > 0) e = hipStreamWaitEvent(sq, f->ev_fork, 0);
-            if (e == hipSuccess) e = (plan.mixed && Bq >= 64) ? run_mixed(f, sq, z, w, x, c0, Bq, iters, prox, dc_c, pp)
-                                                               : run_chunk(f, sq, z, w, x, c0, Bq, iters, prox, dc_c, pp);
-            if (q > 0 && e == hipSuccess) e = hipEventRecord(f->ev_join[q - 1], sq);
-            if (q > 0 && e == hipSuccess) e = hipStreamWaitEvent(s, f->ev_join[q - 1], 0);
-            c0 += Bq;
-        }
-        return e;
-    }
-    if (plan.mixed && B >= 64) return run_mixed(f, s, z, w, x, 0, B, iters, prox, dc_c, pp);
-    hipError_t e = hipSuccess;
-    for (int c0 = 0; c0 < B && e == hipSuccess; c0 += plan.chunk)
-        e = run_chunk(f, s, z, w, x, c0, (B - c0 < plan.chunk) ? (B - c0) : plan.chunk, iters, prox, dc_c, pp);
-    return e;
+    const int prox = prox_kind(cnc, sch);
+    const LoopPlan plan = plan_fused256(B, sch);
+    return run_parts(f->queues, s, plan, B, [&](hipStream_t sq, const Part& p) {
+        if (takes_mixed(plan, p)) return run_mixed(f, sq, z, w, x, p.first, p.count, iters, prox, dc_c, pp);
+        return chain_part(f, sq, chain_row_args(f, z, w, z, w, x, p.first, p.count, pp), p.first, p.count, iters, prox, dc_c);
+    });
 }
 
 hipError_t fused256_dc(Fused256* f, hipStream_t s, const float* z, const float* w, float* x, int B, float dc_c) {
-    const int np = (B + 1) / 2;
-    FRowArgs a;
-    a.T = f->T; a.z_in = z; a.w_in = w; a.z_out = nullptr; a.w_out = nullptr; a.x_out = x; a.B = B;
-    a.scale = 1.0f / 65536.0f; a.prox = ProxCoef{}; a.u_first = 1;
-    hipError_t e = launch_frows<false, 0, true, false>(s, np, a);
-    if (e == hipSuccess) e = launch_fcols(f, s, 0, np, dc_c);
-    if (e == hipSuccess) e = launch_frows<true, 0, false, true>(s, np, a);
-    return e;
+    return chain_dc(f, s, z, w, x, B, dc_c);
 }
 
 
@@ -714,16 +589,22 @@ __global__ __launch_bounds__(256) void k_fcols2(FCol2Args<R> p) {
     }
 }
 
-// engine on the split-chain kernels: sequential rows / columns launches over `queues` HIP queues
+// engine on the split-chain kernels: sequential rows / columns launches, chunks over queues (plan_chunked)
 template <typename R>
 struct Fused256S {
+    static constexpr size_t N = 65536;
     int Bmax = 0, np = 0;
     cxT<R>* T = nullptr;
     cxT<R>* Yh = nullptr;
     uint32_t* Mh = nullptr;
-    static constexpr int MAXQ2 = 4;
-    hipStream_t side[MAXQ2] = {};             // further queues; [0] unused
-    hipEvent_t ev_fork = nullptr, ev_join[MAXQ2] = {};
+    SideQueues queues;
+
+    template <typename K> hipError_t rows(K k, hipStream_t s, int pairs, const FRowArgsT<R>& a) const { return launch_frows(k, s, pairs, a); }
+    hipError_t cols(hipStream_t s, int pair0, int pairs, R c) const {
+        const FCol2Args<R> a{T + (size_t)pair0 * 65536, Yh + (size_t)pair0 * YH2_PAIR, Mh + (size_t)pair0 * MH2_PAIR, c};
+        hipLaunchKernelGGL(k_fcols2<R>, dim3(pairs * F2_TILES), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
 };
 
 template <typename R>
@@ -732,11 +613,6 @@ void fused256s_destroy(Fused256S<R>* f) {
     if (f->T) (void)hipFree(f->T);
     if (f->Yh) (void)hipFree(f->Yh);
     if (f->Mh) (void)hipFree(f->Mh);
-    for (int q = 1; q < Fused256S<R>::MAXQ2; ++q) {
-        if (f->side[q]) (void)hipStreamDestroy(f->side[q]);
-        if (f->ev_join[q]) (void)hipEventDestroy(f->ev_join[q]);
-    }
-    if (f->ev_fork) (void)hipEventDestroy(f->ev_fork);
     delete f;
 }
 
@@ -748,17 +624,8 @@ Fused256S<R>* fused256s_create(int Bmax, hipError_t* err) {
     hipError_t e = hipMalloc((void**)&f->T, (size_t)f->np * 65536 * sizeof(cxT<R>));
     if (e == hipSuccess) e = hipMalloc((void**)&f->Yh, (size_t)f->np * YH2_PAIR * sizeof(cxT<R>));
     if (e == hipSuccess) e = hipMalloc((void**)&f->Mh, (size_t)f->np * MH2_PAIR * sizeof(uint32_t));
-    if (e == hipSuccess) {
-        static thread_local c32 hf[256];
-        static thread_local c64 hd[256];
-        for (int m = 0; m < 256; ++m) {
-            const double a = -2.0 * M_PI * (double)m / 256.0;
-            hd[m] = mk<double>(cos(a), sin(a));
-            hf[m] = mk<float>((float)cos(a), (float)sin(a));
-        }
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_twf), hf, sizeof(hf));
-        if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_twd), hd, sizeof(hd));
-    }
+    if (e == hipSuccess) e = upload_twiddle_table<float>(HIP_SYMBOL(g_twf), 256);
+    if (e == hipSuccess) e = upload_twiddle_table<double>(HIP_SYMBOL(g_twd), 256);
     if (e != hipSuccess) {
         fused256s_destroy(f);
         *err = e;
@@ -778,99 +645,16 @@ hipError_t fused256s_prepare(Fused256S<R>* f, hipStream_t s, const void* y, cons
     return hipGetLastError();
 }
 
-template <typename R, bool HAS_INV, int PROX, bool HAS_FWD, bool WRITE_X>
-static hipError_t launch_frows_t(hipStream_t s, int np, const FRowArgsT<R>& a) {
-    hipLaunchKernelGGL((k_frows<R, HAS_INV, PROX, HAS_FWD, WRITE_X>), dim3(np * 16), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-template <typename R>
-static hipError_t launch_fcols2(Fused256S<R>* f, hipStream_t s, int pair0, int np, R c) {
-    FCol2Args<R> a;
-    a.T = f->T + (size_t)pair0 * 65536;
-    a.Yh = f->Yh + (size_t)pair0 * YH2_PAIR;
-    a.Mh = f->Mh + (size_t)pair0 * MH2_PAIR;
-    a.c = c;
-    hipLaunchKernelGGL(k_fcols2<R>, dim3(np * F2_TILES), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-template <typename R>
-static ProxCoefT<R> to_coef_t(const ProxParamsT<R>& p) {
-    ProxCoefT<R> c;
-    c.thr = p.thr; c.c1 = p.c1; c.c2 = p.c2; c.c3 = p.c3; c.ib = p.ib;
-    return c;
-}
-
-// K iterations on slices [c0, c0 + Bc) enqueued on stream s
-template <typename R>
-static hipError_t run_chunk2(Fused256S<R>* f, hipStream_t s, R* z, R* w, R* x, int c0, int Bc, int iters, int prox, R dc_c,
-                             const ProxParamsT<R>& pp) {
-    const int np = (Bc + 1) / 2, pair0 = c0 / 2;
-    const size_t so = (size_t)c0 * 65536;
-    FRowArgsT<R> a;
-    a.T = f->T + (size_t)pair0 * 65536;
-    a.z_in = z + so; a.w_in = w + so; a.z_out = z + so; a.w_out = w + so; a.x_out = x + so; a.B = Bc;
-    a.scale = (R)(1.0 / 65536.0); a.prox = to_coef_t<R>(pp); a.u_first = 1;
-    hipError_t e = launch_frows_t<R, false, 0, true, false>(s, np, a);
-    for (int i = 0; i < iters && e == hipSuccess; ++i) {
-        e = launch_fcols2<R>(f, s, pair0, np, dc_c);
-        if (e != hipSuccess) break;
-        const bool last = (i == iters - 1);
-        a.u_first = (i == 0);
-        if (prox == 2)      e = last ? launch_frows_t<R, true, 2, false, true>(s, np, a) : launch_frows_t<R, true, 2, true, false>(s, np, a);
-        else if (prox == 1) e = last ? launch_frows_t<R, true, 1, false, true>(s, np, a) : launch_frows_t<R, true, 1, true, false>(s, np, a);
-        else                e = last ? launch_frows_t<R, true, 3, false, true>(s, np, a) : launch_frows_t<R, true, 3, true, false>(s, np, a);
-    }
-    return e;
-}
-
 template <typename R>
 hipError_t fused256s_run(Fused256S<R>* f, hipStream_t s, R* z, R* w, R* x, int B, int iters, bool cnc, R dc_c,
                          ProxParamsT<R> pp, const FusedSchedule& sch) {
-    if (iters <= 0) return hipSuccess;
-    const int prox = cnc ? 2 : (sch.l1_two_state ? 1 : 3);
-    // chunked round-robin schedule: internal.h, chunk_plan.  sch.chunk < 0 (PNP_FUSED_CHUNK=-1): two halves of the batch on
-    // two queues (the round-1 schedule); sch.chunk_queues overrides the number of queues (experiment builds).
-    const ChunkPlan plan = chunk_plan(B, sch, false, sizeof(R) == 8, sch.chunk_queues);
-    const int Q = plan.queues, chunk = plan.chunk;
-    hipError_t e = hipSuccess;
-    if (Q < 2 || B <= chunk) {
-        for (int c0 = 0; c0 < B && e == hipSuccess; c0 += chunk)
-            e = run_chunk2<R>(f, s, z, w, x, c0, (B - c0 < chunk) ? (B - c0) : chunk, iters, prox, dc_c, pp);
-        return e;
-    }
-    if (!f->ev_fork) e = hipEventCreateWithFlags(&f->ev_fork, hipEventDisableTiming);
-    for (int q = 1; q < Q && e == hipSuccess; ++q) {
-        if (!f->side[q]) {
-            e = hipStreamCreateWithFlags(&f->side[q], hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_join[q], hipEventDisableTiming);
-        }
-    }
-    if (e != hipSuccess) return e;
-    e = hipEventRecord(f->ev_fork, s);
-    for (int q = 1; q < Q && e == hipSuccess; ++q) e = hipStreamWaitEvent(f->side[q], f->ev_fork, 0);
-    int k = 0;
-    for (int c0 = 0; c0 < B && e == hipSuccess; c0 += chunk, ++k) {
-        const int q = k % Q;
-        e = run_chunk2<R>(f, q ? f->side[q] : s, z, w, x, c0, (B - c0 < chunk) ? (B - c0) : chunk, iters, prox, dc_c, pp);
-    }
-    for (int q = 1; q < Q && e == hipSuccess; ++q) {
-        e = hipEventRecord(f->ev_join[q], f->side[q]);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s, f->ev_join[q], 0);
-    }
-    return e;
+    const LoopPlan plan = plan_chunked(B, sch, sizeof(R) == 8 ? Chunked::split_f64 : Chunked::split_f32);
+    return chain_run(f, s, z, w, x, B, iters, prox_kind(cnc, sch), dc_c, pp, plan);
 }
 
 template <typename R>
 hipError_t fused256s_dc(Fused256S<R>* f, hipStream_t s, const R* z, const R* w, R* x, int B, R dc_c) {
-    const int np = (B + 1) / 2;
-    FRowArgsT<R> a;
-    a.T = f->T; a.z_in = z; a.w_in = w; a.z_out = nullptr; a.w_out = nullptr; a.x_out = x; a.B = B;
-    a.scale = (R)(1.0 / 65536.0); a.prox = ProxCoefT<R>{}; a.u_first = 1;
-    hipError_t e = launch_frows_t<R, false, 0, true, false>(s, np, a);
-    if (e == hipSuccess) e = launch_fcols2<R>(f, s, 0, np, dc_c);
-    if (e == hipSuccess) e = launch_frows_t<R, true, 0, false, true>(s, np, a);
-    return e;
+    return chain_dc(f, s, z, w, x, B, dc_c);
 }
 
 #define PNP_INSTANTIATE_F256S(R)                                                                                     \

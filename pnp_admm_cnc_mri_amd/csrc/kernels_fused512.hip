@@ -10,9 +10,8 @@
 //             accesses are 16-byte {P,Q} elements in 128-byte row segments; the radix-2 partner
 //             is lane^8 (DPP row_ror:8)
 // HBM bytes per slice-iteration: 36 N, as at 256x256.
-#include "internal.h"
+#include "engine_host.h"
 #include "fused_layout.h"
-#include "fused_pointwise.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -27,23 +26,7 @@ namespace pnp {
 
 __device__ c32 g_tw512f[512];
 
-struct Fused512 {
-    int Bmax = 0, np = 0;
-    c32* T = nullptr;
-    float4* Yh = nullptr;
-    unsigned long long* Mh = nullptr;
-    static constexpr int MAXQ = 4;
-    hipStream_t side[MAXQ] = {};              // further queues of the chunked schedule (fused512_run); [0] unused
-    hipEvent_t ev_fork = nullptr, ev_join[MAXQ] = {};
-};
-
 constexpr int NN5 = 512 * 512;
-
-static inline ProxCoef to_coef5(const ProxParams& p) {
-    ProxCoef c;
-    c.thr = p.thr; c.c1 = p.c1; c.c2 = p.c2; c.c3 = p.c3; c.ib = p.ib;
-    return c;
-}
 
 __device__ __forceinline__ float dpp_quad_swap1(float v) {      // lane ^ 1
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true));
@@ -319,6 +302,25 @@ __global__ __launch_bounds__(256) void k5_cols(F5ColArgs p) {
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+struct Fused512 {
+    static constexpr size_t N = NN5;
+    int Bmax = 0, np = 0;
+    c32* T = nullptr;
+    float4* Yh = nullptr;
+    unsigned long long* Mh = nullptr;
+    SideQueues queues;              // further queues of the chunked schedule (plan_chunked)
+
+    template <typename K> hipError_t rows(K, hipStream_t s, int pairs, const FRowArgs& a) const {
+        hipLaunchKernelGGL((k5_rows<K::inv, K::prox, K::fwd, K::write_x>), dim3(pairs * 64), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
+    hipError_t cols(hipStream_t s, int pair0, int pairs, float c) const {
+        const F5ColArgs a{T + (size_t)pair0 * NN5, Yh + (size_t)pair0 * YH5_PAIR, Mh + (size_t)pair0 * MH5_PAIR, c};
+        hipLaunchKernelGGL(k5_cols, dim3(pairs * 33), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
+};
+
 Fused512* fused512_create(int Bmax, hipError_t* err) {
     Fused512* f = new Fused512();
     f->Bmax = Bmax;
@@ -326,14 +328,7 @@ Fused512* fused512_create(int Bmax, hipError_t* err) {
     hipError_t e = hipMalloc((void**)&f->T, (size_t)f->np * NN5 * sizeof(c32));
     if (e == hipSuccess) e = hipMalloc((void**)&f->Yh, (size_t)f->np * YH5_PAIR * sizeof(float4));
     if (e == hipSuccess) e = hipMalloc((void**)&f->Mh, (size_t)f->np * MH5_PAIR * sizeof(unsigned long long));
-    if (e == hipSuccess) {
-        static thread_local c32 h[512];
-        for (int m = 0; m < 512; ++m) {
-            const double a = -2.0 * M_PI * (double)m / 512.0;
-            h[m] = mk((float)cos(a), (float)sin(a));
-        }
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_tw512f), h, sizeof(h));
-    }
+    if (e == hipSuccess) e = upload_twiddle_table<float>(HIP_SYMBOL(g_tw512f), 512);
     if (e != hipSuccess) {
         fused512_destroy(f);
         *err = e;
@@ -348,11 +343,6 @@ void fused512_destroy(Fused512* f) {
     if (f->T) (void)hipFree(f->T);
     if (f->Yh) (void)hipFree(f->Yh);
     if (f->Mh) (void)hipFree(f->Mh);
-    for (int q = 1; q < Fused512::MAXQ; ++q) {
-        if (f->side[q]) (void)hipStreamDestroy(f->side[q]);
-        if (f->ev_join[q]) (void)hipEventDestroy(f->ev_join[q]);
-    }
-    if (f->ev_fork) (void)hipEventDestroy(f->ev_fork);
     delete f;
 }
 
@@ -365,93 +355,17 @@ hipError_t fused512_prepare(Fused512* f, hipStream_t s, const float2* y, const u
     return hipGetLastError();
 }
 
-template <bool HAS_INV, int PROX, bool HAS_FWD, bool WRITE_X>
-static hipError_t launch5_rows(hipStream_t s, int np, const FRowArgs& a) {
-    hipLaunchKernelGGL((k5_rows<HAS_INV, PROX, HAS_FWD, WRITE_X>), dim3(np * 64), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-static hipError_t launch5_cols(Fused512* f, hipStream_t s, int pair0, int np, float c) {
-    F5ColArgs a;
-    a.T = f->T + (size_t)pair0 * NN5;
-    a.Yh = f->Yh + (size_t)pair0 * YH5_PAIR;
-    a.Mh = f->Mh + (size_t)pair0 * MH5_PAIR;
-    a.c = c;
-    hipLaunchKernelGGL(k5_cols, dim3(np * 33), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-static hipError_t run5_chunk(Fused512* f, hipStream_t s, float* z, float* w, float* x, int c0, int Bc, int iters,
-                             int prox, float dc_c, const ProxParams& pp) {
-    const int np = (Bc + 1) / 2, pair0 = c0 / 2;
-    const size_t so = (size_t)c0 * NN5;
-    FRowArgs a;
-    a.T = f->T + (size_t)pair0 * NN5;
-    a.z_in = z + so; a.w_in = w + so; a.z_out = z + so; a.w_out = w + so; a.x_out = x + so; a.B = Bc;
-    a.scale = 1.0f / (float)NN5; a.prox = to_coef5(pp); a.u_first = 1;
-    hipError_t e = launch5_rows<false, 0, true, false>(s, np, a);
-    for (int i = 0; i < iters && e == hipSuccess; ++i) {
-        e = launch5_cols(f, s, pair0, np, dc_c);
-        if (e != hipSuccess) break;
-        const bool last = (i == iters - 1);
-        a.u_first = (i == 0);
-        if (prox == 2)      e = last ? launch5_rows<true, 2, false, true>(s, np, a) : launch5_rows<true, 2, true, false>(s, np, a);
-        else if (prox == 1) e = last ? launch5_rows<true, 1, false, true>(s, np, a) : launch5_rows<true, 1, true, false>(s, np, a);
-        else                e = last ? launch5_rows<true, 3, false, true>(s, np, a) : launch5_rows<true, 3, true, false>(s, np, a);
-    }
-    return e;
-}
-
+// One queue per chunk, sequential launches: measured best at 512x512 (two queues 0.473 ms, mixed launches 0.49 ms against
+// 0.451 ms per iteration at 256 slices -- the 240-VGPR column body would drag the row body down to 2 waves/SIMD in a mixed
+// launch), so the queue / mixed knobs of FusedSchedule apply to the 256x256 path only.  Chunks of 4 MiB per slice (z, w, T,
+// Yh) go round-robin to the queues (loop_schedule.h, plan_chunked).
 hipError_t fused512_run(Fused512* f, hipStream_t s, float* z, float* w, float* x, int B, int iters, bool cnc,
                         float dc_c, ProxParams pp, const FusedSchedule& sch) {
-    if (iters <= 0) return hipSuccess;
-    const int prox = cnc ? 2 : (sch.l1_two_state ? 1 : 3);
-    // One queue, sequential launches: measured best at 512x512 (two queues 0.473 ms, mixed launches
-    // 0.49 ms against 0.451 ms per iteration at 256 slices -- the 240-VGPR column body would drag
-    // the row body down to 2 waves/SIMD in a mixed launch), so the queue / mixed knobs of
-    // FusedSchedule apply to the 256x256 path only.
-    // chunked round-robin schedule: internal.h, chunk_plan (4 MiB per slice: z, w, T, Yh).  sch.chunk (PNP_FUSED_CHUNK) overrides
-    // the chunk size, < 0 = whole batch; sch.chunk_queues overrides the number of queues (experiment builds).
-    const ChunkPlan plan = chunk_plan(B, sch, true, false, sch.chunk_queues);
-    const int Q = plan.queues, chunk = plan.chunk;
-    hipError_t e = hipSuccess;
-    if (Q < 2 || B <= chunk) {
-        for (int c0 = 0; c0 < B && e == hipSuccess; c0 += chunk)
-            e = run5_chunk(f, s, z, w, x, c0, (B - c0 < chunk) ? (B - c0) : chunk, iters, prox, dc_c, pp);
-        return e;
-    }
-    // chunks go round-robin to Q queues: Q chunks in flight, each queue runs all iterations of its chunk before its next one
-    if (!f->ev_fork) e = hipEventCreateWithFlags(&f->ev_fork, hipEventDisableTiming);
-    for (int q = 1; q < Q && e == hipSuccess; ++q) {
-        if (!f->side[q]) {
-            e = hipStreamCreateWithFlags(&f->side[q], hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_join[q], hipEventDisableTiming);
-        }
-    }
-    if (e != hipSuccess) return e;
-    e = hipEventRecord(f->ev_fork, s);
-    for (int q = 1; q < Q && e == hipSuccess; ++q) e = hipStreamWaitEvent(f->side[q], f->ev_fork, 0);
-    int k = 0;
-    for (int c0 = 0; c0 < B && e == hipSuccess; c0 += chunk, ++k) {
-        const int q = k % Q;
-        e = run5_chunk(f, q ? f->side[q] : s, z, w, x, c0, (B - c0 < chunk) ? (B - c0) : chunk, iters, prox, dc_c, pp);
-    }
-    for (int q = 1; q < Q && e == hipSuccess; ++q) {
-        e = hipEventRecord(f->ev_join[q], f->side[q]);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s, f->ev_join[q], 0);
-    }
-    return e;
+    return chain_run(f, s, z, w, x, B, iters, prox_kind(cnc, sch), dc_c, pp, plan_chunked(B, sch, Chunked::fused512));
 }
 
 hipError_t fused512_dc(Fused512* f, hipStream_t s, const float* z, const float* w, float* x, int B, float dc_c) {
-    const int np = (B + 1) / 2;
-    FRowArgs a;
-    a.T = f->T; a.z_in = z; a.w_in = w; a.z_out = nullptr; a.w_out = nullptr; a.x_out = x; a.B = B;
-    a.scale = 1.0f / (float)NN5; a.prox = ProxCoef{}; a.u_first = 1;
-    hipError_t e = launch5_rows<false, 0, true, false>(s, np, a);
-    if (e == hipSuccess) e = launch5_cols(f, s, 0, np, dc_c);
-    if (e == hipSuccess) e = launch5_rows<true, 0, false, true>(s, np, a);
-    return e;
+    return chain_dc(f, s, z, w, x, B, dc_c);
 }
 
 }  // namespace pnp

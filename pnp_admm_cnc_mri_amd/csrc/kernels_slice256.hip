@@ -30,10 +30,9 @@
 // latency; only the two transpositions are workgroup barriers.  Same arithmetic cores as the fused
 // path (fft16.h, fused_pointwise.h); index maps verified on the CPU by tests/host/slice_resident_emulation.cpp.
 // Measurements, the road here and the dead ends: DESIGN.md section 4.1.
-#include "internal.h"
+#include "engine_host.h"
 #include "fused_layout.h"
 #include "slice_layout.h"
-#include "fused_pointwise.h"
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -76,7 +75,7 @@ struct SliceArgs {
     int state_stride;         // floats between consecutive slices of z / w (65536 + padding, Slice256::pad)
     int yh_stride;            // complex elements between consecutive slices of Yh (YH3_SLICE + padding)
     float scale, c;
-    ProxCoef prox;
+    ProxParams prox;
     long long* prof;          // phase clock dump of a -DSLICE_PROF build (PNP_SLICE_PROF): [block][2 + 6 per iteration] of wall_clock64()
 };
 
@@ -282,7 +281,7 @@ __device__ __forceinline__ f2 splat(float v) { return k2(v, v); }
 // z / w updates of TWO pixels -- the same column of image rows 2r and 2r + 1 (prox_l1_pt / prox_cnc_pt of fft16.h, same
 // operation order per pixel)
 template <int PROX>
-__device__ __forceinline__ void prox_pair(f2 u, f2& z, f2& w, const ProxCoef& pc) {      // u = x + w
+__device__ __forceinline__ void prox_pair(f2 u, f2& z, f2& w, const ProxParams& pc) {      // u = x + w
     if (PROX == 2) {
         const f2 cz = clamp2(z, pc.ib);                                          // z - soft(z, 1/b)
         const f2 t = fma2(splat(pc.c1), z, fma2(splat(pc.c2), u, splat(pc.c3) * cz));
@@ -300,7 +299,7 @@ __device__ __forceinline__ void prox_pair(f2 u, f2& z, f2& w, const ProxCoef& pc
 // a second instance for the final iteration spills 350-490 bytes per lane), at the price of one unused forward
 // transform per launch.
 template <bool HAS_INV, int PROX, bool HAS_FWD>
-__device__ __forceinline__ void pointwise_q(const SliceBufs& b, const ProxCoef& pc, int u_first, bool last,
+__device__ __forceinline__ void pointwise_q(const SliceBufs& b, const ProxParams& pc, int u_first, bool last,
                                             c32& a0, c32& a1, const float (&z_)[4], const float (&w_)[4], int vs) {
     f2 z[2] = {k2(z_[0], z_[1]), k2(z_[2], z_[3])}, w[2] = {k2(w_[0], w_[1]), k2(w_[2], w_[3])};
     // u = x + w with x = |re|, |im| (the 1/N of the inverse transform is already in the field, col_phase): two v_add_f32 with
@@ -374,7 +373,7 @@ __device__ __forceinline__ void row_phase_prefetch(const SliceBufs& b, RowLoads&
     issue_row_loads<PROX, HAS_INV, 0, row_pf<PROX>()>(b, L, row_set_offset(0, wv), 2048 * (lane >> 4) + 16 * (lane & 15));
 }
 template <bool HAS_INV, int PROX, bool HAS_FWD, bool PRELOADED = false>
-__device__ __forceinline__ void row_phase(const SliceBufs& b, const ProxCoef& pc, int u_first, bool last, c32 (&F)[SL_SETS][16],
+__device__ __forceinline__ void row_phase(const SliceBufs& b, const ProxParams& pc, int u_first, bool last, c32 (&F)[SL_SETS][16],
                                           c32* wreg, const c32* twl, int wv, int lane, RowLoads* pre = nullptr) {
     const int g = lane >> 4, t = lane & 15;
     c32* region = wreg + g * REGION;
@@ -831,10 +830,7 @@ struct Slice256 {
     uint32_t* Mh = nullptr;
     c32* Ys = nullptr;
     uint32_t* Ms = nullptr;
-    static constexpr int MAXQ = 4;
-    hipStream_t side[MAXQ - 1] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr;
-    hipEvent_t ev_join[MAXQ - 1] = {nullptr, nullptr, nullptr};
+    SideQueues queues;                       // experiment knob slice_queues (plan_slice)
 };
 
 int slice256_cus(const Slice256* f) { return f && f->cus > 0 ? f->cus : 256; }
@@ -859,11 +855,6 @@ void slice256_destroy(Slice256* f) {
     if (f->Mh) (void)hipFree(f->Mh);
     if (f->Ys) (void)hipFree(f->Ys);
     if (f->Ms) (void)hipFree(f->Ms);
-    for (int q = 0; q < Slice256::MAXQ - 1; ++q) {
-        if (f->side[q]) (void)hipStreamDestroy(f->side[q]);
-        if (f->ev_join[q]) (void)hipEventDestroy(f->ev_join[q]);
-    }
-    if (f->ev_fork) (void)hipEventDestroy(f->ev_fork);
     delete f;
 }
 
@@ -882,14 +873,7 @@ Slice256* slice256_create(int Bmax, int pad_kb, int yh_pad_kb, hipError_t* err) 
     if (e == hipSuccess) e = hipMalloc((void**)&f->Mh, (size_t)Bmax * MH3_SLICE * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc((void**)&f->Ys, (size_t)Bmax * 256 * sizeof(c32));
     if (e == hipSuccess) e = hipMalloc((void**)&f->Ms, (size_t)Bmax * 16 * sizeof(uint32_t));
-    if (e == hipSuccess) {
-        static thread_local c32 h[256];
-        for (int m = 0; m < 256; ++m) {
-            const double a = -2.0 * M_PI * (double)m / 256.0;
-            h[m] = mk<float>((float)cos(a), (float)sin(a));
-        }
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_tws), h, sizeof(h));
-    }
+    if (e == hipSuccess) e = upload_twiddle_table<float>(HIP_SYMBOL(g_tws), 256);
     if (e == hipSuccess) {
         int dev = 0;
         hipDeviceProp_t prop;
@@ -935,18 +919,13 @@ hipError_t slice256_run(Slice256* f, hipStream_t s, float* z, float* w, float* x
     a.z = f->pad > 0 ? f->zs : z; a.w = f->pad > 0 ? f->ws : w; a.x = x; a.Yh = f->Yh;
     a.state_stride = 65536 + f->pad; a.yh_stride = (int)YH3_SLICE + f->yh_pad; a.Mh = f->Mh; a.Ys = f->Ys; a.Ms = f->Ms;
     a.first = 0; a.B = B; a.iters = iters; a.scale = 1.0f / 65536.0f; a.c = dc_c;
-    a.prox.thr = pp.thr; a.prox.c1 = pp.c1; a.prox.c2 = pp.c2; a.prox.c3 = pp.c3; a.prox.ib = pp.ib;
+    a.prox = pp;
     a.prof = nullptr;
-    a.slice_xor = 0;
     a.flip = 0;
     a.slice_xor = sch.slice_xor;
     if (a.slice_xor < 0 || (B & (B - 1)) != 0 || a.slice_xor >= B) a.slice_xor = 0;      // a permutation only for power-of-two batches
-    const int prox = cnc ? 2 : (sch.l1_two_state ? 1 : 3);
-    int queues = sch.slice_queues, seg_len = sch.slice_segment;                                // measured: 1 launch is best
-    if (queues < 1) queues = 1;
-    if (queues > Slice256::MAXQ) queues = Slice256::MAXQ;
-    if (B < 64 * queues) queues = 1;
-    int segments = seg_len > 0 ? (iters + seg_len - 1) / seg_len : 1;
+    const int prox = prox_kind(cnc, sch);
+    int segments = sch.slice_segment > 0 ? (iters + sch.slice_segment - 1) / sch.slice_segment : 1;    // measured: 1 launch is best
     if (segments < 1) segments = 1;
 
     long long* d_prof = nullptr;
@@ -955,9 +934,10 @@ hipError_t slice256_run(Slice256* f, hipStream_t s, float* z, float* w, float* x
 #else
     const char* prof_path = nullptr;
 #endif
+    const LoopPlan plan = plan_slice(B, prof_path ? FusedSchedule{} : sch);
     const size_t prof_n = (size_t)B * (2 + 6 * (size_t)iters);
     if (prof_path) {
-        queues = 1; segments = 1;
+        segments = 1;
         if (hipMalloc((void**)&d_prof, prof_n * sizeof(long long)) == hipSuccess) {
             (void)hipMemsetAsync(d_prof, 0, prof_n * sizeof(long long), s);
             a.prof = d_prof;
@@ -967,32 +947,17 @@ hipError_t slice256_run(Slice256* f, hipStream_t s, float* z, float* w, float* x
     // are the ones the Infinity Cache still holds when the call returns: every other call walks the batch backwards, so that
     // a following call starts on warm data (DESIGN.md 4.1, round hand-over).  Slices are independent: results do not change.
     if (!prof_path && B > slice256_cus(f) && sch.slice_flip) { a.flip = f->flip; f->flip ^= 1; }
-    hipError_t e = hipSuccess;
-    if (queues > 1) {
-        if (!f->ev_fork) e = hipEventCreateWithFlags(&f->ev_fork, hipEventDisableTiming);
-        for (int q = 0; q < queues - 1 && e == hipSuccess; ++q) {
-            if (f->side[q]) continue;
-            e = hipStreamCreateWithFlags(&f->side[q], hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_join[q], hipEventDisableTiming);
-        }
-        if (e == hipSuccess) e = hipEventRecord(f->ev_fork, s);
-    }
-    int c0 = 0;
-    for (int q = 0; q < queues && e == hipSuccess; ++q) {
-        const int Bq = (q == queues - 1) ? (B - c0) : (B / queues);
-        hipStream_t sq = (q == 0) ? s : f->side[q - 1];
-        if (q > 0) e = hipStreamWaitEvent(sq, f->ev_fork, 0);
+    const hipError_t e = run_parts(f->queues, s, plan, B, [&](hipStream_t sq, const Part& p) {
+        hipError_t r = hipSuccess;
         int done = 0;
-        for (int g = 0; g < segments && e == hipSuccess; ++g) {
+        for (int g = 0; g < segments && r == hipSuccess; ++g) {
             const int n = (iters - done + (segments - g) - 1) / (segments - g);     // even split of what is left
-            a.first = c0; a.B = Bq; a.iters = n;
-            e = launch_slice(sq, a, prox);
+            a.first = p.first; a.B = p.count; a.iters = n;
+            r = launch_slice(sq, a, prox);
             done += n;
         }
-        if (q > 0 && e == hipSuccess) e = hipEventRecord(f->ev_join[q - 1], sq);
-        if (q > 0 && e == hipSuccess) e = hipStreamWaitEvent(s, f->ev_join[q - 1], 0);
-        c0 += Bq;
-    }
+        return r;
+    });
     if (d_prof) {
         std::vector<long long> h(prof_n);
         (void)hipStreamSynchronize(s);

@@ -140,7 +140,7 @@ def test_host_cores_under_address_and_ub_sanitizers(golden_inputs, tmp_path):
     san = ['-O1', '-g', '-std=c++17', '-fsanitize=address,undefined', '-fno-sanitize-recover=all']
     host = os.path.join(ROOT, 'tests', 'host')
     exes = {}
-    for name in ('fused_emulation', 'split_chain_emulation', 'slice_resident_emulation', 'fft512_emulation'):
+    for name in ('fused_emulation', 'split_chain_emulation', 'slice_resident_emulation', 'fft512_emulation', 'loop_schedule_emulation'):
         exes[name] = str(tmp_path / name)
         subprocess.check_call(['g++'] + san + ['-o', exes[name], os.path.join(host, name + '.cpp')])
     z, w, ys, masks = _problem(golden_inputs)
@@ -154,7 +154,8 @@ def test_host_cores_under_address_and_ub_sanitizers(golden_inputs, tmp_path):
                 [exes['split_chain_emulation'], inp, str(tmp_path / 'o2.bin'), 'f'],
                 [exes['split_chain_emulation'], inp, str(tmp_path / 'o3.bin'), 'd'],
                 [exes['slice_resident_emulation'], inp, str(tmp_path / 'o4.bin')],
-                [exes['fft512_emulation']]):
+                [exes['fft512_emulation']],
+                [exes['loop_schedule_emulation']] + list(SCHEDULE_CASES)):
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         assert r.returncode == 0 and b'runtime error' not in r.stderr and b'AddressSanitizer' not in r.stderr, r.stderr.decode()[-1500:]
     a = np.fromfile(str(tmp_path / 'o1.bin'), dtype=np.float32).reshape(3, 2, 256, 256)[0]
@@ -200,3 +201,48 @@ def test_slice_resident_pipeline_matches_oracle(emu, golden_inputs, cnc):
         assert rel_l2(raw[0], xr) <= 2e-6, rel_l2(raw[0], xr)
         assert rel_l2(raw[1], zr) <= 2e-6
         assert np.abs(raw[2] - wr).max() <= 2e-6
+
+
+# csrc/loop_schedule.h: case -> "queues chunk launches | first,count,queue[m: mixed launches] ..." of the plan and its parts
+SCHEDULE_CASES = {
+    # the cases test_plan_reports_what_the_loops_will_do pins on the GPU
+    'f256:40:1:0:15': '1 14 6 | 0,14,0 14,14,0 28,12,0',                        # sequential chunks, even-sized
+    'f512:52:2:0:0': '4 16 8 | 0,16,0 16,16,1 32,16,2 48,4,3',                  # chunks round-robin over 4 queues
+    'f512:52:1:0:0': '1 48 4 | 0,48,0 48,4,0',
+    'f512:52:2:0:-1': '1 52 2 | 0,52,0',
+    's64:100:2:0:0': '4 24 10 | 0,24,0 24,24,1 48,24,2 72,24,3 96,4,0',
+    # two-launch 256x256 over queues: even parts, the last one takes the rest; too small a batch stays on one queue
+    'f256:512:2:0:0': '2 512 4 | 0,256,0 256,256,1',
+    'f256:131:3:0:0': '3 131 6 | 0,44,0 44,44,1 88,43,2',
+    'f256:128:3:0:0': '3 128 6 | 0,42,0 42,42,1 84,44,2',
+    'f256:95:3:0:0': '1 95 2 | 0,95,0',
+    # mixed launches: parts of at least 64 slices; on one queue only when the schedule asks for one
+    'f256:131:2:1:0': '2 131 4 | 0,66,0m 66,65,1m',
+    'f256:100:2:1:0': '2 100 4 | 0,50,0 50,50,1',
+    'f256:64:1:1:0': '1 64 2 | 0,64,0m',
+    'f256:40:1:1:0': '1 40 2 | 0,40,0',
+    'f256:40:2:1:0': '1 40 2 | 0,40,0',
+    'f256:200:1:1:16': '1 16 26 | ' + ' '.join('%d,16,0' % (16 * i) for i in range(12)) + ' 192,8,0',
+    # chunked: split chain in float (two halves, or the whole batch), odd batches, experiment queue counts
+    's32:100:2:0:0': '2 50 4 | 0,50,0 50,50,1',
+    's32:40:2:0:0': '1 40 2 | 0,40,0',
+    's32:101:1:0:0': '1 100 4 | 0,100,0 100,1,0',
+    'f512:51:2:0:-1': '1 50 4 | 0,50,0 50,1,0',
+    'f512:7:2:0:0': '1 7 2 | 0,7,0',
+    's64:100:2:0:0:2': '2 24 10 | 0,24,0 24,24,1 48,24,0 72,24,1 96,4,0',
+    's64:512:1:0:0': '1 96 12 | 0,96,0 96,96,0 192,96,0 288,96,0 384,96,0 480,32,0',
+    # slice-resident: one launch, or (experiment knob) parts of B / q slices with the rest in the last
+    'slice:512:2:0:0': '1 512 0 | 0,512,0',
+    'slice:200:2:0:0:0:3': '3 200 0 | 0,66,0 66,66,1 132,68,2',
+    'slice:200:2:0:0:0:4': '1 200 0 | 0,200,0',
+}
+
+
+def test_loop_schedules(tmp_path):
+    """The engines' plans and the parts they run (csrc/loop_schedule.h, compiled with g++ on its own): the values
+    pnp_get_plan reports, the even / round-robin / B-over-q splits with their rounding, and the mixed-launch rule."""
+    exe = str(tmp_path / 'loop_schedule_emulation')
+    subprocess.check_call(['g++', '-O2', '-std=c++17', '-Wall', '-Werror', '-o', exe,
+                           os.path.join(ROOT, 'tests', 'host', 'loop_schedule_emulation.cpp')])
+    out = subprocess.check_output([exe] + list(SCHEDULE_CASES)).decode().splitlines()
+    assert dict(zip(SCHEDULE_CASES, out)) == SCHEDULE_CASES

@@ -11,10 +11,16 @@
 //
 //   per iteration and slice:  z, w read + written (16 N bytes; 8 N for ADMM_L1's single-state form),
 //                             Hermitian measurement table read (4 N)              = 20 N (12 N) bytes
+//   ADMM_CNC (k_slice<2>) moves less: a quarter of w (row pairs 0..31 = register set 0 of the row form, 64 KiB) is read
+//   from HBM once per launch, lives in LDS for the launch's K iterations and is stored when they are over:
+//   20 N - 2 N (2K - 1) / K bytes per iteration.  The room comes from crossing the transpositions in FOUR passes of a
+//   quarter of the field instead of two of a half (buffer 69 632 B, below the exchange regions it aliases):
+//     exchange regions / buffer 73 728 + W256 table 2 304 + Ys / Ms 2 304 + resident w 65 536 = 143 872 B of LDS
+//   at the price of eight more workgroup barriers per iteration.  The two L1 instances keep the two-pass form (139 776 B).
 //
 //   rows(first)                 v = z - w, row pairs (2r, 2r+1) packed as one complex row, 16-lane FFT-256
 //   repeat iters times:
-//     T1  row form -> column form through LDS (2 passes), real-to-complex unpack on the way (slice_layout.h)
+//     T1  row form -> column form through LDS (2 passes; CNC: 4), real-to-complex unpack on the way (slice_layout.h)
 //     columns                   FFT-256 -> Hermitian blend against Yh / Mh -> inverse FFT-256
 //                               (127 half-plane columns + the packed column {k2 = 0, k2 = 128})
 //     T2  column form -> row form, complex-to-real repack on the way
@@ -28,7 +34,8 @@
 // Row and column phases are wave-local (a 16-lane transform group never leaves its wave, each wave
 // has its own LDS region), so the 8 waves of the workgroup drift apart and cover each other's HBM
 // latency; only the two transpositions are workgroup barriers.  Same arithmetic cores as the fused
-// path (fft16.h, fused_pointwise.h); index maps verified on the CPU by tests/host/slice_resident_emulation.cpp.
+// path (fft16.h, fused_pointwise.h); index maps verified on the CPU by tests/host/slice_resident_emulation.cpp
+// (two-pass form) and tests/host/slice_resident4_emulation.cpp (four-pass form and the resident share of w).
 // Measurements, the road here and the dead ends: DESIGN.md section 4.1.
 #include "engine_host.h"
 #include "fused_layout.h"
@@ -52,6 +59,9 @@
 #endif
 #ifndef SLICE_ST_AUX
 #define SLICE_ST_AUX 0      // cache policy bits of the state stores (experiment knob)
+#endif
+#ifndef SLICE_RESIDENT
+#define SLICE_RESIDENT 1    // k_slice<2>: register set 0 of w stays in LDS for a launch (0: four-pass transpositions alone, the cost side of the A/B)
 #endif
 #ifndef SLICE_PF
 #define SLICE_PF 3          // of a set's 8 z / w accesses per lane: fetched ahead of the transforms (experiment knob)
@@ -89,6 +99,22 @@ constexpr int WREG = 4 * REGION;              // complex elements of a wave's pr
 constexpr int SL_YS = SL_BUF + REGION;            // operands of the packed column's second half (k2 = 128): Ys (256 complex) + Ms (64 words), see col_phase
 constexpr int SL_LDS = SL_YS + 256 + 32;       // transposition buffer (the 8 wave regions alias its start) + W256 table + those
 static_assert(SL_WAVES * WREG <= SL_BUF, "wave regions must fit in the buffer they alias");
+// Four-pass form (k_slice<2>): the buffer (SL_BUF4) is SMALLER than the wave regions it aliases; behind the tables sits the
+// resident share of w (SL_RES row pairs x 512 floats, never aliased):  73 728 + 2 304 + 2 304 + 65 536 = 143 872 bytes.
+constexpr int SL4_XB = SL_WAVES * WREG;           // exchange regions / transposition buffer
+constexpr int SL4_YS = SL4_XB + REGION;
+constexpr int SL4_RES = SL4_YS + 256 + 32;        // complex index of the resident region (16-byte aligned)
+constexpr int SL4_LDS = SL4_RES + SL_RES * 256;
+static_assert(SL_BUF4 <= SL4_XB && SL4_RES % 2 == 0 && SL4_LDS * 8 <= 160 * 1024, "four-pass LDS map");
+// which instances cross in four passes and keep set 0 of w in LDS: ADMM_CNC.  The two L1 forms stay on two passes: the
+// single-state form is bound by the compute unit and extra barriers only cost it.
+template <int PROX> constexpr bool slice_four() { return PROX == 2; }
+template <int PROX> constexpr bool slice_res() { return slice_four<PROX>() && SLICE_RESIDENT; }
+__device__ __forceinline__ void lds_ld4(const float* p, float (&v)[4]) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+}
+__device__ __forceinline__ void lds_st4(float* p, const float (&v)[4]) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
 
 // wave-synchronous ordering of LDS traffic: a wave's LDS instructions execute in order, so no
 // s_barrier is needed between lanes of one wave -- only the compiler has to keep the order
@@ -257,12 +283,16 @@ __device__ __forceinline__ int row_set_offset(int set, int wv) { return (32 * se
 constexpr int ROW_QSTRIDE = 256;                                  // bytes between a lane's consecutive accesses of a row pair
 
 // voff = 2048 g + 16 t (bytes inside the wave's 8 KiB of a set); the q-th access adds 256 q as an instruction offset
-template <int PROX, bool HAS_INV, int Q0, int Q1>
-__device__ __forceinline__ void issue_row_loads(const SliceBufs& b, RowLoads& L, int soff, int voff, int qbase = 0) {
+// RESW: the set's w is resident -- read from LDS at resw (the lane's first access; 64 floats between accesses), not from HBM
+template <int PROX, bool HAS_INV, int Q0, int Q1, bool RESW = false>
+__device__ __forceinline__ void issue_row_loads(const SliceBufs& b, RowLoads& L, int soff, int voff, int qbase = 0, const float* resw = nullptr) {
 #pragma unroll
     for (int q = qbase + Q0; q < qbase + Q1; ++q) {
         const int vo = voff + ROW_QSTRIDE * q, so = soff;
-        if (PROX == 3) {                                                   // single-state ADMM_L1: only the w buffer (it carries u)
+        if (RESW) {
+            ld4(b.z, vo, so, L.z[q]);
+            lds_ld4(resw + 64 * q, L.w[q]);
+        } else if (PROX == 3) {                                                   // single-state ADMM_L1: only the w buffer (it carries u)
             ld4(b.w, vo, so, L.w[q]);
         } else if (PROX != 0 || !HAS_INV) {
             ld4(b.z, vo, so, L.z[q]);
@@ -298,9 +328,10 @@ __device__ __forceinline__ void prox_pair(f2 u, f2& z, f2& w, const ProxParams& 
 // the loop has ONE row-phase body for all its iterations (the kernel is 80+ KB of code and the instruction cache 64 KB;
 // a second instance for the final iteration spills 350-490 bytes per lane), at the price of one unused forward
 // transform per launch.
-template <bool HAS_INV, int PROX, bool HAS_FWD>
+// RESW (compile time, per set): w of this access stays in LDS at resw (resident set); its HBM copy is written when the launch ends.
+template <bool HAS_INV, int PROX, bool HAS_FWD, bool RESW = false>
 __device__ __forceinline__ void pointwise_q(const SliceBufs& b, const ProxParams& pc, int u_first, bool last,
-                                            c32& a0, c32& a1, const float (&z_)[4], const float (&w_)[4], int vs) {
+                                            c32& a0, c32& a1, const float (&z_)[4], const float (&w_)[4], int vs, float* resw = nullptr) {
     f2 z[2] = {k2(z_[0], z_[1]), k2(z_[2], z_[3])}, w[2] = {k2(w_[0], w_[1]), k2(w_[2], w_[3])};
     // u = x + w with x = |re|, |im| (the 1/N of the inverse transform is already in the field, col_phase): two v_add_f32 with
     // the |.| source modifier per register pair -- a packed add has no such modifier and would cost two v_and on top
@@ -329,7 +360,8 @@ __device__ __forceinline__ void pointwise_q(const SliceBufs& b, const ProxParams
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) prox_pair<PROX>(SL_X_PLUS(jj ? a1 : a0, w[jj]), z[jj], w[jj], pc);
         SL_ST4(b.z, z);
-        SL_ST4(b.w, w);
+        if (RESW) { const float q_[4] = {w[0].x, w[0].y, w[1].x, w[1].y}; lds_st4(resw, q_); }
+        else SL_ST4(b.w, w);
     }
 #undef SL_ST4
 #undef SL_X_PLUS
@@ -368,21 +400,27 @@ __device__ __forceinline__ void store_x_natural(const SliceBufs& b, const c32 (&
 #endif                      // next set's inverse transform -- the overlap the form's 8 N fewer bytes leave room for (experiment knob: 4, 2 = less of it)
 template <int PROX> constexpr int row_pf() { return (PROX == 3) ? SLICE_L1_PF : SLICE_PF; }
 // the first accesses of set 0, issued by the caller ahead of the phase (SLICE_EARLY: between the two passes of T2)
-template <int PROX, bool HAS_INV>
-__device__ __forceinline__ void row_phase_prefetch(const SliceBufs& b, RowLoads& L, int wv, int lane) {
-    issue_row_loads<PROX, HAS_INV, 0, row_pf<PROX>()>(b, L, row_set_offset(0, wv), 2048 * (lane >> 4) + 16 * (lane & 15));
+// the lane's first resident access: row pair 4 wv + g of set 0 (sl_res_index, slice_layout.h)
+__device__ __forceinline__ float* res_lane(float* res, int wv, int lane) { return res + sl_res_index(4 * wv + (lane >> 4), lane & 15, 0); }
+template <int PROX, bool HAS_INV, bool RES = false>
+__device__ __forceinline__ void row_phase_prefetch(const SliceBufs& b, RowLoads& L, int wv, int lane, float* res = nullptr) {
+    issue_row_loads<PROX, HAS_INV, 0, row_pf<PROX>(), RES>(b, L, row_set_offset(0, wv), 2048 * (lane >> 4) + 16 * (lane & 15), 0, RES ? res_lane(res, wv, lane) : nullptr);
 }
-template <bool HAS_INV, int PROX, bool HAS_FWD, bool PRELOADED = false>
+// RES: set 0 of w is resident in LDS at `res`.  The prologue (!HAS_INV) copies it there as it reads it; the loop reads and writes
+// it there; resident_flush below stores it to HBM when the launch's iterations are over.
+template <bool HAS_INV, int PROX, bool HAS_FWD, bool PRELOADED = false, bool RES = false>
 __device__ __forceinline__ void row_phase(const SliceBufs& b, const ProxParams& pc, int u_first, bool last, c32 (&F)[SL_SETS][16],
-                                          c32* wreg, const c32* twl, int wv, int lane, RowLoads* pre = nullptr) {
+                                          c32* wreg, const c32* twl, int wv, int lane, RowLoads* pre = nullptr, float* res = nullptr) {
     const int g = lane >> 4, t = lane & 15;
     c32* region = wreg + g * REGION;
     const int voff = 2048 * g + 16 * t;
+    float* resw = RES ? res_lane(res, wv, lane) : nullptr;
+    constexpr bool RES_LOOP = RES && HAS_INV;                    // set 0's w comes from and goes to LDS
     // PF accesses of the next set are fetched ahead across the transforms; the rest when the set's pointwise phase starts
     constexpr int PF = row_pf<PROX>();
     RowLoads L;
     if (PRELOADED) L = *pre;
-    else issue_row_loads<PROX, HAS_INV, 0, PF>(b, L, row_set_offset(0, wv), voff);
+    else issue_row_loads<PROX, HAS_INV, 0, PF, RES_LOOP>(b, L, row_set_offset(0, wv), voff, 0, resw);
 #pragma unroll
     for (int set = 0; set < SL_SETS; ++set) {
         c32 (&a)[16] = F[set];
@@ -397,8 +435,14 @@ __device__ __forceinline__ void row_phase(const SliceBufs& b, const ProxParams& 
         // once, on top of the 128 data registers, made hipcc spill)
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            if (q + PF < 8) issue_row_loads<PROX, HAS_INV, 0, 1>(b, L, soff, voff, q + PF);
-            pointwise_q<HAS_INV, PROX, HAS_FWD>(b, pc, u_first, last, a[2 * q], a[2 * q + 1], L.z[q], L.w[q], vs + ROW_QSTRIDE * q);
+            if (RES_LOOP && set == 0) {
+                if (q + PF < 8) issue_row_loads<PROX, HAS_INV, 0, 1, true>(b, L, soff, voff, q + PF, resw);
+                pointwise_q<HAS_INV, PROX, HAS_FWD, true>(b, pc, u_first, last, a[2 * q], a[2 * q + 1], L.z[q], L.w[q], vs + ROW_QSTRIDE * q, resw + 64 * q);
+            } else {
+                if (q + PF < 8) issue_row_loads<PROX, HAS_INV, 0, 1>(b, L, soff, voff, q + PF);
+                if (RES && !HAS_INV && set == 0) lds_st4(resw + 64 * q, L.w[q]);         // prologue: the resident rows enter LDS
+                pointwise_q<HAS_INV, PROX, HAS_FWD>(b, pc, u_first, last, a[2 * q], a[2 * q + 1], L.z[q], L.w[q], vs + ROW_QSTRIDE * q);
+            }
         }
         if (set + 1 < SL_SETS) issue_row_loads<PROX, HAS_INV, 0, PF>(b, L, row_set_offset(set + 1, wv), voff);
         if (HAS_FWD) {
@@ -407,8 +451,20 @@ __device__ __forceinline__ void row_phase(const SliceBufs& b, const ProxParams& 
     }
 }
 
+// end of a launch's iterations: the resident share of w goes back to HBM (each lane stores what it wrote itself)
+__device__ __forceinline__ void resident_flush(const SliceBufs& b, const float* res, int wv, int lane) {
+    const float* resw = res_lane(const_cast<float*>(res), wv, lane);
+    const int vs = 2048 * (lane >> 4) + 16 * (lane & 15) + row_set_offset(0, wv);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        float v[4];
+        lds_ld4(resw + 64 * q, v);
+        st4(b.w, vs + ROW_QSTRIDE * q, 0, v);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
-// transpositions (workgroup-wide, two passes each); slots: slice_layout.h
+// transpositions (workgroup-wide, two passes each -- four for k_slice<2>, below); slots: slice_layout.h
 // ------------------------------------------------------------------------------------------
 // The 8 registers of a row-form set that cross in pass P, with their slots (sl_pass / sl_slot of
 // slice_layout.h, k = t + 16 j).  Register indices must be literals (register arrays), so the lists
@@ -423,6 +479,14 @@ __device__ __forceinline__ void row_phase(const SliceBufs& b, const ProxParams& 
     X(8, 12, ((t) ? SL_M + 64 - (t) : SL_M))                                                      \
     X(9, 9, SL_M + 48 - (t)) X(10, 10, SL_M + 32 - (t)) X(11, 11, SL_M + 16 - (t))
 
+// Four-pass form (sl_pass4 / sl_slot4): pass Q takes 4 of a set's 16 registers -- 2Q, 2Q + 1 direct, 14 - 2Q, 15 - 2Q mirrored;
+// lane 0 sends, in place of register 14 - 2Q (k = 224 - 32 Q: next pass), the one that holds the mirror of column 32 Q:
+// k = 128 (register 8) in pass 0, k = 256 - 32 Q (register 16 - 2Q) after it.
+#define SL_PASS4_REGS(X, t, Q)                                                                    \
+    X(2 * (Q), 2 * (Q), (t)) X(2 * (Q) + 1, 2 * (Q) + 1, (t) + 16)                                  \
+    X(14 - 2 * (Q), ((Q) ? 16 - 2 * (Q) : 8), ((t) ? SL_M4 + 32 - (t) : SL_M4))                   \
+    X(15 - 2 * (Q), 15 - 2 * (Q), SL_M4 + 16 - (t))
+
 // The MIRROR half of a buffer row (slots SL_M ..) holds its values with re and im SWAPPED.  Both lanes of a pair then run
 // the same two instructions in both transpositions (no selects by lane parity): with own = the lane's value as stored and
 // (.)' = the partner lane's, T1 needs ((own.x + own.y'), (own.y - own.x')) / 2 and T2 writes (own.x - own.y', own.y + own.x').
@@ -436,19 +500,26 @@ __device__ __forceinline__ c32 lds_get(const c32* p, bool swapped) {
     return swapped ? mk<float>(f[1], f[0]) : *p;
 }
 // row-form registers of one set -> buffer row `rp`
-template <int P>
+template <int P, bool FOUR = false>
 __device__ __forceinline__ void t_store_rows(const c32 (&F)[16], c32* rp, int t) {
 #define SL_T1_STORE(ja, jb, slot) { lds_put(rp + (slot), t ? F[ja] : F[jb], (ja) >= 8); }
-    if (P == 0) { SL_PASS0_REGS(SL_T1_STORE, t) } else { SL_PASS1_REGS(SL_T1_STORE, t) }
+    if (FOUR) { SL_PASS4_REGS(SL_T1_STORE, t, P) } else if (P == 0) { SL_PASS0_REGS(SL_T1_STORE, t) } else { SL_PASS1_REGS(SL_T1_STORE, t) }
 #undef SL_T1_STORE
 }
 // buffer row `rp` -> row-form registers of one set (lane 0 of a group is fixed up after pass 1)
-template <int P>
+template <int P, bool FOUR = false>
 __device__ __forceinline__ void t_load_rows(c32 (&F)[16], const c32* rp, int t) {
 #define SL_T2_LOAD(ja, jb, slot) { F[ja] = lds_get(rp + (slot), (ja) >= 8); }
-    if (P == 0) { SL_PASS0_REGS(SL_T2_LOAD, t) } else { SL_PASS1_REGS(SL_T2_LOAD, t) }
+    if (FOUR) { SL_PASS4_REGS(SL_T2_LOAD, t, P) } else if (P == 0) { SL_PASS0_REGS(SL_T2_LOAD, t) } else { SL_PASS1_REGS(SL_T2_LOAD, t) }
 #undef SL_T2_LOAD
-    if (P == 1) {         // lane 0 received k = 128 in register 12 (pass 0) and k = 192 in register 8 (pass 1): swap them
+    if (FOUR && P == 3) {   // lane 0 received k = 128, 224, 192, 160 in registers 14, 12, 10, 8: they belong in 8, 14, 12, 10
+        const c32 a8 = F[8];
+        F[8] = t ? a8 : F[14];
+        F[14] = t ? F[14] : F[12];
+        F[12] = t ? F[12] : F[10];
+        F[10] = t ? F[10] : a8;
+    }
+    if (!FOUR && P == 1) {         // lane 0 received k = 128 in register 12 (pass 0) and k = 192 in register 8 (pass 1): swap them
         const c32 a0 = F[8];
         F[8] = t ? a0 : F[12];
         F[12] = t ? F[12] : a0;
@@ -466,16 +537,16 @@ __device__ __forceinline__ void t_load_rows(c32 (&F)[16], const c32* rp, int t) 
 // One column-form set's 16 values from the buffer.  MAYBE_PACKED: this wave owns the packed column c = 0 (wave 0, first
 // set of pass 0, lanes 0..15 -- `packed` says which lanes); every other (wave, set) runs the plain two-instruction unpack.
 // Buffer rows 64.. (j >= 8) lie beyond the 16-bit offset of a DS instruction: a second base keeps the offsets immediates.
-template <bool MAYBE_PACKED>
+template <bool MAYBE_PACKED, int PITCH = SL_P>
 __device__ __forceinline__ void t1_read_col(c32 (&Gs)[16], const c32* buf, int off, int odd, bool packed) {
-    int off_hi = off + 64 * SL_P;
+    int off_hi = off + 64 * PITCH;
     asm volatile("" : "+v"(off_hi));                // an index, not a pointer: the address space stays visible to the compiler
     const c32 *col = buf + off, *col_hi = buf + off_hi;
 #pragma unroll
     for (int jb = 0; jb < 16; jb += 8) {
         c32 own[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) own[k] = jb ? col_hi[8 * k * SL_P] : col[8 * k * SL_P];
+        for (int k = 0; k < 8; ++k) own[k] = jb ? col_hi[8 * k * PITCH] : col[8 * k * PITCH];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             // TWICE the unpacked value: the 1/2 is folded into the blend coefficients (blend_scaled, exact)
@@ -506,9 +577,9 @@ __device__ __forceinline__ void t1_pass(const c32 (&F)[SL_SETS][16], c32 (&G)[SL
     __syncthreads();
 }
 
-template <bool MAYBE_PACKED>
+template <bool MAYBE_PACKED, int PITCH = SL_P>
 __device__ __forceinline__ void t2_write_col(const c32 (&Gs)[16], c32* buf, int off, int odd, bool packed) {
-    int off_hi = off + 64 * SL_P;
+    int off_hi = off + 64 * PITCH;
     asm volatile("" : "+v"(off_hi));
     c32 *col = buf + off, *col_hi = buf + off_hi;
 #pragma unroll
@@ -523,7 +594,7 @@ __device__ __forceinline__ void t2_write_col(const c32 (&Gs)[16], c32* buf, int 
             const c32 raw = mk<float>(odd ? own.y : own.x, odd ? other.y : other.x);
             v = packed ? raw : v;
         }
-        if (j < 8) col[8 * j * SL_P] = v; else col_hi[8 * (j - 8) * SL_P] = v;
+        if (j < 8) col[8 * j * PITCH] = v; else col_hi[8 * (j - 8) * PITCH] = v;
     }
 }
 template <int P>
@@ -539,6 +610,33 @@ __device__ __forceinline__ void t2_pass(const c32 (&G)[SL_SETS][16], c32 (&F)[SL
     __syncthreads();
 #pragma unroll
     for (int set = 0; set < SL_SETS; ++set) t_load_rows<P>(F[set], buf + (32 * set + 4 * wv + g) * SL_P, t);
+    __syncthreads();
+}
+
+// Four-pass form: pass Q moves 4 registers of every row-form set out and column-form set Q in (T1), or back (T2): the same
+// renaming of 32 registers per pass as above, a buffer of a quarter of the field, and ONE instance of the column code per pass.
+template <int Q>
+__device__ __forceinline__ void t1_pass4(const c32 (&F)[SL_SETS][16], c32 (&G)[SL_SETS][16], c32* buf, int wv, int lane) {
+    const int g = lane >> 4, t = lane & 15;
+#pragma unroll
+    for (int set = 0; set < SL_SETS; ++set) t_store_rows<Q, true>(F[set], buf + (32 * set + 4 * wv + g) * SL_P4, t);
+    __syncthreads();
+    const int cc = 4 * wv + g, odd = t & 1;
+    const int off = (t >> 1) * SL_P4 + cc + (odd ? SL_M4 : 0);
+    if (Q == 0 && wv == 0) t1_read_col<true, SL_P4>(G[Q], buf, off, odd, cc == 0);
+    else t1_read_col<false, SL_P4>(G[Q], buf, off, odd, false);
+    __syncthreads();
+}
+template <int Q>
+__device__ __forceinline__ void t2_pass4(const c32 (&G)[SL_SETS][16], c32 (&F)[SL_SETS][16], c32* buf, int wv, int lane) {
+    const int g = lane >> 4, t = lane & 15;
+    const int cc = 4 * wv + g, odd = t & 1;
+    const int off = (t >> 1) * SL_P4 + cc + (odd ? SL_M4 : 0);
+    if (Q == 0 && wv == 0) t2_write_col<true, SL_P4>(G[Q], buf, off, odd, cc == 0);
+    else t2_write_col<false, SL_P4>(G[Q], buf, off, odd, false);
+    __syncthreads();
+#pragma unroll
+    for (int set = 0; set < SL_SETS; ++set) t_load_rows<Q, true>(F[set], buf + (32 * set + 4 * wv + g) * SL_P4, t);
     __syncthreads();
 }
 
@@ -637,10 +735,13 @@ __device__ __forceinline__ void col_phase(const SliceBufs& b, float cdc, float s
 // ------------------------------------------------------------------------------------------
 template <int PROX>
 __global__ __launch_bounds__(512) void k_slice(SliceArgs p) {
-    __shared__ __attribute__((aligned(16))) c32 lds[SL_LDS];
+    constexpr bool FOUR = slice_four<PROX>(), RES = slice_res<PROX>();     // four-pass transpositions; set 0 of w resident in LDS
+    __shared__ __attribute__((aligned(16))) c32 lds[FOUR ? SL4_LDS : SL_LDS];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave index as a scalar: bases below stay in SGPRs
-    c32* twl = lds + SL_BUF;
+    c32* twl = lds + (FOUR ? SL4_XB : SL_BUF);
+    c32* ysl = lds + (FOUR ? SL4_YS : SL_YS);
+    float* res = RES ? reinterpret_cast<float*>(lds + SL4_RES) : nullptr;
     if (tid < 256) twl[RP * (tid >> 4) + (tid & 15)] = g_tws[((tid >> 4) * (tid & 15)) & 255];     // [t][k] = W256^(t k), rows of RP
     c32* wreg = lds + wv * WREG;
     __syncthreads();
@@ -662,38 +763,53 @@ __global__ __launch_bounds__(512) void k_slice(SliceArgs p) {
 #define SL_STAMP()
 #endif
         SL_STAMP();
-        row_phase<false, 0, true>(b, p.prox, 1, false, F, wreg, twl, wv, opaque(lane));
+        row_phase<false, 0, true, false, RES>(b, p.prox, 1, false, F, wreg, twl, wv, opaque(lane), nullptr, res);
         SL_STAMP();
         for (int it = 0; it < p.iters; ++it) {
             c32 G[SL_SETS][16];
             __syncthreads();                      // every wave is done with its private region: the buffer aliases them
             SL_STAMP();                           // wave 0's wait for the slowest wave of the row phase ends here
-            t1_pass<0>(F, G, lds, wv, opaque(lane));
-            t1_pass<1>(F, G, lds, wv, opaque(lane));
+            if (FOUR) {
+                t1_pass4<0>(F, G, lds, wv, opaque(lane));
+                t1_pass4<1>(F, G, lds, wv, opaque(lane));
+                t1_pass4<2>(F, G, lds, wv, opaque(lane));
+                t1_pass4<3>(F, G, lds, wv, opaque(lane));
+            } else {
+                t1_pass<0>(F, G, lds, wv, opaque(lane));
+                t1_pass<1>(F, G, lds, wv, opaque(lane));
+            }
 #ifdef SLICE_PROF_CLOCK                      // diagnostic build: this slot carries the SHADER clock (s_memtime) instead of the 100 MHz wall clock
             if (prof) *prof++ = (long long)__builtin_readcyclecounter();
 #else
             SL_STAMP();
 #endif
-            col_phase(b, p.c, p.scale, G, wreg, lds + SL_YS, twl, wv, opaque(lane));
+            col_phase(b, p.c, p.scale, G, wreg, ysl, twl, wv, opaque(lane));
             SL_STAMP();
             __syncthreads();
             SL_STAMP();
-            t2_pass<0>(G, F, lds, wv, opaque(lane));
+            if (FOUR) {
+                t2_pass4<0>(G, F, lds, wv, opaque(lane));
+                t2_pass4<1>(G, F, lds, wv, opaque(lane));
+                t2_pass4<2>(G, F, lds, wv, opaque(lane));
+            } else {
+                t2_pass<0>(G, F, lds, wv, opaque(lane));
+            }
 #if SLICE_EARLY
             RowLoads L0;
-            row_phase_prefetch<PROX, true>(b, L0, wv, opaque(lane));
+            row_phase_prefetch<PROX, true, RES>(b, L0, wv, opaque(lane), res);
 #endif
-            t2_pass<1>(G, F, lds, wv, opaque(lane));
+            if (FOUR) t2_pass4<3>(G, F, lds, wv, opaque(lane));
+            else t2_pass<1>(G, F, lds, wv, opaque(lane));
             SL_STAMP();
             const int u_first = (it == 0);
 #if SLICE_EARLY
-            row_phase<true, PROX, true, true>(b, p.prox, u_first, it + 1 == p.iters, F, wreg, twl, wv, opaque(lane), &L0);
+            row_phase<true, PROX, true, true, RES>(b, p.prox, u_first, it + 1 == p.iters, F, wreg, twl, wv, opaque(lane), &L0, res);
 #else
-            row_phase<true, PROX, true>(b, p.prox, u_first, it + 1 == p.iters, F, wreg, twl, wv, opaque(lane));
+            row_phase<true, PROX, true, false, RES>(b, p.prox, u_first, it + 1 == p.iters, F, wreg, twl, wv, opaque(lane), nullptr, res);
 #endif
             SL_STAMP();
         }
+        if (RES) resident_flush(b, res, wv, opaque(lane));
         __syncthreads();
     }
 }
@@ -898,7 +1014,7 @@ hipError_t slice256_prepare(Slice256* f, hipStream_t s, const float2* y, const u
 }
 
 static hipError_t launch_slice(hipStream_t s, const SliceArgs& a, int prox) {
-    // one workgroup per slice; a workgroup fills a compute unit (512 threads x 256 VGPRs, 134 KiB of LDS)
+    // one workgroup per slice; a workgroup fills a compute unit (512 threads x 256 VGPRs, 137-141 KiB of LDS)
     const dim3 grid(a.B);
     if (prox == 2)      hipLaunchKernelGGL(k_slice<2>, grid, dim3(512), 0, s, a);
     else if (prox == 1) hipLaunchKernelGGL(k_slice<1>, grid, dim3(512), 0, s, a);

@@ -1,5 +1,5 @@
 // Index maps of the slice-resident 256x256 kernel (kernels_slice256.hip), shared with the g++ host
-// emulation (tests/host/slice_resident_emulation.cpp).
+// emulations (tests/host/slice_resident_emulation.cpp: two-pass form; slice_resident4_emulation.cpp: four-pass form + resident w).
 //
 // One 512-thread workgroup (8 waves, 2 per SIMD, 256 VGPRs each) keeps ONE real slice on a compute
 // unit for a whole ADMM run: the 65536 values live in the register file (128 VGPRs per thread, four
@@ -14,7 +14,8 @@
 //                k2 = 128 as V_rho[0] + i V_rho[128].  Same thread shape:
 //                c = 32 s + 4 wv + (l >> 4),  lane t holds rho (or k1) = t + 16 j
 //
-// Row form <-> column form goes through LDS in two passes (the buffer holds half the field):
+// Row form <-> column form goes through LDS in two passes (the buffer holds half the field; the ADMM_L1 instances) or in
+// four (a quarter; ADMM_CNC, whose freed LDS keeps a quarter of w on the compute unit: SL_P4 ... SL_RES below).  Two passes:
 //   pass p moves the columns c = 64 p .. 64 p + 63 (register sets 2p and 2p + 1 of the column form).  A row pair needs, per column c, C_r[c] and its
 //   mirror C_r[256 - c] (for c = 0: C_r[0] and C_r[128]) because
 //     V_2r[k2] = (C_r[k2] + conj C_r[-k2]) / 2,   V_2r+1[k2] = (C_r[k2] - conj C_r[-k2]) / (2i)
@@ -42,6 +43,24 @@ PNP_HD int sl_slot(int k) {
     if (k < 128) return k - 64;                // pass 1, direct:  c = k = 64..127
     return SL_M + 192 - k;                     // pass 1, mirror of c = 256 - k = 64..127  (k = 129..192)
 }
+// FOUR-pass form (ADMM_CNC, k_slice<2>): pass q moves the columns c = 32 q .. 32 q + 31 = register set q of the column form, so
+// the buffer holds a quarter of the field -- 128 row pairs x pitch 68 x 8 B = 69 632 bytes, less than the wave-private exchange
+// regions it aliases -- and LDS has room for SL_RES row pairs of w that stay on the compute unit for a whole launch (below).
+//   slot of (r, c): c - 32 q direct, SL_M4 + c - 32 q mirror (k = 256 - c; for c = 0: k = 128).  Register j of lane t holds
+//   k = t + 16 j, so pass q takes registers 2q, 2q + 1 (direct) and 15 - 2q, 14 - 2q (mirror) -- except in lane 0 of a group,
+//   whose register 14 - 2q holds k = 224 - 32 q, the mirror of column 32 (q + 1): it crosses one pass later (k = 224, 192, 160),
+//   and lane 0's k = 128 (register 8) partners the packed column c = 0 in pass 0.
+constexpr int SL_P4 = 68;     // pitch; 68 % 32 == 4, the bank property of SL_P
+constexpr int SL_M4 = 34;     // mirrored half; 34 % 4 == 2 as SL_M
+constexpr int SL_BUF4 = 128 * SL_P4;
+PNP_HD int sl_pass4(int k) { return k == 128 ? 0 : k < 128 ? (k >> 5) : ((256 - k) >> 5); }
+PNP_HD int sl_slot4(int k) { return k == 128 ? SL_M4 : k < 128 ? (k & 31) : SL_M4 + ((256 - k) & 31); }
+// Resident w: the row pairs r = 0 .. SL_RES - 1 (register set 0 of the row form: 4 wave + group, the same share for every
+// wave) keep w in LDS between the iterations of a launch, in the order of a row pair in HBM (sl_state_index): the lane's
+// q-th 16-byte access of row pair r starts at float sl_res_index(r, t, q) of the region.  A lane reads back what it wrote.
+constexpr int SL_RES = 32;
+PNP_HD int sl_res_index(int r, int t, int q) { return 512 * r + 64 * q + 4 * t; }
+
 // thread shape shared by both forms
 constexpr int SL_WAVES = 8, SL_SETS = 4;
 PNP_HD int sl_unit(int set, int wv, int lane) { return 32 * set + 4 * wv + (lane >> 4); }     // r or c

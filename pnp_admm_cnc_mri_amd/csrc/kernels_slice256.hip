@@ -11,11 +11,13 @@
 //
 //   per iteration and slice:  z, w read + written (16 N bytes; 8 N for ADMM_L1's single-state form),
 //                             Hermitian measurement table read (4 N)              = 20 N (12 N) bytes
-//   ADMM_CNC (k_slice<2>) moves less: a quarter of w (row pairs 0..31 = register set 0 of the row form, 64 KiB) is read
-//   from HBM once per launch, lives in LDS for the launch's K iterations and is stored when they are over:
-//   20 N - 2 N (2K - 1) / K bytes per iteration.  The room comes from crossing the transpositions in FOUR passes of a
+//   ADMM_CNC (k_slice<2>) moves less: part of w is read from HBM once per launch, lives on the compute unit for the launch's K
+//   iterations and is stored when they are over.  The share is counted in UNITS (slice_layout.h): unit (s, q) = the q-th 16-byte
+//   access of register set s, 8 KiB per slice, a compile-time property of that instruction slot.  U units: 20 N - U (N / 8) (2K - 1) / K
+//   bytes per iteration.  Resident: set 0 (8 units = row pairs 0..31, 64 KiB) and the units (1, 0), (1, 1) in LDS, the units (3, 0), (3, 1)
+//   in eight registers of every lane: U = 12.  The LDS comes from crossing the transpositions in FOUR passes of a
 //   quarter of the field instead of two of a half (buffer 69 632 B, below the exchange regions it aliases):
-//     exchange regions / buffer 73 728 + W256 table 2 304 + Ys / Ms 2 304 + resident w 65 536 = 143 872 B of LDS
+//     exchange regions / buffer 73 728 + W256 table 2 304 + Ys / Ms 2 304 + resident w 65 536 + 16 384 = 160 256 B of LDS
 //   at the price of eight more workgroup barriers per iteration.  The two L1 instances keep the two-pass form (139 776 B).
 //
 //   rows(first)                 v = z - w, row pairs (2r, 2r+1) packed as one complex row, 16-lane FFT-256
@@ -60,9 +62,7 @@
 #ifndef SLICE_ST_AUX
 #define SLICE_ST_AUX 0      // cache policy bits of the state stores (experiment knob)
 #endif
-#ifndef SLICE_RESIDENT
-#define SLICE_RESIDENT 1    // k_slice<2>: register set 0 of w stays in LDS for a launch (0: four-pass transpositions alone, the cost side of the A/B)
-#endif
+// SLICE_RESIDENT, SLICE_UNITS_LDS1, SLICE_UNITS_REG (which part of w stays on the compute unit): slice_layout.h
 #ifndef SLICE_PF
 #define SLICE_PF 3          // of a set's 8 z / w accesses per lane: fetched ahead of the transforms (experiment knob)
 #endif
@@ -104,9 +104,14 @@ static_assert(SL_WAVES * WREG <= SL_BUF, "wave regions must fit in the buffer th
 constexpr int SL4_XB = SL_WAVES * WREG;           // exchange regions / transposition buffer
 constexpr int SL4_YS = SL4_XB + REGION;
 constexpr int SL4_RES = SL4_YS + 256 + 32;        // complex index of the resident region (16-byte aligned)
-constexpr int SL4_LDS = SL4_RES + SL_RES * 256;
+// The resident share of w, ONE table for prologue, loop and flush: per register set a mask of the accesses q whose w lives in LDS
+// and one of those whose w lives in registers (units: slice_layout.h).  Set 0 is the region of SL_RES row pairs; the LDS units
+// of set 1 follow it (SL_RES1 x 8 KiB): 143 872 + 16 384 = 160 256 bytes.
+// LDS unit (set, q): floats behind the lane's first access of the set's region (res_lane below)
+__device__ __forceinline__ int sl_lds_float(int set, int q) { return set == 0 ? sl_res_index(0, 0, q) : sl_res1_index(popc8(sl_units_lds(set) & ((1u << q) - 1)), 0, 0); }
+constexpr int SL4_LDS = SL4_RES + SL_RES * 256 + SL_NLDS1 * 1024;
 static_assert(SL_BUF4 <= SL4_XB && SL4_RES % 2 == 0 && SL4_LDS * 8 <= 160 * 1024, "four-pass LDS map");
-// which instances cross in four passes and keep set 0 of w in LDS: ADMM_CNC.  The two L1 forms stay on two passes: the
+// which instances cross in four passes and keep part of w on the compute unit: ADMM_CNC.  The two L1 forms stay on two passes: the
 // single-state form is bound by the compute unit and extra barriers only cost it.
 template <int PROX> constexpr bool slice_four() { return PROX == 2; }
 template <int PROX> constexpr bool slice_res() { return slice_four<PROX>() && SLICE_RESIDENT; }
@@ -283,15 +288,17 @@ __device__ __forceinline__ int row_set_offset(int set, int wv) { return (32 * se
 constexpr int ROW_QSTRIDE = 256;                                  // bytes between a lane's consecutive accesses of a row pair
 
 // voff = 2048 g + 16 t (bytes inside the wave's 8 KiB of a set); the q-th access adds 256 q as an instruction offset
-// RESW: the set's w is resident -- read from LDS at resw (the lane's first access; 64 floats between accesses), not from HBM
+// RESW: the resident units of `set` are at home -- w of an LDS unit is read from LDS (resl = the lane's first access of the set's
+// region), w of a register unit is not fetched at all (it is in the lane's resident registers), neither comes from HBM
 template <int PROX, bool HAS_INV, int Q0, int Q1, bool RESW = false>
-__device__ __forceinline__ void issue_row_loads(const SliceBufs& b, RowLoads& L, int soff, int voff, int qbase = 0, const float* resw = nullptr) {
+__device__ __forceinline__ void issue_row_loads(const SliceBufs& b, RowLoads& L, int soff, int voff, int qbase = 0, int set = 0, const float* resl = nullptr) {
 #pragma unroll
     for (int q = qbase + Q0; q < qbase + Q1; ++q) {
         const int vo = voff + ROW_QSTRIDE * q, so = soff;
-        if (RESW) {
+        const int home = RESW ? w_home(set, q) : W_HBM;
+        if (home != W_HBM) {
             ld4(b.z, vo, so, L.z[q]);
-            lds_ld4(resw + 64 * q, L.w[q]);
+            if (home == W_LDS) lds_ld4(resl + sl_lds_float(set, q), L.w[q]);
         } else if (PROX == 3) {                                                   // single-state ADMM_L1: only the w buffer (it carries u)
             ld4(b.w, vo, so, L.w[q]);
         } else if (PROX != 0 || !HAS_INV) {
@@ -328,10 +335,12 @@ __device__ __forceinline__ void prox_pair(f2 u, f2& z, f2& w, const ProxParams& 
 // the loop has ONE row-phase body for all its iterations (the kernel is 80+ KB of code and the instruction cache 64 KB;
 // a second instance for the final iteration spills 350-490 bytes per lane), at the price of one unused forward
 // transform per launch.
-// RESW (compile time, per set): w of this access stays in LDS at resw (resident set); its HBM copy is written when the launch ends.
-template <bool HAS_INV, int PROX, bool HAS_FWD, bool RESW = false>
+// home (a compile-time constant at every call, per unit): W_LDS -- the new w of this access goes to LDS at resw; W_REG -- it goes
+// back into the lane's resident registers wq (where w_ came from); its HBM copy is written when the launch ends.
+template <bool HAS_INV, int PROX, bool HAS_FWD>
 __device__ __forceinline__ void pointwise_q(const SliceBufs& b, const ProxParams& pc, int u_first, bool last,
-                                            c32& a0, c32& a1, const float (&z_)[4], const float (&w_)[4], int vs, float* resw = nullptr) {
+                                            c32& a0, c32& a1, const float (&z_)[4], const float (&w_)[4], int vs,
+                                            int home = W_HBM, float* resw = nullptr, float* wq = nullptr) {
     f2 z[2] = {k2(z_[0], z_[1]), k2(z_[2], z_[3])}, w[2] = {k2(w_[0], w_[1]), k2(w_[2], w_[3])};
     // u = x + w with x = |re|, |im| (the 1/N of the inverse transform is already in the field, col_phase): two v_add_f32 with
     // the |.| source modifier per register pair -- a packed add has no such modifier and would cost two v_and on top
@@ -360,7 +369,8 @@ __device__ __forceinline__ void pointwise_q(const SliceBufs& b, const ProxParams
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) prox_pair<PROX>(SL_X_PLUS(jj ? a1 : a0, w[jj]), z[jj], w[jj], pc);
         SL_ST4(b.z, z);
-        if (RESW) { const float q_[4] = {w[0].x, w[0].y, w[1].x, w[1].y}; lds_st4(resw, q_); }
+        if (home == W_LDS) { const float q_[4] = {w[0].x, w[0].y, w[1].x, w[1].y}; lds_st4(resw, q_); }
+        else if (home == W_REG) { wq[0] = w[0].x; wq[1] = w[0].y; wq[2] = w[1].x; wq[3] = w[1].y; }
         else SL_ST4(b.w, w);
     }
 #undef SL_ST4
@@ -400,27 +410,32 @@ __device__ __forceinline__ void store_x_natural(const SliceBufs& b, const c32 (&
 #endif                      // next set's inverse transform -- the overlap the form's 8 N fewer bytes leave room for (experiment knob: 4, 2 = less of it)
 template <int PROX> constexpr int row_pf() { return (PROX == 3) ? SLICE_L1_PF : SLICE_PF; }
 // the first accesses of set 0, issued by the caller ahead of the phase (SLICE_EARLY: between the two passes of T2)
-// the lane's first resident access: row pair 4 wv + g of set 0 (sl_res_index, slice_layout.h)
-__device__ __forceinline__ float* res_lane(float* res, int wv, int lane) { return res + sl_res_index(4 * wv + (lane >> 4), lane & 15, 0); }
+// the lane's first resident access in the LDS region of `set`: row pair 4 wv + g of set 0 (sl_res_index, slice_layout.h), or the
+// lane's place in the first unit of the second region (sl_res1_index), which follows the SL_RES row pairs of the first
+__device__ __forceinline__ float* res_lane(float* res, int set, int wv, int lane) {
+    return set == 0 ? res + sl_res_index(4 * wv + (lane >> 4), lane & 15, 0) : res + SL_RES * 512 + sl_res1_index(0, 4 * wv + (lane >> 4), lane & 15);
+}
+typedef float ResRegs[SL_NREG > 0 ? SL_NREG : 1][4];        // the lane's register-resident w: [sl_reg_slot(set, q)] = the four values of that access
 template <int PROX, bool HAS_INV, bool RES = false>
 __device__ __forceinline__ void row_phase_prefetch(const SliceBufs& b, RowLoads& L, int wv, int lane, float* res = nullptr) {
-    issue_row_loads<PROX, HAS_INV, 0, row_pf<PROX>(), RES>(b, L, row_set_offset(0, wv), 2048 * (lane >> 4) + 16 * (lane & 15), 0, RES ? res_lane(res, wv, lane) : nullptr);
+    issue_row_loads<PROX, HAS_INV, 0, row_pf<PROX>(), RES>(b, L, row_set_offset(0, wv), 2048 * (lane >> 4) + 16 * (lane & 15), 0, 0, RES ? res_lane(res, 0, wv, lane) : nullptr);
 }
-// RES: set 0 of w is resident in LDS at `res`.  The prologue (!HAS_INV) copies it there as it reads it; the loop reads and writes
-// it there; resident_flush below stores it to HBM when the launch's iterations are over.
+// RES: the units of the table (sl_units_lds / sl_units_reg) keep w in LDS at `res` or in the registers `wr`.  The prologue (!HAS_INV)
+// copies them there as it reads them; the loop reads and writes them there; resident_flush below stores them to HBM when the
+// launch's iterations are over.
 template <bool HAS_INV, int PROX, bool HAS_FWD, bool PRELOADED = false, bool RES = false>
 __device__ __forceinline__ void row_phase(const SliceBufs& b, const ProxParams& pc, int u_first, bool last, c32 (&F)[SL_SETS][16],
-                                          c32* wreg, const c32* twl, int wv, int lane, RowLoads* pre = nullptr, float* res = nullptr) {
+                                          c32* wreg, const c32* twl, int wv, int lane, ResRegs& wr, RowLoads* pre = nullptr, float* res = nullptr) {
     const int g = lane >> 4, t = lane & 15;
     c32* region = wreg + g * REGION;
     const int voff = 2048 * g + 16 * t;
-    float* resw = RES ? res_lane(res, wv, lane) : nullptr;
-    constexpr bool RES_LOOP = RES && HAS_INV;                    // set 0's w comes from and goes to LDS
+    float* const resl[2] = {RES ? res_lane(res, 0, wv, lane) : nullptr, RES && SL_NLDS1 ? res_lane(res, 1, wv, lane) : nullptr};
+    constexpr bool RES_LOOP = RES && HAS_INV;                    // the resident units' w comes from and goes to LDS / registers
     // PF accesses of the next set are fetched ahead across the transforms; the rest when the set's pointwise phase starts
     constexpr int PF = row_pf<PROX>();
     RowLoads L;
     if (PRELOADED) L = *pre;
-    else issue_row_loads<PROX, HAS_INV, 0, PF, RES_LOOP>(b, L, row_set_offset(0, wv), voff, 0, resw);
+    else issue_row_loads<PROX, HAS_INV, 0, PF, RES_LOOP>(b, L, row_set_offset(0, wv), voff, 0, 0, resl[0]);
 #pragma unroll
     for (int set = 0; set < SL_SETS; ++set) {
         c32 (&a)[16] = F[set];
@@ -435,16 +450,20 @@ __device__ __forceinline__ void row_phase(const SliceBufs& b, const ProxParams& 
         // once, on top of the 128 data registers, made hipcc spill)
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            if (RES_LOOP && set == 0) {
-                if (q + PF < 8) issue_row_loads<PROX, HAS_INV, 0, 1, true>(b, L, soff, voff, q + PF, resw);
-                pointwise_q<HAS_INV, PROX, HAS_FWD, true>(b, pc, u_first, last, a[2 * q], a[2 * q + 1], L.z[q], L.w[q], vs + ROW_QSTRIDE * q, resw + 64 * q);
+            const int home = RES ? w_home(set, q) : W_HBM;               // compile time per (set, q): the loops are unrolled
+            float* const rl = home == W_LDS ? resl[set] + sl_lds_float(set, q) : nullptr;       // (LDS units exist in sets 0 and 1 only)
+            float* const wq = wr[home == W_REG ? sl_reg_slot(set, q) : 0];
+            if (q + PF < 8) issue_row_loads<PROX, HAS_INV, 0, 1, RES_LOOP>(b, L, soff, voff, q + PF, set, resl[set < 2 ? set : 0]);
+            if (RES_LOOP && home != W_HBM) {
+                pointwise_q<HAS_INV, PROX, HAS_FWD>(b, pc, u_first, last, a[2 * q], a[2 * q + 1], L.z[q], home == W_REG ? wr[sl_reg_slot(set, q)] : L.w[q],
+                                                    vs + ROW_QSTRIDE * q, home, rl, wq);
             } else {
-                if (q + PF < 8) issue_row_loads<PROX, HAS_INV, 0, 1>(b, L, soff, voff, q + PF);
-                if (RES && !HAS_INV && set == 0) lds_st4(resw + 64 * q, L.w[q]);         // prologue: the resident rows enter LDS
+                if (home == W_LDS) lds_st4(rl, L.w[q]);                  // prologue: the resident units enter LDS ...
+                if (home == W_REG) { wq[0] = L.w[q][0]; wq[1] = L.w[q][1]; wq[2] = L.w[q][2]; wq[3] = L.w[q][3]; }       // ... or their registers
                 pointwise_q<HAS_INV, PROX, HAS_FWD>(b, pc, u_first, last, a[2 * q], a[2 * q + 1], L.z[q], L.w[q], vs + ROW_QSTRIDE * q);
             }
         }
-        if (set + 1 < SL_SETS) issue_row_loads<PROX, HAS_INV, 0, PF>(b, L, row_set_offset(set + 1, wv), voff);
+        if (set + 1 < SL_SETS) issue_row_loads<PROX, HAS_INV, 0, PF, RES_LOOP>(b, L, row_set_offset(set + 1, wv), voff, 0, set + 1, resl[set + 1 < 2 ? set + 1 : 0]);
         if (HAS_FWD) {
             group_fft256<false>(a, twl, region, t);
         }
@@ -452,14 +471,21 @@ __device__ __forceinline__ void row_phase(const SliceBufs& b, const ProxParams& 
 }
 
 // end of a launch's iterations: the resident share of w goes back to HBM (each lane stores what it wrote itself)
-__device__ __forceinline__ void resident_flush(const SliceBufs& b, const float* res, int wv, int lane) {
-    const float* resw = res_lane(const_cast<float*>(res), wv, lane);
-    const int vs = 2048 * (lane >> 4) + 16 * (lane & 15) + row_set_offset(0, wv);
+__device__ __forceinline__ void resident_flush(const SliceBufs& b, float* res, const ResRegs& wr, int wv, int lane) {
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        float v[4];
-        lds_ld4(resw + 64 * q, v);
-        st4(b.w, vs + ROW_QSTRIDE * q, 0, v);
+    for (int set = 0; set < SL_SETS; ++set) {
+        const int vs = 2048 * (lane >> 4) + 16 * (lane & 15) + row_set_offset(set, wv);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int home = w_home(set, q);
+            if (home == W_LDS) {
+                float v[4];
+                lds_ld4(res_lane(res, set, wv, lane) + sl_lds_float(set, q), v);
+                st4(b.w, vs + ROW_QSTRIDE * q, 0, v);
+            } else if (home == W_REG) {
+                st4(b.w, vs + ROW_QSTRIDE * q, 0, wr[sl_reg_slot(set, q)]);
+            }
+        }
     }
 }
 
@@ -735,7 +761,7 @@ __device__ __forceinline__ void col_phase(const SliceBufs& b, float cdc, float s
 // ------------------------------------------------------------------------------------------
 template <int PROX>
 __global__ __launch_bounds__(512) void k_slice(SliceArgs p) {
-    constexpr bool FOUR = slice_four<PROX>(), RES = slice_res<PROX>();     // four-pass transpositions; set 0 of w resident in LDS
+    constexpr bool FOUR = slice_four<PROX>(), RES = slice_res<PROX>();     // four-pass transpositions; the table's units of w resident in LDS / registers
     __shared__ __attribute__((aligned(16))) c32 lds[FOUR ? SL4_LDS : SL_LDS];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave index as a scalar: bases below stay in SGPRs
@@ -754,6 +780,7 @@ __global__ __launch_bounds__(512) void k_slice(SliceArgs p) {
         b.yh = make_rsrc(p.Yh + (size_t)slice * p.yh_stride, YH3_SLICE * 8); b.mh = make_rsrc(p.Mh + (size_t)slice * MH3_SLICE, MH3_SLICE * 4);
         b.ys = make_rsrc(p.Ys + (size_t)slice * 256, 256 * 8); b.ms = make_rsrc(p.Ms + (size_t)slice * 16, 16 * 4);
         c32 F[SL_SETS][16];
+        ResRegs wres;                             // register-resident units of w (RES; otherwise unused and gone)
         // phase clocks exist only in a -DSLICE_PROF build (profiles/variants.sh): in the product they cost two registers
         // and a dozen branches of a kernel that has neither to spare
 #ifdef SLICE_PROF
@@ -763,7 +790,7 @@ __global__ __launch_bounds__(512) void k_slice(SliceArgs p) {
 #define SL_STAMP()
 #endif
         SL_STAMP();
-        row_phase<false, 0, true, false, RES>(b, p.prox, 1, false, F, wreg, twl, wv, opaque(lane), nullptr, res);
+        row_phase<false, 0, true, false, RES>(b, p.prox, 1, false, F, wreg, twl, wv, opaque(lane), wres, nullptr, res);
         SL_STAMP();
         for (int it = 0; it < p.iters; ++it) {
             c32 G[SL_SETS][16];
@@ -803,13 +830,13 @@ __global__ __launch_bounds__(512) void k_slice(SliceArgs p) {
             SL_STAMP();
             const int u_first = (it == 0);
 #if SLICE_EARLY
-            row_phase<true, PROX, true, true, RES>(b, p.prox, u_first, it + 1 == p.iters, F, wreg, twl, wv, opaque(lane), &L0, res);
+            row_phase<true, PROX, true, true, RES>(b, p.prox, u_first, it + 1 == p.iters, F, wreg, twl, wv, opaque(lane), wres, &L0, res);
 #else
-            row_phase<true, PROX, true, false, RES>(b, p.prox, u_first, it + 1 == p.iters, F, wreg, twl, wv, opaque(lane), nullptr, res);
+            row_phase<true, PROX, true, false, RES>(b, p.prox, u_first, it + 1 == p.iters, F, wreg, twl, wv, opaque(lane), wres, nullptr, res);
 #endif
             SL_STAMP();
         }
-        if (RES) resident_flush(b, res, wv, opaque(lane));
+        if (RES) resident_flush(b, res, wres, wv, opaque(lane));
         __syncthreads();
     }
 }

@@ -1,5 +1,6 @@
 // Index maps of the slice-resident 256x256 kernel (kernels_slice256.hip), shared with the g++ host
-// emulations (tests/host/slice_resident_emulation.cpp: two-pass form; slice_resident4_emulation.cpp: four-pass form + resident w).
+// emulations (tests/host/slice_resident_emulation.cpp: two-pass form; slice_resident4_emulation.cpp: four-pass form + resident w;
+// slice_resident_units_emulation.cpp: the resident units of w).
 //
 // One 512-thread workgroup (8 waves, 2 per SIMD, 256 VGPRs each) keeps ONE real slice on a compute
 // unit for a whole ADMM run: the 65536 values live in the register file (128 VGPRs per thread, four
@@ -15,7 +16,8 @@
 //                c = 32 s + 4 wv + (l >> 4),  lane t holds rho (or k1) = t + 16 j
 //
 // Row form <-> column form goes through LDS in two passes (the buffer holds half the field; the ADMM_L1 instances) or in
-// four (a quarter; ADMM_CNC, whose freed LDS keeps a quarter of w on the compute unit: SL_P4 ... SL_RES below).  Two passes:
+// four (a quarter; ADMM_CNC, whose freed LDS keeps part of w on the compute unit -- a quarter as whole row pairs, SL_RES, and
+// further (register set, access) units in LDS and in registers: SL_P4 ... the table sl_units_lds / sl_units_reg below).  Two passes:
 //   pass p moves the columns c = 64 p .. 64 p + 63 (register sets 2p and 2p + 1 of the column form).  A row pair needs, per column c, C_r[c] and its
 //   mirror C_r[256 - c] (for c = 0: C_r[0] and C_r[128]) because
 //     V_2r[k2] = (C_r[k2] + conj C_r[-k2]) / 2,   V_2r+1[k2] = (C_r[k2] - conj C_r[-k2]) / (2i)
@@ -55,14 +57,47 @@ constexpr int SL_M4 = 34;     // mirrored half; 34 % 4 == 2 as SL_M
 constexpr int SL_BUF4 = 128 * SL_P4;
 PNP_HD int sl_pass4(int k) { return k == 128 ? 0 : k < 128 ? (k >> 5) : ((256 - k) >> 5); }
 PNP_HD int sl_slot4(int k) { return k == 128 ? SL_M4 : k < 128 ? (k & 31) : SL_M4 + ((256 - k) & 31); }
+// thread shape shared by both forms
+constexpr int SL_WAVES = 8, SL_SETS = 4;
 // Resident w: the row pairs r = 0 .. SL_RES - 1 (register set 0 of the row form: 4 wave + group, the same share for every
 // wave) keep w in LDS between the iterations of a launch, in the order of a row pair in HBM (sl_state_index): the lane's
 // q-th 16-byte access of row pair r starts at float sl_res_index(r, t, q) of the region.  A lane reads back what it wrote.
 constexpr int SL_RES = 32;
 PNP_HD int sl_res_index(int r, int t, int q) { return 512 * r + 64 * q + 4 * t; }
+// Residency is counted in UNITS: unit (s, q) = the q-th 16-byte access of register set s -- the same instruction slot in every
+// lane of every wave, for the workgroup 8 KiB = the q-th eighth (256 bytes) of each of the set's 32 row pairs.  Whether a
+// unit's w lives in HBM, in LDS or in registers is a compile-time property of that slot (the table sl_units_lds / sl_units_reg
+// below): no wave-dependent choice.  The region above is the units (0, 0) .. (0, 7).  The units (1, q) that
+// stay in LDS follow it in a second region of SL_RES1 units x 2048 floats, numbered u = 0 .. SL_RES1 - 1 by rising q: the
+// access of row pair 32 + rr (rr = 4 wave + group = 0..31) and lane t starts at float sl_res1_index(u, rr, t) -- a wave's
+// 64 lanes read 1 KiB contiguous.  A lane reads back what it wrote.
+constexpr int SL_RES1 = 2;
+PNP_HD int sl_res1_index(int u, int rr, int t) { return 2048 * u + 64 * rr + 4 * t; }
+// The table: which units are resident, and where (compile-time knobs of the kernel; the host emulation reads the same table).
+#ifndef SLICE_RESIDENT
+#define SLICE_RESIDENT 1    // k_slice<2>: part of w stays on the compute unit for a launch, by (register set, access) units -- set 0 in LDS and the units of the
+#endif                      // two masks below (0: no residency at all, four-pass transpositions alone; 2: set 0 only, the kernel before the unit form: the arms of the A/B)
+#ifndef SLICE_UNITS_LDS1
+#define SLICE_UNITS_LDS1 0x03       // bit q: unit (1, q) of w lives in the second LDS region (at most SL_RES1 units)
+#endif
+#ifndef SLICE_UNITS_REG
+#define SLICE_UNITS_REG 0x03000000  // bit 8 s + q: unit (s, q) of w lives in four registers of every lane across the iteration loop (default: (3, 0), (3, 1))
+#endif
+constexpr int popc8(unsigned m) { int n = 0; for (int i = 0; i < 8; ++i) n += (m >> i) & 1; return n; }
+constexpr unsigned sl_units_lds(int set) { return SLICE_RESIDENT == 0 ? 0u : set == 0 ? 0xFFu : (SLICE_RESIDENT == 1 && set == 1) ? (SLICE_UNITS_LDS1 & 0xFFu) : 0u; }
+constexpr unsigned sl_units_reg(int set) { return SLICE_RESIDENT == 1 && set < SL_SETS ? ((unsigned)SLICE_UNITS_REG >> (8 * set)) & 0xFFu & ~sl_units_lds(set) : 0u; }
+enum { W_HBM = 0, W_LDS = 1, W_REG = 2 };                  // where the w of a unit is between the iterations of a launch
+constexpr int w_home(int set, int q) { return ((sl_units_lds(set) >> q) & 1) ? W_LDS : ((sl_units_reg(set) >> q) & 1) ? W_REG : W_HBM; }
+// register unit (set, q): its place among the lane's resident registers
+constexpr int sl_reg_slot(int set, int q) {
+    int n = 0;
+    for (int s = 0; s < set; ++s) n += popc8(sl_units_reg(s));
+    return n + (set < SL_SETS ? popc8(sl_units_reg(set) & ((1u << q) - 1)) : 0);
+}
+constexpr int SL_NREG = sl_reg_slot(SL_SETS, 0);         // register units
+constexpr int SL_NLDS1 = popc8(sl_units_lds(1));          // LDS units of set 1
+static_assert(SL_NLDS1 <= SL_RES1, "the second resident region holds SL_RES1 units");
 
-// thread shape shared by both forms
-constexpr int SL_WAVES = 8, SL_SETS = 4;
 PNP_HD int sl_unit(int set, int wv, int lane) { return 32 * set + 4 * wv + (lane >> 4); }     // r or c
 
 // per-slice operand tables in column-form thread order

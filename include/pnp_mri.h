@@ -42,7 +42,7 @@ extern "C" {
 #define PNP_E_STATE      -3   /* call order (e.g. run before upload)        */
 #define PNP_E_NOMEM      -4
 
-#define PNP_ABI_VERSION   12
+#define PNP_ABI_VERSION   13
 
 typedef struct pnp_ctx pnp_ctx;
 
@@ -131,6 +131,39 @@ int pnp_admm_l1_run(pnp_ctx* ctx, int iters, double lambda1, double reo);
  * t = (1-alpha) z + alpha (x+w) + alpha*reo*lambda1*b (z-s); z = soft(t, alpha*reo*lambda1);
  * w += x - z. */
 int pnp_admm_cnc_run(pnp_ctx* ctx, int iters, double alpha, double lambda1, double reo, double b);
+/* ---- convergence trace and residual-based stopping (new in ABI 13; the reference has no counterpart: its loops, S1:111-126 and
+ * S4:115-132, run a fixed iter_num and keep nothing but the last x) ---------------------------------------------------------
+ * The same loops as pnp_admm_l1_run / pnp_admm_cnc_run (S4:115-132 is the loop they observe), with the state reduced at CHECKED
+ * iterations: every multiple of `every` (>= 1) that is <= the iterations run, plus the last iteration run if it is not one.
+ * Row of a check at iteration k (k completed iterations, 1-based), per slice, PNP_TRACE_Q values:
+ *   r_pri = ||x_k - z_k||, r_dual = ||z_k - z_{k-1}|| (z_0: the state the call started from), ||x_k||, ||z_k||, ||w_k||, and --
+ *   with a ground truth gt (uint8 [B][H][W], host or device as for pnp_metrics; NULL: none, the two values are NaN) -- PSNR and
+ *   RE of img_E = 255 x_k by pnp_metrics' formulas, so the row of the last iteration equals pnp_metrics of the returned x.
+ * x, z, w are what the loop holds after iteration k -- what pnp_download_x / pnp_get_state return after an untraced run of k
+ * iterations, bit for bit: the run is cut into launches at k - 1 and k (a run split into launches equals one launch), z of
+ * k - 1 is copied, and ONE reduction kernel per check (all slices, double accumulation, a fixed tree: the same inputs give the
+ * same bits) reads the state where it lies.  No loop kernel differs from the untraced call's.
+ * tol <= 0: no stopping rule; the host reads nothing until the run is over.  tol > 0: slice b MEETS the rule at a check when
+ *   max(r_pri, r_dual) <= tol * ||z_k||;  the run stops after the first check at which every slice meets it (all slices always
+ *   run the same number of iterations); one small copy and one synchronisation per check.
+ * Outputs: *checks = rows recorded, *iters_done = iterations run (= iters unless stopped).  iters = 0: zero checks and exactly
+ * pnp_admm_*_run(iters = 0).  every < 1: PNP_E_ARG.  The rows are kept by the context until its next traced run: */
+#define PNP_TRACE_R_PRI   0
+#define PNP_TRACE_R_DUAL  1
+#define PNP_TRACE_X_NORM  2
+#define PNP_TRACE_Z_NORM  3
+#define PNP_TRACE_W_NORM  4
+#define PNP_TRACE_PSNR    5
+#define PNP_TRACE_RE      6
+#define PNP_TRACE_Q       7
+int pnp_admm_l1_run_traced(pnp_ctx* ctx, int iters, double lambda1, double reo, int every, double tol,
+                           const uint8_t* gt, int gt_on_device, int* checks, int* iters_done);
+int pnp_admm_cnc_run_traced(pnp_ctx* ctx, int iters, double alpha, double lambda1, double reo, double b, int every, double tol,
+                            const uint8_t* gt, int gt_on_device, int* checks, int* iters_done);
+/* The last traced run of the context (host arrays; any pointer may be NULL): iters [checks] the checked iterations,
+ * values [checks][PNP_TRACE_Q][B] as above, converged_at [B] the first checked iteration at which the slice met the rule (0: never,
+ * or no tol). */
+int pnp_trace_read(pnp_ctx* ctx, int32_t* iters, double* values, int32_t* converged_at);
 /* x of the last iteration ([B][H][W] float32) -- what the solvers return (S4:138). */
 int pnp_download_x(pnp_ctx* ctx, float* x, int on_device);
 
@@ -152,6 +185,16 @@ int pnp_add(pnp_ctx* ctx, const float* a_dev, const float* b_dev, float* out_dev
 /* w = w + x - z, then x,z,w <- clamp(.,0,1) with torch.clamp_'s semantics: NaN stays NaN, +-inf go to the bounds, so a
  * non-finite denoiser output reaches the returned x instead of turning into 0                (S6:305-308) */
 int pnp_dual_clamp(pnp_ctx* ctx, float* x_dev, float* z_dev, float* w_dev);
+
+/* The reduction of the traced loops alone, on caller-owned device tensors in natural order (what the PnP solvers call after
+ * pnp_dual_clamp; new in ABI 13): out [PNP_TRACE_Q][B] doubles, the SUMS OF SQUARES behind a trace row, per slice --
+ *   sum (x - z)^2, sum (z - z_prev)^2, sum x^2, sum z^2, sum w^2, sum (255 x' - gt)^2, sum gt^2
+ * -- the last two 0 with gt = NULL; x' = x, or with quantise != 0 round(255 x) * (1 / 255) in the state's arithmetic (the img_E the PnP solvers
+ * score, S6:314, as torch forms round(x * 255) / 255 on the device: half to even, times the reciprocal).
+ * out is host memory (the call synchronises) or, with out_on_device, device memory (asynchronous on the ctx stream; it must not
+ * overlap an input: PNP_E_ARG).  The inputs may alias each other.  One launch, deterministic. */
+int pnp_residuals(pnp_ctx* ctx, const float* x_dev, const float* z_dev, const float* zprev_dev, const float* w_dev,
+                  const uint8_t* gt, int gt_on_device, int quantise, double* out, int out_on_device);
 
 /* ---- operator API (batched; B slices of the ctx's H x W; complex64 device pointers) ------- */
 int pnp_fft2_fwd(pnp_ctx* ctx, const float* in_dev, float* out_dev, int B);   /* np.fft.fft2  */
@@ -209,6 +252,9 @@ int pnp_is_f64(pnp_ctx* ctx);
 int pnp_metrics_f64(pnp_ctx* ctx, const double* x_dev, const uint8_t* gt, int gt_on_device,
                     double* psnr_host, double* re_host);
 int pnp_ssim_f64(pnp_ctx* ctx, const double* x_dev, const uint8_t* gt, int gt_on_device, double* ssim_host);
+/* pnp_residuals on a double-precision context (double device tensors).  New in ABI 13. */
+int pnp_residuals_f64(pnp_ctx* ctx, const double* x_dev, const double* z_dev, const double* zprev_dev, const double* w_dev,
+                      const uint8_t* gt, int gt_on_device, int quantise, double* out, int out_on_device);
 
 /* ---- optional HIP backend of the denoisers' plain conv stacks ------------------------------
  * The north star keeps the CNN forward pass in PyTorch-ROCm; these two entry points are the opt-in `Denoiser(backend='hip')`

@@ -42,6 +42,13 @@ SIGNATURES = {
     'pnp_admm_l1_run': (C.c_int, [ctx_p, C.c_int, C.c_double, C.c_double]),
     'pnp_admm_cnc_run': (C.c_int, [ctx_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]),
     'pnp_download_x': (C.c_int, [ctx_p, _vp, C.c_int]),
+    'pnp_admm_l1_run_traced': (C.c_int, [ctx_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, _vp, C.c_int,
+                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'pnp_admm_cnc_run_traced': (C.c_int, [ctx_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _vp, C.c_int,
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'pnp_trace_read': (C.c_int, [ctx_p, _vp, _vp, _vp]),
+    'pnp_residuals': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int]),
+    'pnp_residuals_f64': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int]),
     'pnp_dc_step': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_double]),
     'pnp_prox_l1_dual': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_double]),
     'pnp_prox_cnc_dual': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double]),
@@ -94,7 +101,7 @@ SIGNATURES = {
     'pnp_fft_plan': (C.c_int, [ctx_p, C.c_int, C.c_char_p, C.c_int]),
 }
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 _lib = None
 
 

@@ -81,6 +81,20 @@ struct Problem {
     bool slice_built = false;         // the slice-resident tables
 };
 
+// Convergence trace (trace_plan.h, kernels_trace.hip): the device buffers of the reduction and the host copy of the last traced run.
+struct Trace {
+    double* partial = nullptr;        // scratch of the reduction (trace_scratch_bytes)
+    unsigned* counter = nullptr;      // [Bmax] ticket counters, zero between launches
+    double* rows = nullptr;           // [rows_cap][TRACE_Q][Bmax] sums of squares, row c = check c
+    int rows_cap = 0;
+    void* zprev = nullptr;            // [Bmax][H][W] z of the iteration before a check (natural order; on first use)
+    void *zc = nullptr, *wc = nullptr;  // two-launch engines: z, w of a checked iteration, materialised beside the running chain
+    // what pnp_trace_read returns: the last traced run
+    int B = 0;
+    std::vector<int32_t> iters, converged_at;
+    std::vector<double> values;       // [checks][TRACE_Q][B]: r_pri, r_dual, x_norm, z_norm, w_norm, psnr, re
+};
+
 struct pnp_ctx {
     int device = 0, H = 0, W = 0, Bmax = 0;
     int B = 0, K = 0;                 // current problem (0 = none uploaded)
@@ -107,6 +121,7 @@ struct pnp_ctx {
     AnySize* any = nullptr;           // H, W not both in {256, 512}: the row / column transforms run on the any-size kernels
     Problem prob;
     FusedSchedule sched;              // defaults overridable by PNP_FUSED_* (read at creation) / pnp_set_schedule
+    Trace trace;
 };
 
 // The context's buffers as the element type of its precision (R = float | double).
@@ -478,6 +493,222 @@ static int run_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, d
     return PNP_OK;
 }
 
+// ---- convergence trace: legs of launches by trace_plan.h, one reduction per check ----
+
+// the reduction's scratch, and room for `checks` rows
+static int trace_buffers(pnp_ctx* c, int checks) {
+    Trace& t = c->trace;
+    if (!t.partial) HIPCHK(hipMalloc((void**)&t.partial, trace_scratch_bytes(c->Bmax)));
+    if (!t.counter) {
+        HIPCHK(hipMalloc((void**)&t.counter, (size_t)c->Bmax * sizeof(unsigned)));
+        HIPCHK(hipMemset(t.counter, 0, (size_t)c->Bmax * sizeof(unsigned)));          // every launch leaves it zero again
+    }
+    if (checks > t.rows_cap) {
+        if (t.rows) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(t.rows)); t.rows = nullptr; t.rows_cap = 0; }
+        HIPCHK(hipMalloc((void**)&t.rows, (size_t)checks * TRACE_Q * c->Bmax * sizeof(double)));
+        t.rows_cap = checks;
+    }
+    return PNP_OK;
+}
+
+// sums of squares [TRACE_Q][B] -> r_pri, r_dual, x_norm, z_norm, w_norm, psnr, re (pnp_metrics' formulas; NaN without a ground truth)
+static void trace_values(const double* sums, double* out, int B, size_t N, bool have_gt) {
+    for (int b = 0; b < B; ++b) {
+        for (int q = TR_XZ; q <= TR_W; ++q) out[(size_t)q * B + b] = sqrt(sums[(size_t)q * B + b]);
+        const double se = sums[(size_t)TR_E * B + b], sg = sums[(size_t)TR_G * B + b], mse = se / (double)N;
+        out[(size_t)PNP_TRACE_PSNR * B + b] = !have_gt ? NAN : (mse == 0.0) ? INFINITY : 20.0 * log10(255.0 / sqrt(mse));
+        out[(size_t)PNP_TRACE_RE * B + b] = !have_gt ? NAN : sqrt(se) / sqrt(sg);
+    }
+}
+
+// One launch of the chain of the context's two-launch engine (engine_host.h, chain_step), on a float state ...
+static hipError_t fast_step(pnp_ctx* c, ChainStep st, const float* z, const float* w, float* zo, float* wo, float* x, bool cnc, float cdc,
+                            const ProxParams& pp, bool u_first) {
+    switch (c->eng.kind) {
+    case Engine::fused256:  return fused256_step(c->eng.f256, c->stream, st, z, w, zo, wo, x, c->B, cnc, cdc, pp, c->sched, u_first);
+    case Engine::split_f32: return fused256s_step<float>(c->eng.s32, c->stream, st, z, w, zo, wo, x, c->B, cnc, cdc, pp, c->sched, u_first);
+    case Engine::fused512:  return fused512_step(c->eng.f512, c->stream, st, z, w, zo, wo, x, c->B, cnc, cdc, pp, c->sched, u_first);
+    case Engine::none: case Engine::split_f64: break;
+    }
+    return hipErrorInvalidValue;
+}
+// ... and on a double state
+static hipError_t fast_step(pnp_ctx* c, ChainStep st, const double* z, const double* w, double* zo, double* wo, double* x, bool cnc, double cdc,
+                            const ProxParamsT<double>& pp, bool u_first) {
+    return fused256s_step<double>(c->eng.s64, c->stream, st, z, w, zo, wo, x, c->B, cnc, cdc, pp, c->sched, u_first);
+}
+
+struct TraceRun {                     // what run_traced's two drivers share
+    int iters, every, checks;
+    double tol;
+    const uint8_t* gt;                // device, or null
+};
+// after the reduction of check k into row `out`: with tol, read the row, note who meets the rule; -> 1 = stop, 0 = go on, < 0 error
+static int trace_checked(pnp_ctx* c, const TraceRun& r, int iter, const double* out) {
+    if (!(r.tol > 0.0)) return 0;                                                  // the whole trace is read after the run
+    Trace& t = c->trace;
+    const int B = c->B;
+    const size_t row = (size_t)TRACE_Q * B;
+    std::vector<double> sums(row), vals(row);
+    if (int rc = copy_out(c, sums.data(), out, row * sizeof(double), 0)) return rc;      // one small copy and one sync per check
+    trace_values(sums.data(), vals.data(), B, c->N, r.gt != nullptr);
+    t.iters.push_back(iter);
+    t.values.insert(t.values.end(), vals.begin(), vals.end());
+    bool all = true;
+    for (int s = 0; s < B; ++s) {
+        const double rp = vals[(size_t)PNP_TRACE_R_PRI * B + s], rd = vals[(size_t)PNP_TRACE_R_DUAL * B + s];
+        const bool met = (rp > rd ? rp : rd) <= r.tol * vals[(size_t)PNP_TRACE_Z_NORM * B + s];
+        if (met && t.converged_at[s] == 0) t.converged_at[s] = iter;
+        all = all && met;
+    }
+    return all ? 1 : 0;
+}
+
+// The two-launch engines (Path::fused).  Their run is a chain of launches already -- forward rows, then columns and rows per iteration --
+// but it is NOT cut: two slices share one complex transform, and the absent partner of an odd batch's last slice lives on in the
+// transform buffer from iteration to iteration, so a run cut into launches of fewer iterations rounds that slice differently (DESIGN.md
+// section 11).  The chain therefore runs on unbroken, launch for launch what the untraced run enqueues (on one queue: scheduling never
+// changes results), and where an iteration's state is wanted -- k a checked iteration, or k + 1 one (its z is that check's z_prev) -- a
+// LAST-stage row launch between the iteration's columns and its mid-stage rows writes x, z, w of that iteration into side buffers: the
+// very launch that ends an untraced run of k iterations, on the same inputs, so the rows are the norms of exactly that run's state.
+template <typename R>
+static int run_traced_chain(pnp_ctx* c, const TraceRun& r, bool cnc, const ProxParamsT<R>& pp, R cdc, int* nrows, int* done) {
+    Trace& t = c->trace;
+    const Bufs<R> b = bufs<R>(c);
+    const int B = c->B;
+    const size_t row = (size_t)TRACE_Q * B, bytes = (size_t)B * c->N * sizeof(R), cap = (size_t)c->Bmax * c->N * sizeof(R);
+    for (void** p : {&t.zprev, &t.zc, &t.wc}) if (!*p) HIPCHK(hipMalloc(p, cap));
+    R *zp = (R*)t.zprev, *zc = (R*)t.zc, *wc = (R*)t.wc;
+    int k_check = 0, next = trace_check_iter(r.iters, r.every, 0);
+    if (next == 1) HIPCHK(hipMemcpyAsync(zp, b.z, bytes, hipMemcpyDeviceToDevice, c->stream));          // z_0
+    HIPCHK(fast_step(c, ChainStep::open, b.z, b.w, (R*)nullptr, (R*)nullptr, b.x, cnc, cdc, pp, true));
+    for (int k = 1; k <= r.iters; ++k) {
+        const bool first = k == 1, last = k == r.iters;
+        HIPCHK(fast_step(c, ChainStep::cols, b.z, b.w, (R*)nullptr, (R*)nullptr, b.x, cnc, cdc, pp, first));
+        if (k == next) {
+            double* out = t.rows + (size_t)k_check * row;
+            if (last) {                                                            // the run's own last stage, in place
+                HIPCHK(fast_step(c, ChainStep::last, b.z, b.w, b.z, b.w, b.x, cnc, cdc, pp, first));
+                HIPCHK(launch_residuals<R>(c->stream, b.x, b.z, zp, b.w, r.gt, 0, B, c->N, c->N, false, t.partial, t.counter, out));
+            } else {
+                HIPCHK(fast_step(c, ChainStep::last, b.z, b.w, zc, wc, b.x, cnc, cdc, pp, first));
+                HIPCHK(launch_residuals<R>(c->stream, b.x, zc, zp, wc, r.gt, 0, B, c->N, c->N, false, t.partial, t.counter, out));
+            }
+            *nrows = ++k_check; *done = k;
+            const int stop = trace_checked(c, r, k, out);
+            if (stop < 0) return stop;
+            if (stop == 1) {
+                if (!last) {                                                       // the state of iteration k becomes the context's
+                    HIPCHK(hipMemcpyAsync(b.z, zc, bytes, hipMemcpyDeviceToDevice, c->stream));
+                    HIPCHK(hipMemcpyAsync(b.w, wc, bytes, hipMemcpyDeviceToDevice, c->stream));
+                }
+                return PNP_OK;
+            }
+            if (last) return PNP_OK;
+            next = trace_check_iter(r.iters, r.every, k_check);
+            if (next == k + 1) { R* tmp = zp; zp = zc; zc = tmp; t.zprev = zp; t.zc = zc; }      // z_k is the next check's z_prev
+        } else if (k + 1 == next) {
+            HIPCHK(fast_step(c, ChainStep::last, b.z, b.w, zp, wc, b.x, cnc, cdc, pp, first));      // z_k for the check at k + 1
+        }
+        HIPCHK(fast_step(c, last ? ChainStep::last : ChainStep::mid, b.z, b.w, b.z, b.w, b.x, cnc, cdc, pp, first));
+    }
+    return PNP_OK;
+}
+
+// A run of `iters` iterations with a check every `every`.  Slice-resident and generic paths: per check a leg of trace_plan.h -- [launch
+// of leg.pre iterations], snapshot of z, one iteration, reduction into row c -- all on the context's stream, each behind the join that
+// ends the launch before it.  Two-launch engines: run_traced_chain above.  Without tol the host reads nothing until the run is over;
+// with tol it reads one row per check and stops once every slice meets the rule.
+template <typename R>
+static int run_traced(pnp_ctx* c, const char* who, int iters, bool cnc, const ProxParamsT<R>& pp, double reo, int every, double tol,
+                      const uint8_t* gt, int gt_on_device, int* checks_out, int* iters_done) {
+    if (every < 1) return fail(PNP_E_ARG, "%s: every must be >= 1 (got %d)", who, every);
+    if (!checks_out || !iters_done) return fail(PNP_E_ARG, "%s: checks / iters_done is null", who);
+    if (tol != tol) return fail(PNP_E_ARG, "%s: tol is NaN", who);
+    Trace& t = c->trace;
+    const Bufs<R> b = bufs<R>(c);
+    const int B = c->B, checks = trace_checks(iters, every);
+    const size_t row = (size_t)TRACE_Q * B, state_bytes = (size_t)B * c->N * sizeof(R);
+    t.B = B; t.iters.clear(); t.values.clear(); t.converged_at.assign((size_t)B, 0);
+    *checks_out = 0; *iters_done = 0;
+    if (checks == 0) return run_loop<R>(c, iters, cnc, pp, reo);                    // iters == 0: the untraced call
+    if (int rc = trace_buffers(c, checks)) return rc;
+    if (gt && !gt_on_device) {
+        if (!c->gt) HIPCHK(hipMalloc((void**)&c->gt, (size_t)c->Bmax * c->N));
+        if (int rc = copy_in(c, c->gt, gt, (size_t)B * c->N, 0)) return rc;
+        gt = c->gt;
+    }
+    const TraceRun r{iters, every, checks, tol, gt};
+    int done = 0, nrows = 0;
+    if (loop_path(c) == Path::fused) {
+        if (int rc = ensure_tables(c, Path::fused)) return rc;
+        if (int rc = state_order<R>(c, false)) return rc;
+        if (int rc = run_traced_chain<R>(c, r, cnc, pp, dc_coeff<R>(reo), &nrows, &done)) return rc;
+        c->have_x = true;
+    } else for (int k = 0; k < checks; ++k) {
+        const TraceLeg leg = trace_leg(iters, every, k);
+        if (leg.pre > 0) if (int rc = run_loop<R>(c, leg.pre, cnc, pp, reo)) return rc;
+        // z of iteration leg.iter - 1, in the order the coming launch leaves z in
+        const bool sliced = loop_path(c) == Path::slice;
+        if (int rc = state_order<R>(c, sliced)) return rc;
+        if constexpr (std::is_same_v<R, float>) {
+            if (sliced) HIPCHK(slice256_trace_snapshot(c->eng.slice, c->stream, b.z, B));
+        }
+        if (!sliced) {
+            if (!t.zprev) HIPCHK(hipMalloc(&t.zprev, (size_t)c->Bmax * c->N * sizeof(R)));
+            HIPCHK(hipMemcpyAsync(t.zprev, b.z, state_bytes, hipMemcpyDeviceToDevice, c->stream));
+        }
+        if (int rc = run_loop<R>(c, 1, cnc, pp, reo)) return rc;
+        done = leg.iter;
+        double* out = t.rows + (size_t)k * row;
+        if constexpr (std::is_same_v<R, float>) {
+            if (sliced) HIPCHK(slice256_residuals(c->eng.slice, c->stream, b.x, b.z, b.w, gt, B, t.partial, t.counter, out));
+        }
+        if (!sliced) HIPCHK(launch_residuals<R>(c->stream, b.x, b.z, (const R*)t.zprev, b.w, gt, 0, B, c->N, c->N, false, t.partial, t.counter, out));
+        nrows = k + 1;
+        const int stop = trace_checked(c, r, leg.iter, out);
+        if (stop < 0) return stop;
+        if (stop == 1) break;
+    }
+    if (!(tol > 0.0)) {                                                              // the whole trace in one copy
+        std::vector<double> all((size_t)nrows * row);
+        if (int rc = copy_out(c, all.data(), t.rows, all.size() * sizeof(double), 0)) return rc;
+        t.values.resize(all.size());
+        for (int k = 0; k < nrows; ++k) {
+            t.iters.push_back(trace_check_iter(iters, every, k));
+            trace_values(all.data() + (size_t)k * row, t.values.data() + (size_t)k * row, B, c->N, gt != nullptr);
+        }
+    }
+    *checks_out = nrows; *iters_done = done;
+    return PNP_OK;
+}
+
+// pnp_residuals[_f64]: the reduction alone, on caller pointers in natural order
+template <typename R>
+static int residuals_any(pnp_ctx* c, const char* who, const R* x, const R* z, const R* zp, const R* w, const uint8_t* gt, int gt_on_device,
+                         int quantise, double* out, int out_on_device) {
+    if (!x || !z || !zp || !w || !out) return fail(PNP_E_ARG, "%s: null pointer", who);
+    const size_t row = (size_t)TRACE_Q * c->B;
+    if (out_on_device) {
+        const char *o0 = (const char*)out, *o1 = o0 + row * sizeof(double);
+        const size_t bytes = (size_t)c->B * c->N * sizeof(R);
+        for (const void* p : {(const void*)x, (const void*)z, (const void*)zp, (const void*)w})
+            if (o0 < (const char*)p + bytes && (const char*)p < o1) return fail(PNP_E_ARG, "%s: out must not alias x, z, z_prev or w", who);
+        if (gt && gt_on_device && o0 < (const char*)gt + (size_t)c->B * c->N && (const char*)gt < o1)
+            return fail(PNP_E_ARG, "%s: out must not alias gt", who);
+        if ((uintptr_t)out % sizeof(double)) return fail(PNP_E_ARG, "%s: out is not aligned to 8 bytes", who);
+    }
+    if (int rc = trace_buffers(c, 1)) return rc;
+    if (gt && !gt_on_device) {
+        if (!c->gt) HIPCHK(hipMalloc((void**)&c->gt, (size_t)c->Bmax * c->N));
+        if (int rc = copy_in(c, c->gt, gt, (size_t)c->B * c->N, 0)) return rc;
+        gt = c->gt;
+    }
+    double* dst = out_on_device ? out : c->trace.rows;
+    HIPCHK(launch_residuals<R>(c->stream, x, z, zp, w, gt, quantise != 0, c->B, c->N, c->N, false, c->trace.partial, c->trace.counter, dst));
+    return out_on_device ? PNP_OK : copy_out(c, out, dst, row * sizeof(double), 0);
+}
+
 // What the next loop call runs (pnp_get_plan): the plans the engines themselves run by (loop_schedule.h).
 static LoopPlan loop_plan(const pnp_ctx* c) {
     switch (loop_path(c)) {
@@ -687,7 +918,8 @@ int pnp_ctx_destroy(pnp_ctx* c) {
     }
     slice256_destroy(c->eng.slice);
     anysize_destroy(c->any);
-    void* ptrs[] = {c->y, c->work, c->z, c->w, c->x, c->mask_bank, c->mask_id, c->gt, c->acc, c->stage, c->ssim_part};
+    void* ptrs[] = {c->y, c->work, c->z, c->w, c->x, c->mask_bank, c->mask_id, c->gt, c->acc, c->stage, c->ssim_part,
+                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -765,6 +997,47 @@ int pnp_admm_cnc_run(pnp_ctx* c, int iters, double alpha, double lambda1, double
     if (iters < 0) return fail(PNP_E_ARG, "%s: iters must be >= 0", __func__);
     return c->f64 ? run_loop(c, iters, true, prox_cnc<double>(alpha, lambda1, reo, b), reo)
                   : run_loop(c, iters, true, prox_cnc<float>(alpha, lambda1, reo, b), reo);
+}
+
+int pnp_admm_l1_run_traced(pnp_ctx* c, int iters, double lambda1, double reo, int every, double tol, const uint8_t* gt, int gt_on_device,
+                           int* checks, int* iters_done) {
+    CTX(c); NEED_PROBLEM(c); NEED_STATE(c);
+    Range r("pnp_admm_l1_run_traced");
+    if (int rv = check_thresholds(__func__, 0.0, lambda1, reo)) return rv;
+    if (iters < 0) return fail(PNP_E_ARG, "%s: iters must be >= 0", __func__);
+    return c->f64 ? run_traced<double>(c, __func__, iters, false, prox_l1<double>(lambda1, reo), reo, every, tol, gt, gt_on_device, checks, iters_done)
+                  : run_traced<float>(c, __func__, iters, false, prox_l1<float>(lambda1, reo), reo, every, tol, gt, gt_on_device, checks, iters_done);
+}
+
+int pnp_admm_cnc_run_traced(pnp_ctx* c, int iters, double alpha, double lambda1, double reo, double b, int every, double tol,
+                            const uint8_t* gt, int gt_on_device, int* checks, int* iters_done) {
+    CTX(c); NEED_PROBLEM(c); NEED_STATE(c);
+    Range r("pnp_admm_cnc_run_traced");
+    if (!(b > 0.0)) return fail(PNP_E_ARG, "%s: b must be > 0", __func__);
+    if (int rv = check_thresholds(__func__, alpha, lambda1, reo)) return rv;
+    if (iters < 0) return fail(PNP_E_ARG, "%s: iters must be >= 0", __func__);
+    return c->f64 ? run_traced<double>(c, __func__, iters, true, prox_cnc<double>(alpha, lambda1, reo, b), reo, every, tol, gt, gt_on_device, checks, iters_done)
+                  : run_traced<float>(c, __func__, iters, true, prox_cnc<float>(alpha, lambda1, reo, b), reo, every, tol, gt, gt_on_device, checks, iters_done);
+}
+
+int pnp_trace_read(pnp_ctx* c, int32_t* iters, double* values, int32_t* converged_at) {
+    CTX(c);
+    const Trace& t = c->trace;
+    if (iters) memcpy(iters, t.iters.data(), t.iters.size() * sizeof(int32_t));
+    if (values) memcpy(values, t.values.data(), t.values.size() * sizeof(double));
+    if (converged_at) memcpy(converged_at, t.converged_at.data(), t.converged_at.size() * sizeof(int32_t));
+    return PNP_OK;
+}
+
+int pnp_residuals(pnp_ctx* c, const float* x, const float* z, const float* zprev, const float* w, const uint8_t* gt, int gt_on_device,
+                  int quantise, double* out, int out_on_device) {
+    CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
+    return residuals_any<float>(c, __func__, x, z, zprev, w, gt, gt_on_device, quantise, out, out_on_device);
+}
+int pnp_residuals_f64(pnp_ctx* c, const double* x, const double* z, const double* zprev, const double* w, const uint8_t* gt, int gt_on_device,
+                      int quantise, double* out, int out_on_device) {
+    CTX(c); F64_ONLY(c); NEED_PROBLEM(c);
+    return residuals_any<double>(c, __func__, x, z, zprev, w, gt, gt_on_device, quantise, out, out_on_device);
 }
 
 int pnp_download_x(pnp_ctx* c, float* x, int on_device) { CTX(c); F32_ONLY(c); NEED_PROBLEM(c); return download_x(c, __func__, x, on_device); }

@@ -117,6 +117,22 @@ hipError_t chain_dc(const E* f, hipStream_t s, const R* z, const R* w, R* x, int
     return chain_part(f, s, chain_row_args<E, R>(f, z, w, nullptr, nullptr, x, 0, B, ProxParamsT<R>{}), 0, B, 1, 0, c);
 }
 
+// One step of a run whose chain the caller drives itself (the convergence trace, api.hip): the whole batch on one stream, the launches
+// of chain_part one by one -- open = the forward rows that start a run, cols = the column launch of an iteration, mid / last = its row
+// launch in the mid or the last stage -- plus what a trace needs: a LAST-stage row launch writes z, w, x wherever zo, wo, x point and
+// leaves the transform buffer and its inputs alone, so between the columns and the mid-stage rows of an iteration it materialises
+// the state of that iteration beside a chain that goes on unbroken.  The launches on the data are those of the uncut run.
+template <typename E, typename R>
+hipError_t chain_step(const E* f, hipStream_t s, ChainStep st, const R* z, const R* w, R* zo, R* wo, R* x, int B, int prox, R c,
+                      const ProxParamsT<R>& pp, bool u_first) {
+    const int np = (B + 1) / 2;
+    if (st == ChainStep::cols) return f->cols(s, 0, np, c);
+    FRowArgsT<R> a = chain_row_args(f, z, w, zo, wo, x, 0, B, pp);
+    a.u_first = u_first;
+    return with_row_kind(st == ChainStep::open ? Stage::first : st == ChainStep::mid ? Stage::mid : Stage::last, prox,
+                         [&](auto k) { return f->rows(k, s, np, a); });
+}
+
 // W_n^m = exp(-2 pi i m / n), m in [0, n): computed in double, rounded once to R, copied to the __device__ table `symbol`
 template <typename R>
 hipError_t upload_twiddle_table(const void* symbol, int n) {

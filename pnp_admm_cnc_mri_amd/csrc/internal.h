@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include "loop_schedule.h"
 #include "prox_params.h"
+#include "trace_plan.h"
 
 namespace pnp {
 
@@ -74,6 +75,14 @@ hipError_t upload_gauss();
 template <typename X> hipError_t launch_ssim(hipStream_t s, const X* x, const uint8_t* gt, double* partial /*[B][tiles]*/, int B, int H, int W);
 hipError_t launch_widen(hipStream_t s, const float* in, double* out, size_t n);      // float -> double
 
+// convergence trace (kernels_trace.hip): the TRACE_Q sums of squares of trace_plan.h for B slices of N elements into out [TRACE_Q][B], one
+// launch.  x (and gt, or null) in natural order at stride N; z, zp, w at stride `state_stride`, in natural order or -- slice_order, 256 x 256
+// float -- by sl_state_index.  partial / counter: scratch of trace_scratch_bytes(Bmax) bytes resp. Bmax zeroed unsigneds, one stream at a time.
+size_t trace_scratch_bytes(int Bmax);
+template <typename R>
+hipError_t launch_residuals(hipStream_t s, const R* x, const R* z, const R* zp, const R* w, const uint8_t* gt, int quantise, int B, size_t N,
+                            size_t state_stride, bool slice_order, double* partial, unsigned* counter, double* out);
+
 // calibration (pnp_calibrate_stream): the slice-resident loop's access shape without its arithmetic, `passes` passes over `slices` slices of 256 KiB
 hipError_t launch_calibrate_stream(hipStream_t s, float* z, float* w, const float* y, int slices, int passes);
 // optional HIP backend of the denoisers' 64-channel conv3x3 body layers (kernels_conv.hip); activations NHWC float32
@@ -106,6 +115,9 @@ hipError_t launch_conv3x3_head(hipStream_t s, const float* x_nchw, const float* 
 hipError_t launch_conv3x3_tail(hipStream_t s, const float* x_nhwc, const float* w_oihw, const float* bias, float* y_nchw,
                                int n, int cout, int H, int W);
 
+// steps of a run driven launch by launch (engine_host.h, chain_step; the *_step functions of the two-launch engines below)
+enum class ChainStep { open, cols, mid, last };
+
 // fused 256x256 path (kernels_fused256.hip): state resident in the ctx, two slices packed into
 // one complex transform.  See DESIGN.md.
 struct Fused256;
@@ -119,6 +131,9 @@ hipError_t fused256_run(Fused256*, hipStream_t s, float* z, float* w, float* x, 
                         bool cnc, float dc_c, ProxParams p, const FusedSchedule& sch);
 // one data-consistency step on caller pointers
 hipError_t fused256_dc(Fused256*, hipStream_t s, const float* z, const float* w, float* x, int B, float dc_c);
+// one launch of a run's chain on the whole batch (chain_step): rows read z, w and write zo, wo, x (last) or zo, wo (mid)
+hipError_t fused256_step(Fused256*, hipStream_t s, ChainStep st, const float* z, const float* w, float* zo, float* wo, float* x, int B,
+                         bool cnc, float dc_c, ProxParams p, const FusedSchedule& sch, bool u_first);
 
 // "split chain" engine for 256x256 (kernels_fused256.hip, k_fcols2): one column chain per thread and
 // slice; R = float | double.  y is [B][256][256] complex in R (float2 / double2 layout).
@@ -130,6 +145,8 @@ template <typename R> hipError_t    fused256s_prepare(Fused256S<R>*, hipStream_t
 template <typename R> hipError_t    fused256s_run(Fused256S<R>*, hipStream_t s, R* z, R* w, R* x, int B, int iters, bool cnc,
                                                   R dc_c, ProxParamsT<R> p, const FusedSchedule& sch);
 template <typename R> hipError_t    fused256s_dc(Fused256S<R>*, hipStream_t s, const R* z, const R* w, R* x, int B, R dc_c);
+template <typename R> hipError_t    fused256s_step(Fused256S<R>*, hipStream_t s, ChainStep st, const R* z, const R* w, R* zo, R* wo, R* x, int B,
+                                                   bool cnc, R dc_c, ProxParamsT<R> p, const FusedSchedule& sch, bool u_first);
 
 // slice-resident 256x256 path (kernels_slice256.hip): one workgroup keeps one slice in registers for a whole run
 struct Slice256;
@@ -142,6 +159,12 @@ hipError_t slice256_run(Slice256*, hipStream_t s, float* z, float* w, float* x, 
                         ProxParams p, const FusedSchedule& sch);
 // in-place conversion of both state arrays [B][256][256] between natural order and slice order
 hipError_t slice256_state_order(Slice256*, hipStream_t s, float* z, float* w, int B, bool to_slice);
+// Convergence trace of a slice-order state (z, w as slice256_run leaves them; the caller's arrays when the engine keeps no padded ones):
+// keep z as it lies now as the z_prev of the next check (the copy is the engine's), and the reduction of launch_residuals on x (natural),
+// z, that z_prev and w where they lie.
+hipError_t slice256_trace_snapshot(Slice256*, hipStream_t s, const float* z, int B);
+hipError_t slice256_residuals(Slice256*, hipStream_t s, const float* x, const float* z, const float* w, const uint8_t* gt, int B,
+                              double* partial, unsigned* counter, double* out);
 
 // fused 512x512 path (kernels_fused512.hip): same scheme with 32-lane transforms
 struct Fused512;
@@ -152,5 +175,7 @@ hipError_t fused512_prepare(Fused512*, hipStream_t s, const float2* y, const uin
 hipError_t fused512_run(Fused512*, hipStream_t s, float* z, float* w, float* x, int B, int iters,
                         bool cnc, float dc_c, ProxParams p, const FusedSchedule& sch);
 hipError_t fused512_dc(Fused512*, hipStream_t s, const float* z, const float* w, float* x, int B, float dc_c);
+hipError_t fused512_step(Fused512*, hipStream_t s, ChainStep st, const float* z, const float* w, float* zo, float* wo, float* x, int B,
+                         bool cnc, float dc_c, ProxParams p, const FusedSchedule& sch, bool u_first);
 
 }  // namespace pnp

@@ -437,6 +437,11 @@ hipError_t fused256_dc(Fused256* f, hipStream_t s, const float* z, const float* 
     return chain_dc(f, s, z, w, x, B, dc_c);
 }
 
+hipError_t fused256_step(Fused256* f, hipStream_t s, ChainStep st, const float* z, const float* w, float* zo, float* wo, float* x, int B,
+                         bool cnc, float dc_c, ProxParams pp, const FusedSchedule& sch, bool u_first) {
+    return chain_step(f, s, st, z, w, zo, wo, x, B, prox_kind(cnc, sch), dc_c, pp, u_first);
+}
+
 
 // ==========================================================================================
 // "Split chain" column kernel and the engine built on it (float and double).
@@ -657,12 +662,19 @@ hipError_t fused256s_dc(Fused256S<R>* f, hipStream_t s, const R* z, const R* w, 
     return chain_dc(f, s, z, w, x, B, dc_c);
 }
 
+template <typename R>
+hipError_t fused256s_step(Fused256S<R>* f, hipStream_t s, ChainStep st, const R* z, const R* w, R* zo, R* wo, R* x, int B, bool cnc, R dc_c,
+                          ProxParamsT<R> pp, const FusedSchedule& sch, bool u_first) {
+    return chain_step(f, s, st, z, w, zo, wo, x, B, prox_kind(cnc, sch), dc_c, pp, u_first);
+}
+
 #define PNP_INSTANTIATE_F256S(R)                                                                                     \
     template Fused256S<R>* fused256s_create<R>(int, hipError_t*);                                                   \
     template void fused256s_destroy<R>(Fused256S<R>*);                                                               \
     template hipError_t fused256s_prepare<R>(Fused256S<R>*, hipStream_t, const void*, const uint8_t*, const int32_t*, int); \
     template hipError_t fused256s_run<R>(Fused256S<R>*, hipStream_t, R*, R*, R*, int, int, bool, R, ProxParamsT<R>, const FusedSchedule&); \
-    template hipError_t fused256s_dc<R>(Fused256S<R>*, hipStream_t, const R*, const R*, R*, int, R);
+    template hipError_t fused256s_dc<R>(Fused256S<R>*, hipStream_t, const R*, const R*, R*, int, R);                 \
+    template hipError_t fused256s_step<R>(Fused256S<R>*, hipStream_t, ChainStep, const R*, const R*, R*, R*, R*, int, bool, R, ProxParamsT<R>, const FusedSchedule&, bool);
 PNP_INSTANTIATE_F256S(float)
 PNP_INSTANTIATE_F256S(double)
 

@@ -368,4 +368,9 @@ hipError_t fused512_dc(Fused512* f, hipStream_t s, const float* z, const float* 
     return chain_dc(f, s, z, w, x, B, dc_c);
 }
 
+hipError_t fused512_step(Fused512* f, hipStream_t s, ChainStep st, const float* z, const float* w, float* zo, float* wo, float* x, int B,
+                         bool cnc, float dc_c, ProxParams pp, const FusedSchedule& sch, bool u_first) {
+    return chain_step(f, s, st, z, w, zo, wo, x, B, prox_kind(cnc, sch), dc_c, pp, u_first);
+}
+
 }  // namespace pnp

@@ -969,6 +969,7 @@ struct Slice256 {
     int pad = 0, yh_pad = 0;
     float* zs = nullptr;
     float* ws = nullptr;
+    float* zprev = nullptr;                  // convergence trace: z of the launch boundary before a check, laid out as zs (on first use)
     c32* Yh = nullptr;
     uint32_t* Mh = nullptr;
     c32* Ys = nullptr;
@@ -990,10 +991,25 @@ hipError_t slice256_state_order(Slice256* f, hipStream_t s, float* z, float* w, 
     return hipGetLastError();
 }
 
+// Convergence trace (kernels_trace.hip): the state is read where the loop left it -- the padded arrays, or the caller's with pad = 0.
+hipError_t slice256_trace_snapshot(Slice256* f, hipStream_t s, const float* z, int B) {
+    const size_t stride = 65536 + (size_t)f->pad;
+    if (B > f->Bmax) return hipErrorInvalidValue;
+    if (!f->zprev) { hipError_t e = hipMalloc((void**)&f->zprev, (size_t)f->Bmax * stride * sizeof(float)); if (e != hipSuccess) return e; }
+    return hipMemcpyAsync(f->zprev, f->pad > 0 ? f->zs : z, (size_t)B * stride * sizeof(float), hipMemcpyDeviceToDevice, s);
+}
+hipError_t slice256_residuals(Slice256* f, hipStream_t s, const float* x, const float* z, const float* w, const uint8_t* gt, int B,
+                              double* partial, unsigned* counter, double* out) {
+    if (!f->zprev || B > f->Bmax) return hipErrorInvalidValue;
+    return launch_residuals<float>(s, x, f->pad > 0 ? f->zs : z, f->zprev, f->pad > 0 ? f->ws : w, gt, 0, B, 65536, 65536 + (size_t)f->pad, true,
+                                   partial, counter, out);
+}
+
 void slice256_destroy(Slice256* f) {
     if (!f) return;
     if (f->zs) (void)hipFree(f->zs);
     if (f->ws) (void)hipFree(f->ws);
+    if (f->zprev) (void)hipFree(f->zprev);
     if (f->Yh) (void)hipFree(f->Yh);
     if (f->Mh) (void)hipFree(f->Mh);
     if (f->Ys) (void)hipFree(f->Ys);

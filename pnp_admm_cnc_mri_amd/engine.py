@@ -27,6 +27,27 @@ def _host(a, dtype):
     return a
 
 
+TRACE_FIELDS = ('r_pri', 'r_dual', 'x_norm', 'z_norm', 'w_norm', 'psnr', 're')      # PNP_TRACE_* of include/pnp_mri.h, in order
+
+
+def trace_rows(sums, npix, have_gt=True):
+    """Sums of squares [..., 7, B] (pnp_residuals) -> dict of the trace quantities [..., B]: square roots, and PSNR / RE by
+    pnp_metrics' formulas (utils/utils_image.py:543-556, 622-636) when a ground truth went in."""
+    sums = np.asarray(sums, np.float64)
+    out = {name: np.sqrt(sums[..., q, :]) for q, name in enumerate(TRACE_FIELDS[:5])}
+    if have_gt:
+        se, sg = sums[..., 5, :], sums[..., 6, :]
+        with np.errstate(divide='ignore'):
+            out['psnr'] = np.where(se == 0, np.inf, 20.0 * np.log10(255.0 / np.sqrt(se / float(npix))))
+        out['re'] = np.sqrt(se) / np.sqrt(sg)
+    return out
+
+
+def trace_meets(rows, tol):
+    """The stopping rule per slice: max(r_pri, r_dual) <= tol * z_norm."""
+    return np.maximum(rows['r_pri'], rows['r_dual']) <= float(tol) * rows['z_norm']
+
+
 class Engine:
     """One context per (device, H, W, Bmax), H, W in [128, 1024].  Not thread-safe, not re-entrant (as the ABI says)."""
 
@@ -198,11 +219,48 @@ class Engine:
         return z, w
 
     # -- whole loops ----------------------------------------------------------------------
-    def admm_l1(self, iters, lambda1, reo):
-        _lib.check(self._L.pnp_admm_l1_run(self._ctx, int(iters), float(lambda1), float(reo)))
+    def admm_l1(self, iters, lambda1, reo, trace_every=0, tol=None, gt=None):
+        """S1:111-126.  trace_every / tol / gt: the convergence trace and the stopping rule (`_traced`); both off: None, as ever."""
+        if not trace_every and tol is None:
+            _lib.check(self._L.pnp_admm_l1_run(self._ctx, int(iters), float(lambda1), float(reo)))
+            return None
+        return self._traced(self._L.pnp_admm_l1_run_traced, (int(iters), float(lambda1), float(reo)), trace_every, tol, gt)
 
-    def admm_cnc(self, iters, alpha, lambda1, reo, b):
-        _lib.check(self._L.pnp_admm_cnc_run(self._ctx, int(iters), float(alpha), float(lambda1), float(reo), float(b)))
+    def admm_cnc(self, iters, alpha, lambda1, reo, b, trace_every=0, tol=None, gt=None):
+        """S4:115-132.  trace_every / tol / gt as for admm_l1."""
+        if not trace_every and tol is None:
+            _lib.check(self._L.pnp_admm_cnc_run(self._ctx, int(iters), float(alpha), float(lambda1), float(reo), float(b)))
+            return None
+        return self._traced(self._L.pnp_admm_cnc_run_traced, (int(iters), float(alpha), float(lambda1), float(reo), float(b)),
+                            trace_every, tol, gt)
+
+    def _traced(self, fn, args, trace_every, tol, gt):
+        """A traced run (pnp_admm_*_run_traced): a check every `trace_every` iterations and after the last one; tol: stop after the
+        first check at which every slice has max(r_pri, r_dual) <= tol * z_norm (tol alone means trace_every=1); gt: uint8 [B,H,W]
+        ground truth (host array or device tensor) for the psnr / re rows.  -> dict: 'iter' [C], 'r_pri', 'r_dual', 'x_norm',
+        'z_norm', 'w_norm' [C, B] ('psnr', 're' with gt), 'iters_done', 'converged_at' [B] (0: never)."""
+        every = 1 if (not trace_every and tol is not None) else int(trace_every)
+        if every < 1:
+            raise ValueError('trace_every must be >= 1 (got %r)' % (trace_every,))
+        if tol is not None and not float(tol) > 0:
+            raise ValueError('tol must be > 0 (got %r)' % (tol,))
+        if gt is not None and not _is_dev(gt):
+            gt = _host(gt, np.uint8)
+            if gt.size != self.B * self.H * self.W:
+                raise ValueError('gt must be [B,H,W] uint8')
+        checks, done = C.c_int(0), C.c_int(0)
+        _lib.check(fn(self._ctx, *args, every, float(tol) if tol is not None else 0.0, _ptr(gt), 1 if _is_dev(gt) else 0,
+                      C.byref(checks), C.byref(done)))
+        n = checks.value
+        it = np.zeros(n, np.int32)
+        vals = np.zeros((n, len(TRACE_FIELDS), self.B), np.float64)
+        conv = np.zeros(self.B, np.int32)
+        _lib.check(self._L.pnp_trace_read(self._ctx, _ptr(it), _ptr(vals), _ptr(conv)))
+        trace = {'iter': it, 'iters_done': done.value, 'converged_at': conv}
+        for q, name in enumerate(TRACE_FIELDS):
+            if gt is not None or name not in ('psnr', 're'):
+                trace[name] = vals[:, q, :].copy()
+        return trace
 
     def x(self, out=None):
         fn = self._L.pnp_download_x_f64 if self.f64 else self._L.pnp_download_x
@@ -233,6 +291,22 @@ class Engine:
 
     def dual_clamp(self, x, z, w):
         _lib.check(self._L.pnp_dual_clamp(self._ctx, _ptr(x), _ptr(z), _ptr(w)))
+
+    def residuals(self, x, z, z_prev, w, gt=None, quantise=False, out=None):
+        """The reduction of the traced loops on device tensors [B,H,W] in natural order (pnp_residuals): the sums of squares
+        [7, B] behind a trace row (`trace_rows` forms the norms, PSNR and RE).  gt: uint8 [B,H,W], host array or device tensor;
+        quantise: score round(255 x) / 255 as the PnP solvers do.  out: a float64 device tensor [7, B] -- written asynchronously on
+        the engine's stream and returned -- or None: a host array, after a synchronisation."""
+        if gt is not None and not _is_dev(gt):
+            gt = _host(gt, np.uint8)
+        fn = self._L.pnp_residuals_f64 if self.f64 else self._L.pnp_residuals
+        dev = out is not None
+        if dev and not _is_dev(out):
+            raise TypeError('residuals: out must be a device tensor (or None for a host array)')
+        res = out if dev else np.empty((len(TRACE_FIELDS), self.B), np.float64)
+        _lib.check(fn(self._ctx, _ptr(x), _ptr(z), _ptr(z_prev), _ptr(w), _ptr(gt), 1 if _is_dev(gt) else 0, 1 if quantise else 0,
+                      _ptr(res), 1 if dev else 0))
+        return res
 
     # -- operator API on device tensors ---------------------------------------------------
     def fft2(self, inp, out, B):

@@ -21,6 +21,12 @@ bypass the file system through the extra keyword arguments
     precision= 'f32' (default: float32 / complex64 device arithmetic, the throughput path) or 'f64' (the reference's own
                float64 arithmetic, S4:109: every buffer and step in double -- the setting that meets 1e-5 relative L2 on the
                committed 50-iteration CNC presets and beyond)
+    trace_every=0, tol=None   convergence trace and residual-based stopping (all five solvers; needs return_info=True, the trace is
+              info['trace']): every `trace_every` iterations and after the last one the residuals r_pri = ||x - z||, r_dual =
+              ||z_k - z_{k-1}||, the norms of x, z, w and -- with a ground truth -- PSNR / RE of that iteration are recorded per slice
+              (Engine._traced has the fields); tol: the run stops after the first check at which every slice has
+              max(r_pri, r_dual) <= tol * ||z|| (tol alone: a check every iteration) -- out, metrics, PNGs and log lines are then
+              those of iteration trace['iters_done'], and one more log line says so.  Both off: nothing changes
 
 The PnP entry points (PNP_ADMM_L1_D, PNP_ADMM_CNC_D, PNP_ADMM_CNC_DnCNN) live in solvers_pnp.py.
 """
@@ -190,6 +196,25 @@ class _Job:
         return out, psnr1, info
 
 
+def trace_request(trace_every, tol, return_info):
+    """-> whether the call asks for a trace / a stopping rule; it comes back in `info`, so it needs return_info=True."""
+    on = bool(trace_every) or tol is not None
+    if on and not return_info:
+        raise ValueError('trace_every= / tol= return the trace as info[\'trace\']: pass return_info=True')
+    if on and trace_every is not None and int(trace_every) < 0:
+        raise ValueError('trace_every must be >= 1 (got %r)' % (trace_every,))
+    if tol is not None and not float(tol) > 0:
+        raise ValueError('tol must be > 0 (got %r)' % (tol,))
+    return on
+
+
+def log_early_stop(job, trace, iter_num, tol):
+    """the one extra log line of a run that the stopping rule ended before iter_num"""
+    if trace is not None and tol is not None and trace['iters_done'] < iter_num and job.log is not None:
+        job.log.info('stopped after iteration {:d} of {:d}: max(r_pri, r_dual) <= {:g} * ||z|| for every slice'.format(
+            int(trace['iters_done']), int(iter_num), float(tol)))
+
+
 def _device_x(eng, job):
     """the ctx's x copied device-to-device into a torch tensor that outlives the engine"""
     import torch
@@ -201,32 +226,45 @@ def _device_x(eng, job):
 
 
 def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
-            results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, **ADMM_L1_opts):
+            results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
+            **ADMM_L1_opts):
     """ADMM with L1 prox on the MI355X engine.  Reference: "【1】ADMM_L1.py":29-169."""
     iter_num = ADMM_L1_opts.get('iter_num', 20)          # S1:35
     lambda1 = ADMM_L1_opts.get('lambda1', 0.04)          # S1:36
     reo = ADMM_L1_opts.get('reo', 0.04)                  # S1:37
+    traced = trace_request(trace_every, tol, return_info)
     job = _Job(mask, noises, 'ADMM_L1', '_PDG L1', images, y, mask_id, testsets, testset_name, results, save_E, device,
                psnr_fmt='{:.2f}', precision=precision)   # S1:150
     with job.open_engine() as eng:
-        eng.admm_l1(iter_num, lambda1, reo)              # S1:111-126, all slices, on device
+        # S1:111-126, all slices, on device
+        trace = eng.admm_l1(iter_num, lambda1, reo, trace_every, tol, job.gt_u8) if traced else eng.admm_l1(iter_num, lambda1, reo)
+        log_early_stop(job, trace, iter_num, tol)
         x = _device_x(eng, job) if return_device else eng.x()      # iter_num = 0: the initial x = |ifft2(y)| (S4:103, 138)
         out, _, info = job.finish(eng, x)
+        if traced:
+            info['trace'] = trace
     return (out, info) if return_info else out
 
 
 def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
-             results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, **ADMM_CNC_opts):
+             results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
+             **ADMM_CNC_opts):
     """ADMM with the convex-non-convex z-step.  Reference: "【4】ADMM_CNC .py":31-174."""
     iter_num = ADMM_CNC_opts.get('iter_num', 4)          # S4:37
     alpha = ADMM_CNC_opts.get('alpha', 0.4)              # S4:38
     lambda1 = ADMM_CNC_opts.get('lambda1', 0.04)         # S4:39
     reo = ADMM_CNC_opts.get('reo', 2.75)                 # S4:40  (reo is 1/beta of the paper)
     b = ADMM_CNC_opts.get('b', 1)                        # S4:41  (b is b^2 of the paper)
+    traced = trace_request(trace_every, tol, return_info)
     job = _Job(mask, noises, 'ADMM_CNC', '_ADMM CNC', images, y, mask_id, testsets, testset_name, results, save_E, device,
                precision=precision)
     with job.open_engine() as eng:
-        eng.admm_cnc(iter_num, alpha, lambda1, reo, b)   # S4:115-132
+        # S4:115-132
+        trace = (eng.admm_cnc(iter_num, alpha, lambda1, reo, b, trace_every, tol, job.gt_u8) if traced
+                 else eng.admm_cnc(iter_num, alpha, lambda1, reo, b))
+        log_early_stop(job, trace, iter_num, tol)
         x = _device_x(eng, job) if return_device else eng.x()      # iter_num = 0: the initial x = |ifft2(y)| (S4:103, 138)
         out, _, info = job.finish(eng, x)
+        if traced:
+            info['trace'] = trace
     return (out, info) if return_info else out

@@ -33,6 +33,10 @@ save_E=, device=, return_info=  as in solvers.py, plus
                             iter_start, the loop then runs iterations iter_start .. iter_num - 1 (sigma schedule, bank switch and x8 mode of
                             those indices).  With return_info=True the final (z, w) come back as info['z'], info['w'].  What the
                             teacher-forced parity tests use: one iteration from the reference's own state (tests/test_gpu_pnp.py)
+    trace_every=0, tol=None convergence trace and residual-based stopping as in solvers.py (info['trace']; needs return_info=True): the rows are
+                            reduced on the device from the loop's own tensors after the clamp (S6:306-308) -- Engine.residuals, one launch per
+                            check, PSNR / RE on round(255 x) / 255 as the final metric -- and read once after the loop, or once per check with
+                            tol.  With state0= / iter_start= the iteration numbers continue from iter_start
     cnn_graph=False         True: a denoiser forward of at most cnn_batch slices is captured once per shape into a HIP graph and replayed
                             (the reference's one-slice calls: a forward is a train of short launches; FFDNet 0.50 -> see DESIGN.md 4.8)
 """
@@ -42,7 +46,8 @@ import numpy as np
 
 from . import denoisers as D
 from . import utils_pnp as pnp
-from .solvers import _Job, resolve_device
+from .engine import TRACE_FIELDS, trace_meets, trace_rows
+from .solvers import _Job, log_early_stop, resolve_device, trace_request
 
 PRESETS = {
     # PNP_ADMM_CNC_D(alpha, iter, lambda1, reo, b), S6:569-577
@@ -122,10 +127,54 @@ def _finish_pnp(torch, job, eng, x, extra, return_device=False):
     return out, psnr1, info
 
 
+class _Tracer:
+    """The convergence trace of a PnP loop: check(k, x, z, z_prev, w) after iteration k (1-based, counted from the very first iteration
+    also when the loop resumes at iter_start) reduces the tensors on the device when k is a checked iteration and says whether the
+    stopping rule ends the loop there; result() is the trace of Engine._traced.  Off (`on` False): check() does nothing."""
+
+    def __init__(self, torch, eng, job, dev, trace_every, tol, return_info, iter_start, iter_num):
+        self.on = trace_request(trace_every, tol, return_info)
+        self.tol, self.iter_num, self.done = tol, iter_num, iter_num if iter_num > iter_start else iter_start
+        if not self.on:
+            return
+        every = 1 if (not trace_every and tol is not None) else int(trace_every)
+        self.torch, self.eng, self.job = torch, eng, job
+        self.iters = [k for k in range(iter_start + 1, iter_num + 1) if k % every == 0 or k == iter_num]
+        self.gt = None if job.gt_u8 is None else torch.from_numpy(job.gt_u8).to(dev)
+        self.sums = torch.zeros((max(len(self.iters), 1), len(TRACE_FIELDS), job.B), dtype=torch.float64, device=dev)
+        self.rows = 0
+        self.converged_at = np.zeros(job.B, np.int32)
+
+    def wants(self, k):
+        return self.on and self.rows < len(self.iters) and self.iters[self.rows] == k
+
+    def check(self, k, x, z, z_prev, w):
+        """-> True when the loop is to stop after iteration k"""
+        if not self.wants(k):
+            return False
+        row = self.sums[self.rows]
+        self.eng.residuals(x, z, z_prev, w, gt=self.gt, quantise=True, out=row)
+        self.rows += 1
+        if self.tol is None:
+            return False
+        self.torch.cuda.current_stream(row.device).synchronize()
+        met = trace_meets(trace_rows(row.cpu().numpy(), self.job.H * self.job.W, self.gt is not None), self.tol)
+        self.converged_at[met & (self.converged_at == 0)] = k
+        if met.all():
+            self.done = k
+        return bool(met.all())
+
+    def result(self):
+        trace = trace_rows(self.sums[:self.rows].cpu().numpy(), self.job.H * self.job.W, self.gt is not None)
+        trace.update(iter=np.asarray(self.iters[:self.rows], np.int32), iters_done=int(self.done), converged_at=self.converged_at)
+        log_early_stop(self.job, trace, self.iter_num, self.tol)
+        return trace
+
+
 def PNP_ADMM_CNC_D(model_name, mask, noises, images=None, y=None, mask_id=None, testsets='testsets',
                    testset_name='Set1', results='results', save_E=None, device=None, return_info=False,
                    model_zoo='model_zoo', model=None, cnn_batch=None, cnn_dtype=None, miopen_find='auto', cnn_backend='auto', cnn_graph=False, return_device=False,
-                   state0=None, iter_start=0, **PNP_ADMM_CNC_D_opts):
+                   state0=None, iter_start=0, trace_every=0, tol=None, **PNP_ADMM_CNC_D_opts):
     """CNC ADMM with a CNN denoiser in place of both soft-thresholds.  Reference: S6:79-351."""
     import torch
     alpha = PNP_ADMM_CNC_D_opts.get('alpha', 0.4)          # S6:85-89
@@ -145,6 +194,7 @@ def PNP_ADMM_CNC_D(model_name, mask, noises, images=None, y=None, mask_id=None, 
         s = torch.empty_like(z)
         t = torch.empty_like(z)
         z_new = torch.empty_like(z)
+        tracer = _Tracer(torch, eng, job, dev, trace_every, tol, return_info, iter_start, iter_num)
         for i in range(iter_start, iter_num):                                 # S6:262
             eng.dc_step(z, w, x, reo)                                         # S6:266-271
             den.select_bank(i)                                                # S6:289-298
@@ -153,17 +203,23 @@ def PNP_ADMM_CNC_D(model_name, mask, noises, images=None, y=None, mask_id=None, 
             den(t, i, out=z_new)                                              # S6:302
             eng.dual_clamp(x, z_new, w)                                       # S6:305-308
             z, z_new = z_new, z
+            if tracer.check(i + 1, x, z, z_new, w):                           # z_new now holds z of the iteration before
+                break
         torch.cuda.current_stream(dev).synchronize()
+        trace = tracer.result() if tracer.on else None
         out, psnr1, info = _finish_pnp(torch, job, eng, x, 'alpha: ({:.3f}), '.format(alpha), return_device)
         if return_info:
             info['z'], info['w'] = z.reshape(B, H, W).cpu().numpy(), w.reshape(B, H, W).cpu().numpy()
+        if tracer.on:
+            info['trace'] = trace
     return (out, psnr1, info) if return_info else (out, psnr1)
 
 
 def PNP_ADMM_CNC_DnCNN(model_name1, model_name2, mask, noises, images=None, y=None, mask_id=None,
                        testsets='testsets', testset_name='Set1', results='results', save_E=None, device=None,
                        return_info=False, model_zoo='model_zoo', model=None, model2=None, cnn_batch=None,
-                       cnn_dtype=None, faithful_model2_path=True, miopen_find='auto', cnn_backend='auto', cnn_graph=False, return_device=False, **opts):
+                       cnn_dtype=None, faithful_model2_path=True, miopen_find='auto', cnn_backend='auto', cnn_graph=False, return_device=False,
+                       trace_every=0, tol=None, **opts):
     """Two DnCNN-17 nets: s = D1(z), z = D2(t).  Reference: S6:372-567.
     `faithful_model2_path`: the reference loads model_path1 into BOTH nets (S6:435) although it logs
     path 2; True reproduces that, False loads model_name2's own weights."""
@@ -186,6 +242,7 @@ def PNP_ADMM_CNC_DnCNN(model_name1, model_name2, mask, noises, images=None, y=No
         B, H, W = job.B, job.H, job.W
         x, z, w = _device_state(torch, eng, B, H, W, dev)
         s, t, z_new = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
+        tracer = _Tracer(torch, eng, job, dev, trace_every, tol, return_info, 0, iter_num)
         for i in range(iter_num):                                             # S6:491
             eng.dc_step(z, w, x, reo)                                         # S6:495-500
             den1(z, i, out=s)                                                 # S6:517
@@ -193,15 +250,22 @@ def PNP_ADMM_CNC_DnCNN(model_name1, model_name2, mask, noises, images=None, y=No
             den2(t, i, out=z_new)                                             # S6:519
             eng.dual_clamp(x, z_new, w)                                       # S6:522-525
             z, z_new = z_new, z
+            if tracer.check(i + 1, x, z, z_new, w):
+                break
         torch.cuda.current_stream(dev).synchronize()
+        trace = tracer.result() if tracer.on else None
         out, psnr1, info = _finish_pnp(torch, job, eng, x, 'alpha: ({:.3f}), '.format(alpha), return_device)
+        if return_info:
+            info['z'], info['w'] = z.reshape(B, H, W).cpu().numpy(), w.reshape(B, H, W).cpu().numpy()
+        if tracer.on:
+            info['trace'] = trace
     return (out, psnr1, info) if return_info else (out, psnr1)
 
 
 def PNP_ADMM_L1_D(model_name, mask, noises, images=None, y=None, mask_id=None, testsets='testsets',
                   testset_name='Set1', results='results', save_E=None, device=None, return_info=False,
                   model_zoo='model_zoo', model=None, cnn_batch=None, cnn_dtype=None, miopen_find='auto', cnn_backend='auto', cnn_graph=False, return_device=False,
-                  state0=None, iter_start=0, **PNP_ADMM_L1_D_opts):
+                  state0=None, iter_start=0, trace_every=0, tol=None, **PNP_ADMM_L1_D_opts):
     """L1-ADMM with the CNN as the prox: z = D(x + w).  Reference: S3:77-337."""
     import torch
     iter_num = PNP_ADMM_L1_D_opts.get('iter_num', 20)      # S3:83-84
@@ -218,14 +282,23 @@ def PNP_ADMM_L1_D(model_name, mask, noises, images=None, y=None, mask_id=None, t
         x, z, w = _device_state(torch, eng, B, H, W, dev)
         _resume(torch, z, w, state0, dev)
         t = torch.empty_like(z)
+        tracer = _Tracer(torch, eng, job, dev, trace_every, tol, return_info, iter_start, iter_num)
+        z_prev = torch.empty_like(z) if tracer.on else None                   # this loop updates z in place: a checked iteration keeps the z before it
         for i in range(iter_start, iter_num):                                 # S3:255
             eng.dc_step(z, w, x, reo)                                         # S3:259-264
             den.select_bank(i)
             eng.add(x, w, t)                                                  # x + w
+            if tracer.wants(i + 1):
+                z_prev.copy_(z)
             den(t, i, out=z)                                                  # S3:290
             eng.dual_clamp(x, z, w)                                           # S3:293-296
+            if tracer.check(i + 1, x, z, z_prev, w):
+                break
         torch.cuda.current_stream(dev).synchronize()
+        trace = tracer.result() if tracer.on else None
         out, _, info = _finish_pnp(torch, job, eng, x, '', return_device)
         if return_info:
             info['z'], info['w'] = z.reshape(B, H, W).cpu().numpy(), w.reshape(B, H, W).cpu().numpy()
+        if tracer.on:
+            info['trace'] = trace
     return (out, info) if return_info else out

@@ -345,6 +345,48 @@ int pnp_conv3x3_tail_nchw(void* hip_stream, const float* x_nhwc_dev, const float
 int pnp_ffdnet_head_nhwc(void* hip_stream, const float* x_dev, const float* sigma_dev, int sigma_per_image, const float* w_oihw_dev,
                          const float* bias_dev, float* y_nhwc_dev, int n, int h, int w, int relu);
 int pnp_ffdnet_tail_f16x3(void* hip_stream, const float* x_nhwc_dev, const float* w_oihw_dev, const float* bias_dev, float* y_dev, int n, int h, int w);
+/* ---- the denoisers' layers in HALF precision: `Denoiser(backend='hip_f16')`.  Added after ABI 13, additive (PNP_ABI_VERSION stays) ----
+ * csrc/kernels_conv_f16.hip, csrc/kernels_pix2x2_f16.hip.  Activations between layers are IEEE halves, NHWC, 128 bytes per pixel and
+ * block of 64 channels (passed as void*); weights are rounded to half (round to nearest even) once, at pack time.  A layer computes
+ *     y = round_half( relu?( sum_fp32( x_half * w_half ) + bias_fp32 + float(skip_half) ) )
+ * on v_mfma_f32_16x16x32_f16: exact products, float32 accumulation, ONE rounding on store.  A value beyond +-65504 is stored as inf,
+ * NaN propagates.  A network's first layer keeps the float32 direct arithmetic on the float32 network input and stores halves; its
+ * last layer stores float32.  A throughput mode: it does NOT meet the 1e-5 parity bar of the float32 backends.
+ *
+ * pnp_conv3x3_nhwc_f16: torch.nn.Conv2d(C, C, 3, 1, d, dilation=d), C a multiple of 64 up to 1024; dilation 1..4 at C = 64, 1 otherwise.
+ * x, skip, y [n][H][W][C]; w_packed: 9 C C halves from pnp_conv3x3_pack_f16; bias [C] float32 or NULL; skip NULL or added before the
+ * ReLU; y must alias neither x nor skip.  fmt says which tensors are float32 INSTEAD of half (0 = all half): a float32 x is rounded
+ * to half while it is staged (same bits as a pre-rounded x), a float32 y is the accumulator result without the final rounding.  One
+ * image with 16 more rows must stay below 2 GiB as a float32 tensor ((H + 16) W C floats), whatever its format: the kernels let the
+ * byte offsets of halo and overhang rows fall out of the buffer's range, and those must not wrap around 2^32. */
+#define PNP_F16_X_F32    1
+#define PNP_F16_SKIP_F32 2
+#define PNP_F16_Y_F32    4
+int pnp_conv3x3_nhwc_f16(void* hip_stream, const void* x_dev, const void* w_packed_dev, const float* bias_dev, const void* skip_dev,
+                         void* y_dev, int n, int C, int H, int W, int relu, int dilation, int fmt);
+/* w_oihw_dev: a torch Conv2d(C, C, 3) weight, float32 [C][C][3][3] contiguous -> 9 C C halves in the kernel's fragment order. */
+int pnp_conv3x3_pack_f16(void* hip_stream, const float* w_oihw_dev, void* w_packed_dev, int C);
+/* First layers: pnp_conv3x3_head_nhwc / pnp_ffdnet_head_nhwc with the same float32 arithmetic, y [n][H][W][64] stored as halves. */
+int pnp_conv3x3_head_nhwc_f16(void* hip_stream, const float* x_nchw_dev, const float* w_oihw_dev, const float* bias_dev,
+                              void* y_nhwc_dev, int n, int cin, int H, int W, int relu);
+int pnp_ffdnet_head_nhwc_f16(void* hip_stream, const float* x_dev, const float* sigma_dev, int sigma_per_image, const float* w_oihw_dev,
+                             const float* bias_dev, void* y_nhwc_dev, int n, int h, int w, int relu);
+/* Last layers: x [n][H][W][64] halves, w a float32 torch Conv2d(64, cout, 3) weight (rounded to half inside the kernel), 1 <= cout <= 4
+ * -> y float32.  pnp_conv3x3_tail_nchw_f16: y [n][cout][H][W]; x2_dev NULL, or a half tensor of x's shape added to x in float32 while
+ * it is staged, the sum rounded to half once (the U-Net's last skip sum).  pnp_ffdnet_tail_f16: x at ceil(h/2) x ceil(w/2), the four
+ * output channels written pixel-shuffled and cropped into y [n][1][h][w]. */
+int pnp_conv3x3_tail_nchw_f16(void* hip_stream, const void* x_nhwc_dev, const void* x2_nhwc_dev, const float* w_oihw_dev,
+                              const float* bias_dev, float* y_nchw_dev, int n, int cout, int H, int W);
+int pnp_ffdnet_tail_f16(void* hip_stream, const void* x_nhwc_dev, const float* w_oihw_dev, const float* bias_dev, float* y_dev, int n, int h, int w);
+/* DRUNet's scale changes on halves (shapes and x2 as pnp_conv2x2s2_nhwc_f16x3 / pnp_convT2x2s2_nhwc_f16x3; x, x2, y halves; the sum
+ * x + x2 is formed in float32 and rounded to half once, as the operand; y_f32 != 0: y is float32, the accumulator result without the
+ * final rounding -- what the one-layer tests compare with float64).  w_packed from pnp_conv2x2_pack_f16: 8 C C halves
+ * (transposed = 0, a Conv2d weight [2C][C][2][2]) or 2 C C halves (1, a ConvTranspose2d weight [C][C/2][2][2]). */
+int pnp_conv2x2s2_nhwc_f16(void* hip_stream, const void* x_dev, const void* x2_dev, const void* w_packed_dev, void* y_dev,
+                           int n, int C, int H, int W, int y_f32);
+int pnp_convT2x2s2_nhwc_f16(void* hip_stream, const void* x_dev, const void* x2_dev, const void* w_packed_dev, void* y_dev,
+                            int n, int C, int H, int W, int y_f32);
+int pnp_conv2x2_pack_f16(void* hip_stream, const float* w_dev, void* w_packed_dev, int C, int transposed);
 /* [n][64][H][W] <-> [n][H][W][64] (to_nhwc = 1 / 0): hand-over between PyTorch layers (NCHW) and the kernels above. */
 int pnp_relayout_c64(void* hip_stream, const float* in_dev, float* out_dev, int n, int H, int W, int to_nhwc);
 

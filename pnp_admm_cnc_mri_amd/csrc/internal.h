@@ -115,6 +115,18 @@ hipError_t launch_conv3x3_head(hipStream_t s, const float* x_nchw, const float* 
 hipError_t launch_conv3x3_tail(hipStream_t s, const float* x_nhwc, const float* w_oihw, const float* bias, float* y_nchw,
                                int n, int cout, int H, int W);
 
+// the denoisers' layers in HALF precision (kernels_conv_f16.hip, kernels_pix2x2_f16.hip): activations NHWC halves, weights
+// rounded to half at pack time, float32 accumulation, one rounding on store.  fmt: HF_FMT_X32 | HF_FMT_SKIP32 | HF_FMT_Y32 (f16_common.h)
+hipError_t launch_conv_pack_w_f16(hipStream_t s, const float* w_oihw /*[C][C][3][3]*/, void* wfrag /*9 C C halves*/, int C);
+hipError_t launch_conv3x3_f16(hipStream_t s, const void* x, const void* wfrag, const float* bias, const void* skip, void* y,
+                              int n, int C /* 64 k <= 1024 */, int H, int W, int relu, int dilation /* 1..4; 1 if C > 64 */, int fmt);
+hipError_t launch_conv3x3_head_f16(hipStream_t s, const float* x, const float* sigma, int sigma_per_image, const float* w_oihw, const float* bias,
+                                   void* y_nhwc, int n, int cin, int H, int W, int relu, int ffdnet /* x = the full-resolution [n][1][H][W] image */);
+hipError_t launch_conv3x3_tail_f16(hipStream_t s, const void* x_nhwc, const void* x2_nhwc /* null or added to x */, const float* w_oihw,
+                                   const float* bias, float* y, int n, int cout, int H, int W, int shuffle_h = 0, int shuffle_w = 0);
+hipError_t launch_pix2_pack_w_f16(hipStream_t s, const float* w, void* wfrag /* 8 C C halves (down), 2 C C (up) */, int C, int up);
+hipError_t launch_pix2x2_f16(hipStream_t s, const void* x, const void* x2, const void* wfrag, void* y, int n, int C, int H, int W, int up, int y_f32);
+
 // steps of a run driven launch by launch (engine_host.h, chain_step; the *_step functions of the two-launch engines below)
 enum class ChainStep { open, cols, mid, last };
 

@@ -141,6 +141,42 @@ def dma_order_violations(body, group=4, ahead=0, labels=None, primed=0):
     return bad
 
 
+def lds_pending_at_barriers(body, labels=None):
+    """LDS accesses that may still be outstanding when a wave arrives at an `s_barrier`: [(index, 's_barrier', the oldest such access)].
+    A raw s_barrier waits for no counter, so a `ds_read` in flight across it races with the other waves' writes behind it (and a `ds_write`
+    in flight is not yet visible to them): every barrier of a kernel that re-uses an LDS tile must stand behind an `s_waitcnt lgkmcnt(0)`
+    (or an lgkmcnt(n) that retires every LDS access -- LDS returns in order; scalar loads share the counter and return out of order, so
+    with one pending only lgkmcnt(0) counts).  Backward branches are followed once more with the state the pass before left."""
+    bad, pend = [], []
+
+    def step(idx, ins):
+        nonlocal pend
+        if ins.startswith('ds_'):
+            pend.append(ins)
+        elif ins.startswith(('s_load', 's_buffer_load')):
+            pend.append('S')
+        elif ins.startswith('s_waitcnt'):
+            m = re.search(r'lgkmcnt\((\d+)\)', ins)
+            if m:
+                n = int(m.group(1))
+                if n == 0:
+                    pend = []
+                elif 'S' not in pend:
+                    pend = pend[len(pend) - n:] if n < len(pend) else pend
+        elif ins.startswith('s_barrier'):
+            lds = [x for x in pend if x != 'S']
+            if lds:
+                bad.append((idx, ins, lds[0]))
+
+    for idx, ins in enumerate(body):
+        step(idx, ins)
+        mb = re.match(r's_c?branch\w*\s+(\.LBB\w+)', ins) if labels else None
+        if mb and labels.get(mb.group(1), idx + 1) <= idx:
+            for k in range(labels[mb.group(1)], idx + 1):
+                step(k, body[k])
+    return bad
+
+
 def scan_text(text):
     """[(kernel, store, overwriting instruction)] of one assembly file, and the number of wide buffer stores seen."""
     bad, n = [], 0
@@ -155,6 +191,8 @@ def scan_text(text):
             bad += [(name, 'LDS-DMA order: ' + why, ins)
                     for _, why, ins in dma_order_violations(k['body'], group=2 if pipe else 4, ahead=1 if wide or pipe else 0,
                                                             primed=1 if wide or pipe else 0, labels=k['labels'])]
+        if '_f16E' in name or '_f16I' in name:                      # the half-precision kernels (kernels_conv_f16.hip, kernels_pix2x2_f16.hip)
+            bad += [(name, 'LDS-DMA order: an LDS access may be outstanding at a barrier', ins) for _, _, ins in lds_pending_at_barriers(k['body'], k['labels'])]
     return bad, n
 
 

@@ -48,13 +48,21 @@ def _conv_stack(in_nc, out_nc, nc, nb, dilations=None):
 #   'hip_f16x3'  float32 operands as pairs of halves, three exact-product f16 matrix instructions per product, float32 accumulation
 #                (csrc/kernels_conv_f16x3.hip: float32-level error, 1.9-2.6 x the fp32 matrix peak; also DRUNet's 128 / 256 / 512-
 #                channel blocks)
+#   'hip_f16'    HALF precision between the layers (csrc/kernels_conv_f16.hip, kernels_pix2x2_f16.hip): activations stored
+#                as halves, weights rounded to half at pack time, ONE matrix instruction per product, float32 accumulation, one rounding
+#                per layer on store; the network's input, output and first layer stay float32.  A throughput mode: it does NOT meet the
+#                1e-5 parity bar, is opt-in, is never chosen by 'auto', and needs EVERY layer on libpnpmri.so (no mixing with PyTorch layers).
 # Same weights, same state_dict; the default backend is PyTorch-ROCm / MIOpen (the north star's split).
 # ----------------------------------------------------------------------------------------------
-HIP_BACKENDS = ('hip', 'hip_f16x3')       # 'hip': float32 matrix cores; 'hip_f16x3': split-half arithmetic on the f16 matrix cores
+HIP_BACKENDS = ('hip', 'hip_f16x3', 'hip_f16')       # 'hip': float32 matrix cores; 'hip_f16x3': split-half arithmetic on the f16 matrix cores; 'hip_f16': half precision
 
 
 def _hip_math(backend):
-    return 'f16x3' if backend == 'hip_f16x3' else 'f32'
+    return {'hip_f16x3': 'f16x3', 'hip_f16': 'f16'}.get(backend, 'f32')
+
+
+# pnp_conv3x3_nhwc_f16's format mask: which tensors are float32 INSTEAD of half (include/pnp_mri.h)
+F16_X_F32, F16_SKIP_F32, F16_Y_F32 = 1, 2, 4
 
 
 # The SPLIT activation format the f16x3 layers hand to each other (include/pnp_mri.h, pnp_conv3x3_nhwc_f16x3_fmt): same shape and bytes
@@ -87,6 +95,11 @@ def _check_range(t_nhwc, split, where):
     if os.environ.get('PNP_CONV_CHECK_RANGE') != '1':
         return
     v = unsplit_activations(t_nhwc) if split else t_nhwc
+    if v.dtype == torch.float16:                                   # backend 'hip_f16': a value that left the half range was STORED as inf
+        if not bool(torch.isfinite(v).all()):
+            raise FloatingPointError("backend='hip_f16': an activation entering %s is not finite: a layer's result left the half range "
+                                     "(|x| <= 65504) or NaN came in" % where)
+        return
     if not bool(torch.isfinite(v).all()) or float(v.abs().max()) > 65504.:
         raise FloatingPointError("backend='hip_f16x3': an activation entering %s is not finite or lies outside the half range "
                                  "(|x| <= 65504): max |x| = %r" % (where, float(torch.nan_to_num(v.abs(), nan=float('inf')).max())))
@@ -102,7 +115,7 @@ def _hip_body_ok(conv, math='f32'):
         return False
     if conv.in_channels == 64:
         return 1 <= conv.dilation[0] <= 4
-    return math == 'f16x3' and conv.in_channels % 64 == 0 and 64 < conv.in_channels <= 1024 and conv.dilation[0] == 1
+    return math in ('f16x3', 'f16') and conv.in_channels % 64 == 0 and 64 < conv.in_channels <= 1024 and conv.dilation[0] == 1
 
 
 def _hip_weights(seq, k, conv, L, stream, math='f32'):
@@ -116,8 +129,12 @@ def _hip_weights(seq, k, conv, L, stream, math='f32'):
     hit = cache.get((k, math))
     if hit is None or hit[0] != key:
         src = w.detach().contiguous()                          # [out][in][3][3] whatever the parameter's memory format
-        packed = torch.empty(9 * conv.in_channels * conv.out_channels, dtype=torch.float32, device=w.device)
-        if math == 'f16x3':
+        packed = torch.empty(9 * conv.in_channels * conv.out_channels, dtype=torch.float16 if math == 'f16' else torch.float32, device=w.device)
+        if math == 'f16':                                          # rounded to half once, here (round to nearest even)
+            if not bool(torch.isfinite(src).all()) or float(src.abs().max()) > 65504.:
+                raise ValueError("backend='hip_f16': a convolution weight lies outside the half range (|w| <= 65504)")
+            _lib.check(L.pnp_conv3x3_pack_f16(stream, C.c_void_p(src.data_ptr()), C.c_void_p(packed.data_ptr()), conv.in_channels))
+        elif math == 'f16x3':
             if not bool(torch.isfinite(src).all()) or float(src.abs().max()) > 65504.:
                 raise ValueError("backend='hip_f16x3': a convolution weight lies outside the half range (|w| <= 65504)")
             _lib.check(L.pnp_conv3x3_pack_f16x3(stream, C.c_void_p(src.data_ptr()), C.c_void_p(packed.data_ptr()), conv.in_channels))
@@ -127,21 +144,24 @@ def _hip_weights(seq, k, conv, L, stream, math='f32'):
     return hit[1]
 
 
-def _hip_weights2x2(owner, conv, L, stream, transposed):
-    """a 2 x 2 stride-2 (transposed) convolution's weight in the fragment order of csrc/kernels_pix2x2_f16x3.hip, cached like _hip_weights"""
+def _hip_weights2x2(owner, conv, L, stream, transposed, math='f16x3'):
+    """a 2 x 2 stride-2 (transposed) convolution's weight in the fragment order of csrc/kernels_pix2x2_f16x3.hip (math='f16': halves in
+    that of csrc/kernels_pix2x2_f16.hip, under a key of its own), cached like _hip_weights"""
     import ctypes as C
     from . import _lib
     cache = owner.__dict__.setdefault('_pnp_hip_w2', {})
     w = conv.weight
     key = (w.data_ptr(), w._version, str(w.device))
-    hit = cache.get(id(conv))
+    slot = id(conv) if math == 'f16x3' else (id(conv), math)
+    hit = cache.get(slot)
     if hit is None or hit[0] != key:
         src = w.detach().contiguous(memory_format=torch.contiguous_format)
         if not bool(torch.isfinite(src).all()) or float(src.abs().max()) > 65504.:
-            raise ValueError("backend='hip_f16x3': a convolution weight lies outside the half range (|w| <= 65504)")
-        packed = torch.empty(src.numel(), dtype=torch.float32, device=w.device)
-        _lib.check(L.pnp_conv2x2_pack_f16x3(stream, C.c_void_p(src.data_ptr()), C.c_void_p(packed.data_ptr()), conv.in_channels, 1 if transposed else 0))
-        cache[id(conv)] = hit = (key, packed, src)
+            raise ValueError("backend='hip_%s': a convolution weight lies outside the half range (|w| <= 65504)" % math)
+        packed = torch.empty(src.numel(), dtype=torch.float16 if math == 'f16' else torch.float32, device=w.device)
+        _lib.check((L.pnp_conv2x2_pack_f16 if math == 'f16' else L.pnp_conv2x2_pack_f16x3)(
+            stream, C.c_void_p(src.data_ptr()), C.c_void_p(packed.data_ptr()), conv.in_channels, 1 if transposed else 0))
+        cache[slot] = hit = (key, packed, src)
     return hit[1]
 
 
@@ -237,6 +257,85 @@ def hip_stack_forward(seq, x, math='f32', head=None, tail=None):
     return h if nhwc is None else nhwc.permute(0, 3, 1, 2)
 
 
+def _f16_conv(L, stream, x_nhwc, packed, bias, skip_nhwc, relu, dilation=1, fmt=0):
+    """one C -> C conv3x3 of backend 'hip_f16' (pnp_conv3x3_nhwc_f16): halves in and out unless `fmt` says float32"""
+    import ctypes as C
+    from . import _lib
+    n, H, W, ch = x_nhwc.shape
+    for t, bit in ((x_nhwc, F16_X_F32), (skip_nhwc, F16_SKIP_F32)):
+        if t is not None and t.dtype != (torch.float32 if fmt & bit else torch.float16):
+            raise TypeError('pnp_conv3x3_nhwc_f16: tensor dtype %s does not match fmt=%d' % (t.dtype, fmt))
+    _check_range(x_nhwc, False, 'a %d-channel conv3x3' % ch)
+    out = torch.empty((n, H, W, ch), dtype=torch.float32 if fmt & F16_Y_F32 else torch.float16, device=x_nhwc.device)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    _lib.check(L.pnp_conv3x3_nhwc_f16(stream, ptr(x_nhwc), ptr(packed), ptr(bias), ptr(skip_nhwc), ptr(out), n, ch, H, W, 1 if relu else 0,
+                                      int(dilation), int(fmt)))
+    return out
+
+
+def hip_f16_stack_forward(seq, x, head=None, tail=None):
+    """`seq(x)` for a fully covered [Conv3x3, ReLU] * (nb - 1) + Conv3x3 stack (hip_covers_stack) in HALF precision (backend 'hip_f16',
+    DESIGN.md 4.12): the first layer in float32 direct arithmetic storing halves, the 64 -> 64 layers on pnp_conv3x3_nhwc_f16, the last
+    layer reading halves and storing float32.  No layer runs anywhere else: an uncovered stack raises.  head / tail: as hip_stack_forward."""
+    import ctypes as C
+    from . import _lib
+    if not (x.is_cuda and x.dtype == torch.float32):
+        raise RuntimeError("Denoiser(backend='hip_f16') needs float32 CUDA tensors")
+    bad = f16_uncovered_stack(seq)
+    if bad:
+        raise ValueError("backend='hip_f16': libpnpmri.so does not take %s" % bad)
+    L = _lib.lib()
+    stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    mods = list(seq)
+    convs = [k for k, m in enumerate(mods) if isinstance(m, nn.Conv2d)]
+    relu_after = lambda k: k + 1 < len(mods) and isinstance(mods[k + 1], nn.ReLU)
+    k0, m0 = convs[0], mods[convs[0]]
+    if head is not None:
+        nhwc = head(m0, relu_after(k0))
+    else:
+        hc = x.contiguous()
+        n, _, H, W = hc.shape
+        nhwc = torch.empty((n, H, W, 64), dtype=torch.float16, device=x.device)
+        _lib.check(L.pnp_conv3x3_head_nhwc_f16(stream, ptr(hc), ptr(_hip_oihw(seq, k0, m0)), ptr(m0.bias), ptr(nhwc), n, m0.in_channels, H, W,
+                                               1 if relu_after(k0) else 0))
+    for k in convs[1:-1]:
+        m = mods[k]
+        nhwc = _f16_conv(L, stream, nhwc, _hip_weights(seq, k, m, L, stream, 'f16'), m.bias, None, relu_after(k), m.dilation[0])
+    kt, mt = convs[-1], mods[convs[-1]]
+    _check_range(nhwc, False, 'the last layer')
+    if tail is not None:
+        return tail(mt, nhwc)
+    n, H, W, _ = nhwc.shape
+    out = torch.empty((n, mt.out_channels, H, W), dtype=torch.float32, device=x.device)
+    _lib.check(L.pnp_conv3x3_tail_nchw_f16(stream, ptr(nhwc), None, ptr(_hip_oihw(seq, kt, mt)), ptr(mt.bias), ptr(out), n, mt.out_channels, H, W))
+    return out
+
+
+def f16_uncovered_stack(seq):
+    """None when backend 'hip_f16' takes every layer of the stack, else a description of the first one it does not take"""
+    mods = list(seq)
+    convs = [k for k, m in enumerate(mods) if isinstance(m, nn.Conv2d)]
+    for k, m in enumerate(mods):
+        if not isinstance(m, (nn.Conv2d, nn.ReLU)):
+            return 'layer %d: %r' % (k, m)
+        if isinstance(m, nn.ReLU) and (k == 0 or not isinstance(mods[k - 1], nn.Conv2d)):
+            return 'layer %d: %r (not behind a convolution)' % (k, m)
+    if len(convs) < 2:
+        return 'a stack of fewer than two convolutions'
+    for n, k in enumerate(convs):
+        m = mods[k]
+        if n == 0:
+            ok = _plain3x3(m) and m.in_channels <= 8 and m.out_channels == 64
+        elif n == len(convs) - 1:
+            ok = _plain3x3(m) and m.in_channels == 64 and m.out_channels <= 4 and not (k + 1 < len(mods) and isinstance(mods[k + 1], nn.ReLU))
+        else:
+            ok = _hip_body_ok(m, 'f16')
+        if not ok:
+            return 'layer %d: %r' % (k, m)
+    return None
+
+
 def hip_covers_stack(seq):
     """True when every convolution of the stack runs on libpnpmri.so under backend 'hip' (head, 64 -> 64 body, tail): such a
     forward makes no MIOpen call at all."""
@@ -253,6 +352,8 @@ class _PlainStack(nn.Module):
     backend = 'torch'
 
     def _stack(self, x):
+        if self.backend == 'hip_f16':
+            return hip_f16_stack_forward(self.model, x)
         return hip_stack_forward(self.model, x, _hip_math(self.backend)) if self.backend in HIP_BACKENDS else self.model(x)
 
 
@@ -292,7 +393,7 @@ class FFDNet(_PlainStack):
         """backend 'hip_f16x3', gray in and out, every layer on libpnpmri.so: the pad / pixel-unshuffle / concatenation in front of the stack
         and the pixel-shuffle / crop behind it are folded into the first and last layer's kernels (pnp_ffdnet_head_nhwc, pnp_ffdnet_tail_f16x3)"""
         convs = [m for m in self.model if isinstance(m, nn.Conv2d)]
-        return (self.backend == 'hip_f16x3' and x.is_cuda and x.dtype == torch.float32 and x.shape[1] == 1 and hip_covers_stack(self.model)
+        return (self.backend in ('hip_f16x3', 'hip_f16') and x.is_cuda and x.dtype == torch.float32 and x.shape[1] == 1 and hip_covers_stack(self.model)
                 and convs[0].in_channels == 5 and convs[-1].out_channels == 4 and sigma.numel() in (1, x.shape[0]))
 
     def _forward_fused(self, x, sigma, out=None):
@@ -309,15 +410,19 @@ class FFDNet(_PlainStack):
         elif not (out.is_contiguous() and out.shape == xc.shape and out.dtype == torch.float32 and out.device == x.device):
             raise ValueError('FFDNet: `out` must be a contiguous float32 tensor of the input\'s shape on its device')
 
+        f16 = self.backend == 'hip_f16'
+
         def head(conv, relu):
-            y = torch.empty((n, (h + 1) // 2, (w + 1) // 2, 64), dtype=torch.float32, device=x.device)
-            _lib.check(L.pnp_ffdnet_head_nhwc(stream, ptr(xc), ptr(sg), 1 if sg.numel() > 1 else 0, ptr(_hip_oihw(self.model, 0, conv)), ptr(conv.bias),
+            y = torch.empty((n, (h + 1) // 2, (w + 1) // 2, 64), dtype=torch.float16 if f16 else torch.float32, device=x.device)
+            _lib.check((L.pnp_ffdnet_head_nhwc_f16 if f16 else L.pnp_ffdnet_head_nhwc)(stream, ptr(xc), ptr(sg), 1 if sg.numel() > 1 else 0, ptr(_hip_oihw(self.model, 0, conv)), ptr(conv.bias),
                                               ptr(y), n, h, w, 1 if relu else 0))
             return y
 
         def tail(conv, nhwc):
-            _lib.check(L.pnp_ffdnet_tail_f16x3(stream, ptr(nhwc), ptr(_hip_oihw(self.model, len(self.model) - 1, conv)), ptr(conv.bias), ptr(out), n, h, w))
+            _lib.check((L.pnp_ffdnet_tail_f16 if f16 else L.pnp_ffdnet_tail_f16x3)(stream, ptr(nhwc), ptr(_hip_oihw(self.model, len(self.model) - 1, conv)), ptr(conv.bias), ptr(out), n, h, w))
             return out
+        if f16:
+            return hip_f16_stack_forward(self.model, xc, head=head, tail=tail)
         return hip_stack_forward(self.model, xc, 'f16x3', head=head, tail=tail)
 
     def forward(self, x, sigma, out=None):
@@ -393,7 +498,25 @@ class _ResBlock(nn.Module):
         h = _hip_conv64(L, stream, xn, _hip_weights(self.res, 0, self.res[0], L, stream, math), self.res[0].bias, None, True, 1, math, f0)
         return _hip_conv64(L, stream, h, _hip_weights(self.res, 2, self.res[2], L, stream, math), self.res[2].bias, xn, False, 1, math, f2)
 
+    def forward_nhwc_f16(self, xn, f32_io=False):
+        """the block under backend 'hip_f16' on a contiguous [n][H][W][C] tensor of halves (f32_io: of float32, in and out -- the block
+        called on its own; its input is then rounded to half as the first convolution's operand and added unrounded as the skip)"""
+        import ctypes as C
+        from . import _lib
+        if not (xn.is_cuda and xn.dtype == (torch.float32 if f32_io else torch.float16)):
+            raise RuntimeError("Denoiser(backend='hip_f16') needs CUDA tensors (float32 at the network's boundary, halves between layers)")
+        L = _lib.lib()
+        stream = C.c_void_p(torch.cuda.current_stream(xn.device).cuda_stream)
+        h = _f16_conv(L, stream, xn, _hip_weights(self.res, 0, self.res[0], L, stream, 'f16'), self.res[0].bias, None, True, 1, F16_X_F32 if f32_io else 0)
+        return _f16_conv(L, stream, h, _hip_weights(self.res, 2, self.res[2], L, stream, 'f16'), self.res[2].bias, xn, False, 1,
+                         (F16_SKIP_F32 | F16_Y_F32) if f32_io else 0)
+
     def forward(self, x):
+        if self.backend == 'hip_f16':
+            if not self.hip_ok():
+                raise ValueError("backend='hip_f16': libpnpmri.so does not take %r" % self.res)
+            xn = x.permute(0, 2, 3, 1)
+            return self.forward_nhwc_f16(xn if xn.is_contiguous() else xn.contiguous(), f32_io=True).permute(0, 3, 1, 2)
         if self.hip_ok():
             xn = x.permute(0, 2, 3, 1)
             if not xn.is_contiguous():
@@ -431,7 +554,7 @@ class UNetRes(nn.Module):
         """True when EVERY convolution of the U-Net runs on libpnpmri.so under backend 'hip_f16x3': first / last layer, all residual
         blocks, the three 2 x 2 stride-2 convolutions and the three 2 x 2 transposed ones (csrc/kernels_pix2x2_f16x3.hip) -- such a
         forward makes no MIOpen call at all.  H, W (if given) must survive three halvings."""
-        if (backend or self.backend) != 'hip_f16x3' or (H is not None and (H % 8 or W % 8)):      # backend=: "would it, under that backend?" (auto_backend)
+        if (backend or self.backend) not in ('hip_f16x3', 'hip_f16') or (H is not None and (H % 8 or W % 8)):      # backend=: "would it, under that backend?" (auto_backend)
             return False
         if not (_plain3x3(self.m_head) and self.m_head.in_channels <= 8 and self.m_head.out_channels == 64 and self.m_head.bias is None
                 and _plain3x3(self.m_tail) and self.m_tail.in_channels == 64 and self.m_tail.out_channels <= 4):
@@ -496,7 +619,54 @@ class UNetRes(nn.Module):
                                                      n, self.m_tail.out_channels, H, W))
         return out
 
+    def _forward_f16(self, x0):
+        """the same walk under backend 'hip_f16': halves between the layers, the skip sums formed in float32 inside the
+        kernel that consumes them and rounded to half once, as its operand"""
+        import ctypes as C
+        from . import _lib
+        L = _lib.lib()
+        stream = C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        xc = x0.contiguous()
+        n, _, H, W = xc.shape
+        x1 = torch.empty((n, H, W, 64), dtype=torch.float16, device=x0.device)
+        _lib.check(L.pnp_conv3x3_head_nhwc_f16(stream, ptr(xc), ptr(_hip_oihw(self, 'head', self.m_head)), None, ptr(x1), n, self.m_head.in_channels, H, W, 0))
+
+        def scale(conv, t, t2, up):
+            c = conv.in_channels
+            nn_, h, w, _ = t.shape
+            _check_range(t, False, 'a 2 x 2 convolution')
+            out = torch.empty((nn_, 2 * h, 2 * w, c // 2) if up else (nn_, h // 2, w // 2, 2 * c), dtype=torch.float16, device=t.device)
+            wp = _hip_weights2x2(self, conv, L, stream, up, 'f16')
+            _lib.check((L.pnp_convT2x2s2_nhwc_f16 if up else L.pnp_conv2x2s2_nhwc_f16)(stream, ptr(t), ptr(t2), ptr(wp), ptr(out), nn_, c, h, w, 0))
+            return out
+
+        def blocks(ms, t):
+            for m in ms:
+                t = m.forward_nhwc_f16(t)
+            return t
+
+        x2 = scale(self.m_down1[-1], blocks(self.m_down1[:-1], x1), None, False)
+        x3 = scale(self.m_down2[-1], blocks(self.m_down2[:-1], x2), None, False)
+        x4 = scale(self.m_down3[-1], blocks(self.m_down3[:-1], x3), None, False)
+        x = blocks(self.m_body, x4)
+        x = blocks(self.m_up3[1:], scale(self.m_up3[0], x, x4, True))      # m_up(x + x_skip)
+        x = blocks(self.m_up2[1:], scale(self.m_up2[0], x, x3, True))
+        x = blocks(self.m_up1[1:], scale(self.m_up1[0], x, x2, True))
+        _check_range(x, False, 'the last layer')
+        out = torch.empty((n, self.m_tail.out_channels, H, W), dtype=torch.float32, device=x0.device)
+        _lib.check(L.pnp_conv3x3_tail_nchw_f16(stream, ptr(x), ptr(x1), ptr(_hip_oihw(self, 'tail', self.m_tail)), ptr(self.m_tail.bias), ptr(out),
+                                               n, self.m_tail.out_channels, H, W))
+        return out
+
     def forward(self, x0):
+        if self.backend == 'hip_f16':                          # all of it on libpnpmri.so, or an error: no mixing with PyTorch layers
+            if not (x0.is_cuda and x0.dtype == torch.float32):
+                raise RuntimeError("Denoiser(backend='hip_f16') needs float32 CUDA tensors")
+            if not self.hip_covers(x0.shape[-2], x0.shape[-1]):
+                raise ValueError("backend='hip_f16': libpnpmri.so does not take this U-Net at %d x %d (every layer must be one it takes, "
+                                 "H and W multiples of 8)" % (x0.shape[-2], x0.shape[-1]))
+            return self._forward_f16(x0)
         if x0.is_cuda and x0.dtype == torch.float32 and self.hip_covers(x0.shape[-2], x0.shape[-1]):
             return self._forward_f16x3(x0)
         hip = self._hip_ends(x0)
@@ -532,6 +702,25 @@ class UNetRes(nn.Module):
                 stream, ptr(xn), ptr(_hip_oihw(self, 'tail', self.m_tail)), ptr(self.m_tail.bias), ptr(out), n, self.m_tail.out_channels, H, W))
             return out
         return self.m_tail(x)
+
+
+def f16_uncovered_unet(model):
+    """a description of the first layer of a UNetRes that backend 'hip_f16' does not take (UNetRes.hip_covers says whether there is one)"""
+    for name, m in model.named_modules():
+        if isinstance(m, _ResBlock) and not m.hip_ok('hip_f16'):
+            return '%s: %r' % (name, m.res)
+    for name in ('m_head', 'm_tail'):
+        m = getattr(model, name)
+        if not (_plain3x3(m) and (m.bias is None or name == 'm_tail')):
+            return '%s: %r' % (name, m)
+    for name in ('m_down1', 'm_down2', 'm_down3', 'm_up3', 'm_up2', 'm_up1', 'm_body'):
+        for k, m in enumerate(getattr(model, name)):
+            if not isinstance(m, _ResBlock):
+                ok = ((isinstance(m, nn.ConvTranspose2d) and name.startswith('m_up') and k == 0)
+                      or (type(m) is nn.Conv2d and name.startswith('m_down') and k == len(getattr(model, name)) - 1))
+                if not (ok and m.kernel_size == (2, 2) and m.stride == (2, 2) and m.padding == (0, 0) and m.bias is None):
+                    return '%s.%d: %r' % (name, k, m)
+    return 'this U-Net (channel counts or layer order are not DRUNet\'s)'
 
 
 # ----------------------------------------------------------------------------------------------
@@ -795,7 +984,9 @@ class Denoiser:
         """backend: 'torch' (default: the whole forward in PyTorch-ROCm / MIOpen, as the north star keeps it) or 'hip' (the
         64 -> 64 conv3x3 (+ ReLU) layers of DnCNN / FDnCNN / FFDNet / IRCNN (dilations 1..4) and DRUNet's 64-channel residual
         blocks on libpnpmri.so's fp32-MFMA kernel, the plain stacks' first and last layers on its direct kernels; float32 only)
-        or 'hip_f16x3' (the same, with the 64 -> 64 layers in split-half arithmetic on the f16 matrix cores: float32 operands
+        or 'hip_f16' (opt-in throughput mode, never chosen by 'auto': halves between the layers, one matrix instruction per product,
+        float32 accumulation -- NOT at the 1e-5 parity bar; every layer must be one libpnpmri.so takes, or the constructor raises)
+        or 'hip_f16x3' (the same as 'hip', with the 64 -> 64 layers in split-half arithmetic on the f16 matrix cores: float32 operands
         carried as two halves, three exact-product matrix instructions per product, float32 accumulation -- float32-level
         results at several times the float32 matrix rate; operands must lie within the half range, |x| <= 65504).  shape: the slices' (H, W),
         for backend='auto' (auto_backend)."""
@@ -810,9 +1001,18 @@ class Denoiser:
             backend, why = auto_backend(model, None, bank, cnn_dtype, shape)
             logging.getLogger('pnp_admm_cnc_mri_amd').info('cnn_backend=auto -> %s (%s)', backend, why)
         if backend not in ('torch',) + HIP_BACKENDS:
-            raise ValueError("backend must be 'auto', 'torch', 'hip' or 'hip_f16x3'")
+            raise ValueError("backend must be 'auto', 'torch', 'hip', 'hip_f16x3' or 'hip_f16'")
         if backend in HIP_BACKENDS and cnn_dtype not in (None, 'fp32'):
             raise ValueError("backend='%s' takes and returns float32 only" % backend)
+        if backend == 'hip_f16':                               # full coverage or nothing: no PyTorch layer in a half-precision forward
+            if isinstance(model, UNetRes):
+                bad = None if model.hip_covers(backend='hip_f16') else f16_uncovered_unet(model)
+            elif isinstance(model, _PlainStack):
+                bad = f16_uncovered_stack(model.model)
+            else:
+                bad = 'a %s' % type(model).__name__
+            if bad:
+                raise ValueError("backend='hip_f16' needs every layer on libpnpmri.so; it does not take %s" % bad)
         self.name, self.fam = model_name, family(model_name)
         self.model = model
         self.backend = backend
@@ -958,7 +1158,7 @@ class Denoiser:
             if self._cnn_batch_auto and cb > 64:          # the automatic 256 is for 256 x 256 slices: the same pixel count per call for larger ones
                 cb = max(64, cb * 65536 // max(65536, x.shape[-2] * x.shape[-1]))
             for b0 in range(0, B, cb):
-                if (self.cnn_dtype is None and self.backend == 'hip_f16x3' and isinstance(self.model, FFDNet) and x.is_cuda and out.is_contiguous()
+                if (self.cnn_dtype is None and self.backend in ('hip_f16x3', 'hip_f16') and isinstance(self.model, FFDNet) and x.is_cuda and out.is_contiguous()
                         and out.dtype == torch.float32 and out.device == x.device):
                     self._one(x[b0:b0 + cb], i, out=out[b0:b0 + cb])     # no copy: the last layer writes the slice itself
                 elif self.cnn_dtype is None:

@@ -27,7 +27,10 @@ save_E=, device=, return_info=  as in solvers.py, plus
                             arithmetic, ~1e-6 from MIOpen's results; first and last layer on its direct kernels);
                             'hip_f16x3': the same with the 64 -> 64 layers in split-half arithmetic on the f16 matrix cores
                             (float32 operands as two halves, exact products, float32 accumulation: float32-level results,
-                            2.3 x the float32 kernel's rate; operands must lie within the half range)
+                            2.3 x the float32 kernel's rate; operands must lie within the half range);
+                            'hip_f16': opt-in throughput mode, never what 'auto' picks -- halves between the layers, one matrix
+                            instruction per product, float32 accumulation: off the 1e-5 parity bar (rel-L2 ~2e-4 from
+                            the float32 loop at 10 iterations, PSNR within 0.01 dB); every layer must be one libpnpmri.so takes
     return_device=False     True: `out` is one torch tensor [B,H,W] on the device instead of the 22-slot list of host arrays (solvers.py)
     state0=None, iter_start=0   (PNP_ADMM_CNC_D, PNP_ADMM_L1_D) resume the loop: state0 = (z, w) arrays [B,H,W] as they stand AFTER iteration
                             iter_start, the loop then runs iterations iter_start .. iter_num - 1 (sigma schedule, bank switch and x8 mode of

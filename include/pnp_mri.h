@@ -256,6 +256,48 @@ int pnp_ssim_f64(pnp_ctx* ctx, const double* x_dev, const uint8_t* gt, int gt_on
 int pnp_residuals_f64(pnp_ctx* ctx, const double* x_dev, const double* z_dev, const double* zprev_dev, const double* w_dev,
                       const uint8_t* gt, int gt_on_device, int quantise, double* out, int out_on_device);
 
+/* ---- wavelet-domain sparsity (added after ABI 13, additive) -------------------------------------
+ * ADMM_L1 / ADMM_CNC with their penalty on the WAVELET COEFFICIENTS of the image instead of its pixels.  This regulariser has NO
+ * counterpart in the reference scripts (their prox acts on the pixels: S1:123, S4:127-129); with PNP_WAVELET_NONE -- the default --
+ * every entry point is bit for bit what it was.
+ * Psi is the orthonormal periodic 2-D DWT with low-pass filter h of length T and g[n] = (-1)^n h[T-1-n]:
+ *   haar  T = 2  [1, 1] / sqrt 2
+ *   db2   T = 4  [1 + sqrt 3, 3 + sqrt 3, 3 - sqrt 3, 1 - sqrt 3] / (4 sqrt 2)
+ *   db4   T = 8  minimum-phase Daubechies, four vanishing moments: 0.2303778133, 0.7148465706, 0.6308807679, -0.0279837694, ...
+ * one level along an axis of length M:  a[k] = sum_n h[n] s[(2k + n) mod M],  d[k] = sum_n g[n] s[(2k + n) mod M],  k < M / 2;
+ * synthesis is the transpose.  2-D, `levels` levels, Mallat layout: level l = 0 .. levels - 1 works on the top-left
+ * (H >> l) x (W >> l) block, rows first ([a | d]), then columns ([a ; d]); the final LL band is the top-left
+ * (H >> levels) x (W >> levels) and is never thresholded.  With u = x + w and "detail" = every coefficient outside that band:
+ *   L1   c = Psi u;  c <- soft(c, thr) on detail;  z+ = Psi^T c;  w+ = u - z+
+ *   CNC  cz = Psi z, cu = Psi u;  t = (1 - alpha) cz + alpha cu  [+ alpha reo lambda1 b clip(cz, -1/b, 1/b) on detail];
+ *        z+ = Psi^T (soft(t, alpha reo lambda1) on detail, t on LL);  w+ = u - z+
+ * (scalars combined in double and rounded once, as for the pixel-domain step).  Two launches per prox, both precisions.
+ * Valid: 1 <= levels <= 4, H and W divisible by 2^levels, min(H, W) >> (levels - 1) >= T; anything else is PNP_E_ARG, decided by
+ * pnp_sparsity_check -- no context, no device -- which pnp_set_sparsity calls before any device work. */
+#define PNP_WAVELET_NONE 0
+#define PNP_WAVELET_HAAR 1
+#define PNP_WAVELET_DB2  2
+#define PNP_WAVELET_DB4  3
+int pnp_sparsity_check(int wavelet, int levels, int H, int W);
+/* PNP_WAVELET_NONE (the default): `levels` is ignored and everything is as before.  With a wavelet set
+ *   - pnp_admm_l1_run, pnp_admm_cnc_run and their _traced forms run, per iteration, the context's own data-consistency step (what
+ *     pnp_dc_step launches: the two-launch engine where the shape has one, the generic / any-size kernels otherwise; three launches)
+ *     and the two prox launches: five launches per iteration, which pnp_get_plan / pnp_kernels_per_iteration report.  The state
+ *     stays in natural order, the slice-resident path is never taken (pnp_path_name says "fused"), a run cut into calls is bit-equal
+ *     to one call, and the same loop body runs in double on a double-precision context.  The traced forms check the iterations they
+ *     always check, with pnp_residuals' reduction.  iters = 0 behaves as without a wavelet.
+ *   - pnp_prox_l1_dual and pnp_prox_cnc_dual apply the wavelet-domain step (x, z, w must not overlap).
+ * The setting belongs to the context and survives uploads.  The first non-NONE setting allocates one scratch array of Bmax slices. */
+int pnp_set_sparsity(pnp_ctx* ctx, int wavelet, int levels);
+int pnp_get_sparsity(pnp_ctx* ctx, int* wavelet, int* levels);
+/* Psi / Psi^T alone with the context's setting on B <= Bmax real slices [B][H][W] (no problem needed); in_dev may EQUAL out_dev
+ * (bit-equal to the out-of-place call), any other overlap is PNP_E_ARG.  PNP_WAVELET_NONE set: PNP_E_STATE. */
+int pnp_dwt2_fwd(pnp_ctx* ctx, const float* in_dev, float* out_dev, int B);
+int pnp_dwt2_inv(pnp_ctx* ctx, const float* in_dev, float* out_dev, int B);
+/* the same on a double-precision context (double tensors) */
+int pnp_dwt2_fwd_f64(pnp_ctx* ctx, const double* in_dev, double* out_dev, int B);
+int pnp_dwt2_inv_f64(pnp_ctx* ctx, const double* in_dev, double* out_dev, int B);
+
 /* ---- optional HIP backend of the denoisers' plain conv stacks ------------------------------
  * The north star keeps the CNN forward pass in PyTorch-ROCm; these two entry points are the opt-in `Denoiser(backend='hip')`
  * for the 64 -> 64 channel conv3x3 (+ bias, + ReLU) body layers of FFDNet / DnCNN / FDnCNN (models/network_ffdnet.py:58-73,

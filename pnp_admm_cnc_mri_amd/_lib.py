@@ -102,6 +102,14 @@ SIGNATURES = {
     'pnp_convT2x2s2_nhwc_f16': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'pnp_conv2x2_pack_f16': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int]),
     'pnp_relayout_c64': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # wavelet-domain sparsity (added after ABI 13, additive)
+    'pnp_sparsity_check': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'pnp_set_sparsity': (C.c_int, [ctx_p, C.c_int, C.c_int]),
+    'pnp_get_sparsity': (C.c_int, [ctx_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'pnp_dwt2_fwd': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
+    'pnp_dwt2_inv': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
+    'pnp_dwt2_fwd_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
+    'pnp_dwt2_inv_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
     'pnp_ssim': (C.c_int, [ctx_p, _vp, _vp, C.c_int, c_double_p]),
     'pnp_timer_start': (C.c_int, [ctx_p]),
     'pnp_timer_stop': (C.c_int, [ctx_p, c_float_p]),

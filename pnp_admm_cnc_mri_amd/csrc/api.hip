@@ -2,6 +2,7 @@
 // operators, the denoisers' conv layers.  Host-side only; the kernels live in the kernels_*.hip files.
 #include "../../include/pnp_mri.h"
 #include "internal.h"
+#include "wavelet_plan.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -122,6 +123,8 @@ struct pnp_ctx {
     Problem prob;
     FusedSchedule sched;              // defaults overridable by PNP_FUSED_* (read at creation) / pnp_set_schedule
     Trace trace;
+    int wavelet = WV_NONE, wv_levels = 0;   // pnp_set_sparsity: the prox of the loops acts on the coefficients of this transform
+    void* wv_coef = nullptr;          // [Bmax][H][W] real: the coefficients between the two prox launches (on first use)
 };
 
 // The context's buffers as the element type of its precision (R = float | double).
@@ -305,6 +308,8 @@ static int finish_problem(pnp_ctx* c, int rc) {
 
 // The loops' path now: pnp_set_fast_path may change it after the upload.
 static Path loop_path(const pnp_ctx* c) { return c->fast ? c->prob.path : Path::generic; }
+// ... and where the data-consistency step alone runs (pnp_dc_step; the loops with a wavelet set): it has no slice-resident form
+static Path dc_path(const pnp_ctx* c) { return loop_path(c) == Path::generic ? Path::generic : Path::fused; }
 
 // The slice-resident loops keep z / w in their own order; everything else (the other kernel families, pnp_get_state /
 // pnp_set_state, pnp_init_state) sees natural [H][W].  One kernel converts when the need changes (into the slice path's own
@@ -468,8 +473,66 @@ static hipError_t fast_run(pnp_ctx* c, Path, int iters, bool cnc, double cdc, co
     return fused256s_run<double>(c->eng.s64, c->stream, b.z, b.w, b.x, c->B, iters, cnc, cdc, pp, c->sched);
 }
 
+// One data-consistency step x = dc(z, w) on pointers in natural order, on the context's own kernels: the two-launch engine of the shape
+// and precision where there is one, the generic / any-size kernels otherwise.
+template <typename R> static int dc_any(pnp_ctx* c, const R* z, const R* w, R* x, R cdc) {
+    if (dc_path(c) == Path::generic || c->eng.kind == Engine::none)
+        return generic_iteration<R>(c, z, w, EPI_ABS_REAL, ProxParamsT<R>{}, cdc, x, nullptr, nullptr);
+    if (int rc = ensure_tables(c, Path::fused)) return rc;
+    if constexpr (std::is_same_v<R, double>) {
+        HIPCHK(fused256s_dc<double>(c->eng.s64, c->stream, z, w, x, c->B, cdc));
+    } else {
+        switch (c->eng.kind) {
+        case Engine::fused256:  HIPCHK(fused256_dc(c->eng.f256, c->stream, z, w, x, c->B, cdc)); break;
+        case Engine::split_f32: HIPCHK(fused256s_dc<float>(c->eng.s32, c->stream, z, w, x, c->B, cdc)); break;
+        case Engine::fused512:  HIPCHK(fused512_dc(c->eng.f512, c->stream, z, w, x, c->B, cdc)); break;
+        case Engine::none: case Engine::split_f64: break;
+        }
+    }
+    return PNP_OK;
+}
+
+// ---- wavelet-domain sparsity (pnp_set_sparsity; wavelet_plan.h, kernels_wavelet.hip) ----
+
+static int wavelet_scratch(pnp_ctx* c) {
+    if (!c->wv_coef) HIPCHK(hipMalloc(&c->wv_coef, (size_t)c->Bmax * c->N * (c->f64 ? sizeof(double) : sizeof(float))));
+    return PNP_OK;
+}
+
+// Psi / Psi^T on caller pointers.  A tile reads its neighbours' halo, so an in-place call goes through the context's scratch.
+template <typename R> static int dwt2_any(pnp_ctx* c, const char* who, const R* in, R* out, int B, bool inv) {
+    if (c->wavelet == WV_NONE) return fail(PNP_E_STATE, "%s: no wavelet set (pnp_set_sparsity)", who);
+    if (!in || !out) return fail(PNP_E_ARG, "%s: null pointer", who);
+    if (B < 1 || B > c->Bmax) return fail(PNP_E_ARG, "%s: B=%d out of range [1,%d]", who, B, c->Bmax);
+    const size_t bytes = (size_t)B * c->N * sizeof(R);
+    const char *pi = (const char*)in, *po = (const char*)out;
+    if (pi != po && pi < po + bytes && po < pi + bytes) return fail(PNP_E_ARG, "%s: in and out overlap without being equal", who);
+    R* dst = out;
+    if (pi == po) { if (int rc = wavelet_scratch(c)) return rc; dst = (R*)c->wv_coef; }
+    HIPCHK(launch_dwt2<R>(c->stream, c->wavelet, c->wv_levels, inv, in, dst, B, c->H, c->W));
+    if (dst != out) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return PNP_OK;
+}
+
+// The loops with a wavelet set: per iteration the data-consistency step and the two prox launches, on the state in natural order.  Every
+// iteration stands alone -- nothing but x, z, w passes from one to the next -- so a run cut anywhere is bit-equal to the uncut run.
+template <typename R>
+static int run_wavelet_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
+    const Bufs<R> b = bufs<R>(c);
+    if (int rc = state_order<R>(c, false)) return rc;
+    if (int rc = wavelet_scratch(c)) return rc;
+    const R cdc = dc_coeff<R>(reo);
+    for (int i = 0; i < iters; ++i) {
+        if (int rc = dc_any<R>(c, b.z, b.w, b.x, cdc)) return rc;
+        HIPCHK(launch_wavelet_prox<R>(c->stream, c->wavelet, c->wv_levels, cnc, b.x, b.z, b.w, (R*)c->wv_coef, pp, c->B, c->H, c->W));
+    }
+    c->have_x = true;
+    return PNP_OK;
+}
+
 template <typename R>
 static int run_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
+    if (c->wavelet != WV_NONE && iters > 0) return run_wavelet_loop<R>(c, iters, cnc, pp, reo);
     const Bufs<R> b = bufs<R>(c);
     const Path path = iters > 0 ? loop_path(c) : Path::generic;
     if (int rc = ensure_tables(c, path)) return rc;
@@ -640,7 +703,9 @@ static int run_traced(pnp_ctx* c, const char* who, int iters, bool cnc, const Pr
     }
     const TraceRun r{iters, every, checks, tol, gt};
     int done = 0, nrows = 0;
-    if (loop_path(c) == Path::fused) {
+    // with a wavelet set every iteration is a launch boundary with the state in natural order: the legs below, on run_loop's wavelet loop
+    const Path path = c->wavelet != WV_NONE ? Path::generic : loop_path(c);
+    if (path == Path::fused) {
         if (int rc = ensure_tables(c, Path::fused)) return rc;
         if (int rc = state_order<R>(c, false)) return rc;
         if (int rc = run_traced_chain<R>(c, r, cnc, pp, dc_coeff<R>(reo), &nrows, &done)) return rc;
@@ -649,7 +714,7 @@ static int run_traced(pnp_ctx* c, const char* who, int iters, bool cnc, const Pr
         const TraceLeg leg = trace_leg(iters, every, k);
         if (leg.pre > 0) if (int rc = run_loop<R>(c, leg.pre, cnc, pp, reo)) return rc;
         // z of iteration leg.iter - 1, in the order the coming launch leaves z in
-        const bool sliced = loop_path(c) == Path::slice;
+        const bool sliced = path == Path::slice;
         if (int rc = state_order<R>(c, sliced)) return rc;
         if constexpr (std::is_same_v<R, float>) {
             if (sliced) HIPCHK(slice256_trace_snapshot(c->eng.slice, c->stream, b.z, B));
@@ -711,6 +776,7 @@ static int residuals_any(pnp_ctx* c, const char* who, const R* x, const R* z, co
 
 // What the next loop call runs (pnp_get_plan): the plans the engines themselves run by (loop_schedule.h).
 static LoopPlan loop_plan(const pnp_ctx* c) {
+    if (c->wavelet != WV_NONE) return {1, c->B, 5, false, 1, c->B};   // the data-consistency step (three launches on every path) + two prox launches
     switch (loop_path(c)) {
     case Path::generic: break;
     case Path::slice:   return plan_slice(c->B, c->sched);         // one launch per RUN: the iterations are a loop inside it
@@ -919,7 +985,7 @@ int pnp_ctx_destroy(pnp_ctx* c) {
     slice256_destroy(c->eng.slice);
     anysize_destroy(c->any);
     void* ptrs[] = {c->y, c->work, c->z, c->w, c->x, c->mask_bank, c->mask_id, c->gt, c->acc, c->stage, c->ssim_part,
-                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc};
+                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc, c->wv_coef};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1048,21 +1114,17 @@ int pnp_dc_step(pnp_ctx* c, const float* z, const float* w, float* x, double reo
     Range r("pnp_dc_step");
     if (!z || !w || !x) return fail(PNP_E_ARG, "pnp_dc_step: null pointer");
     if (!(reo > 0.0)) return fail(PNP_E_ARG, "pnp_dc_step: reo must be > 0");
-    const float cdc = dc_coeff<float>(reo);
-    switch (loop_path(c)) {
-    case Path::generic:
-        return generic_iteration<float>(c, z, w, EPI_ABS_REAL, ProxParams{}, cdc, x, nullptr, nullptr);
-    case Path::slice:                                  // no single-step form: the step runs on the engine's own tables
-    case Path::fused:
-        break;
-    }
-    if (int rc = ensure_tables(c, Path::fused)) return rc;
-    switch (c->eng.kind) {
-    case Engine::fused256:  HIPCHK(fused256_dc(c->eng.f256, c->stream, z, w, x, c->B, cdc)); break;
-    case Engine::split_f32: HIPCHK(fused256s_dc<float>(c->eng.s32, c->stream, z, w, x, c->B, cdc)); break;
-    case Engine::fused512:  HIPCHK(fused512_dc(c->eng.f512, c->stream, z, w, x, c->B, cdc)); break;
-    case Engine::none: case Engine::split_f64: break;         // no fast path; a double context
-    }
+    return dc_any<float>(c, z, w, x, dc_coeff<float>(reo));
+}
+
+// the step-wise prox with a wavelet set: the two launches of kernels_wavelet.hip on caller pointers
+static int wavelet_prox_dual(pnp_ctx* c, const char* who, bool cnc, const float* x, float* z, float* w, const ProxParams& p) {
+    const size_t bytes = (size_t)c->B * c->N * sizeof(float);
+    const char *px = (const char*)x, *pz = (const char*)z, *pw = (const char*)w;
+    if ((px < pz + bytes && pz < px + bytes) || (px < pw + bytes && pw < px + bytes) || (pz < pw + bytes && pw < pz + bytes))
+        return fail(PNP_E_ARG, "%s: x, z and w must not overlap with a wavelet set (tiles read their neighbours' halo)", who);
+    if (int rc = wavelet_scratch(c)) return rc;
+    HIPCHK(launch_wavelet_prox<float>(c->stream, c->wavelet, c->wv_levels, cnc, x, z, w, (float*)c->wv_coef, p, c->B, c->H, c->W));
     return PNP_OK;
 }
 
@@ -1071,6 +1133,7 @@ int pnp_prox_l1_dual(pnp_ctx* c, const float* x, float* z, float* w, double thr)
     if (!x || !z || !w) return fail(PNP_E_ARG, "pnp_prox_l1_dual: null pointer");
     if (!(thr >= 0.0)) return fail(PNP_E_ARG, "pnp_prox_l1_dual: thr must be >= 0");
     ProxParams p{}; p.thr = (float)thr;
+    if (c->wavelet != WV_NONE) return wavelet_prox_dual(c, __func__, false, x, z, w, p);
     HIPCHK(launch_prox(c->stream, false, x, z, w, p, (size_t)c->B * c->N));
     return PNP_OK;
 }
@@ -1080,6 +1143,7 @@ int pnp_prox_cnc_dual(pnp_ctx* c, const float* x, float* z, float* w, double alp
     if (!x || !z || !w) return fail(PNP_E_ARG, "pnp_prox_cnc_dual: null pointer");
     if (!(b > 0.0)) return fail(PNP_E_ARG, "pnp_prox_cnc_dual: b must be > 0");
     if (int rv = check_thresholds("pnp_prox_cnc_dual", alpha, lambda1, reo)) return rv;
+    if (c->wavelet != WV_NONE) return wavelet_prox_dual(c, __func__, true, x, z, w, prox_cnc<float>(alpha, lambda1, reo, b));
     HIPCHK(launch_prox(c->stream, true, x, z, w, prox_cnc<float>(alpha, lambda1, reo, b), (size_t)c->B * c->N));
     return PNP_OK;
 }
@@ -1435,10 +1499,44 @@ const char* pnp_path_name(pnp_ctx* c) {
     if (!c) return "generic";
     switch (loop_path(c)) {
     case Path::generic: return "generic";
-    case Path::slice:   return "slice";
+    case Path::slice:   return c->wavelet != WV_NONE ? "fused" : "slice";      // with a wavelet set the loops never run slice-resident
     case Path::fused:   return "fused";
     }
     return "generic";
 }
+
+int pnp_sparsity_check(int wavelet, int levels, int H, int W) {
+    if (wavelet == PNP_WAVELET_NONE) return PNP_OK;
+    switch (wv_check(wavelet, levels, H, W)) {
+    case WV_OK:          return PNP_OK;
+    case WV_BAD_NAME:    return fail(PNP_E_ARG, "sparsity: wavelet must be PNP_WAVELET_NONE, _HAAR, _DB2 or _DB4 (got %d)", wavelet);
+    case WV_BAD_LEVELS:  return fail(PNP_E_ARG, "sparsity: levels must be 1..%d (got %d)", WV_MAX_LEVELS, levels);
+    case WV_BAD_DIVISOR: return fail(PNP_E_ARG, "sparsity: H and W must be divisible by 2^levels = %d (got %d x %d)", 1 << levels, H, W);
+    default:             return fail(PNP_E_ARG, "sparsity: the input of level %d is %d samples, shorter than the filter (%d taps)", levels,
+                                     (H < W ? H : W) >> (levels - 1), wv_taps(wavelet));
+    }
+}
+
+int pnp_set_sparsity(pnp_ctx* c, int wavelet, int levels) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
+    if (int rc = pnp_sparsity_check(wavelet, levels, c->H, c->W)) return rc;         // before any device work
+    CTX(c);
+    if (wavelet != PNP_WAVELET_NONE) if (int rc = wavelet_scratch(c)) return rc;
+    c->wavelet = wavelet;
+    c->wv_levels = wavelet == PNP_WAVELET_NONE ? 0 : levels;
+    return PNP_OK;
+}
+
+int pnp_get_sparsity(pnp_ctx* c, int* wavelet, int* levels) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
+    if (wavelet) *wavelet = c->wavelet;
+    if (levels) *levels = c->wv_levels;
+    return PNP_OK;
+}
+
+int pnp_dwt2_fwd(pnp_ctx* c, const float* in, float* out, int B) { CTX(c); F32_ONLY(c); return dwt2_any<float>(c, __func__, in, out, B, false); }
+int pnp_dwt2_inv(pnp_ctx* c, const float* in, float* out, int B) { CTX(c); F32_ONLY(c); return dwt2_any<float>(c, __func__, in, out, B, true); }
+int pnp_dwt2_fwd_f64(pnp_ctx* c, const double* in, double* out, int B) { CTX(c); F64_ONLY(c); return dwt2_any<double>(c, __func__, in, out, B, false); }
+int pnp_dwt2_inv_f64(pnp_ctx* c, const double* in, double* out, int B) { CTX(c); F64_ONLY(c); return dwt2_any<double>(c, __func__, in, out, B, true); }
 
 }  // extern "C"

@@ -83,6 +83,12 @@ template <typename R>
 hipError_t launch_residuals(hipStream_t s, const R* x, const R* z, const R* zp, const R* w, const uint8_t* gt, int quantise, int B, size_t N,
                             size_t state_stride, bool slice_order, double* partial, unsigned* counter, double* out);
 
+// wavelet-domain sparsity (kernels_wavelet.hip, wavelet_plan.h): Psi / Psi^T of B slices [H][W] (in != out: tiles read their neighbours'
+// halo), and the prox step z+ = Psi^T thresholded(Psi ...), w+ = (x + w) - z+ in place, through `coef`, scratch of B H W values
+template <typename R> hipError_t launch_dwt2(hipStream_t s, int wavelet, int levels, bool inv, const R* in, R* out, int B, int H, int W);
+template <typename R> hipError_t launch_wavelet_prox(hipStream_t s, int wavelet, int levels, bool cnc, const R* x, R* z, R* w, R* coef,
+                                                     const ProxParamsT<R>& p, int B, int H, int W);
+
 // calibration (pnp_calibrate_stream): the slice-resident loop's access shape without its arithmetic, `passes` passes over `slices` slices of 256 KiB
 hipError_t launch_calibrate_stream(hipStream_t s, float* z, float* w, const float* y, int slices, int passes);
 // optional HIP backend of the denoisers' 64-channel conv3x3 body layers (kernels_conv.hip); activations NHWC float32

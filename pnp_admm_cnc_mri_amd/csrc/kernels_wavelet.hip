@@ -1,0 +1,188 @@
+// Wavelet-domain sparsity: Psi = orthonormal periodic 2-D DWT (wavelet_plan.h), prox of thr ||Psi z||_1 = Psi^T soft(Psi v, thr) in closed
+// form, and the CNC pair of thresholds coefficient-wise.  Two launches per prox, both tiled through LDS:
+//   k_wv_fwd  analysis + threshold: a workgroup stages nothing but what a level hands to the next -- level 0's row pass reads the image
+//             (x + w formed on the way in) with periodic wrap, all L levels run in LDS, the coefficients leave thresholded, in Mallat
+//             layout, for the context's scratch.  CNC: z goes through first and its raw coefficients wait in the scratch; x + w follows
+//             through the same LDS, and the thread that wrote a coefficient of z combines it with that of x + w (same item -> same thread).
+//   k_wv_inv  synthesis + dual: reads the coefficient tile with its left / top halo, undoes all levels in LDS, writes z+ and
+//             w+ = (x + w) - z+ in place.
+// The work of every pass is wavelet_plan.h's item functions, one item per thread and step; tests/host/wavelet_emulation.cpp runs the
+// same functions on the host.  -ffp-contract=off (Makefile); products are chained by explicit fma.
+#include "internal.h"
+#include "prox_ops.h"
+#include "wavelet_plan.h"
+
+namespace pnp {
+
+namespace {
+
+template <typename R>
+struct WvArgs {
+    const R* in0;      // fwd: image (NONE), x (L1, CNC);   inv: coefficients
+    const R* in1;      // fwd: null (NONE), w
+    const R* zin;      // fwd CNC: z
+    R* out;            // fwd: coefficients;   inv NONE: image
+    const R* x;        // inv with dual: x, w (read), z, w (written)
+    R *z, *w;
+    ProxParamsT<R> p;
+    int H, W, L, tile, tiles_x, tiles_y;
+};
+
+template <typename R> __device__ __forceinline__ WvTile wv_tile_of_block(const WvArgs<R>& a) {
+    const int per = a.tiles_x * a.tiles_y, b = blockIdx.x / per, rem = blockIdx.x - b * per, ty = rem / a.tiles_x, tx = rem - ty * a.tiles_x;
+    return WvTile{a.H, a.W, a.L, a.tile, ty * a.tile, tx * a.tile, (size_t)b * a.H * a.W};
+}
+
+// what happens to a coefficient on its way out
+template <typename R> struct EmitStore {            // Psi alone; CNC: the raw coefficients of z
+    R* c;
+    __device__ void operator()(size_t o, R v, bool) const { c[o] = v; }
+};
+template <typename R> struct EmitL1 {
+    R* c; R thr;
+    __device__ void operator()(size_t o, R v, bool detail) const { c[o] = detail ? soft(v, thr) : v; }
+};
+template <typename R> struct EmitCnc {              // v = coefficient of x + w; c[o] = that of z, written by this thread
+    R* c; ProxParamsT<R> p;
+    __device__ void operator()(size_t o, R v, bool detail) const {
+        const R cz = c[o];
+        if (detail) {
+            const R clipz = cz < -p.ib ? -p.ib : (cz > p.ib ? p.ib : cz);
+            c[o] = soft(fma_r(p.c1, cz, fma_r(p.c2, v, p.c3 * clipz)), p.thr);
+        } else {
+            c[o] = fma_r(p.c1, cz, p.c2 * v);
+        }
+    }
+};
+
+template <typename R, int T, typename Emit>
+__device__ __forceinline__ void wv_fwd_image(const WvTile& t, const R* in0, const R* in1, R* rowbuf, R* ll, Emit emit) {
+    for (int l = 0; l < t.L; ++l) {
+        for (int it = threadIdx.x, n = wv_fwd_row_items(T, t, l); it < n; it += WV_THREADS) wv_fwd_row_item<R, T>(it, l, t, in0, in1, ll, rowbuf);
+        __syncthreads();
+        for (int it = threadIdx.x, n = wv_fwd_col_items(T, t, l); it < n; it += WV_THREADS) wv_fwd_col_item<R, T>(it, l, t, rowbuf, ll, emit);
+        __syncthreads();
+    }
+}
+
+// PROX: 0 none, 1 L1, 2 CNC
+template <typename R, int PROX, int T>
+__global__ __launch_bounds__(WV_THREADS) void k_wv_fwd(const WvArgs<R> a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char wv_smem[];
+    const WvTile t = wv_tile_of_block(a);
+    R* rowbuf = (R*)wv_smem;
+    R* ll = rowbuf + wv_fwd_rowbuf_elems(T, a.L, a.tile);
+    if constexpr (PROX == 0) wv_fwd_image<R, T>(t, a.in0, a.in1, rowbuf, ll, EmitStore<R>{a.out});
+    if constexpr (PROX == 1) wv_fwd_image<R, T>(t, a.in0, a.in1, rowbuf, ll, EmitL1<R>{a.out, a.p.thr});
+    if constexpr (PROX == 2) {
+        wv_fwd_image<R, T>(t, a.zin, (const R*)nullptr, rowbuf, ll, EmitStore<R>{a.out});
+        wv_fwd_image<R, T>(t, a.in0, a.in1, rowbuf, ll, EmitCnc<R>{a.out, a.p});
+    }
+}
+
+template <typename R> struct EmitImage {
+    R* o;
+    __device__ void operator()(size_t i, R v) const { o[i] = v; }
+};
+template <typename R> struct EmitDual {             // z+ = v, w+ = (x + w) - z+
+    const R* x; R *z, *w;
+    __device__ void operator()(size_t i, R v) const {
+        const R u = x[i] + w[i];
+        z[i] = v;
+        w[i] = u - v;
+    }
+};
+
+template <typename R, bool DUAL, int T>
+__global__ __launch_bounds__(WV_THREADS) void k_wv_inv(const WvArgs<R> a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char wv_smem[];
+    const WvTile t = wv_tile_of_block(a);
+    R* colbuf = (R*)wv_smem;
+    R* ll = colbuf + wv_inv_colbuf_elems(T, a.tile);
+    for (int l = a.L - 1; l >= 0; --l) {
+        for (int it = threadIdx.x, n = wv_inv_col_items(T, t, l); it < n; it += WV_THREADS) wv_inv_col_item<R, T>(it, l, t, a.in0, ll, colbuf);
+        __syncthreads();
+        for (int it = threadIdx.x, n = wv_inv_row_items(T, t, l); it < n; it += WV_THREADS) {
+            if constexpr (DUAL) wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitDual<R>{a.x, a.z, a.w});
+            else wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitImage<R>{a.out});
+        }
+        __syncthreads();
+    }
+}
+
+// >64 KiB dynamic LDS needs the opt-in once per kernel and device
+template <typename K, typename A> hipError_t wv_launch(K kernel, hipStream_t s, int blocks, size_t lds, bool* attr_done, const A& a) {
+    if (lds > WV_LDS_MAX) return hipErrorInvalidValue;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (!attr_done[dev]) {
+        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WV_LDS_MAX);
+        if (e != hipSuccess) return e;
+        attr_done[dev] = true;
+    }
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(WV_THREADS), lds, s, a);
+    return hipGetLastError();
+}
+
+template <typename R, int PROX, int T> hipError_t wv_fwd_t(hipStream_t s, const WvArgs<R>& a, int B) {
+    static bool attr_done[64] = {};
+    return wv_launch(k_wv_fwd<R, PROX, T>, s, B * a.tiles_x * a.tiles_y, wv_fwd_lds_elems(T, a.L, a.tile) * sizeof(R), attr_done, a);
+}
+template <typename R, bool DUAL, int T> hipError_t wv_inv_t(hipStream_t s, const WvArgs<R>& a, int B) {
+    static bool attr_done[64] = {};
+    return wv_launch(k_wv_inv<R, DUAL, T>, s, B * a.tiles_x * a.tiles_y, wv_inv_lds_elems(T, a.tile) * sizeof(R), attr_done, a);
+}
+
+template <typename R> WvArgs<R> wv_args(int wavelet, int levels, int H, int W) {
+    WvArgs<R> a{};
+    const int T = wv_taps(wavelet);
+    a.H = H; a.W = W; a.L = levels; a.tile = wv_tile(T, levels);
+    a.tiles_x = wv_tiles(W, a.tile); a.tiles_y = wv_tiles(H, a.tile);
+    return a;
+}
+
+template <typename R, int PROX> hipError_t wv_fwd_p(hipStream_t s, int wavelet, const WvArgs<R>& a, int B) {
+    switch (wavelet) {
+    case WV_HAAR: return wv_fwd_t<R, PROX, 2>(s, a, B);
+    case WV_DB2:  return wv_fwd_t<R, PROX, 4>(s, a, B);
+    case WV_DB4:  return wv_fwd_t<R, PROX, 8>(s, a, B);
+    }
+    return hipErrorInvalidValue;
+}
+template <typename R, bool DUAL> hipError_t wv_inv_p(hipStream_t s, int wavelet, const WvArgs<R>& a, int B) {
+    switch (wavelet) {
+    case WV_HAAR: return wv_inv_t<R, DUAL, 2>(s, a, B);
+    case WV_DB2:  return wv_inv_t<R, DUAL, 4>(s, a, B);
+    case WV_DB4:  return wv_inv_t<R, DUAL, 8>(s, a, B);
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+template <typename R>
+hipError_t launch_dwt2(hipStream_t s, int wavelet, int levels, bool inv, const R* in, R* out, int B, int H, int W) {
+    if (wv_check(wavelet, levels, H, W) != WV_OK || B < 1) return hipErrorInvalidValue;
+    WvArgs<R> a = wv_args<R>(wavelet, levels, H, W);
+    a.in0 = in; a.out = out;
+    return inv ? wv_inv_p<R, false>(s, wavelet, a, B) : wv_fwd_p<R, 0>(s, wavelet, a, B);
+}
+
+template <typename R>
+hipError_t launch_wavelet_prox(hipStream_t s, int wavelet, int levels, bool cnc, const R* x, R* z, R* w, R* coef, const ProxParamsT<R>& p,
+                               int B, int H, int W) {
+    if (wv_check(wavelet, levels, H, W) != WV_OK || B < 1) return hipErrorInvalidValue;
+    WvArgs<R> a = wv_args<R>(wavelet, levels, H, W);
+    a.in0 = x; a.in1 = w; a.zin = z; a.out = coef; a.p = p;
+    hipError_t e = cnc ? wv_fwd_p<R, 2>(s, wavelet, a, B) : wv_fwd_p<R, 1>(s, wavelet, a, B);
+    if (e != hipSuccess) return e;
+    a.in0 = coef; a.in1 = nullptr; a.zin = nullptr; a.out = nullptr; a.x = x; a.z = z; a.w = w;
+    return wv_inv_p<R, true>(s, wavelet, a, B);
+}
+
+template hipError_t launch_dwt2<float>(hipStream_t, int, int, bool, const float*, float*, int, int, int);
+template hipError_t launch_dwt2<double>(hipStream_t, int, int, bool, const double*, double*, int, int, int);
+template hipError_t launch_wavelet_prox<float>(hipStream_t, int, int, bool, const float*, float*, float*, float*, const ProxParamsT<float>&, int, int, int);
+template hipError_t launch_wavelet_prox<double>(hipStream_t, int, int, bool, const double*, double*, double*, double*, const ProxParamsT<double>&, int, int, int);
+
+}  // namespace pnp

@@ -27,6 +27,23 @@ def _host(a, dtype):
     return a
 
 
+WAVELETS = {None: 0, 'haar': 1, 'db2': 2, 'db4': 3}                                    # PNP_WAVELET_* of include/pnp_mri.h
+
+
+def check_sparsity(wavelet, levels, H, W):
+    """ValueError unless (wavelet, levels) is a valid sparsity setting for H x W slices (pnp_sparsity_check: the library's own rule,
+    no context and no device needed).  -> the PNP_WAVELET_* code."""
+    if wavelet not in WAVELETS:
+        raise ValueError("transform must be one of None, 'haar', 'db2', 'db4' (got %r)" % (wavelet,))
+    if wavelet is not None:
+        if int(levels) != levels:
+            raise ValueError('levels must be an integer (got %r)' % (levels,))
+        L = _lib.lib()
+        if L.pnp_sparsity_check(WAVELETS[wavelet], int(levels), int(H), int(W)) != 0:
+            raise ValueError(L.pnp_last_error().decode('utf-8', 'replace'))
+    return WAVELETS[wavelet]
+
+
 TRACE_FIELDS = ('r_pri', 'r_dual', 'x_norm', 'z_norm', 'w_norm', 'psnr', 're')      # PNP_TRACE_* of include/pnp_mri.h, in order
 
 
@@ -104,6 +121,19 @@ class Engine:
         q, m, ch = C.c_int(0), C.c_int(0), C.c_int(0)
         _lib.check(self._L.pnp_get_schedule(self._ctx, C.byref(q), C.byref(m), C.byref(ch)))
         return {'queues': q.value, 'mixed': m.value, 'chunk': ch.value}
+
+    def set_sparsity(self, wavelet=None, levels=3):
+        """The penalty of admm_l1 / admm_cnc / prox_*_dual on the coefficients of the periodic 2-D DWT `wavelet` ('haar', 'db2',
+        'db4') with `levels` levels instead of the pixels; None: the pixels, as ever (pnp_set_sparsity)."""
+        code = check_sparsity(wavelet, levels, self.H, self.W)
+        _lib.check(self._L.pnp_set_sparsity(self._ctx, code, int(levels) if wavelet is not None else 0))
+
+    @property
+    def sparsity(self):
+        """(wavelet, levels) of set_sparsity; (None, 0) without one."""
+        wv, lv = C.c_int(0), C.c_int(0)
+        _lib.check(self._L.pnp_get_sparsity(self._ctx, C.byref(wv), C.byref(lv)))
+        return {v: k for k, v in WAVELETS.items()}[wv.value], lv.value
 
     @property
     def plan(self):
@@ -314,6 +344,16 @@ class Engine:
 
     def ifft2(self, inp, out, B):
         _lib.check(self._L.pnp_fft2_inv(self._ctx, _ptr(inp), _ptr(out), int(B)))
+
+    def dwt2(self, inp, out, B):
+        """Psi of B real slices with the engine's sparsity setting (pnp_dwt2_fwd; device tensors of the engine's precision; inp may be out)."""
+        fn = self._L.pnp_dwt2_fwd_f64 if self.f64 else self._L.pnp_dwt2_fwd
+        _lib.check(fn(self._ctx, _ptr(inp), _ptr(out), int(B)))
+
+    def idwt2(self, inp, out, B):
+        """Psi^T (pnp_dwt2_inv)."""
+        fn = self._L.pnp_dwt2_inv_f64 if self.f64 else self._L.pnp_dwt2_inv
+        _lib.check(fn(self._ctx, _ptr(inp), _ptr(out), int(B)))
 
     def A(self, x, k):
         _lib.check(self._L.pnp_A(self._ctx, _ptr(x), _ptr(k)))

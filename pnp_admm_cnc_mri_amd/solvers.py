@@ -27,6 +27,11 @@ bypass the file system through the extra keyword arguments
               (Engine._traced has the fields); tol: the run stops after the first check at which every slice has
               max(r_pri, r_dual) <= tol * ||z|| (tol alone: a check every iteration) -- out, metrics, PNGs and log lines are then
               those of iteration trace['iters_done'], and one more log line says so.  Both off: nothing changes
+    transform=None, levels=3   (ADMM_L1 and ADMM_CNC only) 'haar', 'db2' or 'db4': the sparsity penalty acts on the coefficients of that
+              periodic 2-D DWT with `levels` levels (1..4; H and W divisible by 2^levels) instead of the pixels -- the prox becomes
+              Psi^T soft(Psi v), the CNC pair of thresholds is applied coefficient-wise, the coarsest approximation band is never
+              thresholded (include/pnp_mri.h, "wavelet-domain sparsity").  NOT in the reference scripts, whose prox acts on the pixels;
+              None (the default) is bit for bit what it was.  One extra log line names the transform
 
 The PnP entry points (PNP_ADMM_L1_D, PNP_ADMM_CNC_D, PNP_ADMM_CNC_DnCNN) live in solvers_pnp.py.
 """
@@ -37,7 +42,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import imageio
-from .engine import Engine
+from .engine import Engine, check_sparsity
 
 # CLI presets of the reference scripts (positional order differs per script!)
 PRESETS = {
@@ -146,10 +151,16 @@ class _Job:
             self.log.info(os.path.join(testsets, testset_name))
         self.testset_name = testset_name
 
-    def open_engine(self, stream=None):
+    def open_engine(self, stream=None, transform=None, levels=3):
         """stream: HIP stream handle every engine call is ordered on (PnP: torch's current stream),
-        set BEFORE the first kernel so upload / synthesis / init and the loop share one queue."""
+        set BEFORE the first kernel so upload / synthesis / init and the loop share one queue.
+        transform / levels: Engine.set_sparsity (ADMM_L1 / ADMM_CNC)."""
         eng = Engine(self.H, self.W, Bmax=self.B, device=self.device, precision=self.precision)
+        if transform is not None:
+            eng.set_sparsity(transform, levels)
+            if self.log is not None:
+                self.log.info('sparsity transform: {:s}, {:d} levels (periodic 2-D DWT; not in the reference scripts)'.format(
+                    transform, int(levels)))
         if stream is not None:
             eng.set_stream(stream)
         if self.y is not None:
@@ -227,15 +238,16 @@ def _device_x(eng, job):
 
 def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
             results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
-            **ADMM_L1_opts):
+            transform=None, levels=3, **ADMM_L1_opts):
     """ADMM with L1 prox on the MI355X engine.  Reference: "【1】ADMM_L1.py":29-169."""
     iter_num = ADMM_L1_opts.get('iter_num', 20)          # S1:35
     lambda1 = ADMM_L1_opts.get('lambda1', 0.04)          # S1:36
     reo = ADMM_L1_opts.get('reo', 0.04)                  # S1:37
     traced = trace_request(trace_every, tol, return_info)
+    check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
     job = _Job(mask, noises, 'ADMM_L1', '_PDG L1', images, y, mask_id, testsets, testset_name, results, save_E, device,
                psnr_fmt='{:.2f}', precision=precision)   # S1:150
-    with job.open_engine() as eng:
+    with job.open_engine(transform=transform, levels=levels) as eng:
         # S1:111-126, all slices, on device
         trace = eng.admm_l1(iter_num, lambda1, reo, trace_every, tol, job.gt_u8) if traced else eng.admm_l1(iter_num, lambda1, reo)
         log_early_stop(job, trace, iter_num, tol)
@@ -248,7 +260,7 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
 
 def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
              results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
-             **ADMM_CNC_opts):
+             transform=None, levels=3, **ADMM_CNC_opts):
     """ADMM with the convex-non-convex z-step.  Reference: "【4】ADMM_CNC .py":31-174."""
     iter_num = ADMM_CNC_opts.get('iter_num', 4)          # S4:37
     alpha = ADMM_CNC_opts.get('alpha', 0.4)              # S4:38
@@ -256,9 +268,10 @@ def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets
     reo = ADMM_CNC_opts.get('reo', 2.75)                 # S4:40  (reo is 1/beta of the paper)
     b = ADMM_CNC_opts.get('b', 1)                        # S4:41  (b is b^2 of the paper)
     traced = trace_request(trace_every, tol, return_info)
+    check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
     job = _Job(mask, noises, 'ADMM_CNC', '_ADMM CNC', images, y, mask_id, testsets, testset_name, results, save_E, device,
                precision=precision)
-    with job.open_engine() as eng:
+    with job.open_engine(transform=transform, levels=levels) as eng:
         # S4:115-132
         trace = (eng.admm_cnc(iter_num, alpha, lambda1, reo, b, trace_every, tol, job.gt_u8) if traced
                  else eng.admm_cnc(iter_num, alpha, lambda1, reo, b))

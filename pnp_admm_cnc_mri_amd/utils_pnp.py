@@ -59,6 +59,25 @@ def ifft2(eng, k):
     return out
 
 
+def dwt2(eng, x):
+    """Psi x: the periodic 2-D DWT of the engine's sparsity setting (Engine.set_sparsity) of a real batch [B,H,W], Mallat layout.
+    No counterpart in the reference."""
+    torch = _torch()
+    x = _prep(eng, x.to(torch.float64 if eng.f64 else torch.float32))
+    out = torch.empty_like(x)
+    eng.dwt2(x, out, x.shape[0])
+    return out
+
+
+def idwt2(eng, c):
+    """Psi^T c, the inverse of dwt2."""
+    torch = _torch()
+    c = _prep(eng, c.to(torch.float64 if eng.f64 else torch.float32))
+    out = torch.empty_like(c)
+    eng.idwt2(c, out, c.shape[0])
+    return out
+
+
 def A(eng, x):
     """A x = fft2(x) * mask for real x [B,H,W] with the engine's uploaded masks (S4:102)."""
     torch = _torch()

@@ -307,7 +307,13 @@ int pnp_dwt2_inv_f64(pnp_ctx* ctx, const double* in_dev, double* out_dev, int B)
  *   d = 1 the plain stacks and DRUNet, d = 2..4 IRCNN's dilated layers, models/network_dncnn.py:87-101)
  *   x, y, skip: [n][H][W][64] float32 (NHWC); w_packed: 36 864 floats written by pnp_conv3x3_c64_pack (the kernel streams
  *   its weights from L2 in matrix-core fragment order); bias [64] or NULL; skip NULL or a tensor of y's shape added before the
- *   ReLU; y must alias neither x nor skip.  New in ABI 8. */
+ *   ReLU; y must alias neither x nor skip.  New in ABI 8.
+ * Size rule of EVERY conv-layer entry point of this header (float32, f16x3 and half alike; csrc/conv_plan.h): one image with 16 more rows
+ * must stay below 2 GiB as a float32 tensor, (H + 16) W C 4 <= 2^31 - 1 (C = 64 for the first / last layers; the 2 x 2 layers: input and
+ * result both) -- the kernels let the byte offsets of halo and overhang rows fall out of the buffer's range, and those must not wrap
+ * around 2^32.  A larger image is PNP_E_ARG with a message that names the 16 rows.  (The float32 and f16x3 entry points used to bound
+ * H W C 4 only -- 2896 x 2896 at C = 64, now 2888 x 2888 -- and pnp_conv3x3_c64_nhwc, pnp_conv3x3_c64_nhwc_f16x3, pnp_conv3x3_head_nhwc,
+ * pnp_conv3x3_tail_nchw and pnp_conv3x3_tail_nchw_f16x3 reported an oversize image as PNP_E_HIP from the launch.) */
 int pnp_conv3x3_c64_nhwc(void* hip_stream, const float* x_dev, const float* w_packed_dev, const float* bias_dev,
                          const float* skip_dev, float* y_dev, int n, int H, int W, int relu, int dilation);
 /* w_oihw_dev: a torch.nn.Conv2d(64, 64, 3) weight, [64 out][64 in][3][3] contiguous -> w_packed_dev (36 864 floats).  Once
@@ -327,7 +333,8 @@ int pnp_conv3x3_c64_pack_f16x3(void* hip_stream, const float* w_oihw_dev, float*
  * models/network_unet.py:36-58 with models/basicblock.py:213-225): dilation 1, zero padding 1; x, y, skip [n][H][W][C] float32
  * (NHWC); w_packed: 9 C C floats of storage written by pnp_conv3x3_pack_f16x3 from a torch Conv2d(C, C, 3) weight; bias [C] or
  * NULL.  A workgroup computes 8 x 16 pixels x 64 output channels, its K loop runs over the C / 64 chunks of input channels; one
- * image must stay below 2 GiB (H W C floats).  C = 64 is the layer above (same packing).  New in ABI 9. */
+ * image with 16 more rows must stay below 2 GiB ((H + 16) W C floats: the size rule above).  C = 64 is the layer above (same packing).
+ * New in ABI 9. */
 int pnp_conv3x3_nhwc_f16x3(void* hip_stream, const float* x_dev, const float* w_packed_dev, const float* bias_dev,
                            const float* skip_dev, float* y_dev, int n, int C, int H, int W, int relu);
 int pnp_conv3x3_pack_f16x3(void* hip_stream, const float* w_oihw_dev, float* w_packed_dev, int C);
@@ -345,12 +352,12 @@ int pnp_conv3x3_nhwc_f16x3_fmt(void* hip_stream, const float* x_dev, const float
                                const float* skip_dev, float* y_dev, int n, int C, int H, int W, int relu, int dilation, int fmt);
 /* Which kernel the three f16x3 conv3x3 entry points above launch at dilation 1 (the results are bit-equal; tests and A/B measurements pin
  * one): -1 = by size (default: the WIDE kernel -- 16 x 16 pixel tiles, 64 x 64 wave tiles, compute + helper waves, kernels_conv_f16x3_wide.hip --
- * once every compute unit has two items of its own, the narrow one -- 8 x 16 tiles, two workgroups per unit -- below that), 0 = narrow always,
+ * once every compute unit has an item (16 x 16 pixels x 64 output channels) of its own, the narrow one -- 8 x 16 tiles, two workgroups per unit -- below that), 0 = narrow always,
  * 1 = wide always.  Process-wide; returns the previous setting.  The environment variable PNP_CONV_WIDE sets the initial value.  New in ABI 11. */
 int pnp_conv3x3_f16x3_set_variant(int variant);
 /* pnp_conv3x3_tail_nchw (below) in the f16x3 arithmetic: x [n][H][W][64] (NHWC), w a torch Conv2d(64, cout, 3) weight (split inside the
  * kernel), 1 <= cout <= 4 -> y [n][cout][H][W] (NCHW), + bias.  On the vector units this layer costs as much as a 64 -> 64 layer of the
- * f16x3 kernel; as a 16-column matrix product it is bound by reading its input.  Same operand range as above.  New in ABI 9. */
+ * f16x3 kernel; as a 16-column matrix product it is bound by reading its input.  Same operand range and size rule as above.  New in ABI 9. */
 int pnp_conv3x3_tail_nchw_f16x3(void* hip_stream, const float* x_nhwc_dev, const float* w_oihw_dev, const float* bias_dev,
                                 float* y_nchw_dev, int n, int cout, int H, int W);
 /* The same with a second input ADDED to x while it is staged (the U-Net's last skip sum, models/network_unet.py:134-135: the sum never
@@ -372,7 +379,8 @@ int pnp_conv2x2_pack_f16x3(void* hip_stream, const float* w_dev, float* w_packed
 /* First and last layer of the plain stacks (models/network_dncnn.py:52-62, models/network_ffdnet.py:50-56), direct convolutions:
  *   head: x [n][cin][H][W] (NCHW, 1 <= cin <= 8), w a torch Conv2d(cin, 64, 3) weight [64][cin][3][3] -> y [n][H][W][64] (NHWC), + bias, ReLU
  *   tail: x [n][H][W][64] (NHWC), w a torch Conv2d(64, cout, 3) weight [cout][64][3][3], 1 <= cout <= 4 -> y [n][cout][H][W] (NCHW), + bias
- * With them `Denoiser(backend='hip')` runs DnCNN / FDnCNN / FFDNet without a MIOpen call.  New in ABI 8. */
+ * With them `Denoiser(backend='hip')` runs DnCNN / FDnCNN / FFDNet without a MIOpen call.  The size rule above applies with C = 64.
+ * New in ABI 8. */
 int pnp_conv3x3_head_nhwc(void* hip_stream, const float* x_nchw_dev, const float* w_oihw_dev, const float* bias_dev,
                           float* y_nhwc_dev, int n, int cin, int H, int W, int relu);
 int pnp_conv3x3_tail_nchw(void* hip_stream, const float* x_nhwc_dev, const float* w_oihw_dev, const float* bias_dev,

@@ -1,5 +1,5 @@
 // C ABI of libpnpmri.so (include/pnp_mri.h): context, problem upload, whole ADMM loops, step-wise
-// operators, the denoisers' conv layers.  Host-side only; the kernels live in the kernels_*.hip files.
+// operators.  (The denoisers' conv layers: api_conv.hip.)  Host-side only; the kernels live in the kernels_*.hip files.
 #include "../../include/pnp_mri.h"
 #include "internal.h"
 #include "wavelet_plan.h"
@@ -18,20 +18,13 @@ using namespace pnp;
 
 static thread_local char g_err[512] = "";
 
-static int fail(int code, const char* fmt, ...) {
+int pnp::fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
 }
-
-#define HIPCHK(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess)                                                                      \
-            return fail(PNP_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
 
 // roctx ranges around the loops so that rocprofv3 --marker-trace output is self-describing.  The
 // marker library is looked up at run time (it is part of the ROCm image, not a link dependency);
@@ -1243,219 +1236,6 @@ int pnp_ssim_f64(pnp_ctx* c, const double* x, const uint8_t* gt, int gt_on_devic
 }
 
 int pnp_is_f64(pnp_ctx* c) { return (c && c->f64) ? 1 : 0; }
-
-/* ---- optional HIP backend of the denoisers' 64-channel body layers (no ctx: caller-owned device tensors) ---- */
-int pnp_conv3x3_c64_nhwc(void* stream, const float* x, const float* w, const float* bias, const float* skip, float* y,
-                         int n, int H, int W, int relu, int dilation) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "pnp_conv3x3_c64_nhwc: null pointer");
-    if (n < 1 || H < 1 || W < 1) return fail(PNP_E_ARG, "pnp_conv3x3_c64_nhwc: n, H, W must be >= 1");
-    if (x == y || skip == y) return fail(PNP_E_ARG, "pnp_conv3x3_c64_nhwc: y must not alias x or skip (tiles read their neighbours' halo)");
-    if (dilation < 1 || dilation > 4) return fail(PNP_E_ARG, "pnp_conv3x3_c64_nhwc: dilation must be 1..4 (got %d)", dilation);
-    HIPCHK(launch_conv3x3_c64((hipStream_t)stream, x, w, bias, skip, y, n, H, W, relu, dilation));
-    return PNP_OK;
-}
-int pnp_conv3x3_c64_pack(void* stream, const float* w_oihw, float* w_packed) {
-    if (!w_oihw || !w_packed || w_oihw == w_packed) return fail(PNP_E_ARG, "pnp_conv3x3_c64_pack: null or aliased pointers");
-    HIPCHK(launch_conv_pack_w((hipStream_t)stream, w_oihw, w_packed));
-    return PNP_OK;
-}
-int pnp_conv3x3_c64_nhwc_f16x3(void* stream, const float* x, const float* w, const float* bias, const float* skip, float* y,
-                               int n, int H, int W, int relu, int dilation) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "pnp_conv3x3_c64_nhwc_f16x3: null pointer");
-    if (n < 1 || H < 1 || W < 1) return fail(PNP_E_ARG, "pnp_conv3x3_c64_nhwc_f16x3: n, H, W must be >= 1");
-    if (x == y || skip == y) return fail(PNP_E_ARG, "pnp_conv3x3_c64_nhwc_f16x3: y must not alias x or skip (tiles read their neighbours' halo)");
-    if (dilation < 1 || dilation > 4) return fail(PNP_E_ARG, "pnp_conv3x3_c64_nhwc_f16x3: dilation must be 1..4 (got %d)", dilation);
-    HIPCHK(launch_conv3x3_f16x3((hipStream_t)stream, x, w, bias, skip, y, n, 64, H, W, relu, dilation));
-    return PNP_OK;
-}
-int pnp_conv3x3_nhwc_f16x3(void* stream, const float* x, const float* w, const float* bias, const float* skip, float* y,
-                           int n, int C, int H, int W, int relu) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16x3: null pointer");
-    if (n < 1 || H < 1 || W < 1) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16x3: n, H, W must be >= 1");
-    if (C < 64 || C > 1024 || C % 64) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16x3: C must be a multiple of 64 in 64..1024 (got %d)", C);
-    if ((long long)H * W * C * 4 > 0x7fffffffLL) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16x3: an image of %d x %d x %d floats exceeds 2 GiB", H, W, C);
-    if (x == y || skip == y) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16x3: y must not alias x or skip (tiles read their neighbours' halo)");
-    HIPCHK(launch_conv3x3_f16x3((hipStream_t)stream, x, w, bias, skip, y, n, C, H, W, relu, 1));
-    return PNP_OK;
-}
-int pnp_conv3x3_nhwc_f16x3_fmt(void* stream, const float* x, const float* w, const float* bias, const float* skip, float* y,
-                               int n, int C, int H, int W, int relu, int dilation, int fmt) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16x3_fmt: null pointer");
-    if (n < 1 || H < 1 || W < 1) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16x3_fmt: n, H, W must be >= 1");
-    if (C < 64 || C > 1024 || C % 64) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16x3_fmt: C must be a multiple of 64 in 64..1024 (got %d)", C);
-    if (dilation < 1 || dilation > 4 || (C != 64 && dilation != 1)) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16x3_fmt: dilation 1..4 at C = 64, 1 otherwise (got %d)", dilation);
-    if (fmt & ~7) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16x3_fmt: fmt is a mask of PNP_FMT_X_SPLIT | PNP_FMT_SKIP_SPLIT | PNP_FMT_Y_SPLIT (got %d)", fmt);
-    if ((long long)H * W * C * 4 > 0x7fffffffLL) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16x3_fmt: an image of %d x %d x %d floats exceeds 2 GiB", H, W, C);
-    if (x == y || skip == y) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16x3_fmt: y must not alias x or skip (tiles read their neighbours' halo)");
-    HIPCHK(launch_conv3x3_f16x3((hipStream_t)stream, x, w, bias, skip, y, n, C, H, W, relu, dilation, fmt));
-    return PNP_OK;
-}
-int pnp_conv3x3_f16x3_set_variant(int variant) { return conv_set_wide_mode(variant); }
-int pnp_conv3x3_pack_f16x3(void* stream, const float* w_oihw, float* w_packed, int C) {
-    if (!w_oihw || !w_packed || w_oihw == w_packed) return fail(PNP_E_ARG, "pnp_conv3x3_pack_f16x3: null or aliased pointers");
-    if (C < 64 || C > 1024 || C % 64) return fail(PNP_E_ARG, "pnp_conv3x3_pack_f16x3: C must be a multiple of 64 in 64..1024 (got %d)", C);
-    HIPCHK(launch_conv_pack_w_f16x3((hipStream_t)stream, w_oihw, w_packed, C));
-    return PNP_OK;
-}
-int pnp_conv3x3_c64_pack_f16x3(void* stream, const float* w_oihw, float* w_packed) {
-    if (!w_oihw || !w_packed || w_oihw == w_packed) return fail(PNP_E_ARG, "pnp_conv3x3_c64_pack_f16x3: null or aliased pointers");
-    HIPCHK(launch_conv_pack_w_f16x3((hipStream_t)stream, w_oihw, w_packed, 64));
-    return PNP_OK;
-}
-int pnp_conv3x3_head_nhwc(void* stream, const float* x, const float* w, const float* bias, float* y, int n, int cin, int H, int W, int relu) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "pnp_conv3x3_head_nhwc: null pointer");
-    if (n < 1 || H < 1 || W < 1 || cin < 1 || cin > 8) return fail(PNP_E_ARG, "pnp_conv3x3_head_nhwc: n, H, W >= 1 and 1 <= cin <= 8 required");
-    HIPCHK(launch_conv3x3_head((hipStream_t)stream, x, w, bias, y, n, cin, H, W, relu));
-    return PNP_OK;
-}
-int pnp_conv3x3_tail_nchw(void* stream, const float* x, const float* w, const float* bias, float* y, int n, int cout, int H, int W) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "pnp_conv3x3_tail_nchw: null pointer");
-    if (n < 1 || H < 1 || W < 1 || cout < 1 || cout > 4) return fail(PNP_E_ARG, "pnp_conv3x3_tail_nchw: n, H, W >= 1 and 1 <= cout <= 4 required");
-    HIPCHK(launch_conv3x3_tail((hipStream_t)stream, x, w, bias, y, n, cout, H, W));
-    return PNP_OK;
-}
-int pnp_conv3x3_tail_nchw_f16x3(void* stream, const float* x, const float* w, const float* bias, float* y, int n, int cout, int H, int W) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "pnp_conv3x3_tail_nchw_f16x3: null pointer");
-    if (n < 1 || H < 1 || W < 1 || cout < 1 || cout > 4) return fail(PNP_E_ARG, "pnp_conv3x3_tail_nchw_f16x3: n, H, W >= 1 and 1 <= cout <= 4 required");
-    HIPCHK(launch_conv3x3_tail_f16x3((hipStream_t)stream, x, nullptr, w, bias, y, n, cout, H, W));
-    return PNP_OK;
-}
-int pnp_conv3x3_tail_add_nchw_f16x3(void* stream, const float* x, const float* x2, const float* w, const float* bias, float* y, int n, int cout,
-                                    int H, int W) {
-    if (!x || !x2 || !w || !y) return fail(PNP_E_ARG, "pnp_conv3x3_tail_add_nchw_f16x3: null pointer");
-    if (n < 1 || H < 1 || W < 1 || cout < 1 || cout > 4) return fail(PNP_E_ARG, "pnp_conv3x3_tail_add_nchw_f16x3: n, H, W >= 1 and 1 <= cout <= 4 required");
-    if ((long long)H * W * 64 * 4 > 0x7fffffffLL) return fail(PNP_E_ARG, "pnp_conv3x3_tail_add_nchw_f16x3: an image of %d x %d x 64 floats exceeds 2 GiB", H, W);
-    if (x == y || x2 == y) return fail(PNP_E_ARG, "pnp_conv3x3_tail_add_nchw_f16x3: y must not alias x or x2");
-    HIPCHK(launch_conv3x3_tail_f16x3((hipStream_t)stream, x, x2, w, bias, y, n, cout, H, W));
-    return PNP_OK;
-}
-int pnp_ffdnet_head_nhwc(void* stream, const float* x, const float* sigma, int sigma_per_image, const float* w, const float* bias, float* y,
-                         int n, int h, int wd, int relu) {
-    if (!x || !sigma || !w || !y) return fail(PNP_E_ARG, "pnp_ffdnet_head_nhwc: null pointer");
-    if (n < 1 || h < 1 || wd < 1) return fail(PNP_E_ARG, "pnp_ffdnet_head_nhwc: n, h, w must be >= 1");
-    if ((long long)((h + 1) / 2) * ((wd + 1) / 2) * 64 * 4 > 0x7fffffffLL) return fail(PNP_E_ARG, "pnp_ffdnet_head_nhwc: a result of %d x %d x 64 floats exceeds 2 GiB", (h + 1) / 2, (wd + 1) / 2);
-    HIPCHK(launch_ffdnet_head((hipStream_t)stream, x, sigma, sigma_per_image != 0, w, bias, y, n, h, wd, relu));
-    return PNP_OK;
-}
-int pnp_ffdnet_tail_f16x3(void* stream, const float* x, const float* w, const float* bias, float* y, int n, int h, int wd) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "pnp_ffdnet_tail_f16x3: null pointer");
-    if (n < 1 || h < 1 || wd < 1) return fail(PNP_E_ARG, "pnp_ffdnet_tail_f16x3: n, h, w must be >= 1");
-    if ((long long)((h + 1) / 2) * ((wd + 1) / 2) * 64 * 4 > 0x7fffffffLL) return fail(PNP_E_ARG, "pnp_ffdnet_tail_f16x3: an input of %d x %d x 64 floats exceeds 2 GiB", (h + 1) / 2, (wd + 1) / 2);
-    HIPCHK(launch_conv3x3_tail_f16x3((hipStream_t)stream, x, nullptr, w, bias, y, n, 4, (h + 1) / 2, (wd + 1) / 2, h, wd));
-    return PNP_OK;
-}
-static int pix2_args(const char* who, const float* x, const float* x2, const float* w, const float* y, int n, int C, int H, int W, int up) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "%s: null pointer", who);
-    if (n < 1 || H < 1 || W < 1) return fail(PNP_E_ARG, "%s: n, H, W must be >= 1", who);
-    if (C < 64 || C > 1024 || C % (up ? 128 : 64)) return fail(PNP_E_ARG, "%s: C must be a multiple of %d in 64..1024 (got %d)", who, up ? 128 : 64, C);
-    if (!up && ((H | W) & 1)) return fail(PNP_E_ARG, "%s: H and W must be even (got %d x %d)", who, H, W);
-    const long long in_b = (long long)H * W * C * 4, out_b = up ? in_b * 2 : in_b / 2;
-    if (in_b > 0x7fffffffLL || out_b > 0x7fffffffLL) return fail(PNP_E_ARG, "%s: an image of %d x %d x %d floats (or its result) exceeds 2 GiB", who, H, W, C);
-    if (x == y || x2 == y) return fail(PNP_E_ARG, "%s: y must not alias x or x2 (tiles are re-read after their neighbours were written)", who);
-    return PNP_OK;
-}
-int pnp_conv2x2s2_nhwc_f16x3(void* stream, const float* x, const float* x2, const float* w, float* y, int n, int C, int H, int W) {
-    if (int rc = pix2_args("pnp_conv2x2s2_nhwc_f16x3", x, x2, w, y, n, C, H, W, 0)) return rc;
-    HIPCHK(launch_pix2x2_f16x3((hipStream_t)stream, x, x2, w, y, n, C, H, W, 0));
-    return PNP_OK;
-}
-int pnp_convT2x2s2_nhwc_f16x3(void* stream, const float* x, const float* x2, const float* w, float* y, int n, int C, int H, int W) {
-    if (int rc = pix2_args("pnp_convT2x2s2_nhwc_f16x3", x, x2, w, y, n, C, H, W, 1)) return rc;
-    HIPCHK(launch_pix2x2_f16x3((hipStream_t)stream, x, x2, w, y, n, C, H, W, 1));
-    return PNP_OK;
-}
-int pnp_conv2x2_pack_f16x3(void* stream, const float* w, float* w_packed, int C, int transposed) {
-    if (!w || !w_packed || w == w_packed) return fail(PNP_E_ARG, "pnp_conv2x2_pack_f16x3: null or aliased pointers");
-    if (C < 64 || C > 1024 || C % (transposed ? 128 : 64)) return fail(PNP_E_ARG, "pnp_conv2x2_pack_f16x3: C must be a multiple of %d in 64..1024 (got %d)", transposed ? 128 : 64, C);
-    HIPCHK(launch_pix2_pack_w_f16x3((hipStream_t)stream, w, w_packed, C, transposed != 0));
-    return PNP_OK;
-}
-/* ---- the same layers in half precision (added after ABI 13, additive): kernels_conv_f16.hip, kernels_pix2x2_f16.hip ---- */
-static int f16_image_args(const char* who, int n, int C, int H, int W) {
-    if (n < 1 || H < 1 || W < 1) return fail(PNP_E_ARG, "%s: n, H, W must be >= 1", who);
-    // (H + 16: the kernels let the offsets of rows beyond the image fall out of the buffer's range; they must not wrap around 2^32)
-    if ((long long)(H + 16) * W * C * 4 > 0x7fffffffLL) return fail(PNP_E_ARG, "%s: an image of %d x %d x %d values (+ 16 rows) exceeds the 2 GiB a float32 tensor of it may take", who, H, W, C);
-    return PNP_OK;
-}
-int pnp_conv3x3_nhwc_f16(void* stream, const void* x, const void* w, const float* bias, const void* skip, void* y,
-                         int n, int C, int H, int W, int relu, int dilation, int fmt) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16: null pointer");
-    if (C < 64 || C > 1024 || C % 64) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16: C must be a multiple of 64 in 64..1024 (got %d)", C);
-    if (dilation < 1 || dilation > 4 || (C != 64 && dilation != 1)) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16: dilation 1..4 at C = 64, 1 otherwise (got %d)", dilation);
-    if (fmt & ~7) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16: fmt is a mask of PNP_F16_X_F32 | PNP_F16_SKIP_F32 | PNP_F16_Y_F32 (got %d)", fmt);
-    if (int rc = f16_image_args("pnp_conv3x3_nhwc_f16", n, C, H, W)) return rc;
-    if (x == y || skip == y) return fail(PNP_E_ARG, "pnp_conv3x3_nhwc_f16: y must not alias x or skip (tiles read their neighbours' halo)");
-    HIPCHK(launch_conv3x3_f16((hipStream_t)stream, x, w, bias, skip, y, n, C, H, W, relu, dilation, fmt));
-    return PNP_OK;
-}
-int pnp_conv3x3_pack_f16(void* stream, const float* w_oihw, void* w_packed, int C) {
-    if (!w_oihw || !w_packed || (const void*)w_oihw == w_packed) return fail(PNP_E_ARG, "pnp_conv3x3_pack_f16: null or aliased pointers");
-    if (C < 64 || C > 1024 || C % 64) return fail(PNP_E_ARG, "pnp_conv3x3_pack_f16: C must be a multiple of 64 in 64..1024 (got %d)", C);
-    HIPCHK(launch_conv_pack_w_f16((hipStream_t)stream, w_oihw, w_packed, C));
-    return PNP_OK;
-}
-int pnp_conv3x3_head_nhwc_f16(void* stream, const float* x, const float* w, const float* bias, void* y, int n, int cin, int H, int W, int relu) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "pnp_conv3x3_head_nhwc_f16: null pointer");
-    if (cin < 1 || cin > 8) return fail(PNP_E_ARG, "pnp_conv3x3_head_nhwc_f16: 1 <= cin <= 8 required (got %d)", cin);
-    if (int rc = f16_image_args("pnp_conv3x3_head_nhwc_f16", n, 64, H, W)) return rc;
-    HIPCHK(launch_conv3x3_head_f16((hipStream_t)stream, x, nullptr, 0, w, bias, y, n, cin, H, W, relu, 0));
-    return PNP_OK;
-}
-int pnp_ffdnet_head_nhwc_f16(void* stream, const float* x, const float* sigma, int sigma_per_image, const float* w, const float* bias, void* y,
-                             int n, int h, int wd, int relu) {
-    if (!x || !sigma || !w || !y) return fail(PNP_E_ARG, "pnp_ffdnet_head_nhwc_f16: null pointer");
-    if (n < 1 || h < 1 || wd < 1) return fail(PNP_E_ARG, "pnp_ffdnet_head_nhwc_f16: n, h, w must be >= 1");
-    if (int rc = f16_image_args("pnp_ffdnet_head_nhwc_f16", n, 64, (h + 1) / 2, (wd + 1) / 2)) return rc;
-    HIPCHK(launch_conv3x3_head_f16((hipStream_t)stream, x, sigma, sigma_per_image != 0, w, bias, y, n, 5, h, wd, relu, 1));
-    return PNP_OK;
-}
-int pnp_conv3x3_tail_nchw_f16(void* stream, const void* x, const void* x2, const float* w, const float* bias, float* y, int n, int cout, int H, int W) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "pnp_conv3x3_tail_nchw_f16: null pointer");
-    if (cout < 1 || cout > 4) return fail(PNP_E_ARG, "pnp_conv3x3_tail_nchw_f16: 1 <= cout <= 4 required (got %d)", cout);
-    if (int rc = f16_image_args("pnp_conv3x3_tail_nchw_f16", n, 64, H, W)) return rc;
-    if (x == (const void*)y || (x2 && x2 == (const void*)y)) return fail(PNP_E_ARG, "pnp_conv3x3_tail_nchw_f16: y must not alias x or x2");
-    HIPCHK(launch_conv3x3_tail_f16((hipStream_t)stream, x, x2, w, bias, y, n, cout, H, W));
-    return PNP_OK;
-}
-int pnp_ffdnet_tail_f16(void* stream, const void* x, const float* w, const float* bias, float* y, int n, int h, int wd) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "pnp_ffdnet_tail_f16: null pointer");
-    if (n < 1 || h < 1 || wd < 1) return fail(PNP_E_ARG, "pnp_ffdnet_tail_f16: n, h, w must be >= 1");
-    if (int rc = f16_image_args("pnp_ffdnet_tail_f16", n, 64, (h + 1) / 2, (wd + 1) / 2)) return rc;
-    HIPCHK(launch_conv3x3_tail_f16((hipStream_t)stream, x, nullptr, w, bias, y, n, 4, (h + 1) / 2, (wd + 1) / 2, h, wd));
-    return PNP_OK;
-}
-static int pix2_args_f16(const char* who, const void* x, const void* x2, const void* w, const void* y, int n, int C, int H, int W, int up) {
-    if (!x || !w || !y) return fail(PNP_E_ARG, "%s: null pointer", who);
-    if (n < 1 || H < 1 || W < 1) return fail(PNP_E_ARG, "%s: n, H, W must be >= 1", who);
-    if (C < 64 || C > 1024 || C % (up ? 128 : 64)) return fail(PNP_E_ARG, "%s: C must be a multiple of %d in 64..1024 (got %d)", who, up ? 128 : 64, C);
-    if (!up && ((H | W) & 1)) return fail(PNP_E_ARG, "%s: H and W must be even (got %d x %d)", who, H, W);
-    const long long in_b = (long long)(H + 16) * W * C * 4, out_b = up ? (long long)(2 * H + 16) * 2 * W * (C / 2) * 4 : (long long)(H / 2 + 16) * (W / 2) * 2 * C * 4;
-    if (in_b > 0x7fffffffLL || out_b > 0x7fffffffLL) return fail(PNP_E_ARG, "%s: an image of %d x %d x %d values (or its result; + 16 rows) exceeds the 2 GiB a float32 tensor of it may take", who, H, W, C);
-    if (x == y || x2 == y) return fail(PNP_E_ARG, "%s: y must not alias x or x2", who);
-    return PNP_OK;
-}
-int pnp_conv2x2s2_nhwc_f16(void* stream, const void* x, const void* x2, const void* w, void* y, int n, int C, int H, int W, int y_f32) {
-    if (int rc = pix2_args_f16("pnp_conv2x2s2_nhwc_f16", x, x2, w, y, n, C, H, W, 0)) return rc;
-    HIPCHK(launch_pix2x2_f16((hipStream_t)stream, x, x2, w, y, n, C, H, W, 0, y_f32));
-    return PNP_OK;
-}
-int pnp_convT2x2s2_nhwc_f16(void* stream, const void* x, const void* x2, const void* w, void* y, int n, int C, int H, int W, int y_f32) {
-    if (int rc = pix2_args_f16("pnp_convT2x2s2_nhwc_f16", x, x2, w, y, n, C, H, W, 1)) return rc;
-    HIPCHK(launch_pix2x2_f16((hipStream_t)stream, x, x2, w, y, n, C, H, W, 1, y_f32));
-    return PNP_OK;
-}
-int pnp_conv2x2_pack_f16(void* stream, const float* w, void* w_packed, int C, int transposed) {
-    if (!w || !w_packed || (const void*)w == w_packed) return fail(PNP_E_ARG, "pnp_conv2x2_pack_f16: null or aliased pointers");
-    if (C < 64 || C > 1024 || C % (transposed ? 128 : 64)) return fail(PNP_E_ARG, "pnp_conv2x2_pack_f16: C must be a multiple of %d in 64..1024 (got %d)", transposed ? 128 : 64, C);
-    HIPCHK(launch_pix2_pack_w_f16((hipStream_t)stream, w, w_packed, C, transposed != 0));
-    return PNP_OK;
-}
-int pnp_relayout_c64(void* stream, const float* in, float* out, int n, int H, int W, int to_nhwc) {
-    if (!in || !out || in == out) return fail(PNP_E_ARG, "pnp_relayout_c64: null or aliased pointers");
-    if (n < 1 || H < 1 || W < 1) return fail(PNP_E_ARG, "pnp_relayout_c64: n, H, W must be >= 1");
-    HIPCHK(launch_relayout64((hipStream_t)stream, in, out, n, H * W, to_nhwc != 0));
-    return PNP_OK;
-}
 
 int pnp_timer_start(pnp_ctx* c) { CTX(c); HIPCHK(hipEventRecord(c->ev0, c->stream)); return PNP_OK; }
 int pnp_timer_stop(pnp_ctx* c, float* ms) {

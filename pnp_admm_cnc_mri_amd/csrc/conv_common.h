@@ -2,6 +2,7 @@
 // tile geometry, the input staging (global -> registers with out-of-image pixels read as zeros) and the epilogue.
 #pragma once
 #include "internal.h"
+#include "conv_plan.h"
 #include <hip/hip_runtime.h>
 
 namespace pnp {
@@ -13,8 +14,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define CV_MT_N 1
 #endif
 constexpr int CV_MT = CV_MT_N;                 // M tiles (of 32 pixels = 2 tile rows) per wave: 1 -> 8 x 16 tiles, two workgroups per unit; 2 -> 16 x 16, one
-constexpr int CV_TX = 16, CV_TY = 8 * CV_MT;   // output tile
-constexpr int CV_C = 64;                       // channels in and out
+constexpr int CV_TX = CP_NARROW.tx, CV_TY = CP_NARROW.ty * CV_MT;      // output tile (conv_plan.h; the library builds MT = 1, the plan's tile)
+constexpr int CV_C = CP_CSTEP;                 // channels in and out
 constexpr int CV_PS = CV_C + 4;                // floats between consecutive pixels of the LDS tile: 272 bytes, so that the 16 lanes a b128
                                                // read serves per cycle (consecutive pixels, same channels) start 4 banks apart -- and the
                                                // eight operand groups of a tap are IMMEDIATE offsets of one address (no per-group VALU)

@@ -42,8 +42,8 @@ __device__ __forceinline__ f32x4 as_f32x4(const u32x4v& w) {
 
 // Input staging: chunk u of thread tid is channels 8 (tid & 7) .. + 7 of tile pixel p = (tid >> 3) + 32 u = (row r, column c);
 // pk[u] = (r W + c) * pix | c -- pix (bytes between pixels of the tensor) is a multiple of 128 and c < 32: the low seven bits are free
-// for the column, the only coordinate that needs a test (rows fall out of the buffer's range by themselves: the launchers keep
-// (H + 16) W pix below 2^31, so the 32-bit offset of a halo or overhang row cannot wrap back into range) -- or -1: no such chunk.
+// for the column, the only coordinate that needs a test (rows fall out of the buffer's range by themselves: conv_plan.h keeps
+// (H + CP_SPARE_ROWS) W pix below 2^31, so the 32-bit offset of a halo or overhang row cannot wrap back into range) -- or -1: no such chunk.
 template <int DIL> struct StagingF { int pk[GeoF<DIL>::XU]; };
 template <int DIL>
 __device__ __forceinline__ void staging_init_f(int W, int tid, StagingF<DIL>& st, const int pix) {

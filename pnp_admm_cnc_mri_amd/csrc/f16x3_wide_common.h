@@ -6,7 +6,7 @@
 
 namespace pnp {
 
-constexpr int WT_TX = 16, WT_TY = 16;                            // output tile
+constexpr int WT_TX = CP_WIDE.tx, WT_TY = CP_WIDE.ty;            // output tile (conv_plan.h)
 constexpr int WT_HX = WT_TX + 2, WT_HY = WT_TY + 2;              // with halo
 constexpr int WT_PSB = CV_PS * 4;                                // bytes between consecutive pixels of the LDS tile (272)
 constexpr int WT_XIN = WT_HY * WT_HX * CV_PS;                    // floats of the input tile (88 128 bytes)

@@ -9,6 +9,16 @@
 
 namespace pnp {
 
+// Error reporting of the ABI layer (api.hip, api_conv.hip): formats the calling thread's message -- ONE thread_local buffer, owned by api.hip
+// and read by pnp_last_error -- and returns `code`
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+#define HIPCHK(expr)                                                                               \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess)                                                                      \
+            return fail(PNP_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+    } while (0)
+
 // complex / real types per precision: float2 for the production path, double2 for the fp64
 // validation context (pnp_ctx_create_f64)
 template <typename R> struct CxOf;
@@ -91,6 +101,8 @@ template <typename R> hipError_t launch_wavelet_prox(hipStream_t s, int wavelet,
 
 // calibration (pnp_calibrate_stream): the slice-resident loop's access shape without its arithmetic, `passes` passes over `slices` slices of 256 KiB
 hipError_t launch_calibrate_stream(hipStream_t s, float* z, float* w, const float* y, int slices, int passes);
+// The denoisers' conv layers.  Shape rules, tiles / items and the persistent grids of every launcher below: conv_plan.h -- a launcher
+// returns hipErrorInvalidValue for what the plan's check of its layer kind refuses (api_conv.hip turns the same check into a message first).
 // optional HIP backend of the denoisers' 64-channel conv3x3 body layers (kernels_conv.hip); activations NHWC float32
 hipError_t launch_conv_pack_w(hipStream_t s, const float* w_oihw /*[64][64][3][3]*/, float* wfrag /*36 864 floats*/);
 hipError_t launch_conv3x3_c64(hipStream_t s, const float* x, const float* wfrag, const float* bias, const float* skip,
@@ -104,8 +116,8 @@ hipError_t launch_conv3x3_f16x3(hipStream_t s, const float* x, const float* wfra
 // weights, bit-equal results; launch_conv3x3_f16x3 dispatches to it (conv_wide_mode below) -- callers never name it
 hipError_t launch_conv3x3_f16x3_wide(hipStream_t s, const float* x, const float* wfrag, const float* bias, const float* skip,
                                      float* y, int n, int C, int H, int W, int relu, int fmt);
-int conv_wide_mode();            // -1 = by size, 0 = never, 1 = always (dilation 1); initial value: PNP_CONV_WIDE; pnp_conv3x3_f16x3_set_variant
-int conv_set_wide_mode(int m);   // returns the previous setting
+int conv_wide_mode();            // -1 = by size (conv_plan.h: cp_use_wide), 0 = never, 1 = always (dilation 1); initial value: PNP_CONV_WIDE
+int conv_set_wide_mode(int m);   // pnp_conv3x3_f16x3_set_variant; returns the previous setting.  One atomic int: any thread may set it while others launch
 hipError_t launch_conv3x3_tail_f16x3(hipStream_t s, const float* x_nhwc, const float* x2_nhwc /* null or added to x */, const float* w_oihw,
                                      const float* bias, float* y_nchw, int n, int cout, int H, int W,
                                      int shuffle_h = 0, int shuffle_w = 0 /* FFDNet: cout = 4 written as one pixel-shuffled [shuffle_h][shuffle_w] channel */);

@@ -193,9 +193,7 @@ __global__ __launch_bounds__(256) void k_relayout64(const float* in, float* out,
 template <int DIL>
 static hipError_t launch_conv_dil(hipStream_t s, const ConvArgs& a, long long tiles, int cus) {
     // persistent workgroups (77 KiB of LDS or less: two per compute unit, one otherwise); every workgroup's loop ends: tile < ntiles
-    const long long resident = (long long)Geo<DIL>::WPS * cus;
-    const unsigned grid = (unsigned)(tiles < resident ? tiles : resident);
-    hipLaunchKernelGGL(k_conv3x3_c64<DIL>, dim3(grid), dim3(CV_THREADS), 0, s, a, (int)tiles);
+    hipLaunchKernelGGL(k_conv3x3_c64<DIL>, dim3((unsigned)cp_grid(tiles, Geo<DIL>::WPS, cus)), dim3(CV_THREADS), 0, s, a, (int)tiles);
     return hipGetLastError();
 }
 
@@ -214,20 +212,18 @@ int conv_compute_units() {
 
 hipError_t launch_conv3x3_c64(hipStream_t s, const float* x, const float* w, const float* bias, const float* skip, float* y,
                               int n, int H, int W, int relu, int dilation) {
+    if (cp_check_body(n, CV_C, H, W, dilation, 0)) return hipErrorInvalidValue;
+    const ConvTiling t = cp_tiling(n, H, W, {CV_TX, CV_TY});
     ConvArgs a;
     a.x = x; a.w = w; a.bias = bias; a.skip = skip; a.y = y; a.n = n; a.H = H; a.W = W; a.relu = relu; a.C = CV_C; a.fmt = 0;
-    a.tiles_x = (W + CV_TX - 1) / CV_TX; a.tiles_y = (H + CV_TY - 1) / CV_TY;
-    const long long tiles = (long long)n * a.tiles_x * a.tiles_y;
-    if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
-    if ((long long)H * W * CV_C * 4 > 0x7fffffffLL) return hipErrorInvalidValue;        // one image must fit a signed 32-bit buffer offset (8 M pixels)
+    a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
     const int ncu = conv_compute_units();
     if (ncu <= 0) return hipGetLastError();
     switch (dilation) {
-        case 1: return launch_conv_dil<1>(s, a, tiles, ncu);
-        case 2: return launch_conv_dil<2>(s, a, tiles, ncu);
-        case 3: return launch_conv_dil<3>(s, a, tiles, ncu);
-        case 4: return launch_conv_dil<4>(s, a, tiles, ncu);
-        default: return hipErrorInvalidValue;
+        case 1: return launch_conv_dil<1>(s, a, t.items, ncu);
+        case 2: return launch_conv_dil<2>(s, a, t.items, ncu);
+        case 3: return launch_conv_dil<3>(s, a, t.items, ncu);
+        default: return launch_conv_dil<4>(s, a, t.items, ncu);
     }
 }
 
@@ -237,6 +233,7 @@ hipError_t launch_conv_pack_w(hipStream_t s, const float* w_oihw, float* wfrag) 
 }
 
 hipError_t launch_relayout64(hipStream_t s, const float* in, float* out, int n, int HW, bool to_nhwc) {
+    if (cp_check_relayout(n, HW, 1)) return hipErrorInvalidValue;
     const dim3 grid((HW + 63) / 64, n);
     if (to_nhwc) hipLaunchKernelGGL(k_relayout64<true>, grid, dim3(256), 0, s, in, out, HW);
     else         hipLaunchKernelGGL(k_relayout64<false>, grid, dim3(256), 0, s, in, out, HW);
@@ -255,7 +252,7 @@ hipError_t launch_relayout64(hipStream_t s, const float* in, float* out, int n, 
 //         16 partial sums of a pixel meet by four DPP steps inside the lane row
 // ------------------------------------------------------------------------------------------
 constexpr int CV_HX = Geo<1>::HX, CV_HY = Geo<1>::HY, CV_XU = Geo<1>::XU;      // the direct kernels below: dilation 1
-constexpr int HD_MAXC = 8;
+constexpr int HD_MAXC = CP_MAX_CIN;
 struct HeadArgs {
     const float* x; const float* w; const float* bias; float* y;
     int n, cin, H, W, tiles_x, tiles_y, relu;
@@ -341,7 +338,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_head(HeadArgs a) {
     }
 }
 
-constexpr int TL_MAXC = 4;
+static_assert(CP_MAX_COUT == 4, "k_conv3x3_tail is instantiated for 1 .. 4 output channels (launch_conv3x3_tail)");
 struct TailArgs {
     const float* x; const float* w; const float* bias; float* y;
     int n, cout, H, W, tiles_x, tiles_y;
@@ -420,40 +417,35 @@ __global__ __launch_bounds__(256) void k_conv3x3_tail(TailArgs a) {
     }
 }
 
+// the first layer at H x W (checked by the caller).  src_h, src_w != 0: FFDNet's -- x is the full-resolution [n][1][src_h][src_w] image, cin = 5
+static hipError_t launch_head(hipStream_t s, const float* x, const float* sigma, int sigma_stride, const float* w_oihw, const float* bias, float* y_nhwc,
+                              int n, int cin, int H, int W, int relu, int src_h, int src_w) {
+    const ConvTiling t = cp_tiling(n, H, W, {CV_TX, CV_TY});
+    HeadArgs a;
+    a.x = x; a.w = w_oihw; a.bias = bias; a.y = y_nhwc; a.n = n; a.cin = cin; a.H = H; a.W = W; a.relu = relu;
+    a.ffdnet = src_h ? 1 : 0; a.src_h = src_h; a.src_w = src_w; a.sigma = sigma; a.sigma_stride = sigma_stride;
+    a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
+    hipLaunchKernelGGL(k_conv3x3_head, dim3((unsigned)t.items), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
 hipError_t launch_conv3x3_head(hipStream_t s, const float* x_nchw, const float* w_oihw, const float* bias, float* y_nhwc,
                                int n, int cin, int H, int W, int relu) {
-    if (cin < 1 || cin > HD_MAXC || (long long)H * W * CV_C * 4 > 0x7fffffffLL) return hipErrorInvalidValue;
-    HeadArgs a;
-    a.x = x_nchw; a.w = w_oihw; a.bias = bias; a.y = y_nhwc; a.n = n; a.cin = cin; a.H = H; a.W = W; a.relu = relu;
-    a.ffdnet = 0; a.src_h = a.src_w = a.sigma_stride = 0; a.sigma = nullptr;
-    a.tiles_x = (W + CV_TX - 1) / CV_TX; a.tiles_y = (H + CV_TY - 1) / CV_TY;
-    const long long tiles = (long long)n * a.tiles_x * a.tiles_y;
-    if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_conv3x3_head, dim3((unsigned)tiles), dim3(256), 0, s, a);
-    return hipGetLastError();
+    if (cp_check_head(n, cin, H, W)) return hipErrorInvalidValue;
+    return launch_head(s, x_nchw, nullptr, 0, w_oihw, bias, y_nhwc, n, cin, H, W, relu, 0, 0);
 }
 hipError_t launch_ffdnet_head(hipStream_t s, const float* x_full, const float* sigma, int sigma_per_image, const float* w_oihw, const float* bias,
                               float* y_nhwc, int n, int h, int w, int relu) {
-    const int H = (h + 1) / 2, W = (w + 1) / 2;
-    if (h < 1 || w < 1 || (long long)H * W * CV_C * 4 > 0x7fffffffLL) return hipErrorInvalidValue;
-    HeadArgs a;
-    a.x = x_full; a.w = w_oihw; a.bias = bias; a.y = y_nhwc; a.n = n; a.cin = 5; a.H = H; a.W = W; a.relu = relu;
-    a.ffdnet = 1; a.src_h = h; a.src_w = w; a.sigma = sigma; a.sigma_stride = sigma_per_image ? 1 : 0;
-    a.tiles_x = (W + CV_TX - 1) / CV_TX; a.tiles_y = (H + CV_TY - 1) / CV_TY;
-    const long long tiles = (long long)n * a.tiles_x * a.tiles_y;
-    if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_conv3x3_head, dim3((unsigned)tiles), dim3(256), 0, s, a);
-    return hipGetLastError();
+    if (cp_check_ffdnet(n, h, w)) return hipErrorInvalidValue;
+    return launch_head(s, x_full, sigma, sigma_per_image ? 1 : 0, w_oihw, bias, y_nhwc, n, 5, cp_ffdnet_dim(h), cp_ffdnet_dim(w), relu, h, w);
 }
 hipError_t launch_conv3x3_tail(hipStream_t s, const float* x_nhwc, const float* w_oihw, const float* bias, float* y_nchw,
                                int n, int cout, int H, int W) {
-    if (cout < 1 || cout > TL_MAXC || (long long)H * W * CV_C * 4 > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (cp_check_tail(n, cout, H, W)) return hipErrorInvalidValue;
+    const ConvTiling t = cp_tiling(n, H, W, {CV_TX, CV_TY});
     TailArgs a;
     a.x = x_nhwc; a.w = w_oihw; a.bias = bias; a.y = y_nchw; a.n = n; a.cout = cout; a.H = H; a.W = W;
-    a.tiles_x = (W + CV_TX - 1) / CV_TX; a.tiles_y = (H + CV_TY - 1) / CV_TY;
-    const long long tiles = (long long)n * a.tiles_x * a.tiles_y;
-    if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)tiles), block(256);
+    a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
+    const dim3 grid((unsigned)t.items), block(256);
     switch (cout) {
         case 1: hipLaunchKernelGGL(k_conv3x3_tail<1>, grid, block, 0, s, a); break;
         case 2: hipLaunchKernelGGL(k_conv3x3_tail<2>, grid, block, 0, s, a); break;

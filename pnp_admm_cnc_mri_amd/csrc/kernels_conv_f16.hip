@@ -287,7 +287,7 @@ __global__ __launch_bounds__(256) void k_conv_pack_w_f16(const float* w_oihw, _F
 // First layer of the stacks (CIN <= 8 -> 64 channels; FFDNet's pixel-unshuffle / noise-level stage folded in): the float32 direct
 // arithmetic of kernels_conv.hip's k_conv3x3_head on the float32 network input -- same loops, same fma order -- storing halves.
 // ------------------------------------------------------------------------------------------
-constexpr int HFD_HX = Geo<1>::HX, HFD_HY = Geo<1>::HY, HFD_MAXC = 8;
+constexpr int HFD_HX = Geo<1>::HX, HFD_HY = Geo<1>::HY, HFD_MAXC = CP_MAX_CIN;
 struct HeadF16Args {
     const float* x; const float* w; const float* bias; void* y;
     int n, cin, H, W, tiles_x, tiles_y, relu;
@@ -480,42 +480,33 @@ __global__ __launch_bounds__(CV_THREADS, 2) void k_conv3x3_tail_f16(TailF16Args 
 // ------------------------------------------------------------------------------------------
 template <int DIL>
 static hipError_t launch_f16_dil(hipStream_t s, const ConvF16Args& a, long long items, int cus) {
-    // persistent workgroups, GeoFK<DIL>::WPS per compute unit, a multiple of NC = C / 64 of them (a workgroup keeps its block of output channels);
-    // every workgroup's loop ends: item < nitems
-    const int NC = a.C >> 6;
-    long long grid = (long long)GeoFK<DIL>::WPS * cus;
-    grid -= grid % NC;
-    if (grid < NC) grid = NC;
-    if (items < grid) grid = items;                               // items = tiles * NC: a multiple of NC as well
-    if (a.fmt & HF_FMT_X32) hipLaunchKernelGGL((k_conv3x3_f16<DIL, true>), dim3((unsigned)grid), dim3(CV_THREADS), 0, s, a, (int)items);
-    else hipLaunchKernelGGL((k_conv3x3_f16<DIL, false>), dim3((unsigned)grid), dim3(CV_THREADS), 0, s, a, (int)items);
+    // persistent workgroups, GeoFK<DIL>::WPS per compute unit, a multiple of NC = C / 64 of them (a workgroup keeps its block of output channels:
+    // cp_grid); every workgroup's loop ends: item < nitems
+    const dim3 grid((unsigned)cp_grid(items, GeoFK<DIL>::WPS, cus, a.C / CP_CSTEP));
+    if (a.fmt & HF_FMT_X32) hipLaunchKernelGGL((k_conv3x3_f16<DIL, true>), grid, dim3(CV_THREADS), 0, s, a, (int)items);
+    else hipLaunchKernelGGL((k_conv3x3_f16<DIL, false>), grid, dim3(CV_THREADS), 0, s, a, (int)items);
     return hipGetLastError();
 }
 
 hipError_t launch_conv3x3_f16(hipStream_t s, const void* x, const void* w, const float* bias, const void* skip, void* y,
                               int n, int C, int H, int W, int relu, int dilation, int fmt) {
-    if (C < 64 || C > 1024 || (C & 63) || (C != 64 && dilation != 1) || (fmt & ~(HF_FMT_X32 | HF_FMT_SKIP32 | HF_FMT_Y32))) return hipErrorInvalidValue;
+    if (cp_check_body(n, C, H, W, dilation, fmt)) return hipErrorInvalidValue;
+    const ConvTiling t = cp_tiling(n, H, W, CP_NARROW, C / CP_CSTEP);
     ConvF16Args a;
     a.x = x; a.w = w; a.bias = bias; a.skip = skip; a.y = y; a.n = n; a.H = H; a.W = W; a.relu = relu; a.C = C; a.fmt = fmt;
-    a.tiles_x = (W + CV_TX - 1) / CV_TX; a.tiles_y = (H + CV_TY - 1) / CV_TY;
-    const long long items = (long long)n * a.tiles_x * a.tiles_y * (C >> 6);
-    if (items <= 0 || items > 0x7fffffffLL) return hipErrorInvalidValue;
-    // one image must fit a signed 32-bit buffer offset in either format -- with 16 rows to spare: the offsets of a tile's rows above and below
-    // the image (halo, overhang) must fall OUT of the buffer's range, not wrap around 2^32 back into it
-    if ((long long)(H + 16) * W * C * 4 > 0x7fffffffLL) return hipErrorInvalidValue;
+    a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
     const int cus = conv_compute_units();
     if (cus <= 0) return hipGetLastError();
     switch (dilation) {
-        case 1: return launch_f16_dil<1>(s, a, items, cus);
-        case 2: return launch_f16_dil<2>(s, a, items, cus);
-        case 3: return launch_f16_dil<3>(s, a, items, cus);
-        case 4: return launch_f16_dil<4>(s, a, items, cus);
-        default: return hipErrorInvalidValue;
+        case 1: return launch_f16_dil<1>(s, a, t.items, cus);
+        case 2: return launch_f16_dil<2>(s, a, t.items, cus);
+        case 3: return launch_f16_dil<3>(s, a, t.items, cus);
+        default: return launch_f16_dil<4>(s, a, t.items, cus);
     }
 }
 
 hipError_t launch_conv_pack_w_f16(hipStream_t s, const float* w_oihw, void* wfrag, int C) {
-    if (C < 64 || C > 1024 || (C & 63)) return hipErrorInvalidValue;
+    if (cp_check_pack3(C)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_conv_pack_w_f16, dim3((unsigned)(9LL * C * C / 256)), dim3(256), 0, s, w_oihw, reinterpret_cast<_Float16*>(wfrag), C);
     return hipGetLastError();
 }
@@ -523,32 +514,29 @@ hipError_t launch_conv_pack_w_f16(hipStream_t s, const float* w_oihw, void* wfra
 hipError_t launch_conv3x3_head_f16(hipStream_t s, const float* x, const float* sigma, int sigma_per_image, const float* w_oihw, const float* bias,
                                    void* y_nhwc, int n, int cin, int H, int W, int relu, int ffdnet) {
     // ffdnet: x is the full-resolution image [n][1][H][W], the layer runs at ceil(H / 2) x ceil(W / 2) with cin = 5
+    if (ffdnet ? cp_check_ffdnet(n, H, W) : cp_check_head(n, cin, H, W)) return hipErrorInvalidValue;
     HeadF16Args a;
     a.x = x; a.w = w_oihw; a.bias = bias; a.y = y_nhwc; a.n = n; a.relu = relu;
     a.ffdnet = ffdnet ? 1 : 0; a.src_h = ffdnet ? H : 0; a.src_w = ffdnet ? W : 0; a.sigma = sigma; a.sigma_stride = sigma_per_image ? 1 : 0;
-    a.cin = ffdnet ? 5 : cin; a.H = ffdnet ? (H + 1) / 2 : H; a.W = ffdnet ? (W + 1) / 2 : W;
-    if (a.cin < 1 || a.cin > HFD_MAXC || a.H < 1 || a.W < 1 || (long long)(a.H + 16) * a.W * CV_C * 4 > 0x7fffffffLL) return hipErrorInvalidValue;
-    a.tiles_x = (a.W + CV_TX - 1) / CV_TX; a.tiles_y = (a.H + CV_TY - 1) / CV_TY;
-    const long long tiles = (long long)n * a.tiles_x * a.tiles_y;
-    if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_conv3x3_head_f16, dim3((unsigned)tiles), dim3(256), 0, s, a);
+    a.cin = ffdnet ? 5 : cin; a.H = ffdnet ? cp_ffdnet_dim(H) : H; a.W = ffdnet ? cp_ffdnet_dim(W) : W;
+    const ConvTiling t = cp_tiling(n, a.H, a.W, CP_NARROW);
+    a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
+    hipLaunchKernelGGL(k_conv3x3_head_f16, dim3((unsigned)t.items), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_conv3x3_tail_f16(hipStream_t s, const void* x_nhwc, const void* x2_nhwc, const float* w_oihw, const float* bias, float* y,
                                    int n, int cout, int H, int W, int shuffle_h, int shuffle_w) {
-    if (cout < 1 || cout > 4 || (long long)(H + 16) * W * CV_C * 4 > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (shuffle_h && (cout != 4 || (shuffle_h + 1) / 2 != H || (shuffle_w + 1) / 2 != W)) return hipErrorInvalidValue;
+    if (cp_check_tail(n, cout, H, W, shuffle_h, shuffle_w)) return hipErrorInvalidValue;
+    const ConvTiling tl = cp_tiling(n, H, W, CP_NARROW);
     TailF16Args t;
     t.shuffle = shuffle_h ? 1 : 0; t.out_h = shuffle_h; t.out_w = shuffle_w;
     t.x = x_nhwc; t.x2 = x2_nhwc; t.w = w_oihw; t.bias = bias; t.y = y; t.n = n; t.cout = cout; t.H = H; t.W = W;
-    t.tiles_x = (W + CV_TX - 1) / CV_TX; t.tiles_y = (H + CV_TY - 1) / CV_TY;
-    const long long tiles = (long long)n * t.tiles_x * t.tiles_y;
-    if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+    t.tiles_x = tl.tiles_x; t.tiles_y = tl.tiles_y;
     const int cus = conv_compute_units();
     if (cus <= 0) return hipGetLastError();
-    const long long grid = tiles < 2LL * cus ? tiles : 2LL * cus;          // persistent, two workgroups per compute unit; every loop ends: tile < ntiles
-    hipLaunchKernelGGL(k_conv3x3_tail_f16, dim3((unsigned)grid), dim3(CV_THREADS), 0, s, t, (int)tiles);
+    // persistent, two workgroups per compute unit; every loop ends: tile < ntiles
+    hipLaunchKernelGGL(k_conv3x3_tail_f16, dim3((unsigned)cp_grid(tl.items, 2, cus)), dim3(CV_THREADS), 0, s, t, (int)tl.items);
     return hipGetLastError();
 }
 

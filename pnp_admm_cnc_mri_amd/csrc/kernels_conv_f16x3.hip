@@ -31,6 +31,7 @@
 //   first chunk   its own instance of the code: the accumulators start from a constant-zero C operand, not from 64 register moves
 #include "conv_common.h"
 #include "f16x3_common.h"
+#include <atomic>
 #include <type_traits>
 #include <cstdlib>
 
@@ -557,71 +558,58 @@ __global__ __launch_bounds__(CV_THREADS, 2) void k_conv3x3_tail_h3(TailH3Args t,
 
 hipError_t launch_conv3x3_tail_f16x3(hipStream_t s, const float* x_nhwc, const float* x2_nhwc, const float* w_oihw, const float* bias, float* y_nchw,
                                      int n, int cout, int H, int W, int shuffle_h, int shuffle_w) {
-    if (cout < 1 || cout > 4 || (long long)H * W * CV_C * 4 > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (shuffle_h && (cout != 4 || (shuffle_h + 1) / 2 != H || (shuffle_w + 1) / 2 != W)) return hipErrorInvalidValue;
+    if (cp_check_tail(n, cout, H, W, shuffle_h, shuffle_w)) return hipErrorInvalidValue;
+    const ConvTiling tl = cp_tiling(n, H, W, CP_NARROW);
     TailH3Args t;
     t.shuffle = shuffle_h ? 1 : 0; t.out_h = shuffle_h; t.out_w = shuffle_w;
     t.x = x_nhwc; t.x2 = x2_nhwc; t.w = w_oihw; t.bias = bias; t.y = y_nchw; t.n = n; t.cout = cout; t.H = H; t.W = W;
-    t.tiles_x = (W + CV_TX - 1) / CV_TX; t.tiles_y = (H + CV_TY - 1) / CV_TY;
-    const long long tiles = (long long)n * t.tiles_x * t.tiles_y;
-    if (tiles <= 0 || tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+    t.tiles_x = tl.tiles_x; t.tiles_y = tl.tiles_y;
     const int cus = conv_compute_units();
     if (cus <= 0) return hipGetLastError();
-    const long long grid = tiles < 2LL * cus ? tiles : 2LL * cus;          // persistent, two workgroups per compute unit; every loop ends: tile < ntiles
-    hipLaunchKernelGGL(k_conv3x3_tail_h3, dim3((unsigned)grid), dim3(CV_THREADS), 0, s, t, (int)tiles);
+    // persistent, two workgroups per compute unit; every loop ends: tile < ntiles
+    hipLaunchKernelGGL(k_conv3x3_tail_h3, dim3((unsigned)cp_grid(tl.items, 2, cus)), dim3(CV_THREADS), 0, s, t, (int)tl.items);
     return hipGetLastError();
 }
 
 template <int DIL>
 static hipError_t launch_h3_dil(hipStream_t s, const ConvArgs& a, long long items, int cus) {
-    // persistent workgroups, a multiple of NC = C / 64 of them (a workgroup keeps its block of output channels); every
+    // persistent workgroups, a multiple of NC = C / 64 of them (a workgroup keeps its block of output channels: cp_grid); every
     // workgroup's loop ends: item < nitems
-    const int NC = a.C >> 6;
-    long long grid = (long long)GeoH<DIL>::WPS * cus;
-    grid -= grid % NC;
-    if (grid < NC) grid = NC;
-    if (items < grid) grid = items;                               // items = tiles * NC: a multiple of NC as well
-    hipLaunchKernelGGL(k_conv3x3_c64_h3<DIL>, dim3((unsigned)grid), dim3(CV_THREADS), 0, s, a, (int)items);
+    hipLaunchKernelGGL(k_conv3x3_c64_h3<DIL>, dim3((unsigned)cp_grid(items, GeoH<DIL>::WPS, cus, a.C / CP_CSTEP)), dim3(CV_THREADS), 0, s, a, (int)items);
     return hipGetLastError();
 }
 
 hipError_t launch_conv3x3_f16x3(hipStream_t s, const float* x, const float* w, const float* bias, const float* skip, float* y,
                                 int n, int C, int H, int W, int relu, int dilation, int fmt) {
-    if (C < 64 || C > 1024 || (C & 63) || (C != 64 && dilation != 1) || (fmt & ~(CV_FMT_X | CV_FMT_SKIP | CV_FMT_Y))) return hipErrorInvalidValue;
-    ConvArgs a;
-    a.x = x; a.w = w; a.bias = bias; a.skip = skip; a.y = y; a.n = n; a.H = H; a.W = W; a.relu = relu; a.C = C; a.fmt = fmt;
-    a.tiles_x = (W + CV_TX - 1) / CV_TX; a.tiles_y = (H + CV_TY - 1) / CV_TY;
-    const long long items = (long long)n * a.tiles_x * a.tiles_y * (C >> 6);
-    if (items <= 0 || items > 0x7fffffffLL) return hipErrorInvalidValue;
-    if ((long long)H * W * C * 4 > 0x7fffffffLL) return hipErrorInvalidValue;           // one image must fit a signed 32-bit buffer offset
+    if (cp_check_body(n, C, H, W, dilation, fmt)) return hipErrorInvalidValue;
     const int cus = conv_compute_units();
     if (cus <= 0) return hipGetLastError();
-    if (dilation == 1) {
-        // the wide kernel (kernels_conv_f16x3_wide.hip: 16 x 16 tiles, ONE workgroup per compute unit) once every compute unit has an item of
-        // its own -- below that the 8 x 16 tiles on two workgroups per unit spread a small layer better (one 256 x 256 slice at 64 channels:
-        // 17.1 us wide against 18.2 narrow; one 128 x 128 slice: 13.4 against 10.3, profiles/conv_f16x3_wide_probe_r06.txt)
-        const long long items16 = (long long)n * ((W + 15) / 16) * ((H + 15) / 16) * (C >> 6);
-        const int mode = conv_wide_mode();
-        if (mode >= 1 || (mode < 0 && items16 >= (long long)cus)) return launch_conv3x3_f16x3_wide(s, x, w, bias, skip, y, n, C, H, W, relu, fmt);
-    }
+    // the wide kernel (kernels_conv_f16x3_wide.hip: 16 x 16 tiles, ONE workgroup per compute unit) once every compute unit has an item of
+    // its own -- below that the 8 x 16 tiles on two workgroups per unit spread a small layer better (one 256 x 256 slice at 64 channels:
+    // 17.1 us wide against 18.2 narrow; one 128 x 128 slice: 13.4 against 10.3, profiles/conv_f16x3_wide_probe_r06.txt)
+    if (cp_use_wide(conv_wide_mode(), dilation, n, C, H, W, cus)) return launch_conv3x3_f16x3_wide(s, x, w, bias, skip, y, n, C, H, W, relu, fmt);
+    const ConvTiling t = cp_tiling(n, H, W, CP_NARROW, C / CP_CSTEP);
+    ConvArgs a;
+    a.x = x; a.w = w; a.bias = bias; a.skip = skip; a.y = y; a.n = n; a.H = H; a.W = W; a.relu = relu; a.C = C; a.fmt = fmt;
+    a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
     switch (dilation) {
-        case 1: return launch_h3_dil<1>(s, a, items, cus);
-        case 2: return launch_h3_dil<2>(s, a, items, cus);
-        case 3: return launch_h3_dil<3>(s, a, items, cus);
-        case 4: return launch_h3_dil<4>(s, a, items, cus);
-        default: return hipErrorInvalidValue;
+        case 1: return launch_h3_dil<1>(s, a, t.items, cus);
+        case 2: return launch_h3_dil<2>(s, a, t.items, cus);
+        case 3: return launch_h3_dil<3>(s, a, t.items, cus);
+        default: return launch_h3_dil<4>(s, a, t.items, cus);
     }
 }
 
-static int& wide_mode_ref() {
-    static int mode = [] { const char* e = getenv("PNP_CONV_WIDE"); return e ? atoi(e) : -1; }();
+// (atomic, relaxed: pnp_conv3x3_f16x3_set_variant may run while other threads launch; a launch takes the old or the new setting)
+static std::atomic<int>& wide_mode_ref() {
+    static std::atomic<int> mode([] { const char* e = getenv("PNP_CONV_WIDE"); return e ? atoi(e) : -1; }());
     return mode;
 }
-int conv_wide_mode() { return wide_mode_ref(); }
-int conv_set_wide_mode(int m) { int& r = wide_mode_ref(); const int old = r; r = m < 0 ? -1 : m > 0 ? 1 : 0; return old; }
+int conv_wide_mode() { return wide_mode_ref().load(std::memory_order_relaxed); }
+int conv_set_wide_mode(int m) { return wide_mode_ref().exchange(m < 0 ? -1 : m > 0 ? 1 : 0, std::memory_order_relaxed); }
 
 hipError_t launch_conv_pack_w_f16x3(hipStream_t s, const float* w_oihw, float* wfrag, int C) {
-    if (C < 64 || C > 1024 || (C & 63)) return hipErrorInvalidValue;
+    if (cp_check_pack3(C)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_conv_pack_w_h3, dim3((unsigned)(9LL * C * C / 256)), dim3(256), 0, s, w_oihw, reinterpret_cast<_Float16*>(wfrag), C);
     return hipGetLastError();
 }

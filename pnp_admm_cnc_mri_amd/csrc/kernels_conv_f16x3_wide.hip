@@ -147,7 +147,7 @@ __device__ unsigned g_h3wprof[1024 * 8];
 #endif
 
 __global__ __launch_bounds__(WT_THREADS, 2) void k_conv3x3_h3w(ConvArgs a, int nitems) {
-    // ONE LDS array: the input tile, then the three weight buffers
+    // ONE LDS array: the input tile, then the four weight buffers
     __shared__ __attribute__((aligned(16))) float lds[WT_XIN + WT_NBUF * H3_TAP16 * 4 + 64];
     float* const xin = lds;
     float* const lbias = lds + WT_XIN + WT_NBUF * H3_TAP16 * 4;   // the 64 biases of this workgroup's block of output channels (its cb never changes)
@@ -402,23 +402,17 @@ extern "C" int pnp_conv_h3w_prof_read(unsigned* out /* [1024][8] */) {
 
 hipError_t launch_conv3x3_f16x3_wide(hipStream_t s, const float* x, const float* w, const float* bias, const float* skip, float* y,
                                      int n, int C, int H, int W, int relu, int fmt) {
-    if (C < 64 || C > 1024 || (C & 63) || (fmt & ~(CV_FMT_X | CV_FMT_SKIP | CV_FMT_Y))) return hipErrorInvalidValue;
+    if (cp_check_body(n, C, H, W, 1, fmt)) return hipErrorInvalidValue;
+    const int NC = C / CP_CSTEP;
+    const ConvTiling t = cp_tiling(n, H, W, CP_WIDE, NC);              // at most the narrow kernel's items: within the check's bound
     ConvArgs a;
     a.x = x; a.w = w; a.bias = bias; a.skip = skip; a.y = y; a.n = n; a.H = H; a.W = W; a.relu = relu; a.C = C; a.fmt = fmt;
-    a.tiles_x = (W + WT_TX - 1) / WT_TX; a.tiles_y = (H + WT_TY - 1) / WT_TY;
-    const int NC = C >> 6;
-    const long long items = (long long)n * a.tiles_x * a.tiles_y * NC;
-    if (items <= 0 || items > 0x7fffffffLL) return hipErrorInvalidValue;
-    if ((long long)H * W * C * 4 > 0x7fffffffLL) return hipErrorInvalidValue;           // one image must fit a signed 32-bit buffer offset
+    a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
     const int cus = conv_compute_units();
     if (cus <= 0) return hipGetLastError();
-    // persistent workgroups, ONE per compute unit, a multiple of NC of them (a workgroup keeps its block of output channels); every
+    // persistent workgroups, ONE per compute unit, a multiple of NC of them (a workgroup keeps its block of output channels: cp_grid); every
     // workgroup's loop ends: item < nitems, and all eight waves of a workgroup run the same trip counts (the barrier plan)
-    long long grid = cus;
-    grid -= grid % NC;
-    if (grid < NC) grid = NC;
-    if (items < grid) grid = items;                               // items = tiles * NC: a multiple of NC as well
-    hipLaunchKernelGGL(k_conv3x3_h3w, dim3((unsigned)grid), dim3(WT_THREADS), 0, s, a, (int)items);
+    hipLaunchKernelGGL(k_conv3x3_h3w, dim3((unsigned)cp_grid(t.items, 1, cus, NC)), dim3(WT_THREADS), 0, s, a, (int)t.items);
     return hipGetLastError();
 }
 

@@ -24,7 +24,7 @@ struct Pix2F16Args {
     int KC, NB;                         // chunks of 64 along K, blocks of 64 matrix columns
     int y32;
 };
-constexpr int P2F_ROWS = 8, P2F_COLS = 16, P2F_U = 4;             // 16-byte chunks of the A tile per thread
+constexpr int P2F_ROWS = CP_PIX2.ty, P2F_COLS = CP_PIX2.tx, P2F_U = 4;     // the tile (conv_plan.h); 16-byte chunks of the A tile per thread
 constexpr int P2F_TILE = 4 * 32 * H3_STR * 4;                     // bytes: the A tile (128 x 160) lies inside the epilogue's staging area (128 x 68 floats)
 static_assert(P2F_ROWS * P2F_COLS * HF_PS <= P2F_TILE, "the A tile must fit the staging area");
 
@@ -216,24 +216,16 @@ __global__ __launch_bounds__(256) void k_pix2_pack_w_f16(const float* w, _Float1
 }
 
 hipError_t launch_pix2x2_f16(hipStream_t s, const void* x, const void* x2, const void* w, void* y, int n, int C, int H, int W, int up, int y_f32) {
-    if (C < 64 || C > 1024 || (C & 63) || (up && (C & 127))) return hipErrorInvalidValue;
-    if (!up && ((H | W) & 1)) return hipErrorInvalidValue;
+    if (cp_check_pix2(n, C, H, W, up != 0)) return hipErrorInvalidValue;
+    const Pix2Plan p = cp_pix2_plan(n, C, H, W, up != 0);
     Pix2F16Args a;
     a.x = x; a.x2 = x2; a.w = w; a.y = y; a.n = n; a.Hin = H; a.Win = W; a.Cin = C;
-    a.Hout = up ? 2 * H : H / 2; a.Wout = up ? 2 * W : W / 2; a.Cout = up ? C / 2 : 2 * C;
-    a.GH = up ? H : H / 2; a.GW = up ? W : W / 2;
-    a.tiles_x = (a.GW + P2F_COLS - 1) / P2F_COLS; a.tiles_y = (a.GH + P2F_ROWS - 1) / P2F_ROWS;
-    a.KC = (up ? C : 4 * C) >> 6; a.NB = (2 * C) >> 6; a.y32 = y_f32 ? 1 : 0;
-    // (+ 16 rows: the offsets of a tile's rows beyond the image must stay out of the buffer's range, not wrap around 2^32 back into it)
-    if ((long long)(a.Hin + 16) * a.Win * a.Cin * 4 > 0x7fffffffLL || (long long)(a.Hout + 16) * a.Wout * a.Cout * 4 > 0x7fffffffLL) return hipErrorInvalidValue;
-    const long long items = (long long)n * a.tiles_x * a.tiles_y * a.NB;
-    if (items <= 0 || items > 0x7fffffffLL) return hipErrorInvalidValue;
+    a.Hout = p.Hout; a.Wout = p.Wout; a.Cout = p.Cout; a.GH = p.GH; a.GW = p.GW;
+    a.tiles_x = p.t.tiles_x; a.tiles_y = p.t.tiles_y; a.KC = p.KC; a.NB = p.NB; a.y32 = y_f32 ? 1 : 0;
+    const long long items = p.t.items;
     const int cus = conv_compute_units();
     if (cus <= 0) return hipGetLastError();
-    long long grid = 2LL * cus;                                    // persistent workgroups, two per compute unit, a multiple of NB of them
-    grid -= grid % a.NB;
-    if (grid < a.NB) grid = a.NB;
-    if (items < grid) grid = items;                                // items is a multiple of NB as well
+    const long long grid = cp_grid(items, 2, cus, p.NB);         // persistent workgroups, two per compute unit, a multiple of NB of them
     if (up && x2)       hipLaunchKernelGGL((k_pix2x2_f16<true, true>), dim3((unsigned)grid), dim3(CV_THREADS), 0, s, a, (int)items);
     else if (up)        hipLaunchKernelGGL((k_pix2x2_f16<true, false>), dim3((unsigned)grid), dim3(CV_THREADS), 0, s, a, (int)items);
     else if (x2)        hipLaunchKernelGGL((k_pix2x2_f16<false, true>), dim3((unsigned)grid), dim3(CV_THREADS), 0, s, a, (int)items);
@@ -242,7 +234,7 @@ hipError_t launch_pix2x2_f16(hipStream_t s, const void* x, const void* x2, const
 }
 
 hipError_t launch_pix2_pack_w_f16(hipStream_t s, const float* w, void* wfrag, int C, int up) {
-    if (C < 64 || C > 1024 || (C & 63) || (up && (C & 127))) return hipErrorInvalidValue;
+    if (cp_check_pack2(C, up != 0)) return hipErrorInvalidValue;
     const long long n = (long long)(up ? C : 4 * C) * 2 * C;
     hipLaunchKernelGGL(k_pix2_pack_w_f16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, reinterpret_cast<_Float16*>(wfrag), C, up);
     return hipGetLastError();

@@ -29,7 +29,7 @@ struct Pix2Args {
     int GH, GW, tiles_x, tiles_y;      // the tile grid (down: Hout x Wout; up: Hin x Win) and its 8 x 16 tiling
     int KC, NB;                         // chunks of 64 along K, blocks of 64 matrix columns
 };
-constexpr int P2_ROWS = 8, P2_COLS = 16;
+constexpr int P2_ROWS = CP_PIX2.ty, P2_COLS = CP_PIX2.tx;      // the tile (conv_plan.h)
 constexpr int P2_XIN = P2_ROWS * P2_COLS * CV_PS;          // floats of the A tile = of the epilogue's staging area (128 x 68)
 
 template <bool UP, bool X2>
@@ -220,23 +220,16 @@ __global__ __launch_bounds__(256) void k_pix2_pack_w(const float* w, _Float16* w
 }
 
 hipError_t launch_pix2x2_f16x3(hipStream_t s, const float* x, const float* x2, const float* w, float* y, int n, int C, int H, int W, int up) {
-    if (C < 64 || C > 1024 || (C & 63) || (up && (C & 127))) return hipErrorInvalidValue;
-    if (!up && ((H | W) & 1)) return hipErrorInvalidValue;
+    if (cp_check_pix2(n, C, H, W, up != 0)) return hipErrorInvalidValue;
+    const Pix2Plan p = cp_pix2_plan(n, C, H, W, up != 0);
     Pix2Args a;
     a.x = x; a.x2 = x2; a.w = w; a.y = y; a.n = n; a.Hin = H; a.Win = W; a.Cin = C;
-    a.Hout = up ? 2 * H : H / 2; a.Wout = up ? 2 * W : W / 2; a.Cout = up ? C / 2 : 2 * C;
-    a.GH = up ? H : H / 2; a.GW = up ? W : W / 2;
-    a.tiles_x = (a.GW + P2_COLS - 1) / P2_COLS; a.tiles_y = (a.GH + P2_ROWS - 1) / P2_ROWS;
-    a.KC = (up ? C : 4 * C) >> 6; a.NB = (2 * C) >> 6;
-    if ((long long)a.Hin * a.Win * a.Cin * 4 > 0x7fffffffLL || (long long)a.Hout * a.Wout * a.Cout * 4 > 0x7fffffffLL) return hipErrorInvalidValue;
-    const long long items = (long long)n * a.tiles_x * a.tiles_y * a.NB;
-    if (items <= 0 || items > 0x7fffffffLL) return hipErrorInvalidValue;
+    a.Hout = p.Hout; a.Wout = p.Wout; a.Cout = p.Cout; a.GH = p.GH; a.GW = p.GW;
+    a.tiles_x = p.t.tiles_x; a.tiles_y = p.t.tiles_y; a.KC = p.KC; a.NB = p.NB;
+    const long long items = p.t.items;
     const int cus = conv_compute_units();
     if (cus <= 0) return hipGetLastError();
-    long long grid = 2LL * cus;                                    // persistent workgroups, two per compute unit, a multiple of NB of them
-    grid -= grid % a.NB;
-    if (grid < a.NB) grid = a.NB;
-    if (items < grid) grid = items;                                // items is a multiple of NB as well
+    const long long grid = cp_grid(items, 2, cus, p.NB);         // persistent workgroups, two per compute unit, a multiple of NB of them
     if (up && x2)       hipLaunchKernelGGL((k_pix2x2_h3<true, true>), dim3((unsigned)grid), dim3(CV_THREADS), 0, s, a, (int)items);
     else if (up)        hipLaunchKernelGGL((k_pix2x2_h3<true, false>), dim3((unsigned)grid), dim3(CV_THREADS), 0, s, a, (int)items);
     else if (x2)        hipLaunchKernelGGL((k_pix2x2_h3<false, true>), dim3((unsigned)grid), dim3(CV_THREADS), 0, s, a, (int)items);
@@ -245,7 +238,7 @@ hipError_t launch_pix2x2_f16x3(hipStream_t s, const float* x, const float* x2, c
 }
 
 hipError_t launch_pix2_pack_w_f16x3(hipStream_t s, const float* w, float* wfrag, int C, int up) {
-    if (C < 64 || C > 1024 || (C & 63) || (up && (C & 127))) return hipErrorInvalidValue;
+    if (cp_check_pack2(C, up != 0)) return hipErrorInvalidValue;
     const long long pairs = (long long)(up ? C : 4 * C) * 2 * C;
     hipLaunchKernelGGL(k_pix2_pack_w, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, w, reinterpret_cast<_Float16*>(wfrag), C, up);
     return hipGetLastError();

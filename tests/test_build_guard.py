@@ -25,7 +25,7 @@ from conftest import ROOT
 CSRC = os.path.join(ROOT, 'pnp_admm_cnc_mri_amd', 'csrc')
 HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
 SOURCES = ['kernels_slice256.hip', 'kernels_fused256.hip', 'kernels_fused512.hip', 'kernels_generic.hip', 'kernels_conv.hip', 'kernels_conv_f16x3.hip',
-           'kernels_conv_f16x3_wide.hip', 'kernels_pix2x2_f16x3.hip', 'api.hip']
+           'kernels_conv_f16x3_wide.hip', 'kernels_pix2x2_f16x3.hip', 'api.hip', 'api_conv.hip']
 FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-ffp-contract=off']     # = csrc/Makefile CXXFLAGS
 
 import importlib.util
@@ -177,7 +177,7 @@ def test_f16x3_weight_dma_is_older_than_the_loads_counted_behind_it(asm):
 def test_wide_f16x3_kernel_resources(asm):
     """k_conv3x3_h3w (csrc/kernels_conv_f16x3_wide.hip): ONE workgroup of eight waves per compute unit (<= 256 registers, no scratch, 150 KiB
     of LDS), 2 x 9 x 96 half-precision matrix instructions (two instances of the chunk code), inside the compute waves' tap loop nothing but
-    LDS reads, MFMAs, waits and barriers -- the point of the kernel --, and a weight stream (two waves of their own, three buffers) that the compiled
+    LDS reads, MFMAs, waits and barriers -- the point of the kernel --, and a weight stream (two waves of their own, four buffers) that the compiled
     ISA waits for before every barrier, back edges included."""
     ks = {n: k for n, k in kernels_of(asm['kernels_conv_f16x3_wide.hip']).items() if 'k_conv3x3_h3w' in n}
     assert len(ks) == 1, sorted(ks)

@@ -32,6 +32,16 @@ def _rel(a, b):
     return float((a - b).norm() / b.norm())
 
 
+def _assert_grid_is_rounded(env, items, wps, blocks):
+    """The precondition of the cases that exercise the persistent grid's rounding (csrc/conv_plan.h: cp_grid): the `wps` workgroups per
+    compute unit of THIS card are no multiple of the blocks of 64 channels, and there are more items than those workgroups -- so the grid is
+    rounded down and every workgroup loops.  Asserted, not skipped on: 256 compute units give 510 / 255 / 504 workgroups for the shapes below."""
+    cus = C.c_int()
+    env['lib'].check(env['L'].pnp_device_info(0, None, C.byref(cus), None, 0, None, 0))
+    resident = wps * cus.value
+    assert resident % blocks != 0 and items > resident, (cus.value, resident, blocks, items)
+
+
 def _conv(env, x_nhwc, w_oihw, bias, skip, relu, dilation=1, math='f32'):
     torch, L, lib = env['torch'], env['L'], env['lib']
     pack, conv = ((L.pnp_conv3x3_c64_pack, L.pnp_conv3x3_c64_nhwc) if math == 'f32' else
@@ -115,12 +125,37 @@ def test_f16x3_holds_float32_accuracy_over_magnitudes(env, xs, ws):
     assert e16 <= 5e-7 and e16 <= 1.25 * e32, (e16, e32)
 
 
-@pytest.mark.parametrize('ch,n,H,W', [(128, 3, 40, 56), (256, 2, 24, 24), (512, 2, 32, 32), (192, 1, 5, 23), (128, 40, 64, 64), (1024, 1, 9, 9)])
+GRID_CASE = (192, 2, 96, 128)       # 3 blocks: 576 narrow / 288 wide items on 510 / 255 workgroups of 256 compute units -- the grid is rounded down and loops
+
+
+@pytest.mark.parametrize('ch,n,H,W', [(128, 3, 40, 56), (256, 2, 24, 24), (512, 2, 32, 32), (192, 1, 5, 23), (128, 40, 64, 64), (1024, 1, 9, 9), GRID_CASE])
 @pytest.mark.parametrize('variant', ['bias_relu', 'skip'])
 def test_f16x3_wide_layers_against_pytorch(env, ch, n, H, W, variant):
     """C -> C channels, C a multiple of 64 (DRUNet's residual blocks at 128 / 256 / 512 channels, models/network_unet.py:36-58):
     items (tile, 64 output channels) x chunks of 64 input channels.  Shapes off the tile grid, more items than resident
-    workgroups (40 x 32 tiles x 2 blocks), a channel count that is no power of two, the largest count accepted."""
+    workgroups (40 x 32 tiles x 2 blocks), a channel count that is no power of two, the largest count accepted, and GRID_CASE (the
+    kernel is chosen by size here: test_f16x3_grid_rounded_to_the_channel_blocks pins each)."""
+    _f16x3_cc_layer(env, ch, n, H, W, variant)
+
+
+@pytest.mark.parametrize('kernel', [0, 1])
+@pytest.mark.parametrize('variant', ['bias_relu', 'skip'])
+def test_f16x3_grid_rounded_to_the_channel_blocks(env, kernel, variant):
+    """GRID_CASE on the narrow (0) and on the wide (1) kernel, at the tolerance of the list above: more items than resident workgroups, and
+    those no multiple of the three blocks of output channels -- the launch rounds the grid down to a multiple of 3 and every workgroup
+    takes a second item of its own block."""
+    L = env['L']
+    ch, n, H, W = GRID_CASE
+    tile_rows, wps = (16, 1) if kernel else (8, 2)
+    _assert_grid_is_rounded(env, n * ((H + tile_rows - 1) // tile_rows) * ((W + 15) // 16) * (ch // 64), wps, ch // 64)
+    prev = L.pnp_conv3x3_f16x3_set_variant(kernel)
+    try:
+        _f16x3_cc_layer(env, ch, n, H, W, variant)
+    finally:
+        L.pnp_conv3x3_f16x3_set_variant(prev)
+
+
+def _f16x3_cc_layer(env, ch, n, H, W, variant):
     torch, F, L, lib = env['torch'], env['F'], env['L'], env['lib']
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
@@ -251,13 +286,17 @@ def test_hip_backend_makes_no_miopen_call(env, name, backend):
 
 @pytest.mark.parametrize('up,C,n,H,W', [(0, 64, 3, 40, 56), (0, 128, 2, 24, 24), (0, 256, 2, 16, 32), (0, 64, 1, 2, 2), (0, 192, 1, 6, 34),
                                        (1, 128, 3, 20, 28), (1, 256, 2, 12, 12), (1, 512, 2, 8, 16), (1, 128, 1, 1, 1), (1, 384, 1, 3, 17),
-                                       (0, 64, 8, 128, 128), (1, 128, 8, 64, 64)])
+                                       (0, 64, 8, 128, 128), (1, 128, 8, 64, 64), (0, 192, 4, 96, 128), (1, 384, 2, 48, 64)])
 @pytest.mark.parametrize('with_x2', [False, True])
 def test_pix2x2_layers_against_pytorch(env, up, C, n, H, W, with_x2):
     """DRUNet's scale changes on csrc/kernels_pix2x2_f16x3.hip: Conv2d(C, 2C, 2, 2, 0) and ConvTranspose2d(C, C/2, 2, 2, 0), bias-free, NHWC,
     with and without the second input that is added while the operand is staged -- against the float64 PyTorch operator on the same
-    data, at the tolerance of the 3 x 3 layers (one layer <= 2e-6); tiles that overhang the image, one-tile and one-pixel images."""
+    data, at the tolerance of the 3 x 3 layers (one layer <= 2e-6); tiles that overhang the image, one-tile and one-pixel images.  The last
+    two: 576 items in 6 / 12 blocks of matrix columns on two workgroups per compute unit -- the grid is rounded down (510 / 504 of 512)."""
     torch, F, L, lib = env['torch'], env['F'], env['L'], env['lib']
+    if (C, n) in ((192, 4), (384, 2)):
+        gh, gw = (H, W) if up else (H // 2, W // 2)
+        _assert_grid_is_rounded(env, n * ((gh + 7) // 8) * ((gw + 15) // 16) * (2 * C // 64), 2, 2 * C // 64)
     g = torch.Generator(device='cuda').manual_seed(100 * C + 10 * H + up)
     x = torch.randn(n, H, W, C, device='cuda', generator=g)
     x2 = torch.randn(n, H, W, C, device='cuda', generator=g) if with_x2 else None

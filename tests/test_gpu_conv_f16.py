@@ -57,6 +57,19 @@ def _pack(env, w_oihw):
     return w9
 
 
+def _resident(env, wps):
+    cus = C.c_int()
+    env['lib'].check(env['L'].pnp_device_info(0, None, C.byref(cus), None, 0, None, 0))
+    return wps * cus.value
+
+
+def _assert_grid_is_rounded(env, items, wps, blocks):
+    """The precondition of the cases that exercise the persistent grid's rounding (csrc/conv_plan.h: cp_grid): the `wps` workgroups per
+    compute unit of THIS card are no multiple of the blocks of 64 channels, and there are more items than those workgroups.  Asserted, not
+    skipped on."""
+    assert _resident(env, wps) % blocks != 0 and items > _resident(env, wps), (_resident(env, wps), blocks, items)
+
+
 def _conv(env, x_nhwc, w_oihw, bias, skip, relu, dilation=1, fmt=0):
     """x / skip: NHWC, float32 tensors when fmt says so, halves otherwise -> y NHWC (float32 with Y32, else half)"""
     torch, L, lib = env['torch'], env['L'], env['lib']
@@ -134,11 +147,17 @@ def test_dilated_conv3x3_c64_against_float64(env, n, H, W, dilation):
     assert _rel(y1.permute(0, 3, 1, 2), F.conv2d(x1.double(), w.double(), padding=dilation, dilation=dilation)) <= 1e-6
 
 
-@pytest.mark.parametrize('ch,n,H,W', [(128, 3, 40, 56), (256, 2, 24, 24), (512, 2, 32, 32), (192, 1, 5, 23), (128, 40, 64, 64), (1024, 1, 9, 9)])
+@pytest.mark.parametrize('ch,n,H,W', [(128, 3, 40, 56), (256, 2, 24, 24), (512, 2, 32, 32), (192, 1, 5, 23), (128, 40, 64, 64), (1024, 1, 9, 9),
+                                      (192, 2, 96, 128), (320, 2, 96, 128)])
 @pytest.mark.parametrize('variant', ['bias_relu', 'skip'])
 def test_wide_layers_against_float64(env, ch, n, H, W, variant):
-    """C -> C for C = 128 .. 1024 (DRUNet's other scales): the K loop over chunks of 64 input channels, a workgroup per block of 64 output channels"""
+    """C -> C for C = 128 .. 1024 (DRUNet's other scales): the K loop over chunks of 64 input channels, a workgroup per block of 64 output channels.
+    The last two are the shape at which the f16x3 kernels' persistent grid is rounded down to a multiple of the blocks.  This kernel runs THREE
+    workgroups per compute unit at dilation 1, always a multiple of the 3 blocks of C = 192 (576 items on 768 workgroups of 256 units: one
+    trip, nothing to round) -- the rounding needs a block count that does not divide 3 x units: C = 320, 960 items in 5 blocks on 765 of 768."""
     torch, F = env['torch'], env['F']
+    if ch == 320:
+        _assert_grid_is_rounded(env, n * ((H + 7) // 8) * ((W + 15) // 16) * (ch // 64), 3, ch // 64)
     g = torch.Generator(device='cuda').manual_seed(ch + n + H)
     x = torch.randn(n, ch, H, W, device='cuda', generator=g).half()
     w = (torch.randn(ch, ch, 3, 3, device='cuda', generator=g) * (2.0 / (9 * ch)) ** 0.5).half().float()
@@ -237,13 +256,17 @@ def test_the_three_tails_against_float64(env, n, H, W):
 
 @pytest.mark.parametrize('up,ch,n,H,W', [(0, 64, 3, 40, 56), (0, 128, 2, 24, 24), (0, 256, 2, 16, 32), (0, 64, 1, 2, 2), (0, 192, 1, 6, 34),
                                         (1, 128, 3, 20, 28), (1, 256, 2, 12, 12), (1, 512, 2, 8, 16), (1, 128, 1, 1, 1), (1, 384, 1, 3, 17),
-                                        (0, 64, 12, 128, 128), (1, 128, 8, 64, 64)])
+                                        (0, 64, 12, 128, 128), (1, 128, 8, 64, 64), (0, 192, 4, 96, 128), (1, 384, 2, 48, 64)])
 @pytest.mark.parametrize('with_x2', [False, True])
 def test_pix2x2_layers_against_float64(env, up, ch, n, H, W, with_x2):
     """DRUNet's Conv2d(C, 2C, 2, 2) and ConvTranspose2d(C, C/2, 2, 2) on halves, with and without the second input (added in float32,
     rounded to half once, as the operand): float32 output against float64 at the one-layer bar, the half output = its `.half()` bit for bit.
-    (12 x 128 x 128 down: 768 items, 8 x 64 x 64 up: 1024, on 512 persistent workgroups -- the loop's second trip.)"""
+    (12 x 128 x 128 down: 768 items, 8 x 64 x 64 up: 1024, on 512 persistent workgroups -- the loop's second trip.  The last two: 576 items in
+    6 / 12 blocks of matrix columns -- the grid is rounded down to a multiple of the blocks, 510 / 504 of 512.)"""
     torch, F, L, lib = env['torch'], env['F'], env['L'], env['lib']
+    if (ch, n) in ((192, 4), (384, 2)):
+        gh, gw = (H, W) if up else (H // 2, W // 2)
+        _assert_grid_is_rounded(env, n * ((gh + 7) // 8) * ((gw + 15) // 16) * (2 * ch // 64), 2, 2 * ch // 64)
     g = torch.Generator(device='cuda').manual_seed(up * 1000 + ch + H)
     x = torch.randn(n, H, W, ch, device='cuda', generator=g).half()
     x2 = torch.randn(n, H, W, ch, device='cuda', generator=g).half() if with_x2 else None

@@ -16,7 +16,6 @@ plus the dispatch `denoising_step` (S6:18-67 == S3:19-68), the inference wrapper
 reference ships no weights: model_zoo/README.md).
 """
 import hashlib
-import os
 import logging
 import math
 
@@ -24,6 +23,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import hip_layers as HL
+from .hip_layers import HIP_BACKENDS, split_activations, unsplit_activations  # noqa: F401 -- the last two: read from here by tests/test_gpu_conv.py
 
 
 def _conv_stack(in_nc, out_nc, nc, nb, dilations=None):
@@ -39,322 +41,12 @@ def _conv_stack(in_nc, out_nc, nc, nb, dilations=None):
     return nn.Sequential(*L)
 
 
-# ----------------------------------------------------------------------------------------------
-# Optional HIP backends of the denoisers (`Denoiser(backend='hip' | 'hip_f16x3')`): the plain stacks' 64 -> 64 conv3x3 (+ ReLU) layers --
-# 97 % of FFDNet's and DnCNN's arithmetic, IRCNN's dilated ones included -- and DRUNet's residual blocks run on libpnpmri.so with
-# activations in NHWC; the stacks' first (<= 8 -> 64) and last (64 -> <= 4) layers on its direct kernels, so that DnCNN / FDnCNN /
-# FFDNet / IRCNN make no MIOpen call at all.
-#   'hip'        float32 matrix cores (csrc/kernels_conv.hip: 0.77-0.79 of the fp32 matrix peak where MIOpen reaches 0.56-0.59)
-#   'hip_f16x3'  float32 operands as pairs of halves, three exact-product f16 matrix instructions per product, float32 accumulation
-#                (csrc/kernels_conv_f16x3.hip: float32-level error, 1.9-2.6 x the fp32 matrix peak; also DRUNet's 128 / 256 / 512-
-#                channel blocks)
-#   'hip_f16'    HALF precision between the layers (csrc/kernels_conv_f16.hip, kernels_pix2x2_f16.hip): activations stored
-#                as halves, weights rounded to half at pack time, ONE matrix instruction per product, float32 accumulation, one rounding
-#                per layer on store; the network's input, output and first layer stay float32.  A throughput mode: it does NOT meet the
-#                1e-5 parity bar, is opt-in, is never chosen by 'auto', and needs EVERY layer on libpnpmri.so (no mixing with PyTorch layers).
-# Same weights, same state_dict; the default backend is PyTorch-ROCm / MIOpen (the north star's split).
-# ----------------------------------------------------------------------------------------------
-HIP_BACKENDS = ('hip', 'hip_f16x3', 'hip_f16')       # 'hip': float32 matrix cores; 'hip_f16x3': split-half arithmetic on the f16 matrix cores; 'hip_f16': half precision
-
-
-def _hip_math(backend):
-    return {'hip_f16x3': 'f16x3', 'hip_f16': 'f16'}.get(backend, 'f32')
-
-
-# pnp_conv3x3_nhwc_f16's format mask: which tensors are float32 INSTEAD of half (include/pnp_mri.h)
-F16_X_F32, F16_SKIP_F32, F16_Y_F32 = 1, 2, 4
-
-
-# The SPLIT activation format the f16x3 layers hand to each other (include/pnp_mri.h, pnp_conv3x3_nhwc_f16x3_fmt): same shape and bytes
-# as the float32 NHWC tensor, every block of 64 channels stored as [64 hi halves][64 lo halves], value = hi + lo / 2048.
-FMT_X, FMT_SKIP, FMT_Y = 1, 2, 4
-
-
-def split_activations(x_nhwc):
-    """float32 [n][H][W][C] -> the same-shaped float32-typed tensor holding the split format (tests, debugging; the kernels do this
-    in their epilogues)"""
-    n, H, W, Cc = x_nhwc.shape
-    hi = x_nhwc.to(torch.float16)
-    lo = ((x_nhwc - hi.float()) * 2048.0).to(torch.float16)
-    blk = torch.stack((hi.reshape(n, H, W, Cc // 64, 64), lo.reshape(n, H, W, Cc // 64, 64)), dim=4)       # [n][H][W][C/64][2][64] halves
-    return blk.contiguous().view(torch.float32).reshape(n, H, W, Cc)
-
-
-def unsplit_activations(s_nhwc):
-    """the inverse: split format -> float32 values hi + lo / 2048"""
-    n, H, W, Cc = s_nhwc.shape
-    blk = s_nhwc.contiguous().view(torch.float16).reshape(n, H, W, Cc // 64, 2, 64).float()
-    return (blk[..., 0, :] + blk[..., 1, :] / 2048.0).reshape(n, H, W, Cc)
-
-
-def _check_range(t_nhwc, split, where):
-    """PNP_CONV_CHECK_RANGE=1 (bring-up with real KAIR weights): every activation handed to an f16x3 layer must be finite and within the
-    half range -- beyond +-65504 the layer's operands turn into inf / NaN (loudly, but only at the output).  Off by default: it
-    synchronises the stream at every layer."""
-    import os
-    if os.environ.get('PNP_CONV_CHECK_RANGE') != '1':
-        return
-    v = unsplit_activations(t_nhwc) if split else t_nhwc
-    if v.dtype == torch.float16:                                   # backend 'hip_f16': a value that left the half range was STORED as inf
-        if not bool(torch.isfinite(v).all()):
-            raise FloatingPointError("backend='hip_f16': an activation entering %s is not finite: a layer's result left the half range "
-                                     "(|x| <= 65504) or NaN came in" % where)
-        return
-    if not bool(torch.isfinite(v).all()) or float(v.abs().max()) > 65504.:
-        raise FloatingPointError("backend='hip_f16x3': an activation entering %s is not finite or lies outside the half range "
-                                 "(|x| <= 65504): max |x| = %r" % (where, float(torch.nan_to_num(v.abs(), nan=float('inf')).max())))
-
-
-def _hip_body_ok(conv, math='f32'):
-    """a 64 -> 64 conv3x3, stride 1, dilation d in 1..4 with zero padding d: the layers libpnpmri.so's matrix-core kernels take
-    (d = 1: DnCNN / FDnCNN / FFDNet bodies, DRUNet's 64-channel blocks; d = 2..4: IRCNN, models/network_dncnn.py:87-101); the
-    f16x3 kernel also takes C -> C channels for C = 128 .. 1024 in steps of 64 at d = 1 (DRUNet's other scales)"""
-    if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.groups == 1
-            and conv.padding_mode == 'zeros' and conv.dilation[0] == conv.dilation[1] and conv.padding == conv.dilation
-            and conv.in_channels == conv.out_channels):
-        return False
-    if conv.in_channels == 64:
-        return 1 <= conv.dilation[0] <= 4
-    return math in ('f16x3', 'f16') and conv.in_channels % 64 == 0 and 64 < conv.in_channels <= 1024 and conv.dilation[0] == 1
-
-
-def _hip_weights(seq, k, conv, L, stream, math='f32'):
-    """conv.weight packed into the HIP kernel's fragment order (pnp_conv3x3_c64_pack, or pnp_conv3x3_c64_pack_f16x3 for the
-    split-half kernel), rebuilt when the parameter changes (load_state_dict, bank switches).  Kept outside the state_dict."""
-    import ctypes as C
-    from . import _lib
-    cache = seq.__dict__.setdefault('_pnp_hip_w', {})
-    w = conv.weight
-    key = (w.data_ptr(), w._version, str(w.device))
-    hit = cache.get((k, math))
-    if hit is None or hit[0] != key:
-        src = w.detach().contiguous()                          # [out][in][3][3] whatever the parameter's memory format
-        packed = torch.empty(9 * conv.in_channels * conv.out_channels, dtype=torch.float16 if math == 'f16' else torch.float32, device=w.device)
-        if math == 'f16':                                          # rounded to half once, here (round to nearest even)
-            if not bool(torch.isfinite(src).all()) or float(src.abs().max()) > 65504.:
-                raise ValueError("backend='hip_f16': a convolution weight lies outside the half range (|w| <= 65504)")
-            _lib.check(L.pnp_conv3x3_pack_f16(stream, C.c_void_p(src.data_ptr()), C.c_void_p(packed.data_ptr()), conv.in_channels))
-        elif math == 'f16x3':
-            if not bool(torch.isfinite(src).all()) or float(src.abs().max()) > 65504.:
-                raise ValueError("backend='hip_f16x3': a convolution weight lies outside the half range (|w| <= 65504)")
-            _lib.check(L.pnp_conv3x3_pack_f16x3(stream, C.c_void_p(src.data_ptr()), C.c_void_p(packed.data_ptr()), conv.in_channels))
-        else:
-            _lib.check(L.pnp_conv3x3_c64_pack(stream, C.c_void_p(src.data_ptr()), C.c_void_p(packed.data_ptr())))
-        cache[(k, math)] = hit = (key, packed)
-    return hit[1]
-
-
-def _hip_weights2x2(owner, conv, L, stream, transposed, math='f16x3'):
-    """a 2 x 2 stride-2 (transposed) convolution's weight in the fragment order of csrc/kernels_pix2x2_f16x3.hip (math='f16': halves in
-    that of csrc/kernels_pix2x2_f16.hip, under a key of its own), cached like _hip_weights"""
-    import ctypes as C
-    from . import _lib
-    cache = owner.__dict__.setdefault('_pnp_hip_w2', {})
-    w = conv.weight
-    key = (w.data_ptr(), w._version, str(w.device))
-    slot = id(conv) if math == 'f16x3' else (id(conv), math)
-    hit = cache.get(slot)
-    if hit is None or hit[0] != key:
-        src = w.detach().contiguous(memory_format=torch.contiguous_format)
-        if not bool(torch.isfinite(src).all()) or float(src.abs().max()) > 65504.:
-            raise ValueError("backend='hip_%s': a convolution weight lies outside the half range (|w| <= 65504)" % math)
-        packed = torch.empty(src.numel(), dtype=torch.float16 if math == 'f16' else torch.float32, device=w.device)
-        _lib.check((L.pnp_conv2x2_pack_f16 if math == 'f16' else L.pnp_conv2x2_pack_f16x3)(
-            stream, C.c_void_p(src.data_ptr()), C.c_void_p(packed.data_ptr()), conv.in_channels, 1 if transposed else 0))
-        cache[slot] = hit = (key, packed, src)
-    return hit[1]
-
-
-def _hip_oihw(seq, k, conv):
-    """conv.weight as an [out][in][3][3]-contiguous tensor (the parameter may be in channels_last format), cached like the packed
-    weights and rebuilt when the parameter changes."""
-    cache = seq.__dict__.setdefault('_pnp_hip_oihw', {})
-    w = conv.weight
-    key = (w.data_ptr(), w._version, str(w.device))
-    hit = cache.get(k)
-    if hit is None or hit[0] != key:
-        cache[k] = hit = (key, w.detach().contiguous(memory_format=torch.contiguous_format).clone())
-    return hit[1]
-
-
-def _plain3x3(conv):
-    return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros')
-
-
-def hip_stack_forward(seq, x, math='f32', head=None, tail=None):
-    """`seq(x)` for a [Conv3x3, ReLU] * (nb - 1) + Conv3x3 stack on libpnpmri.so's convolution kernels: 64 -> 64 layers on the
-    fp32-MFMA implicit GEMM, a first layer with <= 8 input channels and a last layer with <= 4 output channels on the direct
-    kernels -- DnCNN / FDnCNN / FFDNet then run without a MIOpen call.  Raises if the library or a GPU tensor is missing: no
-    silent fallback to another device; layers the kernels do not cover (other channel counts, dilations) run in PyTorch
-    inside the same call.  math='f16x3': the 64 -> 64 layers in split-half arithmetic on the f16 matrix cores (float32-level
-    results, csrc/kernels_conv_f16x3.hip).
-    head / tail (FFDNet): callables that run the stack's first / last convolution themselves -- `head(conv, relu) -> nhwc tensor`
-    straight from the network's own input, `tail(conv, nhwc) -> result` straight into the network's own output."""
-    import ctypes as C
-    from . import _lib
-    if not (x.is_cuda and x.dtype == torch.float32):
-        raise RuntimeError("Denoiser(backend='hip') needs float32 CUDA tensors")
-    L = _lib.lib()
-    conv64 = L.pnp_conv3x3_c64_nhwc_f16x3 if math == 'f16x3' else L.pnp_conv3x3_c64_nhwc
-    stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    mods = list(seq)
-    h, nhwc, k = x, None, 0                                    # h: NCHW tensor, or nhwc: [n][H][W][64] between HIP layers
-    nhwc_split = False                                         # f16x3: `nhwc` is in the split activation format (between two body layers)
-    while k < len(mods):
-        m = mods[k]
-        relu = k + 1 < len(mods) and isinstance(mods[k + 1], nn.ReLU)
-        if k == 0 and head is not None:
-            nhwc = head(m, relu)
-            k += 2 if relu else 1
-            continue
-        if tail is not None and nhwc is not None and not nhwc_split and k == len(mods) - 1:
-            return tail(m, nhwc)
-        if nhwc is None and _plain3x3(m) and m.in_channels <= 8 and m.out_channels == 64:              # head
-            hc = h.contiguous()
-            n, _, H, W = hc.shape
-            nhwc = torch.empty((n, H, W, 64), dtype=torch.float32, device=h.device)
-            _lib.check(L.pnp_conv3x3_head_nhwc(stream, ptr(hc), ptr(_hip_oihw(seq, k, m)), ptr(m.bias), ptr(nhwc),
-                                               n, m.in_channels, H, W, 1 if relu else 0))
-            k += 2 if relu else 1
-            continue
-        if _hip_body_ok(m):
-            if nhwc is None:
-                hp = h.permute(0, 2, 3, 1)
-                if hp.is_contiguous():                         # channels_last tensor: already NHWC in memory
-                    nhwc = hp
-                else:
-                    nhwc = torch.empty(hp.shape, dtype=h.dtype, device=h.device)
-                    _lib.check(L.pnp_relayout_c64(stream, ptr(h.contiguous()), ptr(nhwc), h.shape[0], h.shape[2], h.shape[3], 1))
-            n, H, W, _ = nhwc.shape
-            if math == 'f16x3':
-                # a body layer followed by another body layer hands its result over in the split activation format
-                kn = k + (2 if relu else 1)
-                out_split = kn < len(mods) and _hip_body_ok(mods[kn])          # the SAME test the branch above applies to the next layer
-                nhwc = _hip_conv64(L, stream, nhwc, _hip_weights(seq, k, m, L, stream, math), m.bias, None, relu, m.dilation[0], math,
-                                   (FMT_X if nhwc_split else 0) | (FMT_Y if out_split else 0))
-                nhwc_split = out_split
-            else:
-                out = torch.empty_like(nhwc)
-                _lib.check(conv64(stream, ptr(nhwc), ptr(_hip_weights(seq, k, m, L, stream, math)), ptr(m.bias), None, ptr(out),
-                                  n, H, W, 1 if relu else 0, m.dilation[0]))
-                nhwc = out
-            k += 2 if relu else 1
-            continue
-        if nhwc is not None and _plain3x3(m) and m.in_channels == 64 and m.out_channels <= 4 and not relu:   # tail
-            n, H, W, _ = nhwc.shape
-            h = torch.empty((n, m.out_channels, H, W), dtype=torch.float32, device=nhwc.device)
-            _lib.check((L.pnp_conv3x3_tail_nchw_f16x3 if math == 'f16x3' else L.pnp_conv3x3_tail_nchw)(
-                stream, ptr(nhwc), ptr(_hip_oihw(seq, k, m)), ptr(m.bias), ptr(h), n, m.out_channels, H, W))
-            nhwc = None
-            k += 1
-            continue
-        if nhwc is not None:
-            h, nhwc = nhwc.permute(0, 3, 1, 2), None           # a channels_last NCHW view: PyTorch takes it as it is
-        h = m(h)
-        k += 1
-    return h if nhwc is None else nhwc.permute(0, 3, 1, 2)
-
-
-def _f16_conv(L, stream, x_nhwc, packed, bias, skip_nhwc, relu, dilation=1, fmt=0):
-    """one C -> C conv3x3 of backend 'hip_f16' (pnp_conv3x3_nhwc_f16): halves in and out unless `fmt` says float32"""
-    import ctypes as C
-    from . import _lib
-    n, H, W, ch = x_nhwc.shape
-    for t, bit in ((x_nhwc, F16_X_F32), (skip_nhwc, F16_SKIP_F32)):
-        if t is not None and t.dtype != (torch.float32 if fmt & bit else torch.float16):
-            raise TypeError('pnp_conv3x3_nhwc_f16: tensor dtype %s does not match fmt=%d' % (t.dtype, fmt))
-    _check_range(x_nhwc, False, 'a %d-channel conv3x3' % ch)
-    out = torch.empty((n, H, W, ch), dtype=torch.float32 if fmt & F16_Y_F32 else torch.float16, device=x_nhwc.device)
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    _lib.check(L.pnp_conv3x3_nhwc_f16(stream, ptr(x_nhwc), ptr(packed), ptr(bias), ptr(skip_nhwc), ptr(out), n, ch, H, W, 1 if relu else 0,
-                                      int(dilation), int(fmt)))
-    return out
-
-
-def hip_f16_stack_forward(seq, x, head=None, tail=None):
-    """`seq(x)` for a fully covered [Conv3x3, ReLU] * (nb - 1) + Conv3x3 stack (hip_covers_stack) in HALF precision (backend 'hip_f16',
-    DESIGN.md 4.12): the first layer in float32 direct arithmetic storing halves, the 64 -> 64 layers on pnp_conv3x3_nhwc_f16, the last
-    layer reading halves and storing float32.  No layer runs anywhere else: an uncovered stack raises.  head / tail: as hip_stack_forward."""
-    import ctypes as C
-    from . import _lib
-    if not (x.is_cuda and x.dtype == torch.float32):
-        raise RuntimeError("Denoiser(backend='hip_f16') needs float32 CUDA tensors")
-    bad = f16_uncovered_stack(seq)
-    if bad:
-        raise ValueError("backend='hip_f16': libpnpmri.so does not take %s" % bad)
-    L = _lib.lib()
-    stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    mods = list(seq)
-    convs = [k for k, m in enumerate(mods) if isinstance(m, nn.Conv2d)]
-    relu_after = lambda k: k + 1 < len(mods) and isinstance(mods[k + 1], nn.ReLU)
-    k0, m0 = convs[0], mods[convs[0]]
-    if head is not None:
-        nhwc = head(m0, relu_after(k0))
-    else:
-        hc = x.contiguous()
-        n, _, H, W = hc.shape
-        nhwc = torch.empty((n, H, W, 64), dtype=torch.float16, device=x.device)
-        _lib.check(L.pnp_conv3x3_head_nhwc_f16(stream, ptr(hc), ptr(_hip_oihw(seq, k0, m0)), ptr(m0.bias), ptr(nhwc), n, m0.in_channels, H, W,
-                                               1 if relu_after(k0) else 0))
-    for k in convs[1:-1]:
-        m = mods[k]
-        nhwc = _f16_conv(L, stream, nhwc, _hip_weights(seq, k, m, L, stream, 'f16'), m.bias, None, relu_after(k), m.dilation[0])
-    kt, mt = convs[-1], mods[convs[-1]]
-    _check_range(nhwc, False, 'the last layer')
-    if tail is not None:
-        return tail(mt, nhwc)
-    n, H, W, _ = nhwc.shape
-    out = torch.empty((n, mt.out_channels, H, W), dtype=torch.float32, device=x.device)
-    _lib.check(L.pnp_conv3x3_tail_nchw_f16(stream, ptr(nhwc), None, ptr(_hip_oihw(seq, kt, mt)), ptr(mt.bias), ptr(out), n, mt.out_channels, H, W))
-    return out
-
-
-def f16_uncovered_stack(seq):
-    """None when backend 'hip_f16' takes every layer of the stack, else a description of the first one it does not take"""
-    mods = list(seq)
-    convs = [k for k, m in enumerate(mods) if isinstance(m, nn.Conv2d)]
-    for k, m in enumerate(mods):
-        if not isinstance(m, (nn.Conv2d, nn.ReLU)):
-            return 'layer %d: %r' % (k, m)
-        if isinstance(m, nn.ReLU) and (k == 0 or not isinstance(mods[k - 1], nn.Conv2d)):
-            return 'layer %d: %r (not behind a convolution)' % (k, m)
-    if len(convs) < 2:
-        return 'a stack of fewer than two convolutions'
-    for n, k in enumerate(convs):
-        m = mods[k]
-        if n == 0:
-            ok = _plain3x3(m) and m.in_channels <= 8 and m.out_channels == 64
-        elif n == len(convs) - 1:
-            ok = _plain3x3(m) and m.in_channels == 64 and m.out_channels <= 4 and not (k + 1 < len(mods) and isinstance(mods[k + 1], nn.ReLU))
-        else:
-            ok = _hip_body_ok(m, 'f16')
-        if not ok:
-            return 'layer %d: %r' % (k, m)
-    return None
-
-
-def hip_covers_stack(seq):
-    """True when every convolution of the stack runs on libpnpmri.so under backend 'hip' (head, 64 -> 64 body, tail): such a
-    forward makes no MIOpen call at all."""
-    convs = [m for m in seq if isinstance(m, nn.Conv2d)]
-    if len(convs) < 2 or any(not isinstance(m, (nn.Conv2d, nn.ReLU)) for m in seq):
-        return False
-    head, tail = convs[0], convs[-1]
-    return (_plain3x3(head) and head.in_channels <= 8 and head.out_channels == 64 and _plain3x3(tail) and tail.in_channels == 64
-            and tail.out_channels <= 4 and all(_hip_body_ok(m) for m in convs[1:-1]))
-
-
 class _PlainStack(nn.Module):
-    """shared by DnCNN / FDnCNN / FFDNet: `self.model` is the conv stack, `backend` selects who runs its body"""
+    """shared by DnCNN / FDnCNN / FFDNet / IRCNN: `self.model` is the conv stack, `backend` selects who runs it (hip_layers.stack_forward)"""
     backend = 'torch'
 
     def _stack(self, x):
-        if self.backend == 'hip_f16':
-            return hip_f16_stack_forward(self.model, x)
-        return hip_stack_forward(self.model, x, _hip_math(self.backend)) if self.backend in HIP_BACKENDS else self.model(x)
+        return HL.stack_forward(self.model, x, self.backend) if self.backend in HIP_BACKENDS else self.model(x)
 
 
 class DnCNN(_PlainStack):
@@ -390,40 +82,19 @@ class FFDNet(_PlainStack):
         self.model = _conv_stack(in_nc * 4 + 1, out_nc * 4, nc, nb)
 
     def _fused_ok(self, x, sigma):
-        """backend 'hip_f16x3', gray in and out, every layer on libpnpmri.so: the pad / pixel-unshuffle / concatenation in front of the stack
-        and the pixel-shuffle / crop behind it are folded into the first and last layer's kernels (pnp_ffdnet_head_nhwc, pnp_ffdnet_tail_f16x3)"""
-        convs = [m for m in self.model if isinstance(m, nn.Conv2d)]
-        return (self.backend in ('hip_f16x3', 'hip_f16') and x.is_cuda and x.dtype == torch.float32 and x.shape[1] == 1 and hip_covers_stack(self.model)
-                and convs[0].in_channels == 5 and convs[-1].out_channels == 4 and sigma.numel() in (1, x.shape[0]))
+        """backends 'hip_f16x3' / 'hip_f16', gray in and out, every layer on libpnpmri.so: the pad / pixel-unshuffle / concatenation in front
+        of the stack and the pixel-shuffle / crop behind it are folded into the first and last layer's kernels (hip_layers.stack_plan)"""
+        return (self.backend in HIP_BACKENDS and x.is_cuda and x.dtype == torch.float32 and x.shape[1] == 1 and sigma.numel() in (1, x.shape[0])
+                and HL.stack_plan(self.model, self.backend, ffdnet=True)[0][0] == 'ffdnet_head')
 
     def _forward_fused(self, x, sigma, out=None):
-        import ctypes as C
-        from . import _lib
-        L = _lib.lib()
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         xc = x.contiguous()
-        n, _, h, w = xc.shape
         sg = sigma.to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
         if out is None:
             out = torch.empty_like(xc)
         elif not (out.is_contiguous() and out.shape == xc.shape and out.dtype == torch.float32 and out.device == x.device):
             raise ValueError('FFDNet: `out` must be a contiguous float32 tensor of the input\'s shape on its device')
-
-        f16 = self.backend == 'hip_f16'
-
-        def head(conv, relu):
-            y = torch.empty((n, (h + 1) // 2, (w + 1) // 2, 64), dtype=torch.float16 if f16 else torch.float32, device=x.device)
-            _lib.check((L.pnp_ffdnet_head_nhwc_f16 if f16 else L.pnp_ffdnet_head_nhwc)(stream, ptr(xc), ptr(sg), 1 if sg.numel() > 1 else 0, ptr(_hip_oihw(self.model, 0, conv)), ptr(conv.bias),
-                                              ptr(y), n, h, w, 1 if relu else 0))
-            return y
-
-        def tail(conv, nhwc):
-            _lib.check((L.pnp_ffdnet_tail_f16 if f16 else L.pnp_ffdnet_tail_f16x3)(stream, ptr(nhwc), ptr(_hip_oihw(self.model, len(self.model) - 1, conv)), ptr(conv.bias), ptr(out), n, h, w))
-            return out
-        if f16:
-            return hip_f16_stack_forward(self.model, xc, head=head, tail=tail)
-        return hip_stack_forward(self.model, xc, 'f16x3', head=head, tail=tail)
+        return HL.stack_forward(self.model, xc, self.backend, sg, out)
 
     def forward(self, x, sigma, out=None):
         """sigma: [B,1,1,1] (or [1,1,1,1], broadcast over the batch -- the reference's
@@ -440,33 +111,10 @@ class FFDNet(_PlainStack):
         return x if out is None else out.copy_(x)
 
 
-def _hip_conv64(L, stream, x_nhwc, packed, bias, skip_nhwc, relu, dilation=1, math='f32', fmt=0):
-    import ctypes as C
-    from . import _lib
-    out = torch.empty_like(x_nhwc)
-    n, H, W, ch = x_nhwc.shape
-    if math == 'f16x3':
-        _check_range(x_nhwc, bool(fmt & FMT_X), 'a %d-channel conv3x3' % ch)
-    if fmt:                                                        # f16x3 only: tensors in the split activation format
-        _lib.check(L.pnp_conv3x3_nhwc_f16x3_fmt(
-            stream, C.c_void_p(x_nhwc.data_ptr()), C.c_void_p(packed.data_ptr()), None if bias is None else C.c_void_p(bias.data_ptr()),
-            None if skip_nhwc is None else C.c_void_p(skip_nhwc.data_ptr()), C.c_void_p(out.data_ptr()), n, ch, H, W, 1 if relu else 0, int(dilation), int(fmt)))
-        return out
-    if ch != 64:                                                   # DRUNet's 128- / 256- / 512-channel blocks: f16x3 only (_hip_body_ok)
-        _lib.check(L.pnp_conv3x3_nhwc_f16x3(
-            stream, C.c_void_p(x_nhwc.data_ptr()), C.c_void_p(packed.data_ptr()), None if bias is None else C.c_void_p(bias.data_ptr()),
-            None if skip_nhwc is None else C.c_void_p(skip_nhwc.data_ptr()), C.c_void_p(out.data_ptr()), n, ch, H, W, 1 if relu else 0))
-        return out
-    _lib.check((L.pnp_conv3x3_c64_nhwc_f16x3 if math == 'f16x3' else L.pnp_conv3x3_c64_nhwc)(stream, C.c_void_p(x_nhwc.data_ptr()), C.c_void_p(packed.data_ptr()),
-        None if bias is None else C.c_void_p(bias.data_ptr()), None if skip_nhwc is None else C.c_void_p(skip_nhwc.data_ptr()),
-        C.c_void_p(out.data_ptr()), n, H, W, 1 if relu else 0, int(dilation)))
-    return out
-
-
 class _ResBlock(nn.Module):
-    """x + conv(relu(conv(x))), bias-free (models/basicblock.py:213-225, mode 'CRC').  With backend 'hip' the 64-channel
-    blocks (DRUNet's full-resolution scale: 28 % of its arithmetic, where MIOpen's fp32 kernels are at their slowest) run on
-    libpnpmri.so's conv kernel, the residual add fused into the second convolution's epilogue."""
+    """x + conv(relu(conv(x))), bias-free (models/basicblock.py:213-225, mode 'CRC').  With a HIP backend the blocks its kernels take
+    (64 channels: DRUNet's full-resolution scale, 28 % of its arithmetic, where MIOpen's fp32 kernels are at their slowest; every
+    scale under 'hip_f16x3' / 'hip_f16') run on libpnpmri.so, the residual add fused into the second convolution's epilogue."""
     backend = 'torch'
 
     def __init__(self, nc):
@@ -475,61 +123,31 @@ class _ResBlock(nn.Module):
                                  nn.Conv2d(nc, nc, 3, 1, 1, bias=False))
 
     def hip_ok(self, backend=None):
-        be = backend or self.backend                                   # backend=: "would it, under that backend?" (auto_backend)
-        return be in HIP_BACKENDS and _hip_body_ok(self.res[0], _hip_math(be)) and _hip_body_ok(self.res[2], _hip_math(be))
+        return HL.block_ok(self, backend or self.backend)             # backend=: "would it, under that backend?"
 
-    def forward_nhwc(self, xn, in_split=False, out_split=False):
-        """the block on a contiguous [n][H][W][C] tensor, on libpnpmri.so (hip_ok() must hold).  Under 'hip_f16x3' the tensor between
-        the block's two convolutions is in the split activation format (the first convolution splits its outputs once, the second
-        copies halves into its operand tile); in_split / out_split: so are the block's input / output -- a chain of blocks hands
-        split tensors from one to the next."""
-        import ctypes as C
-        from . import _lib
-        if not (xn.is_cuda and xn.dtype == torch.float32):
-            raise RuntimeError("Denoiser(backend='hip') needs float32 CUDA tensors")
-        L = _lib.lib()
-        stream = C.c_void_p(torch.cuda.current_stream(xn.device).cuda_stream)
-        math = _hip_math(self.backend)
-        f16 = math == 'f16x3'
-        if (in_split or out_split) and not f16:
-            raise ValueError('the split activation format belongs to the f16x3 kernels')
-        f0 = (FMT_Y | (FMT_X if in_split else 0)) if f16 else 0
-        f2 = (FMT_X | (FMT_SKIP if in_split else 0) | (FMT_Y if out_split else 0)) if f16 else 0
-        h = _hip_conv64(L, stream, xn, _hip_weights(self.res, 0, self.res[0], L, stream, math), self.res[0].bias, None, True, 1, math, f0)
-        return _hip_conv64(L, stream, h, _hip_weights(self.res, 2, self.res[2], L, stream, math), self.res[2].bias, xn, False, 1, math, f2)
-
-    def forward_nhwc_f16(self, xn, f32_io=False):
-        """the block under backend 'hip_f16' on a contiguous [n][H][W][C] tensor of halves (f32_io: of float32, in and out -- the block
-        called on its own; its input is then rounded to half as the first convolution's operand and added unrounded as the skip)"""
-        import ctypes as C
-        from . import _lib
-        if not (xn.is_cuda and xn.dtype == (torch.float32 if f32_io else torch.float16)):
-            raise RuntimeError("Denoiser(backend='hip_f16') needs CUDA tensors (float32 at the network's boundary, halves between layers)")
-        L = _lib.lib()
-        stream = C.c_void_p(torch.cuda.current_stream(xn.device).cuda_stream)
-        h = _f16_conv(L, stream, xn, _hip_weights(self.res, 0, self.res[0], L, stream, 'f16'), self.res[0].bias, None, True, 1, F16_X_F32 if f32_io else 0)
-        return _f16_conv(L, stream, h, _hip_weights(self.res, 2, self.res[2], L, stream, 'f16'), self.res[2].bias, xn, False, 1,
-                         (F16_SKIP_F32 | F16_Y_F32) if f32_io else 0)
+    def forward_nhwc(self, ctx, xn, entry0, fmt0, entry2, fmt2):
+        """the block on a contiguous [n][H][W][C] tensor, on libpnpmri.so; entry points and formats: hip_layers.block_calls"""
+        be = HL.BACKENDS[self.backend]
+        h = HL.conv3x3(ctx, be, entry0, xn, self.res[0], None, True, fmt0)
+        return HL.conv3x3(ctx, be, entry2, h, self.res[2], xn, False, fmt2)
 
     def forward(self, x):
-        if self.backend == 'hip_f16':
-            if not self.hip_ok():
-                raise ValueError("backend='hip_f16': libpnpmri.so does not take %r" % self.res)
-            xn = x.permute(0, 2, 3, 1)
-            return self.forward_nhwc_f16(xn if xn.is_contiguous() else xn.contiguous(), f32_io=True).permute(0, 3, 1, 2)
         if self.hip_ok():
+            ctx = HL.lib_ctx(x, boundary=True)
             xn = x.permute(0, 2, 3, 1)
             if not xn.is_contiguous():
                 xn = xn.contiguous()                           # NCHW-contiguous input: one copy; channels_last tensors pass as they are
-            return self.forward_nhwc(xn).permute(0, 3, 1, 2)   # a channels_last NCHW view
+            return self.forward_nhwc(ctx, xn, *HL.block_calls(HL.BACKENDS[self.backend], self)).permute(0, 3, 1, 2)   # a channels_last NCHW view
+        if self.backend == 'hip_f16':
+            raise ValueError("backend='hip_f16': libpnpmri.so does not take %r" % self.res)
         return x + self.res(x)
 
 
 class UNetRes(nn.Module):
     """DRUNet: 4 scales, 4 residual blocks each, stride-2 conv down, 2x2 transposed conv up, no bias.  With a HIP backend the
-    first (2 -> 64) and last (64 -> 1) convolution run on libpnpmri.so's direct kernels as well; under 'hip_f16x3' so do the 2 x 2
-    strided / transposed convolutions between the scales (csrc/kernels_pix2x2_f16x3.hip) and the skip sums: no MIOpen call is left
-    (hip_covers); under 'hip' (float32 matrix cores: 64-channel blocks only) the other layers stay with PyTorch."""
+    first (2 -> 64) and last (64 -> 1) convolution run on libpnpmri.so's direct kernels as well; under 'hip_f16x3' / 'hip_f16' so do
+    the 2 x 2 strided / transposed convolutions between the scales (csrc/kernels_pix2x2_*.hip) and the skip sums: no MIOpen call is
+    left (hip_covers); under 'hip' (float32 matrix cores: 64-channel blocks only) the other layers stay with PyTorch."""
     backend = 'torch'
 
     def __init__(self, in_nc=2, out_nc=1, nc=(64, 128, 256, 512), nb=4):
@@ -545,145 +163,45 @@ class UNetRes(nn.Module):
         self.m_up1 = nn.Sequential(nn.ConvTranspose2d(nc[1], nc[0], 2, 2, 0, bias=False), *rb(nc[0]))
         self.m_tail = nn.Conv2d(nc[0], out_nc, 3, 1, 1, bias=False)
 
-    def _hip_ends(self, x0):
-        return (self.backend in HIP_BACKENDS and x0.is_cuda and x0.dtype == torch.float32 and _plain3x3(self.m_head)
-                and self.m_head.in_channels <= 8 and self.m_head.out_channels == 64 and _plain3x3(self.m_tail)
-                and self.m_tail.in_channels == 64 and self.m_tail.out_channels <= 4)
-
     def hip_covers(self, H=None, W=None, backend=None):
-        """True when EVERY convolution of the U-Net runs on libpnpmri.so under backend 'hip_f16x3': first / last layer, all residual
-        blocks, the three 2 x 2 stride-2 convolutions and the three 2 x 2 transposed ones (csrc/kernels_pix2x2_f16x3.hip) -- such a
-        forward makes no MIOpen call at all.  H, W (if given) must survive three halvings."""
-        if (backend or self.backend) not in ('hip_f16x3', 'hip_f16') or (H is not None and (H % 8 or W % 8)):      # backend=: "would it, under that backend?" (auto_backend)
-            return False
-        if not (_plain3x3(self.m_head) and self.m_head.in_channels <= 8 and self.m_head.out_channels == 64 and self.m_head.bias is None
-                and _plain3x3(self.m_tail) and self.m_tail.in_channels == 64 and self.m_tail.out_channels <= 4):
-            return False
-        for seq in (self.m_down1, self.m_down2, self.m_down3):
-            d = seq[-1]
-            if not (isinstance(d, nn.Conv2d) and d.kernel_size == (2, 2) and d.stride == (2, 2) and d.padding == (0, 0) and d.bias is None
-                    and d.groups == 1 and d.dilation == (1, 1) and d.out_channels == 2 * d.in_channels and d.in_channels % 64 == 0 and d.in_channels <= 1024
-                    and all(isinstance(m, _ResBlock) and m.hip_ok(backend) for m in seq[:-1])):
-                return False
-        for seq in (self.m_up3, self.m_up2, self.m_up1):
-            u = seq[0]
-            if not (isinstance(u, nn.ConvTranspose2d) and u.kernel_size == (2, 2) and u.stride == (2, 2) and u.padding == (0, 0) and u.bias is None
-                    and u.output_padding == (0, 0) and u.groups == 1 and u.dilation == (1, 1) and 2 * u.out_channels == u.in_channels
-                    and u.in_channels % 128 == 0 and u.in_channels <= 1024 and all(isinstance(m, _ResBlock) and m.hip_ok(backend) for m in seq[1:])):
-                return False
-        return all(isinstance(m, _ResBlock) and m.hip_ok(backend) for m in self.m_body)
+        """True when EVERY layer of the U-Net runs on libpnpmri.so (hip_layers.unet_plan has no PyTorch step): such a forward makes no
+        MIOpen call at all.  H, W (if given) must survive three halvings.  backend=: "would it, under that backend?" """
+        be = backend or self.backend
+        return be in HIP_BACKENDS and HL.uncovered(HL.unet_plan(self, be, H, W)) is None
 
-    def _forward_f16x3(self, x0):
-        """models/network_unet.py:123-136 with every tensor NHWC and every layer on libpnpmri.so; the four skip sums are formed inside the
-        kernel that consumes them (transposed convolution / last layer) and never go to memory."""
-        import ctypes as C
-        from . import _lib
-        L = _lib.lib()
-        stream = C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        xc = x0.contiguous()
-        n, _, H, W = xc.shape
-        x1 = torch.empty((n, H, W, 64), dtype=torch.float32, device=x0.device)
-        _lib.check(L.pnp_conv3x3_head_nhwc(stream, ptr(xc), ptr(_hip_oihw(self, 'head', self.m_head)), None, ptr(x1), n, self.m_head.in_channels, H, W, 0))
-
-        def scale(conv, t, t2, up):
-            c = conv.in_channels
-            nn_, h, w, _ = t.shape
-            out = torch.empty((nn_, 2 * h, 2 * w, c // 2) if up else (nn_, h // 2, w // 2, 2 * c), dtype=torch.float32, device=t.device)
-            wp = _hip_weights2x2(self, conv, L, stream, up)
-            _lib.check((L.pnp_convT2x2s2_nhwc_f16x3 if up else L.pnp_conv2x2s2_nhwc_f16x3)(stream, ptr(t), ptr(t2), ptr(wp), ptr(out), nn_, c, h, w))
-            return out
-
-        def blocks(ms, t):
-            """a run of residual blocks: float32 in, float32 out, split tensors in between"""
-            for k, m in enumerate(ms):
-                t = m.forward_nhwc(t, in_split=k > 0, out_split=k + 1 < len(ms))
-            return t
-
-        def down(seq, t):
-            return scale(seq[-1], blocks(seq[:-1], t), None, False)
-
-        def up(seq, t, skip):
-            t = scale(seq[0], t, skip, True)                   # m_up(x + x_skip): the sum is formed while the operand is staged
-            return blocks(seq[1:], t)
-
-        x2 = down(self.m_down1, x1)
-        x3 = down(self.m_down2, x2)
-        x4 = down(self.m_down3, x3)
-        x = blocks(self.m_body, x4)
-        x = up(self.m_up3, x, x4)
-        x = up(self.m_up2, x, x3)
-        x = up(self.m_up1, x, x2)
-        out = torch.empty((n, self.m_tail.out_channels, H, W), dtype=torch.float32, device=x0.device)
-        _lib.check(L.pnp_conv3x3_tail_add_nchw_f16x3(stream, ptr(x), ptr(x1), ptr(_hip_oihw(self, 'tail', self.m_tail)), ptr(self.m_tail.bias), ptr(out),
-                                                     n, self.m_tail.out_channels, H, W))
-        return out
-
-    def _forward_f16(self, x0):
-        """the same walk under backend 'hip_f16': halves between the layers, the skip sums formed in float32 inside the
-        kernel that consumes them and rounded to half once, as its operand"""
-        import ctypes as C
-        from . import _lib
-        L = _lib.lib()
-        stream = C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        xc = x0.contiguous()
-        n, _, H, W = xc.shape
-        x1 = torch.empty((n, H, W, 64), dtype=torch.float16, device=x0.device)
-        _lib.check(L.pnp_conv3x3_head_nhwc_f16(stream, ptr(xc), ptr(_hip_oihw(self, 'head', self.m_head)), None, ptr(x1), n, self.m_head.in_channels, H, W, 0))
-
-        def scale(conv, t, t2, up):
-            c = conv.in_channels
-            nn_, h, w, _ = t.shape
-            _check_range(t, False, 'a 2 x 2 convolution')
-            out = torch.empty((nn_, 2 * h, 2 * w, c // 2) if up else (nn_, h // 2, w // 2, 2 * c), dtype=torch.float16, device=t.device)
-            wp = _hip_weights2x2(self, conv, L, stream, up, 'f16')
-            _lib.check((L.pnp_convT2x2s2_nhwc_f16 if up else L.pnp_conv2x2s2_nhwc_f16)(stream, ptr(t), ptr(t2), ptr(wp), ptr(out), nn_, c, h, w, 0))
-            return out
-
-        def blocks(ms, t):
-            for m in ms:
-                t = m.forward_nhwc_f16(t)
-            return t
-
-        x2 = scale(self.m_down1[-1], blocks(self.m_down1[:-1], x1), None, False)
-        x3 = scale(self.m_down2[-1], blocks(self.m_down2[:-1], x2), None, False)
-        x4 = scale(self.m_down3[-1], blocks(self.m_down3[:-1], x3), None, False)
-        x = blocks(self.m_body, x4)
-        x = blocks(self.m_up3[1:], scale(self.m_up3[0], x, x4, True))      # m_up(x + x_skip)
-        x = blocks(self.m_up2[1:], scale(self.m_up2[0], x, x3, True))
-        x = blocks(self.m_up1[1:], scale(self.m_up1[0], x, x2, True))
-        _check_range(x, False, 'the last layer')
-        out = torch.empty((n, self.m_tail.out_channels, H, W), dtype=torch.float32, device=x0.device)
-        _lib.check(L.pnp_conv3x3_tail_nchw_f16(stream, ptr(x), ptr(x1), ptr(_hip_oihw(self, 'tail', self.m_tail)), ptr(self.m_tail.bias), ptr(out),
-                                               n, self.m_tail.out_channels, H, W))
-        return out
+    def _forward_nhwc(self, x0, plan):
+        """models/network_unet.py:123-136 by a plan without a PyTorch step: every tensor NHWC (halves under 'hip_f16'), the four skip
+        sums formed inside the kernel that consumes them (transposed convolution / last layer), never in memory"""
+        ctx, be = HL.lib_ctx(x0, boundary=True), HL.BACKENDS[self.backend]
+        kept = {}                                              # results a later layer adds as its skip, by the step that made them
+        for kind, where, m, *a in plan:
+            if kind == 'block':
+                t = m.forward_nhwc(ctx, t, *a)
+            elif kind == 'down':
+                t = kept[where] = HL.conv2x2(ctx, be, a[0], t, None, m, False)
+            elif kind == 'up':
+                t = HL.conv2x2(ctx, be, a[0], t, kept[a[1]], m, True)      # m_up(x + x_skip)
+            elif kind == 'head':
+                t = kept[where] = HL.head(ctx, be, a[0], x0, m, a[1])
+            else:
+                return HL.tail(ctx, be, a[0], t, kept[a[1]], m)
 
     def forward(self, x0):
+        plan = None
+        if self.backend in HIP_BACKENDS and x0.is_cuda and x0.dtype == torch.float32:
+            plan = HL.unet_plan(self, self.backend, x0.shape[-2], x0.shape[-1])
+            if HL.uncovered(plan) is None:
+                return self._forward_nhwc(x0, plan)
         if self.backend == 'hip_f16':                          # all of it on libpnpmri.so, or an error: no mixing with PyTorch layers
-            if not (x0.is_cuda and x0.dtype == torch.float32):
+            if plan is None:
                 raise RuntimeError("Denoiser(backend='hip_f16') needs float32 CUDA tensors")
-            if not self.hip_covers(x0.shape[-2], x0.shape[-1]):
-                raise ValueError("backend='hip_f16': libpnpmri.so does not take this U-Net at %d x %d (every layer must be one it takes, "
-                                 "H and W multiples of 8)" % (x0.shape[-2], x0.shape[-1]))
-            return self._forward_f16(x0)
-        if x0.is_cuda and x0.dtype == torch.float32 and self.hip_covers(x0.shape[-2], x0.shape[-1]):
-            return self._forward_f16x3(x0)
-        hip = self._hip_ends(x0)
-        if hip:
-            import ctypes as C
-            from . import _lib
-            L = _lib.lib()
-            stream = C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)
-            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-            xc = x0.contiguous()
-            n, _, H, W = xc.shape
-            nhwc = torch.empty((n, H, W, 64), dtype=torch.float32, device=x0.device)
-            _lib.check(L.pnp_conv3x3_head_nhwc(stream, ptr(xc), ptr(_hip_oihw(self, 'head', self.m_head)), ptr(self.m_head.bias), ptr(nhwc),
-                                               n, self.m_head.in_channels, H, W, 0))
-            x1 = nhwc.permute(0, 3, 1, 2)                      # a channels_last NCHW view
-        else:
-            x1 = self.m_head(x0)
+            raise ValueError("backend='hip_f16': libpnpmri.so does not take %s of this U-Net at %d x %d (every layer must be one it takes, "
+                             "H and W multiples of 8)" % (HL.uncovered(plan), x0.shape[-2], x0.shape[-1]))
+        # the mixed forward: the ends by the plan, the blocks each on their own (_ResBlock.forward), the rest PyTorch
+        head, tail = (plan[0], plan[-1]) if plan else (('torch',), ('torch',))
+        if plan:
+            ctx, be = HL.lib_ctx(x0, boundary=True), HL.BACKENDS[self.backend]
+        x1 = HL.head(ctx, be, head[3], x0, self.m_head, False).permute(0, 3, 1, 2) if head[0] == 'head' else self.m_head(x0)     # a channels_last NCHW view
         x2 = self.m_down1(x1)
         x3 = self.m_down2(x2)
         x4 = self.m_down3(x3)
@@ -692,35 +210,19 @@ class UNetRes(nn.Module):
         x = self.m_up2(x + x3)
         x = self.m_up1(x + x2)
         x = x + x1
-        if hip:
-            xn = x.permute(0, 2, 3, 1)
-            if not xn.is_contiguous():
-                xn = xn.contiguous()
-            n, H, W, _ = xn.shape
-            out = torch.empty((n, self.m_tail.out_channels, H, W), dtype=torch.float32, device=x.device)
-            _lib.check((L.pnp_conv3x3_tail_nchw_f16x3 if self.backend == 'hip_f16x3' else L.pnp_conv3x3_tail_nchw)(
-                stream, ptr(xn), ptr(_hip_oihw(self, 'tail', self.m_tail)), ptr(self.m_tail.bias), ptr(out), n, self.m_tail.out_channels, H, W))
-            return out
-        return self.m_tail(x)
+        if tail[0] != 'tail':
+            return self.m_tail(x)
+        xn = x.permute(0, 2, 3, 1)
+        return HL.tail(ctx, be, tail[3], xn if xn.is_contiguous() else xn.contiguous(), None, self.m_tail)
 
 
-def f16_uncovered_unet(model):
-    """a description of the first layer of a UNetRes that backend 'hip_f16' does not take (UNetRes.hip_covers says whether there is one)"""
-    for name, m in model.named_modules():
-        if isinstance(m, _ResBlock) and not m.hip_ok('hip_f16'):
-            return '%s: %r' % (name, m.res)
-    for name in ('m_head', 'm_tail'):
-        m = getattr(model, name)
-        if not (_plain3x3(m) and (m.bias is None or name == 'm_tail')):
-            return '%s: %r' % (name, m)
-    for name in ('m_down1', 'm_down2', 'm_down3', 'm_up3', 'm_up2', 'm_up1', 'm_body'):
-        for k, m in enumerate(getattr(model, name)):
-            if not isinstance(m, _ResBlock):
-                ok = ((isinstance(m, nn.ConvTranspose2d) and name.startswith('m_up') and k == 0)
-                      or (type(m) is nn.Conv2d and name.startswith('m_down') and k == len(getattr(model, name)) - 1))
-                if not (ok and m.kernel_size == (2, 2) and m.stride == (2, 2) and m.padding == (0, 0) and m.bias is None):
-                    return '%s.%d: %r' % (name, k, m)
-    return 'this U-Net (channel counts or layer order are not DRUNet\'s)'
+def hip_plan(model, backend, H=None, W=None):
+    """hip_layers' classification of `model`'s layers under a HIP backend (H, W: of the tensor a U-Net is called with)"""
+    if isinstance(model, UNetRes):
+        return HL.unet_plan(model, backend, H, W)
+    if isinstance(model, _PlainStack):
+        return HL.stack_plan(model.model, backend, ffdnet=isinstance(model, FFDNet))
+    return [('torch', 'a %s' % type(model).__name__, None)]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -923,7 +425,7 @@ def forward_flops(den, H, W, device, detail=False):
         else:
             n = out.numel() * (m.in_channels // m.groups) * kh * kw
         macs[0] += n
-        if isinstance(m, nn.Conv2d) and (_hip_body_ok(m, 'f16x3') or (_plain3x3(m) and m.in_channels == 64 and m.out_channels <= 4)):
+        if HL._hip_body_ok(m, 'f16x3') or HL._hip_tail_ok(m):
             macs[1] += n
 
     hs = [m.register_forward_hook(hook) for m in den.model.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.ConvTranspose2d))]
@@ -946,7 +448,7 @@ def auto_backend(model, device=None, bank=None, cnn_dtype=None, shape=None):
     """What `cnn_backend='auto'` (the entry points' default since round 6) resolves to: ('hip_f16x3' | 'torch', reason).
     'hip_f16x3' -- the split-half matrix-core kernels of libpnpmri.so, held to the same goldens and bars as the PyTorch / MIOpen backend at
     every run length (tests/test_gpu_pnp.py) -- when (a) the device is a gfx950 part, (b) EVERY convolution of the network is one the
-    library takes (hip_covers_stack / UNetRes.hip_covers: otherwise part of the forward would still be MIOpen's), (c) every weight -- of
+    library takes (hip_plan has no PyTorch step: otherwise part of the forward would still be MIOpen's), (c) every weight -- of
     every model of an IRCNN bank -- is finite and inside the half range, (d) float32 arithmetic is asked for, (e) the slices' shape (H, W),
     if given, is a multiple of 8 on both sides (the shapes the split-half kernels are held to).  'torch' otherwise."""
     if cnn_dtype not in (None, 'fp32'):
@@ -959,18 +461,12 @@ def auto_backend(model, device=None, bank=None, cnn_dtype=None, shape=None):
     arch = getattr(torch.cuda.get_device_properties(dev), 'gcnArchName', '')
     if not arch.startswith('gfx950'):
         return 'torch', 'device is %s, the kernels are built for gfx950' % (arch or 'unknown')
-    if isinstance(model, UNetRes):
-        covered = model.hip_covers(backend='hip_f16x3')
-    elif isinstance(model, _PlainStack):
-        covered = hip_covers_stack(model.model)
-    else:
-        covered = False
-    if not covered:
+    if HL.uncovered(hip_plan(model, 'hip_f16x3')):
         return 'torch', 'the network has layers libpnpmri.so does not take'
     sds = [model.state_dict()] + ([bank[k] for k in bank] if bank else [])
     for sd in sds:
         for k, v in sd.items():
-            if torch.is_floating_point(v) and (not bool(torch.isfinite(v).all()) or float(v.abs().max()) > 65504.):
+            if torch.is_floating_point(v) and not HL.in_half_range(v):
                 return 'torch', 'weight %s lies outside the half range' % k
     return 'hip_f16x3', 'every convolution on libpnpmri.so (split-half f16 matrix-core kernels), weights inside the half range'
 
@@ -988,7 +484,7 @@ class Denoiser:
         float32 accumulation -- NOT at the 1e-5 parity bar; every layer must be one libpnpmri.so takes, or the constructor raises)
         or 'hip_f16x3' (the same as 'hip', with the 64 -> 64 layers in split-half arithmetic on the f16 matrix cores: float32 operands
         carried as two halves, three exact-product matrix instructions per product, float32 accumulation -- float32-level
-        results at several times the float32 matrix rate; operands must lie within the half range, |x| <= 65504).  shape: the slices' (H, W),
+        results at several times the float32 matrix rate; operands must lie within the half range).  shape: the slices' (H, W),
         for backend='auto' (auto_backend)."""
         # graph=True: a forward of at most `cnn_batch` slices is captured once per input shape into a HIP graph (torch.cuda.CUDAGraph)
         # and replayed -- for the reference's own usage, ONE slice per call (S6:231), where a forward is a train of 17 .. 70 launches
@@ -1005,12 +501,7 @@ class Denoiser:
         if backend in HIP_BACKENDS and cnn_dtype not in (None, 'fp32'):
             raise ValueError("backend='%s' takes and returns float32 only" % backend)
         if backend == 'hip_f16':                               # full coverage or nothing: no PyTorch layer in a half-precision forward
-            if isinstance(model, UNetRes):
-                bad = None if model.hip_covers(backend='hip_f16') else f16_uncovered_unet(model)
-            elif isinstance(model, _PlainStack):
-                bad = f16_uncovered_stack(model.model)
-            else:
-                bad = 'a %s' % type(model).__name__
+            bad = HL.uncovered(hip_plan(model, backend))
             if bad:
                 raise ValueError("backend='hip_f16' needs every layer on libpnpmri.so; it does not take %s" % bad)
         self.name, self.fam = model_name, family(model_name)
@@ -1145,11 +636,10 @@ class Denoiser:
             out.copy_(self._graph_forward(x, i))
             return out
         find = (min(B, self.cnn_batch) >= 16 and x.is_cuda) if self.miopen_find == 'auto' else bool(self.miopen_find)
-        if self.backend in HIP_BACKENDS and isinstance(self.model, _PlainStack) and hip_covers_stack(self.model.model):
-            find = False                      # no MIOpen call in this forward: the process-global flag is left alone
-        if isinstance(self.model, UNetRes) and self.model.hip_covers(*(-(-d // 16) * 16 for d in x.shape[-2:])):
-            find = False                      # DRUNet under 'hip_f16x3': every layer on libpnpmri.so at the size the model is CALLED with -- test_mode pads to
-                                              # multiples of 16 (_one, utils/utils_model.py:60-68), so three halvings always survive
+        if find and self.backend in HIP_BACKENDS and not HL.uncovered(hip_plan(self.model, self.backend, *(-(-d // 16) * 16 for d in x.shape[-2:]))):
+            find = False                      # no MIOpen call in this forward: the process-global flag is left alone.  DRUNet: every layer on
+                                              # libpnpmri.so at the size the model is CALLED with -- test_mode pads to multiples of 16 (_one,
+                                              # utils/utils_model.py:60-68), so three halvings always survive
         cd = torch.backends.cudnn
         before = cd.benchmark
         cd.benchmark = bool(find or before)

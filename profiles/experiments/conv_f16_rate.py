@@ -30,8 +30,8 @@ def layer_rates(torch, L, lib, seconds=2.0):
     x32 = torch.relu(torch.randn(n, H, W, ch, device='cuda', generator=g)) * 0.5          # a body layer's input: ReLU'd, O(1)
     w = torch.randn(ch, ch, 3, 3, device='cuda', generator=g) * (2.0 / 576) ** 0.5
     b = torch.randn(ch, device='cuda', generator=g) * 0.1
-    from pnp_admm_cnc_mri_amd import denoisers as D
-    xs = D.split_activations(x32)
+    from pnp_admm_cnc_mri_amd import denoisers as D, hip_layers as HL
+    xs = HL.split_activations(x32)
     ys = torch.empty_like(xs)
     w3 = torch.empty(9 * ch * ch, device='cuda')
     lib.check(L.pnp_conv3x3_pack_f16x3(s, p(w), p(w3), ch))
@@ -44,7 +44,7 @@ def layer_rates(torch, L, lib, seconds=2.0):
     # same inputs, so the two results agree to half precision (a wrong kernel is not a fast kernel)
     f3(); fh()
     torch.cuda.synchronize()
-    dev = float((yh.float() - D.unsplit_activations(ys)).norm() / D.unsplit_activations(ys).norm())
+    dev = float((yh.float() - HL.unsplit_activations(ys)).norm() / HL.unsplit_activations(ys).norm())
     assert dev < 2e-3, dev
     for _ in range(30):
         f3(); fh()

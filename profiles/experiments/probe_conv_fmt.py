@@ -7,7 +7,7 @@ import ctypes as C, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from pnp_admm_cnc_mri_amd import _lib, denoisers as D
+from pnp_admm_cnc_mri_amd import _lib, denoisers as D, hip_layers as HL
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 only = int(sys.argv[2]) if len(sys.argv) > 2 else None
 H = W = 128
@@ -23,7 +23,7 @@ _lib.check(L.pnp_conv3x3_pack_f16x3(s, p(w), p(wp), 64))
 flop = 2.0 * n * H * W * 64 * 64 * 9
 for data in ('random', 'zeros'):
     x = torch.relu(torch.randn(n, H, W, 64, device=dev)) if data == 'random' else torch.zeros(n, H, W, 64, device=dev)
-    xs = D.split_activations(x)
+    xs = HL.split_activations(x)
     y = torch.empty_like(x)
     for fmt, tag in ((0, 'float32 -> float32'), (4, 'float32 -> split  '), (5, 'split   -> split  '), (1, 'split   -> float32')):
         if only is not None and fmt != only:

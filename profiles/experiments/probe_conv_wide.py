@@ -12,7 +12,7 @@ sys.path.insert(0, ROOT)
 
 def child(what, n):
     import torch
-    from pnp_admm_cnc_mri_amd import _lib, denoisers as D
+    from pnp_admm_cnc_mri_amd import _lib, denoisers as D, hip_layers as HL
     L = _lib.lib()
     dev = torch.device('cuda', 0)
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -32,7 +32,7 @@ def child(what, n):
             x = torch.randn(nn, H, W, Cc, device=dev, generator=g)
             k = torch.randn(nn, H, W, Cc, device=dev, generator=g)
             b = torch.randn(Cc, device=dev, generator=g) * 0.1
-            xs, ks = D.split_activations(x), D.split_activations(k)
+            xs, ks = HL.split_activations(x), HL.split_activations(k)
             for fmt in range(8):
                 for skip in (0, 1):
                     if (fmt & 2) and not skip:
@@ -52,8 +52,8 @@ def child(what, n):
             x = torch.relu(torch.randn(nn, H, W, Cc, device=dev))
             k = torch.randn(nn, H, W, Cc, device=dev)
             b = torch.randn(Cc, device=dev) * 0.1
-            xin = D.split_activations(x) if fmt & 1 else x
-            kin = (D.split_activations(k) if fmt & 2 else k) if skip else None
+            xin = HL.split_activations(x) if fmt & 1 else x
+            kin = (HL.split_activations(k) if fmt & 2 else k) if skip else None
             y = torch.empty_like(x)
             run = lambda: _lib.check(L.pnp_conv3x3_nhwc_f16x3_fmt(s, p(xin), p(wp), p(b), p(kin), p(y), nn, Cc, H, W, 1, 1, fmt))
             for _ in range(5):

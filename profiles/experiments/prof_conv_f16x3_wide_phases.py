@@ -6,11 +6,11 @@ import ctypes as C, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from pnp_admm_cnc_mri_amd import _lib, denoisers as D
+from pnp_admm_cnc_mri_amd import _lib, denoisers as D, hip_layers as HL
 L = _lib.lib()
 n, ch, H, W, fmt = (int(v) for v in sys.argv[1:6]) if len(sys.argv) >= 6 else (64, 64, 128, 128, 5)
 x = torch.relu(torch.randn(n, H, W, ch, device='cuda')); y = torch.empty_like(x)
-xin = D.split_activations(x) if fmt & 1 else x
+xin = HL.split_activations(x) if fmt & 1 else x
 w = torch.randn(ch, ch, 3, 3, device='cuda') * (2.0 / (9 * ch)) ** 0.5; pk = torch.empty(9 * ch * ch, device='cuda')
 b = torch.randn(ch, device='cuda') * 0.1
 s = C.c_void_p(torch.cuda.current_stream().cuda_stream)

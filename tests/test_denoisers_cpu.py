@@ -170,7 +170,7 @@ def test_hip_backend_needs_gpu_tensors_and_float32():
     """`Denoiser(backend='hip')` never computes on the CPU: a CPU tensor raises; autocast modes are refused; the default
     backend is PyTorch."""
     import pytest as _pytest
-    from pnp_admm_cnc_mri_amd import denoisers as D
+    from pnp_admm_cnc_mri_amd import denoisers as D, hip_layers as HL
     net, nlm, _ = D.build('ffdnet_gray')
     net.load_state_dict(D.seeded_state_dict(net, 1))
     assert D.Denoiser('ffdnet_gray', net.eval(), nlm).backend == 'torch' and net.backend == 'torch'
@@ -183,9 +183,9 @@ def test_hip_backend_needs_gpu_tensors_and_float32():
     with _pytest.raises(ValueError):
         D.Denoiser('ffdnet_gray', net, nlm, backend='cuda')
     # the body layers the kernel takes: 13 of FFDNet's 15, 15 of DnCNN-17's, IRCNN's five dilated ones
-    count = lambda m: sum(1 for c in m.model if D._hip_body_ok(c))
+    count = lambda m: sum(1 for c in m.model if HL._hip_body_ok(c))
     assert count(net) == 13 and count(D.build('dncnn_15')[0]) == 15 and count(D.build('ircnn_gray')[0]) == 5
-    assert all(D.hip_covers_stack(D.build(n)[0].model) for n in ('ffdnet_gray', 'dncnn_15', 'fdncnn_gray', 'ircnn_gray'))
+    assert all(HL.hip_covers_stack(D.build(n)[0].model) for n in ('ffdnet_gray', 'dncnn_15', 'fdncnn_gray', 'ircnn_gray'))
 
 
 def test_f16x3_backend_selection_on_the_cpu():
@@ -193,10 +193,10 @@ def test_f16x3_backend_selection_on_the_cpu():
     ones of every family as 'hip' does, and DRUNet's 128 / 256 / 512-channel residual blocks on top (dilation 1 only)"""
     import pytest as _pytest
     import torch.nn as nn
-    from pnp_admm_cnc_mri_amd import denoisers as D
+    from pnp_admm_cnc_mri_amd import denoisers as D, hip_layers as HL
     net, nlm, _ = D.build('dncnn_15')
     den = D.Denoiser('dncnn_15', net.eval(), nlm, backend='hip_f16x3', miopen_find=False)
-    assert net.backend == 'hip_f16x3' and D._hip_math(net.backend) == 'f16x3' and D._hip_math('hip') == 'f32'
+    assert net.backend == 'hip_f16x3' and HL._hip_math(net.backend) == 'f16x3' and HL._hip_math('hip') == 'f32'
     with _pytest.raises(RuntimeError, match='CUDA'):
         den(torch.rand(1, 1, 32, 32), 0)
     with _pytest.raises(ValueError):
@@ -205,11 +205,11 @@ def test_f16x3_backend_selection_on_the_cpu():
     D.Denoiser('drunet_gray', unet.eval(), nlm2, sigmas=torch.tensor([0.1]), backend='hip_f16x3')
     blocks = [m for m in unet.modules() if isinstance(m, D._ResBlock)]
     assert len(blocks) == 28 and all(m.backend == 'hip_f16x3' for m in blocks)
-    taken = lambda math: sum(1 for m in blocks if D._hip_body_ok(m.res[0], math) and D._hip_body_ok(m.res[2], math))
+    taken = lambda math: sum(1 for m in blocks if HL._hip_body_ok(m.res[0], math) and HL._hip_body_ok(m.res[2], math))
     assert taken('f32') == 8 and taken('f16x3') == 28            # float32 kernel: the 64-channel scale only
-    assert not D._hip_body_ok(nn.Conv2d(128, 128, 3, 1, 2, dilation=2), 'f16x3')      # wide layers: dilation 1 only
-    assert not D._hip_body_ok(nn.Conv2d(96, 96, 3, 1, 1), 'f16x3') and not D._hip_body_ok(nn.Conv2d(128, 64, 3, 1, 1), 'f16x3')
-    assert D._hip_body_ok(nn.Conv2d(1024, 1024, 3, 1, 1), 'f16x3') and not D._hip_body_ok(nn.Conv2d(1088, 1088, 3, 1, 1), 'f16x3')
+    assert not HL._hip_body_ok(nn.Conv2d(128, 128, 3, 1, 2, dilation=2), 'f16x3')      # wide layers: dilation 1 only
+    assert not HL._hip_body_ok(nn.Conv2d(96, 96, 3, 1, 1), 'f16x3') and not HL._hip_body_ok(nn.Conv2d(128, 64, 3, 1, 1), 'f16x3')
+    assert HL._hip_body_ok(nn.Conv2d(1024, 1024, 3, 1, 1), 'f16x3') and not HL._hip_body_ok(nn.Conv2d(1088, 1088, 3, 1, 1), 'f16x3')
 
 
 # ----------------------------------------------------------------------------------------------

@@ -28,6 +28,39 @@ __device__ __forceinline__ void split4(const f32x4& v, h4& hi, h4& lo) {
     }
 }
 
+// Packed weights, both families (the pack kernels run once per model): a 64 x 64 block is [K step s][N tile nt][lane 64][8 values j], lane
+// (n, kb) of fragment (s, nt) holding rows k = 32 s + 8 kb + j of column 16 nt + n -- v_mfma_f32_16x16x32_f16: lane l supplies
+// B[k = 8 (l >> 4) + j][column l & 15]; the A side reads input channels in the same order.  Thread o of a pack kernel owns value
+// o = (((blk * 2 + s) * 4 + nt) * 64 + lane) * 8 + j.  SPLIT (f16x3): the fragment is a hi fragment followed by its lo fragment, 16 KiB per
+// block, as many bytes as the float32 weights; else (f16) one fragment of halves rounded to nearest even, 8 KiB.
+struct FragPos { long long blk; int s, nt, lane, j; };
+__device__ __forceinline__ FragPos frag_pos(long long o) {
+    return FragPos{o >> 12, (int)(o >> 11) & 1, (int)(o >> 9) & 3, (int)(o >> 3) & 63, (int)o & 7};
+}
+template <bool SPLIT>
+__device__ __forceinline__ void frag_write(_Float16* wfrag, long long o, const FragPos& p, float v) {
+    const _Float16 hi = (_Float16)v;
+    if (SPLIT) {
+        const size_t frag = ((size_t)p.blk * 2 + p.s) * 8 + p.nt * 2;
+        wfrag[(frag * 64 + p.lane) * 8 + p.j] = hi;
+        wfrag[((frag + 1) * 64 + p.lane) * 8 + p.j] = (_Float16)((v - (float)hi) * H3_SCALE);
+    } else {
+        wfrag[o] = hi;
+    }
+}
+// torch.nn.Conv2d weight [C out][C in][3][3] -> blocks [cb][chunk cc][tap]: value (s, nt, lane (n, kb), j) is
+// W[out = 64 cb + 16 nt + n][in = 64 cc + 32 s + 8 kb + j][tap]
+template <bool SPLIT>
+__device__ __forceinline__ void conv_pack_w_body(const float* w_oihw, _Float16* wfrag, int C) {
+    const long long o = (long long)blockIdx.x * 256 + threadIdx.x;      // one value per thread
+    if (o >= 9LL * C * C) return;
+    const int NC = C >> 6;
+    const FragPos p = frag_pos(o);                                // blk = (cb * NC + cc) * 9 + tap
+    const int tap = (int)(p.blk % 9), cc = (int)((p.blk / 9) % NC), cb = (int)(p.blk / (9 * NC));
+    const int out = 64 * cb + 16 * p.nt + (p.lane & 15), in = 64 * cc + 32 * p.s + 8 * (p.lane >> 4) + p.j;
+    frag_write<SPLIT>(wfrag, o, p, w_oihw[((size_t)out * C + in) * 9 + tap]);
+}
+
 // The operand tile in LDS (kernels_conv_f16x3.hip): a pixel is 256 bytes of halves + 16 bytes of padding (CV_PS floats), in sixteen
 // 16-byte chunks.  Chunk (kb, s2, part) = [hi | lo] halves of input channels 32 s2 + 8 kb .. + 7 -- lane (i, kb) of a wave reads it as the
 // A fragment of K step s2 -- sits at h3_chunk_pos: the chunks of kb and kb ^ 1 lie 128 bytes apart, and the wave's M-tile row i is tile

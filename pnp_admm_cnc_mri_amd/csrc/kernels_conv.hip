@@ -29,7 +29,7 @@
 //            (buffer loads whose out-of-image pixels fall outside the descriptor's range and return zeros: no branches)
 //   epilogue bias = the accumulators' initial value; the wave's 32 x 64 outputs go through 8 KiB of the idle input tile and
 //            leave as eight 16-byte stores per lane (a 256-byte pixel per 16 lanes); skip and ReLU join there
-#include "conv_common.h"
+#include "conv_ends.h"
 
 namespace pnp {
 
@@ -252,91 +252,7 @@ hipError_t launch_relayout64(hipStream_t s, const float* in, float* out, int n, 
 //         16 partial sums of a pixel meet by four DPP steps inside the lane row
 // ------------------------------------------------------------------------------------------
 constexpr int CV_HX = Geo<1>::HX, CV_HY = Geo<1>::HY, CV_XU = Geo<1>::XU;      // the direct kernels below: dilation 1
-constexpr int HD_MAXC = CP_MAX_CIN;
-struct HeadArgs {
-    const float* x; const float* w; const float* bias; float* y;
-    int n, cin, H, W, tiles_x, tiles_y, relu;
-    // FFDNet's input stage folded into the staging loop (models/network_ffdnet.py:58-68): x is the FULL-resolution image [n][1][src_h][src_w];
-    // channels 0..3 of the layer's input are its pixel-unshuffled quarters (channel 2 dy + dx at (y, x) = x[2 y + dy][2 x + dx], replicate-padded
-    // to even size = index clamped), channel 4 the noise level sigma[img * sigma_stride]; H = ceil(src_h / 2), W = ceil(src_w / 2)
-    int ffdnet, src_h, src_w, sigma_stride;
-    const float* sigma;
-};
-__global__ __launch_bounds__(256) void k_conv3x3_head(HeadArgs a) {
-    __shared__ float xin[HD_MAXC * CV_HY * CV_HX];                 // [ci][row 10][col 18]
-    __shared__ __attribute__((aligned(16))) float wl[HD_MAXC * 9 * CV_C];   // [ci * 9 + tap][64 out]
-    const int tid = threadIdx.x;
-    const int per_img = a.tiles_x * a.tiles_y;
-    const int img = blockIdx.x / per_img, trem = blockIdx.x - img * per_img, ty = trem / a.tiles_x;
-    const int y0 = ty * CV_TY, x0 = (trem - ty * a.tiles_x) * CV_TX;
-    const size_t plane = (size_t)a.H * a.W;
-    const float* xb = a.ffdnet ? a.x + (size_t)img * a.src_h * a.src_w : a.x + (size_t)img * a.cin * plane;
-    const float sig = a.ffdnet ? a.sigma[(size_t)img * a.sigma_stride] : 0.f;
-    if (a.ffdnet) {
-        // the full-resolution patch, 2 CV_HY rows x 2 CV_HX columns, read row by row (consecutive threads, consecutive pixels) and
-        // de-interleaved into the four channel planes on the way into LDS
-        for (int e = tid; e < 4 * CV_HY * CV_HX; e += 256) {
-            const int pr = e / (2 * CV_HX), pc = e - pr * (2 * CV_HX), r = pr >> 1, c = pc >> 1, ci = 2 * (pr & 1) + (pc & 1);
-            const int gy = y0 - 1 + r, gx = x0 - 1 + c;
-            const bool in = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-            const int sy = min(2 * (in ? gy : 0) + (pr & 1), a.src_h - 1), sx = min(2 * (in ? gx : 0) + (pc & 1), a.src_w - 1);
-            const float v = xb[(size_t)sy * a.src_w + sx];
-            xin[(ci * CV_HY + r) * CV_HX + c] = in ? v : 0.f;
-        }
-        for (int p = tid; p < CV_HY * CV_HX; p += 256) {           // the convolution zero-pads the noise-level channel too
-            const int r = p / CV_HX, c = p - r * CV_HX, gy = y0 - 1 + r, gx = x0 - 1 + c;
-            xin[4 * CV_HY * CV_HX + p] = (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? sig : 0.f;
-        }
-    } else {
-        for (int e = tid; e < a.cin * CV_HY * CV_HX; e += 256) {
-            const int ci = e / (CV_HY * CV_HX), p = e - ci * (CV_HY * CV_HX), r = p / CV_HX, c = p - r * CV_HX;
-            const int gy = y0 - 1 + r, gx = x0 - 1 + c;
-            const bool in = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-            const float v = xb[(size_t)ci * plane + (size_t)(in ? gy : 0) * a.W + (in ? gx : 0)];
-            xin[e] = in ? v : 0.f;
-        }
-    }
-    for (int e = tid; e < a.cin * 9 * CV_C; e += 256) {            // w_oihw [64][cin][3][3] -> [ci * 9 + tap][out]
-        const int out = e & 63, k = e >> 6;                        // k = ci * 9 + tap
-        wl[e] = a.w[(size_t)out * a.cin * 9 + k];
-    }
-    __syncthreads();
-    const int cq = tid & 15, pg = tid >> 4, row = pg >> 1, col0 = (pg & 1) * 8;
-    f32x4 acc[8];
-    const f32x4 b4 = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + 4 * cq) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int px = 0; px < 8; ++px) acc[px] = b4;
-#pragma unroll 1
-    for (int ci = 0; ci < a.cin; ++ci) {
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            float in[10];
-            const float* rp = xin + (ci * CV_HY + row + ky) * CV_HX + col0;
-#pragma unroll
-            for (int k = 0; k < 10; ++k) in[k] = rp[k];
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const f32x4 w4 = *reinterpret_cast<const f32x4*>(wl + (ci * 9 + ky * 3 + kx) * CV_C + 4 * cq);
-#pragma unroll
-                for (int px = 0; px < 8; ++px) {
-                    acc[px][0] = fmaf(in[px + kx], w4[0], acc[px][0]); acc[px][1] = fmaf(in[px + kx], w4[1], acc[px][1]);
-                    acc[px][2] = fmaf(in[px + kx], w4[2], acc[px][2]); acc[px][3] = fmaf(in[px + kx], w4[3], acc[px][3]);
-                }
-            }
-        }
-    }
-    const __amdgpu_buffer_rsrc_t ry = image_rsrc(a.y + (size_t)img * plane * CV_C, a.H, a.W);
-    const int gy = y0 + row;
-#pragma unroll
-    for (int px = 0; px < 8; ++px) {
-        const int gx = x0 + col0 + px;
-        f32x4 v = acc[px];
-        if (a.relu) { v[0] = relu_keep_nan(v[0]); v[1] = relu_keep_nan(v[1]); v[2] = relu_keep_nan(v[2]); v[3] = relu_keep_nan(v[3]); }
-        const int off = (gx < a.W) ? (gy * a.W + gx) * (CV_C * 4) + cq * 16 : -16;        // rows below the image: out of range, dropped
-        const u32x4v o = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-        __builtin_amdgcn_raw_buffer_store_b128(o, ry, off, 0, 0);
-    }
-}
+__global__ __launch_bounds__(256) void k_conv3x3_head(HeadArgs a) { conv3x3_head_body<false>(a); }      // conv_ends.h
 
 static_assert(CP_MAX_COUT == 4, "k_conv3x3_tail is instantiated for 1 .. 4 output channels (launch_conv3x3_tail)");
 struct TailArgs {

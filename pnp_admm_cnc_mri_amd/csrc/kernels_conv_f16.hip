@@ -15,7 +15,7 @@
 // (f16_common.h: 160 bytes per pixel, conflict-free ds_read_b128), a tap's 8 KiB of weights by LDS-DMA one tap ahead into one of two
 // buffers, a counted s_waitcnt vmcnt and ONE raw s_barrier per tap, the next input tile requested in six pieces behind taps 0..5's
 // DMA.  A wave = 2 M tiles (its two tile rows) x 4 N tiles, ONE accumulator set: 32 registers, 16 MFMAs per tap.
-#include "f16_common.h"
+#include "conv_ends.h"
 #include <type_traits>
 
 namespace pnp {
@@ -272,101 +272,13 @@ __global__ __launch_bounds__(CV_THREADS, GeoFK<DIL>::WPS) void k_conv3x3_f16(Con
 // torch.nn.Conv2d weight [C out][C in][3][3] -> halves (round to nearest even) in fragment order, blocks [cb][chunk cc][tap] of 8 KiB:
 // half j of lane (n, kb) of fragment (K step s, N tile nt) is half(W[out = 64 cb + 16 nt + n][in = 64 cc + 32 s + 8 kb + j][tap]).
 // Half as many bytes as the float32 weights.  Once per model.
-__global__ __launch_bounds__(256) void k_conv_pack_w_f16(const float* w_oihw, _Float16* wfrag, int C) {
-    const long long o = (long long)blockIdx.x * 256 + threadIdx.x;      // one half per thread
-    if (o >= 9LL * C * C) return;
-    const int NC = C >> 6;
-    const int j = o & 7, lane = (o >> 3) & 63, nt = (o >> 9) & 3, s = (o >> 11) & 1;
-    const long long blk = o >> 12;                                // (cb * NC + cc) * 9 + tap
-    const int tap = (int)(blk % 9), cc = (int)((blk / 9) % NC), cb = (int)(blk / (9 * NC));
-    const int out = 64 * cb + 16 * nt + (lane & 15), in = 64 * cc + 32 * s + 8 * (lane >> 4) + j;
-    wfrag[o] = (_Float16)w_oihw[((size_t)out * C + in) * 9 + tap];
-}
+__global__ __launch_bounds__(256) void k_conv_pack_w_f16(const float* w_oihw, _Float16* wfrag, int C) { conv_pack_w_body<false>(w_oihw, wfrag, C); }
 
 // ------------------------------------------------------------------------------------------
 // First layer of the stacks (CIN <= 8 -> 64 channels; FFDNet's pixel-unshuffle / noise-level stage folded in): the float32 direct
-// arithmetic of kernels_conv.hip's k_conv3x3_head on the float32 network input -- same loops, same fma order -- storing halves.
+// arithmetic of kernels_conv.hip's k_conv3x3_head on the float32 network input -- the same body (conv_ends.h) -- storing halves.
 // ------------------------------------------------------------------------------------------
-constexpr int HFD_HX = Geo<1>::HX, HFD_HY = Geo<1>::HY, HFD_MAXC = CP_MAX_CIN;
-struct HeadF16Args {
-    const float* x; const float* w; const float* bias; void* y;
-    int n, cin, H, W, tiles_x, tiles_y, relu;
-    int ffdnet, src_h, src_w, sigma_stride;                       // kernels_conv.hip: HeadArgs
-    const float* sigma;
-};
-__global__ __launch_bounds__(256) void k_conv3x3_head_f16(HeadF16Args a) {
-    __shared__ float xin[HFD_MAXC * HFD_HY * HFD_HX];             // [ci][row 10][col 18]
-    __shared__ __attribute__((aligned(16))) float wl[HFD_MAXC * 9 * CV_C];   // [ci * 9 + tap][64 out]
-    const int tid = threadIdx.x;
-    const int per_img = a.tiles_x * a.tiles_y;
-    const int img = blockIdx.x / per_img, trem = blockIdx.x - img * per_img, ty = trem / a.tiles_x;
-    const int y0 = ty * CV_TY, x0 = (trem - ty * a.tiles_x) * CV_TX;
-    const size_t plane = (size_t)a.H * a.W;
-    const float* xb = a.ffdnet ? a.x + (size_t)img * a.src_h * a.src_w : a.x + (size_t)img * a.cin * plane;
-    const float sig = a.ffdnet ? a.sigma[(size_t)img * a.sigma_stride] : 0.f;
-    if (a.ffdnet) {
-        for (int e = tid; e < 4 * HFD_HY * HFD_HX; e += 256) {
-            const int pr = e / (2 * HFD_HX), pc = e - pr * (2 * HFD_HX), r = pr >> 1, c = pc >> 1, ci = 2 * (pr & 1) + (pc & 1);
-            const int gy = y0 - 1 + r, gx = x0 - 1 + c;
-            const bool in = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-            const int sy = min(2 * (in ? gy : 0) + (pr & 1), a.src_h - 1), sx = min(2 * (in ? gx : 0) + (pc & 1), a.src_w - 1);
-            const float v = xb[(size_t)sy * a.src_w + sx];
-            xin[(ci * HFD_HY + r) * HFD_HX + c] = in ? v : 0.f;
-        }
-        for (int p = tid; p < HFD_HY * HFD_HX; p += 256) {         // the convolution zero-pads the noise-level channel too
-            const int r = p / HFD_HX, c = p - r * HFD_HX, gy = y0 - 1 + r, gx = x0 - 1 + c;
-            xin[4 * HFD_HY * HFD_HX + p] = (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? sig : 0.f;
-        }
-    } else {
-        for (int e = tid; e < a.cin * HFD_HY * HFD_HX; e += 256) {
-            const int ci = e / (HFD_HY * HFD_HX), p = e - ci * (HFD_HY * HFD_HX), r = p / HFD_HX, c = p - r * HFD_HX;
-            const int gy = y0 - 1 + r, gx = x0 - 1 + c;
-            const bool in = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-            const float v = xb[(size_t)ci * plane + (size_t)(in ? gy : 0) * a.W + (in ? gx : 0)];
-            xin[e] = in ? v : 0.f;
-        }
-    }
-    for (int e = tid; e < a.cin * 9 * CV_C; e += 256) {            // w_oihw [64][cin][3][3] -> [ci * 9 + tap][out]
-        const int out = e & 63, k = e >> 6;
-        wl[e] = a.w[(size_t)out * a.cin * 9 + k];
-    }
-    __syncthreads();
-    const int cq = tid & 15, pg = tid >> 4, row = pg >> 1, col0 = (pg & 1) * 8;
-    f32x4 acc[8];
-    const f32x4 b4 = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + 4 * cq) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int px = 0; px < 8; ++px) acc[px] = b4;
-#pragma unroll 1
-    for (int ci = 0; ci < a.cin; ++ci) {
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            float in[10];
-            const float* rp = xin + (ci * HFD_HY + row + ky) * HFD_HX + col0;
-#pragma unroll
-            for (int k = 0; k < 10; ++k) in[k] = rp[k];
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const f32x4 w4 = *reinterpret_cast<const f32x4*>(wl + (ci * 9 + ky * 3 + kx) * CV_C + 4 * cq);
-#pragma unroll
-                for (int px = 0; px < 8; ++px) {
-                    acc[px][0] = fmaf(in[px + kx], w4[0], acc[px][0]); acc[px][1] = fmaf(in[px + kx], w4[1], acc[px][1]);
-                    acc[px][2] = fmaf(in[px + kx], w4[2], acc[px][2]); acc[px][3] = fmaf(in[px + kx], w4[3], acc[px][3]);
-                }
-            }
-        }
-    }
-    const __amdgpu_buffer_rsrc_t ry = bytes_rsrc(a.y, (size_t)img * plane * 128, (unsigned)plane * 128u);
-    const int gy = y0 + row;
-#pragma unroll
-    for (int px = 0; px < 8; ++px) {
-        const int gx = x0 + col0 + px;
-        f32x4 v = acc[px];
-        if (a.relu) { v[0] = relu_keep_nan(v[0]); v[1] = relu_keep_nan(v[1]); v[2] = relu_keep_nan(v[2]); v[3] = relu_keep_nan(v[3]); }
-        const int off = (gx < a.W) ? (gy * a.W + gx) * 128 + cq * 8 : -16;        // rows below the image: out of range, dropped
-        const h4 hv = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, hv), ry, off, 0, 0);
-    }
-}
+__global__ __launch_bounds__(256) void k_conv3x3_head_f16(HeadArgs a) { conv3x3_head_body<true>(a); }
 
 // ------------------------------------------------------------------------------------------
 // Last layer of the stacks (64 -> COUT <= 4 channels, half NHWC in, float32 NCHW out, + bias) as a 16-column matrix product of which
@@ -374,15 +286,10 @@ __global__ __launch_bounds__(256) void k_conv3x3_head_f16(HeadF16Args a) {
 // reading its input.  Persistent, two workgroups per compute unit.  The weights are rounded to half here, once per workgroup.
 // x2: a second half tensor added to x in float32 while it is staged, the sum rounded to half once (the U-Net's last skip sum).
 // ------------------------------------------------------------------------------------------
-struct TailF16Args {
-    const void* x; const void* x2; const float* w; const float* bias; float* y;
-    int n, cout, H, W, tiles_x, tiles_y;
-    int shuffle, out_h, out_w;                                    // FFDNet's pixel shuffle + crop folded into the stores (kernels_conv_f16x3.hip: TailH3Args)
-};
-__global__ __launch_bounds__(CV_THREADS, 2) void k_conv3x3_tail_f16(TailF16Args t, int ntiles) {
+__global__ __launch_bounds__(CV_THREADS, 2) void k_conv3x3_tail_f16(TailMmaArgs t, int ntiles) {
     constexpr int HX = GeoF<1>::HX, XU = GeoF<1>::XU;
     __shared__ __attribute__((aligned(16))) char xin[GeoF<1>::XINB];
-    __shared__ __attribute__((aligned(16))) _Float16 wl[9 * 2 * 4 * 4 * 8];          // [tap][K step][kb][n < 4][8 halves]
+    __shared__ __attribute__((aligned(16))) _Float16 wl[TAIL_WL];                    // [tap][K step][kb][n < 4][8 halves]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, kb = lane >> 4;
@@ -410,10 +317,7 @@ __global__ __launch_bounds__(CV_THREADS, 2) void k_conv3x3_tail_f16(TailF16Args 
         }
     };
     fetch(tile_pos_f(t.tiles_x, t.tiles_y, tile));
-    for (int e = tid; e < 9 * 2 * 4 * 4 * 8; e += CV_THREADS) {
-        const int j = e & 7, n = (e >> 3) & 3, kq = (e >> 5) & 3, s2 = (e >> 7) & 1, tap = e >> 8;
-        wl[e] = n < t.cout ? (_Float16)t.w[((size_t)n * 64 + 32 * s2 + 8 * kq + j) * 9 + tap] : (_Float16)0.f;
-    }
+    for (int e = tid; e < TAIL_WL; e += CV_THREADS) wl[e] = (_Float16)tail_mma_weight(t, e);
     const char* const a0 = xin + (2 * wv * HX + i) * HF_PS + 16 * kb;
     const char* const b0 = reinterpret_cast<const char*>(wl) + kb * 64 + (i & 3) * 16;
     const bool col = i < t.cout;
@@ -442,36 +346,7 @@ __global__ __launch_bounds__(CV_THREADS, 2) void k_conv3x3_tail_f16(TailF16Args 
         }
         // accumulator (reg r, lane (i, kb)) of M tile mt = pixel (tile row 2 w + mt, column 4 kb + r), output channel i
         __syncthreads();                                          // every wave is past its taps: the tile may be reused (below, or by the next tile)
-        if (t.shuffle) {
-            // FFDNet: the tile's 8 x 16 x 4 values are a 16 x 32 block of the full-resolution result, assembled in LDS, leaving as whole rows
-            float* blk = reinterpret_cast<float*>(xin);
-            if (col) {
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        blk[(2 * (2 * wv + mt) + (i >> 1)) * 32 + 2 * (4 * kb + r) + (i & 1)] = acc[mt][r] + b;
-            }
-            __syncthreads();
-            const int orow = tid >> 4, ocol = 2 * (tid & 15), oy = 2 * q.y0 + orow, ox = 2 * q.x0 + ocol;
-            if (oy < t.out_h) {
-                float* dst = t.y + ((size_t)q.img * t.out_h + oy) * t.out_w + ox;
-                if (ox < t.out_w) dst[0] = blk[orow * 32 + ocol];
-                if (ox + 1 < t.out_w) dst[1] = blk[orow * 32 + ocol + 1];
-            }
-            __syncthreads();                                      // the assembled block is read: the next tile may be written
-        } else if (col) {
-            const size_t plane = (size_t)t.H * t.W;
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                const int gy = q.y0 + 2 * wv + mt;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int gx = q.x0 + 4 * kb + r;
-                    if (gy < t.H && gx < t.W) t.y[((size_t)q.img * t.cout + i) * plane + (size_t)gy * t.W + gx] = acc[mt][r] + b;
-                }
-            }
-        }
+        tail_mma_store(t, q, reinterpret_cast<float*>(xin), tid, wv, i, 4 * kb, col, b, acc);
     }
 }
 
@@ -515,7 +390,7 @@ hipError_t launch_conv3x3_head_f16(hipStream_t s, const float* x, const float* s
                                    void* y_nhwc, int n, int cin, int H, int W, int relu, int ffdnet) {
     // ffdnet: x is the full-resolution image [n][1][H][W], the layer runs at ceil(H / 2) x ceil(W / 2) with cin = 5
     if (ffdnet ? cp_check_ffdnet(n, H, W) : cp_check_head(n, cin, H, W)) return hipErrorInvalidValue;
-    HeadF16Args a;
+    HeadArgs a;
     a.x = x; a.w = w_oihw; a.bias = bias; a.y = y_nhwc; a.n = n; a.relu = relu;
     a.ffdnet = ffdnet ? 1 : 0; a.src_h = ffdnet ? H : 0; a.src_w = ffdnet ? W : 0; a.sigma = sigma; a.sigma_stride = sigma_per_image ? 1 : 0;
     a.cin = ffdnet ? 5 : cin; a.H = ffdnet ? cp_ffdnet_dim(H) : H; a.W = ffdnet ? cp_ffdnet_dim(W) : W;
@@ -527,17 +402,7 @@ hipError_t launch_conv3x3_head_f16(hipStream_t s, const float* x, const float* s
 
 hipError_t launch_conv3x3_tail_f16(hipStream_t s, const void* x_nhwc, const void* x2_nhwc, const float* w_oihw, const float* bias, float* y,
                                    int n, int cout, int H, int W, int shuffle_h, int shuffle_w) {
-    if (cp_check_tail(n, cout, H, W, shuffle_h, shuffle_w)) return hipErrorInvalidValue;
-    const ConvTiling tl = cp_tiling(n, H, W, CP_NARROW);
-    TailF16Args t;
-    t.shuffle = shuffle_h ? 1 : 0; t.out_h = shuffle_h; t.out_w = shuffle_w;
-    t.x = x_nhwc; t.x2 = x2_nhwc; t.w = w_oihw; t.bias = bias; t.y = y; t.n = n; t.cout = cout; t.H = H; t.W = W;
-    t.tiles_x = tl.tiles_x; t.tiles_y = tl.tiles_y;
-    const int cus = conv_compute_units();
-    if (cus <= 0) return hipGetLastError();
-    // persistent, two workgroups per compute unit; every loop ends: tile < ntiles
-    hipLaunchKernelGGL(k_conv3x3_tail_f16, dim3((unsigned)cp_grid(tl.items, 2, cus)), dim3(CV_THREADS), 0, s, t, (int)tl.items);
-    return hipGetLastError();
+    return launch_tail_mma(s, k_conv3x3_tail_f16, x_nhwc, x2_nhwc, w_oihw, bias, y, n, cout, H, W, shuffle_h, shuffle_w);
 }
 
 }  // namespace pnp

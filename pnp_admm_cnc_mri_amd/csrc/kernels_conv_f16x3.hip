@@ -29,8 +29,7 @@
 //   prefetch      the next input tile is requested in six pieces, one behind each of taps 0..5's DMA (in-order return: a tile
 //                 requested at once would be waited for at the next weight wait), issued unconditionally so that hipcc counts them
 //   first chunk   its own instance of the code: the accumulators start from a constant-zero C operand, not from 64 register moves
-#include "conv_common.h"
-#include "f16x3_common.h"
+#include "conv_ends.h"
 #include <atomic>
 #include <type_traits>
 #include <cstdlib>
@@ -419,21 +418,7 @@ extern "C" int pnp_conv_h3_prof_read(unsigned long long* out /* [1024][8] */) {
 // (n, kb) of fragment (K step s, N tile nt, part) is part(W[out = 64 cb + 16 nt + n][in = 64 cc + 32 s + 8 kb + j][tap]) --
 // v_mfma_f32_16x16x32_f16: lane l supplies B[k = 8 (l >> 4) + j][column l & 15]; the A side reads input channels in the same
 // order.  As many bytes as the float32 weights.  Once per model.
-__global__ __launch_bounds__(256) void k_conv_pack_w_h3(const float* w_oihw, _Float16* wfrag, int C) {
-    const long long o = (long long)blockIdx.x * 256 + threadIdx.x;      // one (hi, lo) pair per thread
-    if (o >= 9LL * C * C) return;
-    const int NC = C >> 6;
-    const int j = o & 7, lane = (o >> 3) & 63, nt = (o >> 9) & 3, s = (o >> 11) & 1;
-    const long long blk = o >> 12;                                // (cb * NC + cc) * 9 + tap
-    const int tap = (int)(blk % 9), cc = (int)((blk / 9) % NC), cb = (int)(blk / (9 * NC));
-    const int out = 64 * cb + 16 * nt + (lane & 15), in = 64 * cc + 32 * s + 8 * (lane >> 4) + j;
-    const float w = w_oihw[((size_t)out * C + in) * 9 + tap];
-    const _Float16 hi = (_Float16)w;
-    const _Float16 lo = (_Float16)((w - (float)hi) * H3_SCALE);
-    const size_t frag = ((size_t)blk * 2 + s) * 8 + nt * 2;      // the hi fragment; lo follows
-    wfrag[(frag * 64 + lane) * 8 + j] = hi;
-    wfrag[((frag + 1) * 64 + lane) * 8 + j] = lo;
-}
+__global__ __launch_bounds__(256) void k_conv_pack_w_h3(const float* w_oihw, _Float16* wfrag, int C) { conv_pack_w_body<true>(w_oihw, wfrag, C); }
 
 // ------------------------------------------------------------------------------------------
 // Last layer of the stacks (64 -> COUT <= 4 channels, NHWC in, NCHW out, + bias; models/network_ffdnet.py:56, network_dncnn.py:62) in
@@ -442,35 +427,28 @@ __global__ __launch_bounds__(256) void k_conv_pack_w_h3(const float* w_oihw, _Fl
 // one N tile, 18 K steps of 32 x 3 products = 108 MFMAs per tile -- the layer is bound by reading its input.  One workgroup per
 // 8 x 16 tile, 58 KiB of LDS (the split input tile + the split weights of COUT channels): two workgroups per compute unit.
 // ------------------------------------------------------------------------------------------
-struct TailH3Args {
-    const float* x; const float* x2; const float* w; const float* bias; float* y;      // x2: null, or a tensor of x's shape added to it (the U-Net's last skip sum)
-    int n, cout, H, W, tiles_x, tiles_y;
-    // FFDNet's output stage folded into the stores (models/network_ffdnet.py:70-73): cout = 4, and channel 2 dy + dx of pixel (y, x) is pixel
-    // (2 y + dy, 2 x + dx) of the ONE-channel full-resolution result y [n][1][out_h][out_w] (pixel shuffle + the crop of the padded row / column)
-    int shuffle, out_h, out_w;
-};
-__global__ __launch_bounds__(CV_THREADS, 2) void k_conv3x3_tail_h3(TailH3Args t, int ntiles) {
+__global__ __launch_bounds__(CV_THREADS, 2) void k_conv3x3_tail_h3(TailMmaArgs t, int ntiles) {
     // PERSISTENT since round 6 (two workgroups per compute unit, tile = blockIdx.x + k gridDim.x): the next tile's input is requested into
     // registers before this tile's matrix products and split into LDS behind them -- round 5's kernel was one workgroup per tile with nothing
     // to overlap its fetch (130 us for 268 MB at 64 slices of 128 x 128: twice the memory time).
     constexpr int HX = Geo<1>::HX;
     __shared__ __attribute__((aligned(16))) float xin[Geo<1>::XIN];
-    __shared__ __attribute__((aligned(16))) _Float16 wl[9 * 2 * 2 * 4 * 4 * 8];      // [tap][K step][hi, lo][kb][n < 4][8 halves]
+    __shared__ __attribute__((aligned(16))) _Float16 wl[2 * TAIL_WL];               // [tap][K step][hi, lo][kb][n < 4][8 halves]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, kb = lane >> 4;
     int tile = blockIdx.x;
     if (tile >= ntiles) return;                                   // (uniform)
     ConvArgs a;                                                   // the staging helpers' view of the input
-    a.x = t.x; a.H = t.H; a.W = t.W; a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y; a.fmt = 0;
+    a.x = static_cast<const float*>(t.x); a.H = t.H; a.W = t.W; a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y; a.fmt = 0;
     StagingP<1> st;
     staging_init_p<1>(a, tid, st, CV_C * 4);
     f32x4 xpre[Geo<1>::XU];
     auto fetch = [&](const TilePos& q) __attribute__((always_inline)) {
-        a.x = t.x;
+        a.x = static_cast<const float*>(t.x);
         fetch_input_p<1>(a, q, st, xpre, tid, CV_C * 4, 0);
         if (t.x2) {                                               // uniform: x + x2, the sum never goes to memory (models/network_unet.py:134)
-            a.x = t.x2;
+            a.x = static_cast<const float*>(t.x2);
             f32x4 x2pre[Geo<1>::XU];
             fetch_input_p<1>(a, q, st, x2pre, tid, CV_C * 4, 0);
 #pragma unroll
@@ -479,11 +457,10 @@ __global__ __launch_bounds__(CV_THREADS, 2) void k_conv3x3_tail_h3(TailH3Args t,
     };
     fetch(tile_pos(a, tile));
     // weights: w_oihw [cout][64][3][3] -> split halves in the B operand's order (columns >= cout are zeros the lanes supply themselves); once
-    for (int e = tid; e < 9 * 2 * 4 * 4 * 8; e += CV_THREADS) {
-        const int j = e & 7, n = (e >> 3) & 3, kq = (e >> 5) & 3, s2 = (e >> 7) & 1, tap = e >> 8;
-        const float w = n < t.cout ? t.w[((size_t)n * 64 + 32 * s2 + 8 * kq + j) * 9 + tap] : 0.f;
+    for (int e = tid; e < TAIL_WL; e += CV_THREADS) {
+        const float w = tail_mma_weight(t, e);
         const _Float16 hi = (_Float16)w;
-        const int base = (((tap * 2 + s2) * 2) * 4 + kq) * 32 + n * 8 + j;
+        const int base = (e >> 7) * 256 + (e & 127);              // (tap, K step) e >> 7: [hi, lo][kb][n][8]
         wl[base] = hi;
         wl[base + 4 * 32] = (_Float16)((w - (float)hi) * H3_SCALE);
     }
@@ -522,53 +499,18 @@ __global__ __launch_bounds__(CV_THREADS, 2) void k_conv3x3_tail_h3(TailH3Args t,
         }
         // accumulator (reg r, lane (i, kb)) of M tile mt = pixel (tile row 2 w + mt, column h3_row_pixel(4 kb + r)), output channel i
         __syncthreads();                                          // every wave is past its taps: the tile may be reused (below, or by the next tile)
-        if (t.shuffle) {
-            // FFDNet: the tile's 8 x 16 x 4 values are a 16 x 32 block of the full-resolution result; it is assembled in LDS and leaves as
-            // whole rows, two consecutive pixels per thread
-            if (col) {
+        f32x4 out[2];
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
+        for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        xin[(2 * (2 * wv + mt) + (i >> 1)) * 32 + 2 * (h3_row_pixel(4 * kb) + r) + (i & 1)] = fmaf(corrv[mt][r], H3_RSCALE, mainv[mt][r]) + b;
-            }
-            __syncthreads();
-            const int orow = tid >> 4, ocol = 2 * (tid & 15), oy = 2 * q.y0 + orow, ox = 2 * q.x0 + ocol;
-            if (oy < t.out_h) {
-                float* dst = t.y + ((size_t)q.img * t.out_h + oy) * t.out_w + ox;
-                if (ox < t.out_w) dst[0] = xin[orow * 32 + ocol];
-                if (ox + 1 < t.out_w) dst[1] = xin[orow * 32 + ocol + 1];
-            }
-            __syncthreads();                                      // the assembled block is read: the next tile may be written
-        } else if (col) {
-            const size_t plane = (size_t)t.H * t.W;
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                const int gy = q.y0 + 2 * wv + mt;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int gx = q.x0 + h3_row_pixel(4 * kb) + r;
-                    if (gy < t.H && gx < t.W)
-                        t.y[((size_t)q.img * t.cout + i) * plane + (size_t)gy * t.W + gx] = fmaf(corrv[mt][r], H3_RSCALE, mainv[mt][r]) + b;
-                }
-            }
-        }
+            for (int r = 0; r < 4; ++r) out[mt][r] = fmaf(corrv[mt][r], H3_RSCALE, mainv[mt][r]);
+        tail_mma_store(t, q, xin, tid, wv, i, h3_row_pixel(4 * kb), col, b, out);
     }
 }
 
 hipError_t launch_conv3x3_tail_f16x3(hipStream_t s, const float* x_nhwc, const float* x2_nhwc, const float* w_oihw, const float* bias, float* y_nchw,
                                      int n, int cout, int H, int W, int shuffle_h, int shuffle_w) {
-    if (cp_check_tail(n, cout, H, W, shuffle_h, shuffle_w)) return hipErrorInvalidValue;
-    const ConvTiling tl = cp_tiling(n, H, W, CP_NARROW);
-    TailH3Args t;
-    t.shuffle = shuffle_h ? 1 : 0; t.out_h = shuffle_h; t.out_w = shuffle_w;
-    t.x = x_nhwc; t.x2 = x2_nhwc; t.w = w_oihw; t.bias = bias; t.y = y_nchw; t.n = n; t.cout = cout; t.H = H; t.W = W;
-    t.tiles_x = tl.tiles_x; t.tiles_y = tl.tiles_y;
-    const int cus = conv_compute_units();
-    if (cus <= 0) return hipGetLastError();
-    // persistent, two workgroups per compute unit; every loop ends: tile < ntiles
-    hipLaunchKernelGGL(k_conv3x3_tail_h3, dim3((unsigned)cp_grid(tl.items, 2, cus)), dim3(CV_THREADS), 0, s, t, (int)tl.items);
-    return hipGetLastError();
+    return launch_tail_mma(s, k_conv3x3_tail_h3, x_nhwc, x2_nhwc, w_oihw, bias, y_nchw, n, cout, H, W, shuffle_h, shuffle_w);
 }
 
 template <int DIL>

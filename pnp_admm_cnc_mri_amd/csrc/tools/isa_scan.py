@@ -177,6 +177,11 @@ def lds_pending_at_barriers(body, labels=None):
     return bad
 
 
+# kernels that re-use an LDS tile between raw barriers (lds_pending_at_barriers is their protocol): the half-precision kernels
+# (kernels_conv_f16.hip, kernels_pix2x2_f16.hip) and the split-half 2 x 2 kernel that shares pix2x2_body.h with them
+BARRIER_WALK = ('k_conv3x3_f16', 'k_conv3x3_head_f16', 'k_conv3x3_tail_f16', 'k_conv_pack_w_f16', 'k_pix2x2_f16', 'k_pix2_pack_w_f16', 'k_pix2x2_h3')
+
+
 def scan_text(text):
     """[(kernel, store, overwriting instruction)] of one assembly file, and the number of wide buffer stores seen."""
     bad, n = [], 0
@@ -191,7 +196,7 @@ def scan_text(text):
             bad += [(name, 'LDS-DMA order: ' + why, ins)
                     for _, why, ins in dma_order_violations(k['body'], group=2 if pipe else 4, ahead=1 if wide or pipe else 0,
                                                             primed=1 if wide or pipe else 0, labels=k['labels'])]
-        if '_f16E' in name or '_f16I' in name:                      # the half-precision kernels (kernels_conv_f16.hip, kernels_pix2x2_f16.hip)
+        if any('%d%s' % (len(stem), stem) in name for stem in BARRIER_WALK):      # (the mangled name holds <length><identifier>)
             bad += [(name, 'LDS-DMA order: an LDS access may be outstanding at a barrier', ins) for _, _, ins in lds_pending_at_barriers(k['body'], k['labels'])]
     return bad, n
 

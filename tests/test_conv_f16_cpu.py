@@ -176,7 +176,7 @@ def asm(tmp_path_factory):
         pytest.skip('hipcc not installed')
     d = tmp_path_factory.mktemp('gfx950_asm_f16')
     out = {}
-    for src in ('kernels_conv_f16.hip', 'kernels_pix2x2_f16.hip'):
+    for src in ('kernels_conv_f16.hip', 'kernels_pix2x2_f16.hip', 'kernels_pix2x2_f16x3.hip'):
         o = str(d / (src[:-4] + '.s'))
         r = subprocess.run([HIPCC] + FLAGS + ['--cuda-device-only', '-S', os.path.join(CSRC, src), '-o', o], stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=CSRC)
         assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -244,7 +244,8 @@ def test_no_lds_access_is_outstanding_at_any_barrier_of_the_new_kernels(asm):
     waits for no counter: a `ds_read` of the operand tile still in flight when its wave passes the barrier races with the other waves' writes
     of the next tile behind it.  The source puts `s_waitcnt lgkmcnt(0)` in front of every such barrier and a sched_barrier behind each block
     of matrix instructions (hipcc otherwise moves a chunk's reads and MFMAs behind the next chunk's barrier); this walk over the compiled
-    ISA (tools/isa_scan.py, also part of `make`) proves it for every barrier of every new kernel, back edges included."""
+    ISA (tools/isa_scan.py, also part of `make`) proves it for every barrier of every new kernel, back edges included -- and of k_pix2x2_h3
+    (kernels_pix2x2_f16x3.hip), which is the same body (pix2x2_body.h) as k_pix2x2_f16."""
     f = isa_scan.lds_pending_at_barriers
     rd = 'ds_read_b128 v[1:4], v0'
     assert f([rd, 's_waitcnt lgkmcnt(1)', rd, 's_waitcnt vmcnt(4)', 's_barrier'])                   # the shape the 2 x 2 kernel first compiled to
@@ -255,12 +256,12 @@ def test_no_lds_access_is_outstanding_at_any_barrier_of_the_new_kernels(asm):
     loop = ['s_waitcnt lgkmcnt(0)', 's_barrier', rd, 's_cbranch_scc1 .LBB0_1']
     assert not f(loop + ['s_endpgm'], {'.LBB0_1': 0}) and f(loop[1:] + ['s_endpgm'], {'.LBB0_1': 0})
     n_barriers = 0
-    for src in ('kernels_conv_f16.hip', 'kernels_pix2x2_f16.hip'):
+    for src in ('kernels_conv_f16.hip', 'kernels_pix2x2_f16.hip', 'kernels_pix2x2_f16x3.hip'):
         for n, k in isa_scan.kernels_of(asm[src]).items():
             n_barriers += sum(1 for x in k['body'] if x.startswith('s_barrier'))
             bad = f(k['body'], k['labels'])
             assert not bad, (n, bad[:3])
-    assert n_barriers >= 8 * 22 + 4 * 5 + 4                             # 3 x 3 instances, 2 x 2 instances, the last-layer kernel: really walked
+    assert n_barriers >= 8 * 22 + 4 * 5 + 4 + 4 * 5                     # 3 x 3 instances, 2 x 2 instances, the last-layer kernel, the split-half 2 x 2 instances: really walked
 
 
 def test_the_recorded_l1_outputs_of_the_trained_ffdnet_are_the_oracle_loops():

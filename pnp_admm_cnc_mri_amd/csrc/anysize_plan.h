@@ -68,23 +68,34 @@ inline Plan make_plan(int n) {
 
 // ---- host tables, in fp64 (rounded once to float for a float context) ----
 
+// exp(-2 pi i k / L), k in [0, L], to an ulp or two.  The angle is reduced to phi in [0, pi / 4] in integers first (8k = o L + rem:
+// octant o, and phi = pi rem / 4L from the nearer axis), so cos and sin see an argument that carries a relative error of a few
+// 1e-16 of at most pi / 4, and the roots on the axes are exact; cos(2 pi k / L) of the unreduced angle is off by up to 1.3e-15.
+inline void unit_root(long long k, long long L, double& re, double& im) {
+    const long long o = 8 * k / L, rem = 8 * k % L;
+    const bool up = o % 2 == 0;                            // theta = q pi / 2 + phi (up) or q pi / 2 - phi
+    const double phi = M_PI * (double)(up ? rem : L - rem) / (4.0 * (double)L);
+    const double c = cos(phi), s = up ? sin(phi) : -sin(phi);
+    double ct, st;                                         // cos(theta), sin(theta), theta = 2 pi k / L
+    switch (((o + 1) / 2) % 4) {
+    case 0:  ct = c;  st = s;  break;
+    case 1:  ct = -s; st = c;  break;
+    case 2:  ct = -c; st = -s; break;
+    default: ct = s;  st = -c; break;
+    }
+    re = ct; im = -st;
+}
+
 // W_L^i = exp(-2 pi i i / L), i in [0, L)
 inline void twiddles(int L, std::vector<double>& re, std::vector<double>& im) {
     re.resize(L); im.resize(L);
-    for (int i = 0; i < L; ++i) {
-        const double a = -2.0 * M_PI * (double)i / (double)L;
-        re[i] = cos(a); im[i] = sin(a);
-    }
+    for (int i = 0; i < L; ++i) unit_root(i, L, re[i], im[i]);
 }
 
 // w_j = exp(-i pi j^2 / n), j in [0, n); j^2 is reduced mod 2n first (exact in integers) so the angle stays in [0, 2 pi)
 inline void chirp(int n, std::vector<double>& re, std::vector<double>& im) {
     re.resize(n); im.resize(n);
-    for (int j = 0; j < n; ++j) {
-        const long long q = ((long long)j * j) % (2LL * n);
-        const double a = -M_PI * (double)q / (double)n;
-        re[j] = cos(a); im[j] = sin(a);
-    }
+    for (int j = 0; j < n; ++j) unit_root(((long long)j * j) % (2LL * n), 2LL * n, re[j], im[j]);
 }
 
 // ---- butterflies, shared by the host emulation and the kernels (C: float2 / double2 or any struct with x, y) ----

@@ -1,5 +1,6 @@
 """GPU tests of the any-size path (csrc/kernels_anysize.hip): slices of any H, W in [128, 1024] -- 7-smooth lengths on the
-mixed-radix Stockham kernels, the others (218 = 2 * 109, 170 = 2 * 5 * 17, 1021) on Bluestein.
+mixed-radix Stockham kernels (252 = 4 * 3 * 3 * 7 with a radix-7 stage, 135 = 3 * 3 * 3 * 5 with no even stage), the others
+(218 = 2 * 109, 170 = 2 * 5 * 17, 1021) on Bluestein.  Every length on both axes: test_gpu_anysize_sweep.py.
 
   operators  fft2 / ifft2 / A / A^H / Df against NumPy (float, <= 2e-6 relative); synthesis and z0 = |ifft2(y)| of a double
              context against NumPy (<= 1e-12)
@@ -15,8 +16,8 @@ from conftest import rel_l2, weights50
 
 pytestmark = pytest.mark.gpu
 
-OP_SHAPES = [(128, 128), (320, 320), (384, 384), (218, 170), (640, 368), (192, 256), (1021, 1000), (256, 320)]
-LOOP_SHAPES = [(320, 320), (218, 170), (640, 368)]
+OP_SHAPES = [(128, 128), (320, 320), (384, 384), (218, 170), (640, 368), (192, 256), (1021, 1000), (256, 320), (252, 135)]
+LOOP_SHAPES = [(320, 320), (218, 170), (640, 368), (252, 135)]
 KINDS = ('random', 'radial', 'cartesian')
 
 

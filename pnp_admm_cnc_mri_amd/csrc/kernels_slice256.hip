@@ -14,11 +14,13 @@
 //   ADMM_CNC (k_slice<2>) moves less: part of w is read from HBM once per launch, lives on the compute unit for the launch's K
 //   iterations and is stored when they are over.  The share is counted in UNITS (slice_layout.h): unit (s, q) = the q-th 16-byte
 //   access of register set s, 8 KiB per slice, a compile-time property of that instruction slot.  U units: 20 N - U (N / 8) (2K - 1) / K
-//   bytes per iteration.  Resident: set 0 (8 units = row pairs 0..31, 64 KiB) and the units (1, 0), (1, 1) in LDS, the units (3, 0), (3, 1)
-//   in eight registers of every lane: U = 12.  The LDS comes from crossing the transpositions in FOUR passes of a
-//   quarter of the field instead of two of a half (buffer 69 632 B, below the exchange regions it aliases):
-//     exchange regions / buffer 73 728 + W256 table 2 304 + Ys / Ms 2 304 + resident w 65 536 + 16 384 = 160 256 B of LDS
-//   at the price of eight more workgroup barriers per iteration.  The two L1 instances keep the two-pass form (139 776 B).
+//   bytes per iteration.  Resident: set 0 (8 units = row pairs 0..31, 64 KiB) and the units (1, 0) .. (1, 6) in LDS, the units (3, 0), (3, 1)
+//   in eight registers of every lane: U = 17.  The LDS comes from the two transient users of it, both halved: the transpositions cross in
+//   FOUR passes of a quarter of the field, each in two halves of 64 row pairs (buffer 34 816 B), and a transform group's exchange runs in two
+//   planes, real parts and then imaginary parts through the same words (regions of 16 x 17 floats: 34 816 B for the eight waves):
+//     exchange regions / buffer 34 816 + W256 table 2 304 + Ys / Ms 2 304 + resident w 65 536 + 57 344 = 162 304 B of LDS
+//   at the price of 24 more workgroup barriers per iteration (34) and a second LDS round trip per transform.  The two L1 instances keep
+//   the two-pass form and the complex exchange (139 776 B).
 //
 //   rows(first)                 v = z - w, row pairs (2r, 2r+1) packed as one complex row, 16-lane FFT-256
 //   repeat iters times:
@@ -37,7 +39,8 @@
 // has its own LDS region), so the 8 waves of the workgroup drift apart and cover each other's HBM
 // latency; only the two transpositions are workgroup barriers.  Same arithmetic cores as the fused
 // path (fft16.h, fused_pointwise.h); index maps verified on the CPU by tests/host/slice_resident_emulation.cpp
-// (two-pass form) and tests/host/slice_resident4_emulation.cpp (four-pass form and the resident share of w).
+// (two-pass form), tests/host/slice_resident4_emulation.cpp (four-pass form and the resident share of w) and
+// tests/host/slice_split_emulation.cpp (k_slice<2> as it is: planes, halves, units, on one model of the LDS map).
 // Measurements, the road here and the dead ends: DESIGN.md section 4.1.
 #include "engine_host.h"
 #include "fused_layout.h"
@@ -99,21 +102,17 @@ constexpr int WREG = 4 * REGION;              // complex elements of a wave's pr
 constexpr int SL_YS = SL_BUF + REGION;            // operands of the packed column's second half (k2 = 128): Ys (256 complex) + Ms (64 words), see col_phase
 constexpr int SL_LDS = SL_YS + 256 + 32;       // transposition buffer (the 8 wave regions alias its start) + W256 table + those
 static_assert(SL_WAVES * WREG <= SL_BUF, "wave regions must fit in the buffer they alias");
-// Four-pass form (k_slice<2>): the buffer (SL_BUF4) is SMALLER than the wave regions it aliases; behind the tables sits the
-// resident share of w (SL_RES row pairs x 512 floats, never aliased):  73 728 + 2 304 + 2 304 + 65 536 = 143 872 bytes.
-constexpr int SL4_XB = SL_WAVES * WREG;           // exchange regions / transposition buffer
-constexpr int SL4_YS = SL4_XB + REGION;
-constexpr int SL4_RES = SL4_YS + 256 + 32;        // complex index of the resident region (16-byte aligned)
+// k_slice<2> (four passes in eight halves, exchange in two planes): the LDS map SL2_* of slice_layout.h, in bytes --
+//   exchange regions / buffer 34 816 + W256 table 2 304 + Ys / Ms 2 304 + resident w 65 536 + 57 344 = 162 304 bytes.
 // The resident share of w, ONE table for prologue, loop and flush: per register set a mask of the accesses q whose w lives in LDS
 // and one of those whose w lives in registers (units: slice_layout.h).  Set 0 is the region of SL_RES row pairs; the LDS units
-// of set 1 follow it (SL_RES1 x 8 KiB): 143 872 + 16 384 = 160 256 bytes.
+// of set 1 follow it (SL_RES1 x 8 KiB).
 // LDS unit (set, q): floats behind the lane's first access of the set's region (res_lane below)
 __device__ __forceinline__ int sl_lds_float(int set, int q) { return set == 0 ? sl_res_index(0, 0, q) : sl_res1_index(popc8(sl_units_lds(set) & ((1u << q) - 1)), 0, 0); }
-constexpr int SL4_LDS = SL4_RES + SL_RES * 256 + SL_NLDS1 * 1024;
-static_assert(SL_BUF4 <= SL4_XB && SL4_RES % 2 == 0 && SL4_LDS * 8 <= 160 * 1024, "four-pass LDS map");
+static_assert(REGION * 8 == SL2_TW_BYTES && (256 + 32) * 8 == SL2_YS_BYTES && SL2_END % 8 == 0, "tables of the LDS map");
 // which instances cross in four passes and keep part of w on the compute unit: ADMM_CNC.  The two L1 forms stay on two passes: the
 // single-state form is bound by the compute unit and extra barriers only cost it.
-template <int PROX> constexpr bool slice_four() { return PROX == 2; }
+template <int PROX> constexpr bool slice_four() { return PROX == 2; }        // also: exchange in two planes
 template <int PROX> constexpr bool slice_res() { return slice_four<PROX>() && SLICE_RESIDENT; }
 __device__ __forceinline__ void lds_ld4(const float* p, float (&v)[4]) {
     const float4 q = *reinterpret_cast<const float4*>(p);
@@ -232,7 +231,12 @@ __device__ __forceinline__ f2 sub2(f2 a, f2 b) {
 // The packed-fp32 transform core (f2, addsub_rot, rot2, tmul_v, tmul_s, dft16_pk) lives in fft16.h: every float kernel uses it.
 
 // 16-lane FFT-256 on a[16] (lane t holds index t + 16 j), exchange through the group's region
-template <bool INV>
+typedef __attribute__((address_space(3))) float lds_float;
+// SPLIT (k_slice<2>): the region is 16 rows of floats (slice_layout.h: sl_xw) and the exchange runs twice through the same words, real
+// parts and then imaginary parts.  The row comes back dword by dword, each into its own half of a register pair: a 16-byte read
+// delivers four real parts side by side, and 32 moves per exchange would have to pair them with their imaginary parts again
+// (volatile: hipcc otherwise merges the reads into ds_read2_b32 and does move).  The stores pair up as ds_write2_b32.
+template <bool INV, bool SPLIT = false>
 __device__ __forceinline__ void group_fft256(c32 (&ac)[16], const c32* twl, c32* region, int t) {
     // twl is stored per lane in rows of RP: twl[RP t + k] = W256^(t k): one address register + immediate offsets
     typedef float f4 __attribute__((ext_vector_type(4)));
@@ -256,17 +260,31 @@ __device__ __forceinline__ void group_fft256(c32 (&ac)[16], const c32* twl, c32*
         a[2 * m] = tmul_v<INV>(a[2 * m], k2(q.x, q.y));
         a[2 * m + 1] = tmul_v<INV>(a[2 * m + 1], k2(q.z, q.w));
     }
+    if (SPLIT) {
+        float* rf = reinterpret_cast<float*>(region);
+        const volatile lds_float* row = (const volatile lds_float*)(rf + sl_xw(t, 0));     // the address space by hand: it is not inferred for volatile accesses
 #pragma unroll
-    for (int k = 0; k < 16; ++k) reg2[k * RP + t] = a[k];
-    wave_sync();
-    const f4* row4 = reinterpret_cast<const f4*>(reg2 + t * RP);
+        for (int h = 0; h < 2; ++h) {
 #pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        const f4 q = row4[m];
-        a[2 * m] = k2(q.x, q.y);
-        a[2 * m + 1] = k2(q.z, q.w);
+            for (int k = 0; k < 16; ++k) rf[sl_xw(k, t)] = h ? a[k].y : a[k].x;
+            wave_sync();
+#pragma unroll
+            for (int k = 0; k < 16; ++k) { if (h) a[k].y = row[k]; else a[k].x = row[k]; }
+            wave_sync();
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) reg2[k * RP + t] = a[k];
+        wave_sync();
+        const f4* row4 = reinterpret_cast<const f4*>(reg2 + t * RP);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const f4 q = row4[m];
+            a[2 * m] = k2(q.x, q.y);
+            a[2 * m + 1] = k2(q.z, q.w);
+        }
+        wave_sync();
     }
-    wave_sync();
     dft16_pk<INV>(a);
 #pragma unroll
     for (int k = 0; k < 16; ++k) ac[k] = from2(a[k]);
@@ -385,8 +403,28 @@ __device__ __forceinline__ void pointwise_q(const SliceBufs& b, const ProxParams
 // x of the last iteration leaves in NATURAL order (it is the caller's result): the set's x = |re|, |im| / N goes through
 // the wave's four exchange regions once -- region g holds row pair g of the set as 256 complex (row 2r, row 2r + 1) -- and
 // every lane stores 4 consecutive pixels of both rows of each pair.  Once per launch.
+// SPLIT: the regions hold floats (one plane of a row pair): image row 2r goes first, then row 2r + 1.
+template <bool SPLIT = false>
 __device__ __forceinline__ void store_x_natural(const SliceBufs& b, const c32 (&a)[16], c32* wreg, int set, int wv, int lane) {
     const int g = lane >> 4, t = lane & 15;
+    if (SPLIT) {
+        float* wf = reinterpret_cast<float*>(wreg);
+        float* rf = wf + g * SL_XREGION;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) rf[t + 16 * j] = fabsf(h ? a[j].y : a[j].x);
+            wave_sync();
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float v[4];
+                lds_ld4(wf + i * SL_XREGION + 4 * lane, v);
+                st4(b.x, 16 * lane + (2 * (32 * set + 4 * wv + i) + h) * 1024, 0, v);
+            }
+            wave_sync();
+        }
+        return;
+    }
     c32* region = wreg + g * REGION;
 #pragma unroll
     for (int j = 0; j < 16; ++j) region[t + 16 * j] = mk<float>(fabsf(a[j].x), fabsf(a[j].y));
@@ -423,11 +461,11 @@ __device__ __forceinline__ void row_phase_prefetch(const SliceBufs& b, RowLoads&
 // RES: the units of the table (sl_units_lds / sl_units_reg) keep w in LDS at `res` or in the registers `wr`.  The prologue (!HAS_INV)
 // copies them there as it reads them; the loop reads and writes them there; resident_flush below stores them to HBM when the
 // launch's iterations are over.
-template <bool HAS_INV, int PROX, bool HAS_FWD, bool PRELOADED = false, bool RES = false>
+template <bool HAS_INV, int PROX, bool HAS_FWD, bool PRELOADED = false, bool RES = false, bool SPLIT = false>
 __device__ __forceinline__ void row_phase(const SliceBufs& b, const ProxParams& pc, int u_first, bool last, c32 (&F)[SL_SETS][16],
                                           c32* wreg, const c32* twl, int wv, int lane, ResRegs& wr, RowLoads* pre = nullptr, float* res = nullptr) {
     const int g = lane >> 4, t = lane & 15;
-    c32* region = wreg + g * REGION;
+    c32* region = SPLIT ? reinterpret_cast<c32*>(reinterpret_cast<float*>(wreg) + g * SL_XREGION) : wreg + g * REGION;
     const int voff = 2048 * g + 16 * t;
     float* const resl[2] = {RES ? res_lane(res, 0, wv, lane) : nullptr, RES && SL_NLDS1 ? res_lane(res, 1, wv, lane) : nullptr};
     constexpr bool RES_LOOP = RES && HAS_INV;                    // the resident units' w comes from and goes to LDS / registers
@@ -442,9 +480,9 @@ __device__ __forceinline__ void row_phase(const SliceBufs& b, const ProxParams& 
         prio_set(wv, set);
         const int soff = row_set_offset(set, wv);
         if (HAS_INV) {
-            group_fft256<true>(a, twl, region, t);
+            group_fft256<true, SPLIT>(a, twl, region, t);
         }
-        if (HAS_INV && last) store_x_natural(b, a, wreg, set, wv, lane);
+        if (HAS_INV && last) store_x_natural<SPLIT>(b, a, wreg, set, wv, lane);
         const int vs = voff + soff;
         // rolling fetch: access q + PF goes out when access q is consumed (PF accesses = 8 PF registers in flight; all 8 at
         // once, on top of the 128 data registers, made hipcc spill)
@@ -465,7 +503,7 @@ __device__ __forceinline__ void row_phase(const SliceBufs& b, const ProxParams& 
         }
         if (set + 1 < SL_SETS) issue_row_loads<PROX, HAS_INV, 0, PF, RES_LOOP>(b, L, row_set_offset(set + 1, wv), voff, 0, set + 1, resl[set + 1 < 2 ? set + 1 : 0]);
         if (HAS_FWD) {
-            group_fft256<false>(a, twl, region, t);
+            group_fft256<false, SPLIT>(a, twl, region, t);
         }
     }
 }
@@ -563,29 +601,32 @@ __device__ __forceinline__ void t_load_rows(c32 (&F)[16], const c32* rp, int t) 
 // One column-form set's 16 values from the buffer.  MAYBE_PACKED: this wave owns the packed column c = 0 (wave 0, first
 // set of pass 0, lanes 0..15 -- `packed` says which lanes); every other (wave, set) runs the plain two-instruction unpack.
 // Buffer rows 64.. (j >= 8) lie beyond the 16-bit offset of a DS instruction: a second base keeps the offsets immediates.
+// the registers jb .. jb + 7 of a column: 8 buffer rows from `col` on, 8 row pairs apart
+template <bool MAYBE_PACKED, int PITCH>
+__device__ __forceinline__ void t1_read_col8(c32 (&Gs)[16], int jb, const c32* col, int odd, bool packed) {
+    c32 own[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) own[k] = col[8 * k * PITCH];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        // TWICE the unpacked value: the 1/2 is folded into the blend coefficients (blend_scaled, exact)
+        c32 v = mk<float>(add_partner(own[k].x, own[k].y), sub_partner(own[k].y, own[k].x));
+        if (MAYBE_PACKED) {                     // the packed column c = 0 takes the raw values: (C[0], C[128]) -> re / im parts
+            const float oy = dpp_lane_xor1(own[k].y);
+            const c32 raw = mk<float>(odd ? oy : own[k].x, odd ? own[k].x : oy);
+            v = packed ? raw : v;
+        }
+        Gs[jb + k] = v;
+        pin(Gs[jb + k]);                        // unpack as the values arrive: raw values must not pile up across the barrier
+    }
+}
 template <bool MAYBE_PACKED, int PITCH = SL_P>
 __device__ __forceinline__ void t1_read_col(c32 (&Gs)[16], const c32* buf, int off, int odd, bool packed) {
     int off_hi = off + 64 * PITCH;
     asm volatile("" : "+v"(off_hi));                // an index, not a pointer: the address space stays visible to the compiler
     const c32 *col = buf + off, *col_hi = buf + off_hi;
-#pragma unroll
-    for (int jb = 0; jb < 16; jb += 8) {
-        c32 own[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) own[k] = jb ? col_hi[8 * k * PITCH] : col[8 * k * PITCH];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            // TWICE the unpacked value: the 1/2 is folded into the blend coefficients (blend_scaled, exact)
-            c32 v = mk<float>(add_partner(own[k].x, own[k].y), sub_partner(own[k].y, own[k].x));
-            if (MAYBE_PACKED) {                     // the packed column c = 0 takes the raw values: (C[0], C[128]) -> re / im parts
-                const float oy = dpp_lane_xor1(own[k].y);
-                const c32 raw = mk<float>(odd ? oy : own[k].x, odd ? own[k].x : oy);
-                v = packed ? raw : v;
-            }
-            Gs[jb + k] = v;
-            pin(Gs[jb + k]);                        // unpack as the values arrive: raw values must not pile up across the barrier
-        }
-    }
+    t1_read_col8<MAYBE_PACKED, PITCH>(Gs, 0, col, odd, packed);
+    t1_read_col8<MAYBE_PACKED, PITCH>(Gs, 8, col_hi, odd, packed);
 }
 template <int P>
 __device__ __forceinline__ void t1_pass(const c32 (&F)[SL_SETS][16], c32 (&G)[SL_SETS][16], c32* buf, int wv, int lane) {
@@ -603,13 +644,11 @@ __device__ __forceinline__ void t1_pass(const c32 (&F)[SL_SETS][16], c32 (&G)[SL
     __syncthreads();
 }
 
-template <bool MAYBE_PACKED, int PITCH = SL_P>
-__device__ __forceinline__ void t2_write_col(const c32 (&Gs)[16], c32* buf, int off, int odd, bool packed) {
-    int off_hi = off + 64 * PITCH;
-    asm volatile("" : "+v"(off_hi));
-    c32 *col = buf + off, *col_hi = buf + off_hi;
+// the registers jb .. jb + 7 of a column -> 8 buffer rows from `col` on
+template <bool MAYBE_PACKED, int PITCH>
+__device__ __forceinline__ void t2_write_col8(const c32 (&Gs)[16], int jb, c32* col, int odd, bool packed) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
+    for (int j = jb; j < jb + 8; ++j) {
         // the lane pair (even, odd) holds (ue, uo) = column values of image rows 2r, 2r + 1; the even lane writes
         // repack_p(ue, uo) = ue + i uo to the direct slot, the odd lane repack_q(ue, uo) = conj ue + i conj uo to the mirror
         // slot -- with its halves swapped, which makes both lanes' values ( own.x - partner's own.y,  own.y + partner's own.x )
@@ -620,8 +659,16 @@ __device__ __forceinline__ void t2_write_col(const c32 (&Gs)[16], c32* buf, int 
             const c32 raw = mk<float>(odd ? own.y : own.x, odd ? other.y : other.x);
             v = packed ? raw : v;
         }
-        if (j < 8) col[8 * j * PITCH] = v; else col_hi[8 * (j - 8) * PITCH] = v;
+        col[8 * (j - jb) * PITCH] = v;
     }
+}
+template <bool MAYBE_PACKED, int PITCH = SL_P>
+__device__ __forceinline__ void t2_write_col(const c32 (&Gs)[16], c32* buf, int off, int odd, bool packed) {
+    int off_hi = off + 64 * PITCH;
+    asm volatile("" : "+v"(off_hi));
+    c32 *col = buf + off, *col_hi = buf + off_hi;
+    t2_write_col8<MAYBE_PACKED, PITCH>(Gs, 0, col, odd, packed);
+    t2_write_col8<MAYBE_PACKED, PITCH>(Gs, 8, col_hi, odd, packed);
 }
 template <int P>
 __device__ __forceinline__ void t2_pass(const c32 (&G)[SL_SETS][16], c32 (&F)[SL_SETS][16], c32* buf, int wv, int lane) {
@@ -640,30 +687,38 @@ __device__ __forceinline__ void t2_pass(const c32 (&G)[SL_SETS][16], c32 (&F)[SL
 }
 
 // Four-pass form: pass Q moves 4 registers of every row-form set out and column-form set Q in (T1), or back (T2): the same
-// renaming of 32 registers per pass as above, a buffer of a quarter of the field, and ONE instance of the column code per pass.
+// renaming of 32 registers per pass as above and ONE instance of the column code per pass.  Each pass crosses in two HALVES
+// through a buffer of an eighth of the field (slice_layout.h: sl_row8): half h = the row pairs 64 h .. 64 h + 63 = the row-form
+// sets 2h, 2h + 1 = the registers 8h .. 8h + 7 of the column, so every lane stores 8 values and reads 8 in each half.
 template <int Q>
-__device__ __forceinline__ void t1_pass4(const c32 (&F)[SL_SETS][16], c32 (&G)[SL_SETS][16], c32* buf, int wv, int lane) {
+__device__ __forceinline__ void t1_pass8(const c32 (&F)[SL_SETS][16], c32 (&G)[SL_SETS][16], c32* buf, int wv, int lane) {
     const int g = lane >> 4, t = lane & 15;
-#pragma unroll
-    for (int set = 0; set < SL_SETS; ++set) t_store_rows<Q, true>(F[set], buf + (32 * set + 4 * wv + g) * SL_P4, t);
-    __syncthreads();
     const int cc = 4 * wv + g, odd = t & 1;
-    const int off = (t >> 1) * SL_P4 + cc + (odd ? SL_M4 : 0);
-    if (Q == 0 && wv == 0) t1_read_col<true, SL_P4>(G[Q], buf, off, odd, cc == 0);
-    else t1_read_col<false, SL_P4>(G[Q], buf, off, odd, false);
-    __syncthreads();
+    const c32* col = buf + (t >> 1) * SL_P4 + cc + (odd ? SL_M4 : 0);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) t_store_rows<Q, true>(F[2 * h + s], buf + sl_row8(32 * (2 * h + s) + 4 * wv + g) * SL_P4, t);
+        __syncthreads();
+        if (Q == 0 && wv == 0) t1_read_col8<true, SL_P4>(G[Q], 8 * h, col, odd, cc == 0);
+        else t1_read_col8<false, SL_P4>(G[Q], 8 * h, col, odd, false);
+        __syncthreads();
+    }
 }
 template <int Q>
-__device__ __forceinline__ void t2_pass4(const c32 (&G)[SL_SETS][16], c32 (&F)[SL_SETS][16], c32* buf, int wv, int lane) {
+__device__ __forceinline__ void t2_pass8(const c32 (&G)[SL_SETS][16], c32 (&F)[SL_SETS][16], c32* buf, int wv, int lane) {
     const int g = lane >> 4, t = lane & 15;
     const int cc = 4 * wv + g, odd = t & 1;
-    const int off = (t >> 1) * SL_P4 + cc + (odd ? SL_M4 : 0);
-    if (Q == 0 && wv == 0) t2_write_col<true, SL_P4>(G[Q], buf, off, odd, cc == 0);
-    else t2_write_col<false, SL_P4>(G[Q], buf, off, odd, false);
-    __syncthreads();
+    c32* col = buf + (t >> 1) * SL_P4 + cc + (odd ? SL_M4 : 0);
 #pragma unroll
-    for (int set = 0; set < SL_SETS; ++set) t_load_rows<Q, true>(F[set], buf + (32 * set + 4 * wv + g) * SL_P4, t);
-    __syncthreads();
+    for (int h = 0; h < 2; ++h) {
+        if (Q == 0 && wv == 0) t2_write_col8<true, SL_P4>(G[Q], 8 * h, col, odd, cc == 0);
+        else t2_write_col8<false, SL_P4>(G[Q], 8 * h, col, odd, false);
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 2; ++s) t_load_rows<Q, true>(F[2 * h + s], buf + sl_row8(32 * (2 * h + s) + 4 * wv + g) * SL_P4, t);
+        __syncthreads();
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -707,9 +762,12 @@ __device__ __forceinline__ void blend_set(c32 (&a)[16], const c32 (&yh)[16], uns
     }
 }
 
+// SPLIT: plane-split exchanges; the packed column (wave 0, group 0: 272 complex) then borrows the whole of wave 0's region -- the
+// other three groups' exchanges are over there, and a wave's LDS instructions execute in order.
+template <bool SPLIT = false>
 __device__ __forceinline__ void col_phase(const SliceBufs& b, float cdc, float scale, c32 (&G)[SL_SETS][16], c32* wreg, c32* ysl, const c32* twl, int wv, int lane) {
     const int g = lane >> 4, t = lane & 15;
-    c32* region = wreg + g * REGION;
+    c32* region = SPLIT ? reinterpret_cast<c32*>(reinterpret_cast<float*>(wreg) + g * SL_XREGION) : wreg + g * REGION;
     // the blend also applies the inverse transforms' 1/N (scale, a power of two): every coefficient of blend_scaled carries it,
     // the blended field is exactly scale x blend_one's, and the inverse transforms deliver x without a multiplication per pixel
     const float cs = cdc * scale, chs = 0.5f * cdc * scale;
@@ -727,7 +785,7 @@ __device__ __forceinline__ void col_phase(const SliceBufs& b, float cdc, float s
     for (int set = 0; set < SL_SETS; ++set) {
         c32 (&a)[16] = G[set];
         prio_set(wv, set);
-        group_fft256<false>(a, twl, region, t);                   // a[j] = spectrum at k1 = t + 16 j, k2 = c
+        group_fft256<false, SPLIT>(a, twl, region, t);            // a[j] = spectrum at k1 = t + 16 j, k2 = c
         if (set == 0 && wv == 0 && g == 0) {
             // packed column: a = A + i B, A / B = spectra of the real columns k2 = 0 / 128; split with the mirror k1 -> -k1.
             // The region holds the column plus a wrap-around copy of its first 16 values, so that the mirror of
@@ -752,7 +810,7 @@ __device__ __forceinline__ void col_phase(const SliceBufs& b, float cdc, float s
             blend_set(a, Y.yh, Y.code, cs, 0.5f * chs, 0.5f * scale);        // doubled field: half the coefficients
         }
         if (set + 1 < SL_SETS) issue_col_loads(b, Y, set + 1, wv, lane);
-        group_fft256<true>(a, twl, region, t);                    // column c of the blended field, unnormalised
+        group_fft256<true, SPLIT>(a, twl, region, t);             // column c of the blended field, unnormalised
     }
 }
 
@@ -762,14 +820,14 @@ __device__ __forceinline__ void col_phase(const SliceBufs& b, float cdc, float s
 template <int PROX>
 __global__ __launch_bounds__(512) void k_slice(SliceArgs p) {
     constexpr bool FOUR = slice_four<PROX>(), RES = slice_res<PROX>();     // four-pass transpositions; the table's units of w resident in LDS / registers
-    __shared__ __attribute__((aligned(16))) c32 lds[FOUR ? SL4_LDS : SL_LDS];
+    __shared__ __attribute__((aligned(16))) c32 lds[FOUR ? SL2_END / 8 : SL_LDS];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave index as a scalar: bases below stay in SGPRs
-    c32* twl = lds + (FOUR ? SL4_XB : SL_BUF);
-    c32* ysl = lds + (FOUR ? SL4_YS : SL_YS);
-    float* res = RES ? reinterpret_cast<float*>(lds + SL4_RES) : nullptr;
+    c32* twl = lds + (FOUR ? SL2_TW / 8 : SL_BUF);
+    c32* ysl = lds + (FOUR ? SL2_YS / 8 : SL_YS);
+    float* res = RES ? reinterpret_cast<float*>(lds + SL2_RES0 / 8) : nullptr;
     if (tid < 256) twl[RP * (tid >> 4) + (tid & 15)] = g_tws[((tid >> 4) * (tid & 15)) & 255];     // [t][k] = W256^(t k), rows of RP
-    c32* wreg = lds + wv * WREG;
+    c32* wreg = FOUR ? reinterpret_cast<c32*>(reinterpret_cast<float*>(lds) + wv * SL_XWAVE) : lds + wv * WREG;      // FOUR: regions of floats, exchanged in two planes
     __syncthreads();
     for (int sb = blockIdx.x; sb < p.B; sb += gridDim.x) {
         const int sx = ((sb ^ p.slice_xor) < p.B) ? (sb ^ p.slice_xor) : sb;
@@ -790,17 +848,17 @@ __global__ __launch_bounds__(512) void k_slice(SliceArgs p) {
 #define SL_STAMP()
 #endif
         SL_STAMP();
-        row_phase<false, 0, true, false, RES>(b, p.prox, 1, false, F, wreg, twl, wv, opaque(lane), wres, nullptr, res);
+        row_phase<false, 0, true, false, RES, FOUR>(b, p.prox, 1, false, F, wreg, twl, wv, opaque(lane), wres, nullptr, res);
         SL_STAMP();
         for (int it = 0; it < p.iters; ++it) {
             c32 G[SL_SETS][16];
             __syncthreads();                      // every wave is done with its private region: the buffer aliases them
             SL_STAMP();                           // wave 0's wait for the slowest wave of the row phase ends here
             if (FOUR) {
-                t1_pass4<0>(F, G, lds, wv, opaque(lane));
-                t1_pass4<1>(F, G, lds, wv, opaque(lane));
-                t1_pass4<2>(F, G, lds, wv, opaque(lane));
-                t1_pass4<3>(F, G, lds, wv, opaque(lane));
+                t1_pass8<0>(F, G, lds, wv, opaque(lane));
+                t1_pass8<1>(F, G, lds, wv, opaque(lane));
+                t1_pass8<2>(F, G, lds, wv, opaque(lane));
+                t1_pass8<3>(F, G, lds, wv, opaque(lane));
             } else {
                 t1_pass<0>(F, G, lds, wv, opaque(lane));
                 t1_pass<1>(F, G, lds, wv, opaque(lane));
@@ -810,14 +868,14 @@ __global__ __launch_bounds__(512) void k_slice(SliceArgs p) {
 #else
             SL_STAMP();
 #endif
-            col_phase(b, p.c, p.scale, G, wreg, ysl, twl, wv, opaque(lane));
+            col_phase<FOUR>(b, p.c, p.scale, G, wreg, ysl, twl, wv, opaque(lane));
             SL_STAMP();
             __syncthreads();
             SL_STAMP();
             if (FOUR) {
-                t2_pass4<0>(G, F, lds, wv, opaque(lane));
-                t2_pass4<1>(G, F, lds, wv, opaque(lane));
-                t2_pass4<2>(G, F, lds, wv, opaque(lane));
+                t2_pass8<0>(G, F, lds, wv, opaque(lane));
+                t2_pass8<1>(G, F, lds, wv, opaque(lane));
+                t2_pass8<2>(G, F, lds, wv, opaque(lane));
             } else {
                 t2_pass<0>(G, F, lds, wv, opaque(lane));
             }
@@ -825,14 +883,14 @@ __global__ __launch_bounds__(512) void k_slice(SliceArgs p) {
             RowLoads L0;
             row_phase_prefetch<PROX, true, RES>(b, L0, wv, opaque(lane), res);
 #endif
-            if (FOUR) t2_pass4<3>(G, F, lds, wv, opaque(lane));
+            if (FOUR) t2_pass8<3>(G, F, lds, wv, opaque(lane));
             else t2_pass<1>(G, F, lds, wv, opaque(lane));
             SL_STAMP();
             const int u_first = (it == 0);
 #if SLICE_EARLY
-            row_phase<true, PROX, true, true, RES>(b, p.prox, u_first, it + 1 == p.iters, F, wreg, twl, wv, opaque(lane), wres, &L0, res);
+            row_phase<true, PROX, true, true, RES, FOUR>(b, p.prox, u_first, it + 1 == p.iters, F, wreg, twl, wv, opaque(lane), wres, &L0, res);
 #else
-            row_phase<true, PROX, true, false, RES>(b, p.prox, u_first, it + 1 == p.iters, F, wreg, twl, wv, opaque(lane), wres, nullptr, res);
+            row_phase<true, PROX, true, false, RES, FOUR>(b, p.prox, u_first, it + 1 == p.iters, F, wreg, twl, wv, opaque(lane), wres, nullptr, res);
 #endif
             SL_STAMP();
         }
@@ -1057,7 +1115,7 @@ hipError_t slice256_prepare(Slice256* f, hipStream_t s, const float2* y, const u
 }
 
 static hipError_t launch_slice(hipStream_t s, const SliceArgs& a, int prox) {
-    // one workgroup per slice; a workgroup fills a compute unit (512 threads x 256 VGPRs, 137-141 KiB of LDS)
+    // one workgroup per slice; a workgroup fills a compute unit (512 threads x 256 VGPRs, 137-159 KiB of LDS)
     const dim3 grid(a.B);
     if (prox == 2)      hipLaunchKernelGGL(k_slice<2>, grid, dim3(512), 0, s, a);
     else if (prox == 1) hipLaunchKernelGGL(k_slice<1>, grid, dim3(512), 0, s, a);

@@ -1,6 +1,7 @@
 // Index maps of the slice-resident 256x256 kernel (kernels_slice256.hip), shared with the g++ host
 // emulations (tests/host/slice_resident_emulation.cpp: two-pass form; slice_resident4_emulation.cpp: four-pass form + resident w;
-// slice_resident_units_emulation.cpp: the resident units of w).
+// slice_resident_units_emulation.cpp: the resident units of w; slice_split_emulation.cpp: the plane-split exchange, the eighth passes and
+// the LDS map of k_slice<2>).
 //
 // One 512-thread workgroup (8 waves, 2 per SIMD, 256 VGPRs each) keeps ONE real slice on a compute
 // unit for a whole ADMM run: the 65536 values live in the register file (128 VGPRs per thread, four
@@ -17,7 +18,8 @@
 //
 // Row form <-> column form goes through LDS in two passes (the buffer holds half the field; the ADMM_L1 instances) or in
 // four (a quarter; ADMM_CNC, whose freed LDS keeps part of w on the compute unit -- a quarter as whole row pairs, SL_RES, and
-// further (register set, access) units in LDS and in registers: SL_P4 ... the table sl_units_lds / sl_units_reg below).  Two passes:
+// further (register set, access) units in LDS and in registers: SL_P4 ... the table sl_units_lds / sl_units_reg below; each of the
+// four passes crosses in two halves, and the transforms exchange in two planes: "LDS OF k_slice<2>" below).  Two passes:
 //   pass p moves the columns c = 64 p .. 64 p + 63 (register sets 2p and 2p + 1 of the column form).  A row pair needs, per column c, C_r[c] and its
 //   mirror C_r[256 - c] (for c = 0: C_r[0] and C_r[128]) because
 //     V_2r[k2] = (C_r[k2] + conj C_r[-k2]) / 2,   V_2r+1[k2] = (C_r[k2] - conj C_r[-k2]) / (2i)
@@ -46,8 +48,8 @@ PNP_HD int sl_slot(int k) {
     return SL_M + 192 - k;                     // pass 1, mirror of c = 256 - k = 64..127  (k = 129..192)
 }
 // FOUR-pass form (ADMM_CNC, k_slice<2>): pass q moves the columns c = 32 q .. 32 q + 31 = register set q of the column form, so
-// the buffer holds a quarter of the field -- 128 row pairs x pitch 68 x 8 B = 69 632 bytes, less than the wave-private exchange
-// regions it aliases -- and LDS has room for SL_RES row pairs of w that stay on the compute unit for a whole launch (below).
+// a pass moves a quarter of the field -- 128 row pairs x pitch 68 x 8 B = 69 632 bytes; the kernel crosses it in two halves of 64 row
+// pairs (sl_row8 below) -- and LDS has room for SL_RES row pairs of w that stay on the compute unit for a whole launch (below).
 //   slot of (r, c): c - 32 q direct, SL_M4 + c - 32 q mirror (k = 256 - c; for c = 0: k = 128).  Register j of lane t holds
 //   k = t + 16 j, so pass q takes registers 2q, 2q + 1 (direct) and 15 - 2q, 14 - 2q (mirror) -- except in lane 0 of a group,
 //   whose register 14 - 2q holds k = 224 - 32 q, the mirror of column 32 (q + 1): it crosses one pass later (k = 224, 192, 160),
@@ -71,14 +73,17 @@ PNP_HD int sl_res_index(int r, int t, int q) { return 512 * r + 64 * q + 4 * t; 
 // stay in LDS follow it in a second region of SL_RES1 units x 2048 floats, numbered u = 0 .. SL_RES1 - 1 by rising q: the
 // access of row pair 32 + rr (rr = 4 wave + group = 0..31) and lane t starts at float sl_res1_index(u, rr, t) -- a wave's
 // 64 lanes read 1 KiB contiguous.  A lane reads back what it wrote.
-constexpr int SL_RES1 = 2;
+#ifndef SLICE_RES1_UNITS
+#define SLICE_RES1_UNITS 7        // size of the second region: what the compute unit's LDS has room for (the arms of the A/B: 6, 2)
+#endif
+constexpr int SL_RES1 = SLICE_RES1_UNITS;
 PNP_HD int sl_res1_index(int u, int rr, int t) { return 2048 * u + 64 * rr + 4 * t; }
 // The table: which units are resident, and where (compile-time knobs of the kernel; the host emulation reads the same table).
 #ifndef SLICE_RESIDENT
 #define SLICE_RESIDENT 1    // k_slice<2>: part of w stays on the compute unit for a launch, by (register set, access) units -- set 0 in LDS and the units of the
 #endif                      // two masks below (0: no residency at all, four-pass transpositions alone; 2: set 0 only, the kernel before the unit form: the arms of the A/B)
 #ifndef SLICE_UNITS_LDS1
-#define SLICE_UNITS_LDS1 0x03       // bit q: unit (1, q) of w lives in the second LDS region (at most SL_RES1 units)
+#define SLICE_UNITS_LDS1 0x7F       // bit q: unit (1, q) of w lives in the second LDS region (at most SL_RES1 units)
 #endif
 #ifndef SLICE_UNITS_REG
 #define SLICE_UNITS_REG 0x03000000  // bit 8 s + q: unit (s, q) of w lives in four registers of every lane across the iteration loop (default: (3, 0), (3, 1))
@@ -97,6 +102,35 @@ constexpr int sl_reg_slot(int set, int q) {
 constexpr int SL_NREG = sl_reg_slot(SL_SETS, 0);         // register units
 constexpr int SL_NLDS1 = popc8(sl_units_lds(1));          // LDS units of set 1
 static_assert(SL_NLDS1 <= SL_RES1, "the second resident region holds SL_RES1 units");
+
+// LDS OF k_slice<2>, HALVED TRANSIENTS.  The room for SL_RES1 = 7 units comes from the two transient users of LDS:
+//   exchange in two planes: a 16-lane transform group swaps its 16 x 16 complex values through a region of 16 rows of FLOATS, the real
+//     parts first and then the imaginary parts through the same words.  Lane t writes its k-th value to float sl_xw(k, t) and reads its
+//     row, the floats sl_xw(t, 0 .. 15), one dword per access, each straight into the half of the register pair it belongs to.  Pitch 17
+//     and regions of 272 floats: the 32 lanes of a dword access (two groups; bank = word mod 32) hit 32 distinct banks both ways --
+//     17 t mod 32 is the even banks 0 .. 14 and the odd ones 17 .. 31, the next group's region starts 16 banks further.
+//   eighth passes: a transposition pass q (sl_pass4 / sl_slot4 above: same passes, same slots) crosses in two halves, row pairs
+//     0 .. 63 (register sets 0, 1 of the row form = registers j < 8 of the column form) and 64 .. 127; the buffer holds 64 row pairs at
+//     pitch SL_P4, row pair r in row sl_row8(r) of half r >> 6.  Every lane stores 8 values and reads 8 in each half.
+constexpr int SL_XP = 17;
+constexpr int SL_XREGION = 16 * SL_XP;                     // floats of one transform group's region (holds one plane of a row pair in natural order: 256)
+constexpr int SL_XWAVE = 4 * SL_XREGION;                   // floats of a wave's private region (holds the packed column and its wrap-around copy: 2 x 272)
+PNP_HD int sl_xw(int k, int t) { return SL_XP * k + t; }
+constexpr int SL_BUF8 = 64 * SL_P4;                        // complex elements of the eighth-pass buffer
+PNP_HD int sl_row8(int r) { return r & 63; }
+// The map, in bytes, each area behind the one before it (no two can overlap) -- the host emulations check it again:
+//   exchange regions of the 8 waves / the buffer that aliases them | W256 table (16 rows of 18 complex) | Ys (256 complex) + Ms (64 words) |
+//   resident w: set 0 (SL_RES row pairs) | the LDS units of set 1 (SL_RES1 x 8 KiB)
+constexpr int sl_max(int a, int b) { return a > b ? a : b; }
+constexpr int SL2_XB = 0,             SL2_XB_BYTES = sl_max(SL_WAVES * SL_XWAVE * 4, SL_BUF8 * 8);
+constexpr int SL2_TW = SL2_XB + SL2_XB_BYTES,     SL2_TW_BYTES = 16 * 18 * 8;
+constexpr int SL2_YS = SL2_TW + SL2_TW_BYTES,     SL2_YS_BYTES = (256 + 32) * 8;
+constexpr int SL2_RES0 = SL2_YS + SL2_YS_BYTES,   SL2_RES0_BYTES = SL_RES * 2048;
+constexpr int SL2_RES1 = SL2_RES0 + SL2_RES0_BYTES, SL2_RES1_BYTES = SL_RES1 * 8192;
+constexpr int SL2_END = SL2_RES1 + SL2_RES1_BYTES;
+constexpr int SL_LDS_CU = 163840;                          // LDS of a compute unit
+static_assert(SL2_END <= SL_LDS_CU && SL2_TW % 16 == 0 && SL2_RES0 % 16 == 0, "LDS map of k_slice<2>");
+static_assert(2 * SL_XREGION >= 272 && SL_XREGION >= 256 && SL_XREGION % 4 == 0, "what else lives in the exchange regions");
 
 PNP_HD int sl_unit(int set, int wv, int lane) { return 32 * set + 4 * wv + (lane >> 4); }     // r or c
 

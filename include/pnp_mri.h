@@ -298,6 +298,54 @@ int pnp_dwt2_inv(pnp_ctx* ctx, const float* in_dev, float* out_dev, int B);
 int pnp_dwt2_fwd_f64(pnp_ctx* ctx, const double* in_dev, double* out_dev, int B);
 int pnp_dwt2_inv_f64(pnp_ctx* ctx, const double* in_dev, double* out_dev, int B);
 
+/* ---- multi-coil (SENSE) data consistency (added after ABI 13, additive) --------------------------
+ * Measurements from C receive coils with complex sensitivity maps S_c:  y_c = m . fft2(S_c . x),  c = 0 .. C - 1.  NOT in the reference
+ * scripts, whose forward model is one coil of uniform sensitivity; without coils -- the default -- every entry point is bit for bit what
+ * it was.  Conventions as everywhere here: fft2 unnormalised, ifft2 carries 1 / (H W); La2 = 1 / (2 reo); v = z - w is real.
+ *   (A x)_c = m . fft2(S_c . x)         A^H k = sum_c conj(S_c) . ifft2(m . k_c)         G p = A^H A p + La2 p
+ * The x-step solves  G x^ = A^H y + La2 v  over complex x^ by `cg_iters` iterations of plain conjugate gradients warm-started at x^ = v
+ *   r = A^H y + La2 v - G v, p = r;  per iteration  alpha = <r,r> / Re<p,Gp>,  x^ += alpha p,  r -= alpha Gp,  beta = <r+,r+> / <r,r>,
+ *   p = r+ + beta p   (a zero denominator gives alpha resp. beta = 0, never a NaN)
+ * and returns x = |Re x^|.  With C = 1 and S = 1 this is the reference's closed form after ONE iteration.  The initial state is
+ * z = |A^H y|, w = 0.  The z- and w-steps are untouched (pixel prox, wavelet prox, the denoisers of the PnP solvers).
+ * Convergence (maps normalised to sum_c |S_c|^2 = 1, 30 % sampling): the relative distance from the converged solve after 1 / 2 / 3
+ * iterations is 1.1e-4 / 2.8e-6 / 4.9e-8 at reo = 0.05 and 1.1e-5 / 8.6e-8 / 4.7e-10 at reo = 0.015: the default is 3.  UNNORMALISED MAPS
+ * OR A LARGE reo (2.75: condition number about 6.5) NEED MORE: raise cg_iters and watch pnp_cg_residual.
+ * Layout: maps [Ks][C][H][W] interleaved complex in the context's precision -- a bank of Ks coil sets, slice b uses set coil_id[b]
+ * (null: set 0); every k-space argument of a coil context is [B][C][H][W].  On the device one application of G is three launches of the
+ * any-size transform kernels AT EVERY SHAPE (a 256 x 256 or 512 x 512 coil context never enters the slice-resident or two-launch
+ * engines; pnp_path_name says "coils"), an x-step is 5 + 5 cg_iters launches with no host synchronisation, and every sum runs in a
+ * fixed order that depends on (H, W) alone: results are bit-equal from run to run and for a slice alone or inside a batch.
+ * pnp_coils_check: the argument rule (1 <= C <= 32, Ks >= 1, H and W in [128, 1024]) without a context or a device. */
+int pnp_coils_check(int C, int Ks, int H, int W);
+/* Sets (C >= 1) or clears (C = 0; sens and Ks ignored) the coils of the context.  Either way the uploaded problem is dropped (the next
+ * call that needs one returns PNP_E_STATE until an upload).  Setting allocates two [Bmax][C][H][W] complex arrays (transform
+ * intermediate, measurements) and five [Bmax][H][W] complex ones; an allocation that fails is PNP_E_NOMEM with the number of bytes asked
+ * for in the message, and leaves the context without coils.  A batch whose arrays do not fit is not chunked. */
+int pnp_set_coils(pnp_ctx* ctx, const float* sens, int C, int Ks, int on_device);
+int pnp_set_coils_f64(pnp_ctx* ctx, const double* sens, int C, int Ks, int on_device);
+/* CG iterations per x-step, 1 .. 64 (default 3); belongs to the context, survives pnp_set_coils. */
+int pnp_set_cg(pnp_ctx* ctx, int iters);
+int pnp_get_coils(pnp_ctx* ctx, int* C, int* Ks, int* cg_iters);          /* C = 0: no coils */
+/* The problem of a coil context: y [B][C][H][W]; coil_id [B] or null.  A^H y is formed here, once.  The single-coil entry points
+ * (pnp_upload_problem, pnp_synthesize_problem and their _f64 forms) fail with PNP_E_STATE on a coil context, these on one without. */
+int pnp_upload_problem_mc(pnp_ctx* ctx, const float* y, const uint8_t* mask_bank, const int32_t* mask_id, const int32_t* coil_id,
+                          int B, int K, int on_device);
+int pnp_upload_problem_mc_f64(pnp_ctx* ctx, const double* y, const uint8_t* mask_bank, const int32_t* mask_id, const int32_t* coil_id,
+                              int B, int K, int on_device);
+/* y_c = m . fft2(S_c . img) + noise (the noise is added at EVERY k-space point, as pnp_synthesize_problem does).  noise_mode 0: one
+ * [H][W] array for all coils and slices; 1: [C][H][W], shared by the slices; 2: [B][C][H][W]. */
+int pnp_synthesize_problem_mc(pnp_ctx* ctx, const float* img, const float* noise, int noise_mode, const uint8_t* mask_bank,
+                              const int32_t* mask_id, const int32_t* coil_id, int B, int K, int on_device);
+int pnp_synthesize_problem_mc_f64(pnp_ctx* ctx, const float* img, const double* noise, int noise_mode, const uint8_t* mask_bank,
+                                  const int32_t* mask_id, const int32_t* coil_id, int B, int K, int on_device);
+/* On a coil context pnp_init_state, pnp_admm_l1_run, pnp_admm_cnc_run, their _traced forms and pnp_dc_step follow the mathematics
+ * above; pnp_A takes x [B][H][W] real to k [B][C][H][W], pnp_AH takes k to a complex image [B][H][W] (k is not modified);
+ * pnp_download_y[_f64] returns [B][C][H][W]; pnp_get_plan / pnp_kernels_per_iteration report 5 + 5 cg_iters launches plus the prox (1, or
+ * 2 with a wavelet); pnp_Df fails with PNP_E_STATE.
+ * pnp_cg_residual: ||r|| / ||A^H y + La2 v|| of the most recent x-step, per slice, rel [B] on the host (synchronises). */
+int pnp_cg_residual(pnp_ctx* ctx, double* rel);
+
 /* ---- optional HIP backend of the denoisers' plain conv stacks ------------------------------
  * The north star keeps the CNN forward pass in PyTorch-ROCm; these two entry points are the opt-in `Denoiser(backend='hip')`
  * for the 64 -> 64 channel conv3x3 (+ bias, + ReLU) body layers of FFDNet / DnCNN / FDnCNN (models/network_ffdnet.py:58-73,

@@ -110,6 +110,17 @@ SIGNATURES = {
     'pnp_dwt2_inv': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
     'pnp_dwt2_fwd_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
     'pnp_dwt2_inv_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
+    # multi-coil (SENSE) data consistency (added after ABI 13, additive)
+    'pnp_coils_check': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'pnp_set_coils': (C.c_int, [ctx_p, _vp, C.c_int, C.c_int, C.c_int]),
+    'pnp_set_coils_f64': (C.c_int, [ctx_p, _vp, C.c_int, C.c_int, C.c_int]),
+    'pnp_set_cg': (C.c_int, [ctx_p, C.c_int]),
+    'pnp_get_coils': (C.c_int, [ctx_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'pnp_upload_problem_mc': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
+    'pnp_upload_problem_mc_f64': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
+    'pnp_synthesize_problem_mc': (C.c_int, [ctx_p, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
+    'pnp_synthesize_problem_mc_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
+    'pnp_cg_residual': (C.c_int, [ctx_p, c_double_p]),
     'pnp_ssim': (C.c_int, [ctx_p, _vp, _vp, C.c_int, c_double_p]),
     'pnp_timer_start': (C.c_int, [ctx_p]),
     'pnp_timer_stop': (C.c_int, [ctx_p, c_float_p]),

@@ -3,6 +3,7 @@
 #include "../../include/pnp_mri.h"
 #include "internal.h"
 #include "wavelet_plan.h"
+#include "coil_plan.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -89,6 +90,23 @@ struct Trace {
     std::vector<double> values;       // [checks][TRACE_Q][B]: r_pri, r_dual, x_norm, z_norm, w_norm, psnr, re
 };
 
+// Multi-coil (SENSE) data consistency (pnp_set_coils; coil_plan.h): the maps, the coil arrays and the state of the batched CG x-step.
+// C = 0: no coils -- the context is what it was.
+struct Coils {
+    int C = 0, Ks = 0, cg_iters = 3;
+    void* maps = nullptr;             // [Ks][C][H][W] complex
+    int32_t* coil_id = nullptr;       // [Bmax]
+    int32_t* mask_idx = nullptr;      // [Bmax * C]: mask_id expanded to the pseudo-slices of the column kernels
+    void* work = nullptr;             // [Bmax][C][H][W] complex: the coil transform intermediate
+    void* ymc = nullptr;              // [Bmax][C][H][W] complex: the measurements (pnp_download_y)
+    void *aty = nullptr, *xh = nullptr, *r = nullptr, *p = nullptr, *gp = nullptr;      // [Bmax][H][W] complex
+    double *part_row = nullptr, *part_rr[2] = {nullptr, nullptr}, *part_bb = nullptr;   // [Bmax][H] resp. [Bmax][cg_blocks(N)]
+    double *scal = nullptr, *rel = nullptr;                                             // [Bmax][4]: alpha, beta, <r,r>; [Bmax]
+    bool have_rel = false;            // an x-step has run on the current problem
+    AnySize* any = nullptr;           // the transforms of a coil context: the any-size kernels at every shape (the context's own, or made here)
+    bool own_any = false;
+};
+
 struct pnp_ctx {
     int device = 0, H = 0, W = 0, Bmax = 0;
     int B = 0, K = 0;                 // current problem (0 = none uploaded)
@@ -118,6 +136,7 @@ struct pnp_ctx {
     Trace trace;
     int wavelet = WV_NONE, wv_levels = 0;   // pnp_set_sparsity: the prox of the loops acts on the coefficients of this transform
     void* wv_coef = nullptr;          // [Bmax][H][W] real: the coefficients between the two prox launches (on first use)
+    Coils coils;
 };
 
 // The context's buffers as the element type of its precision (R = float | double).
@@ -291,7 +310,7 @@ static int ensure_tables(pnp_ctx* c, Path path) {
 // Ends every upload / synthesize: decides the loops' path of the new problem and builds the tables that must exist now.  Any failure --
 // rc from writing the problem, or a failed build -- leaves no problem behind: B = 0.
 static int finish_problem(pnp_ctx* c, int rc) {
-    if (rc == PNP_OK && c->eng.kind != Engine::none) {
+    if (rc == PNP_OK && c->eng.kind != Engine::none && c->coils.C == 0) {          // a coil context never enters the fast engines
         c->prob.path = (c->eng.slice && slice_pays(c)) ? Path::slice : Path::fused;
         if (c->prob.path == Path::fused) rc = ensure_tables(c, Path::fused);
     }
@@ -300,7 +319,7 @@ static int finish_problem(pnp_ctx* c, int rc) {
 }
 
 // The loops' path now: pnp_set_fast_path may change it after the upload.
-static Path loop_path(const pnp_ctx* c) { return c->fast ? c->prob.path : Path::generic; }
+static Path loop_path(const pnp_ctx* c) { return (c->fast && c->coils.C == 0) ? c->prob.path : Path::generic; }
 // ... and where the data-consistency step alone runs (pnp_dc_step; the loops with a wavelet set): it has no slice-resident form
 static Path dc_path(const pnp_ctx* c) { return loop_path(c) == Path::generic ? Path::generic : Path::fused; }
 
@@ -382,6 +401,7 @@ static int synthesize_problem(pnp_ctx* c, const char* who, const float* img, con
 
 template <typename R> static int download_y(pnp_ctx* c, const char* who, R* y, int on_device) {
     if (!y) return fail(PNP_E_ARG, "%s: null", who);
+    if (c->coils.C > 0) return copy_out(c, y, c->coils.ymc, (size_t)c->B * c->coils.C * c->N * 2 * sizeof(R), on_device);      // [B][C][H][W]
     return copy_out(c, y, c->y, (size_t)c->B * c->N * 2 * sizeof(R), on_device);
 }
 
@@ -395,6 +415,13 @@ template <typename R> static int download_x(pnp_ctx* c, const char* who, R* x, i
 template <typename R> static int init_state(pnp_ctx* c) {
     const Bufs<R> b = bufs<R>(c);
     c->state_sliced = false;                           // both arrays are rewritten below, in natural order
+    if (c->coils.C > 0) {                              // z = |A^H y|, w = 0
+        HIPCHK(launch_cabs<R>(c->stream, (const typename CxOf<R>::type*)c->coils.aty, b.z, (size_t)c->B * c->N));
+        HIPCHK(hipMemsetAsync(b.w, 0, (size_t)c->B * c->N * sizeof(R), c->stream));
+        c->have_x = false;
+        c->have_state = true;
+        return PNP_OK;
+    }
     ColArgsT<R> ca{};
     ca.in = b.y; ca.out = b.work; ca.B = c->B;
     HIPCHK(cols<R>(c, false, MID_NONE, true, ca));
@@ -426,6 +453,248 @@ template <typename R> static int get_state(pnp_ctx* c, R* z, R* w, int on_device
     if ((rc = state_order<R>(c, false))) return rc;
     if (z) { rc = copy_out(c, z, c->z, bytes, on_device); if (rc) return rc; }
     if (w) { rc = copy_out(c, w, c->w, bytes, on_device); if (rc) return rc; }
+    return PNP_OK;
+}
+
+
+// ---- multi-coil (SENSE) data consistency: coil_plan.h, kernels_coils.hip, the coil row roles of kernels_anysize.hip ----
+
+static int wavelet_scratch(pnp_ctx* c);
+
+#define NO_COILS(c, mc) do { if ((c)->coils.C > 0) return fail(PNP_E_STATE, "%s: the context has coils (pnp_set_coils): use %s", __func__, mc); } while (0)
+#define NEED_COILS(c) do { if ((c)->coils.C == 0) return fail(PNP_E_STATE, "%s: the context has no coils (pnp_set_coils); without coils use the call without _mc", __func__); } while (0)
+
+static void coils_free(pnp_ctx* c) {
+    Coils& k = c->coils;
+    void* ptrs[] = {k.maps, k.coil_id, k.mask_idx, k.work, k.ymc, k.aty, k.xh, k.r, k.p, k.gp, k.part_row, k.part_rr[0], k.part_rr[1],
+                    k.part_bb, k.scal, k.rel};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (k.own_any) anysize_destroy(k.any);
+    const int iters = k.cg_iters;
+    k = Coils{};
+    k.cg_iters = iters;
+}
+
+template <typename R> static CoilRowArgsT<R> coil_rows(const pnp_ctx* c, int B) {
+    using C = typename CxOf<R>::type;
+    CoilRowArgsT<R> a{};
+    a.maps = (const C*)c->coils.maps; a.coil_id = c->coils.coil_id; a.ncoils = c->coils.C; a.H = c->H;
+    a.work = (C*)c->coils.work; a.scale = 1; a.nrows = B * c->H;
+    return a;
+}
+template <typename R> static ColArgsT<R> coil_cols(const pnp_ctx* c, const void* in, void* out) {
+    using C = typename CxOf<R>::type;
+    ColArgsT<R> a{};
+    a.in = (const C*)in; a.out = (C*)out; a.mask_bank = c->mask_bank; a.mask_id = c->coils.mask_idx; a.B = c->B * c->coils.C;
+    return a;
+}
+
+// out = A^H k = sum_c conj(S_c) ifft2(m k_c): columns out of place into the work array, combining rows.  k: [B][C][H][W], out: [B][H][W] complex
+template <typename R> static int coil_AH(pnp_ctx* c, const void* k, void* out) {
+    using C = typename CxOf<R>::type;
+    HIPCHK(anysize_cols<R>(c->coils.any, c->stream, false, MID_MASK, true, coil_cols<R>(c, k, c->coils.work)));
+    CoilRowArgsT<R> ra = coil_rows<R>(c, c->B);
+    ra.cout = (C*)out; ra.scale = (R)1 / (R)c->N;
+    HIPCHK(anysize_coil_rows_epi<R>(c->coils.any, c->stream, ra));
+    return PNP_OK;
+}
+
+// gp = G p: three launches.  Leaves the row partials of Re<p, Gp> in part_row.
+template <typename R> static int coil_G(pnp_ctx* c, const void* p, void* gp, R la2) {
+    using C = typename CxOf<R>::type;
+    CoilRowArgsT<R> ra = coil_rows<R>(c, c->B);
+    ra.cin = (const C*)p;
+    HIPCHK(anysize_coil_rows_in<R>(c->coils.any, c->stream, ra));
+    HIPCHK(anysize_cols<R>(c->coils.any, c->stream, true, MID_MASK, true, coil_cols<R>(c, c->coils.work, c->coils.work)));
+    CoilRowArgsT<R> rb = coil_rows<R>(c, c->B);
+    rb.cout = (C*)gp; rb.p = (const C*)p; rb.partial = c->coils.part_row; rb.la2 = la2; rb.scale = (R)1 / (R)c->N;
+    HIPCHK(anysize_coil_rows_epi<R>(c->coils.any, c->stream, rb));
+    return PNP_OK;
+}
+
+// The x-step: cg_iters iterations of CG on G x^ = aty + La2 (z - w), warm-started at z - w; x = |Re x^|.  cg_launches(cg_iters) launches,
+// no host synchronisation: every scalar stays on the device (kernels_coils.hip).
+template <typename R> static int coil_xstep(pnp_ctx* c, const R* z, const R* w, R* x, double reo) {
+    using C = typename CxOf<R>::type;
+    Coils& k = c->coils;
+    const R la2 = (R)(1.0 / 2.0 / reo);
+    const int B = c->B, iters = k.cg_iters;
+    C *xh = (C*)k.xh, *r = (C*)k.r, *p = (C*)k.p, *gp = (C*)k.gp;
+    HIPCHK(launch_cg_begin<R>(c->stream, z, w, xh, B, c->N));
+    if (int rc = coil_G<R>(c, xh, gp, la2)) return rc;
+    HIPCHK(launch_cg_init<R>(c->stream, (const C*)k.aty, xh, gp, r, p, la2, k.part_rr[0], k.part_bb, B, c->N));
+    int cur = 0;
+    for (int i = 0; i < iters; ++i) {
+        const bool last = i == iters - 1;
+        if (int rc = coil_G<R>(c, p, gp, la2)) return rc;
+        HIPCHK(launch_cg_xr<R>(c->stream, xh, r, p, gp, k.part_rr[cur], k.part_row, k.part_rr[cur ^ 1], k.scal, last ? x : (R*)nullptr, B, c->N, c->H));
+        if (!last) HIPCHK(launch_cg_p<R>(c->stream, r, p, k.part_rr[cur], k.part_rr[cur ^ 1], k.scal, B, c->N));
+        cur ^= 1;
+    }
+    HIPCHK(launch_cg_residual(c->stream, k.part_rr[cur], k.part_bb, k.rel, B, c->N));
+    k.have_rel = true;
+    return PNP_OK;
+}
+
+// the loops of a coil context: per iteration the x-step and the pixel prox (one launch) or the wavelet prox (two), on the state in
+// natural order; every iteration stands alone, so a run cut anywhere (the trace's legs) is bit-equal to the uncut run
+template <typename R>
+static int run_coil_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
+    const Bufs<R> b = bufs<R>(c);
+    const size_t n = (size_t)c->B * c->N;
+    if (c->wavelet != WV_NONE && iters > 0) if (int rc = wavelet_scratch(c)) return rc;
+    if (iters == 0) HIPCHK(hipMemcpyAsync(b.x, b.z, n * sizeof(R), hipMemcpyDeviceToDevice, c->stream));
+    for (int i = 0; i < iters; ++i) {
+        if (int rc = coil_xstep<R>(c, b.z, b.w, b.x, reo)) return rc;
+        if (c->wavelet != WV_NONE) {
+            HIPCHK(launch_wavelet_prox<R>(c->stream, c->wavelet, c->wv_levels, cnc, b.x, b.z, b.w, (R*)c->wv_coef, pp, c->B, c->H, c->W));
+        } else if constexpr (std::is_same_v<R, double>) {
+            HIPCHK(launch_prox_f64(c->stream, cnc, b.x, b.z, b.w, pp, n));
+        } else {
+            HIPCHK(launch_prox(c->stream, cnc, b.x, b.z, b.w, pp, n));
+        }
+    }
+    c->have_x = true;
+    return PNP_OK;
+}
+
+// after begin_problem on a coil context: the coil set of every slice, the expanded mask index
+static int coil_begin(pnp_ctx* c, const int32_t* coil_id, int B, int on_device) {
+    Coils& k = c->coils;
+    k.have_rel = false;
+    if (coil_id) {
+        std::vector<int32_t> tmp;
+        const int32_t* ids = coil_id;
+        if (on_device) {
+            tmp.resize((size_t)B);
+            HIPCHK(hipMemcpyAsync(tmp.data(), coil_id, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            ids = tmp.data();
+        }
+        for (int i = 0; i < B; ++i) if (ids[i] < 0 || ids[i] >= k.Ks) return fail(PNP_E_ARG, "coil_id[%d]=%d out of range [0,%d)", i, ids[i], k.Ks);
+        if (int rc = copy_in(c, k.coil_id, coil_id, (size_t)B * sizeof(int32_t), on_device)) return rc;
+    } else {
+        HIPCHK(hipMemsetAsync(k.coil_id, 0, (size_t)B * sizeof(int32_t), c->stream));
+    }
+    HIPCHK(launch_expand_ids(c->stream, c->mask_id, k.mask_idx, B, k.C));
+    return PNP_OK;
+}
+// ends a coil upload / synthesis: aty = A^H y, once per problem; a failure leaves no problem behind
+template <typename R> static int coil_finish(pnp_ctx* c, int rc) {
+    if (rc == PNP_OK) rc = coil_AH<R>(c, c->coils.ymc, c->coils.aty);
+    if (rc != PNP_OK) { c->B = 0; c->prob = Problem{}; }
+    return rc;
+}
+
+template <typename R>
+static int upload_problem_mc(pnp_ctx* c, const char* who, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, const int32_t* coil_id,
+                             int B, int K, int on_device) {
+    if (!y) { c->B = 0; return fail(PNP_E_ARG, "%s: y is null", who); }
+    int rc = begin_problem(c, mask_bank, mask_id, B, K, on_device);
+    if (rc == PNP_OK) rc = coil_begin(c, coil_id, B, on_device);
+    if (rc == PNP_OK) rc = copy_in(c, c->coils.ymc, y, (size_t)B * c->coils.C * c->N * 2 * sizeof(R), on_device);
+    return coil_finish<R>(c, rc);
+}
+
+// y_c = m fft2(S_c img) + noise; noise_mode 0: one [H][W] array for every coil and slice, 1: [C][H][W] for every slice, 2: [B][C][H][W]
+template <typename R>
+static int synthesize_y_mc(pnp_ctx* c, const float* img, const R* noise, int noise_mode, int B, int on_device) {
+    using C = typename CxOf<R>::type;
+    const Bufs<R> b = bufs<R>(c);
+    const int nc = c->coils.C;
+    const size_t img_bytes = (size_t)B * c->N * sizeof(float), coil_bytes = (size_t)nc * c->N * sizeof(C);
+    const size_t noise_bytes = noise_mode == 0 ? c->N * sizeof(C) : (size_t)B * coil_bytes;
+    const float* d_img = img;
+    const C* d_noise = (const C*)noise;
+    if (!on_device || noise_mode == 1) {
+        if (noise_bytes + img_bytes > c->stage_bytes) {
+            if (c->stage) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->stage)); c->stage = nullptr; c->stage_bytes = 0; }
+            HIPCHK(hipMalloc(&c->stage, noise_bytes + img_bytes));
+            c->stage_bytes = noise_bytes + img_bytes;
+        }
+        char* st = (char*)c->stage;
+        if (noise_mode == 1) {
+            for (int s = 0; s < B; ++s) if (int rc = copy_in(c, st + (size_t)s * coil_bytes, noise, coil_bytes, on_device)) return rc;
+            d_noise = (const C*)st;
+        } else if (!on_device) {
+            if (int rc = copy_in(c, st, noise, noise_bytes, 0)) return rc;
+            d_noise = (const C*)st;
+        }
+        if (!on_device) {
+            if (int rc = copy_in(c, st + noise_bytes, img, img_bytes, 0)) return rc;
+            d_img = (const float*)(st + noise_bytes);
+        }
+    }
+    CoilRowArgsT<R> ra = coil_rows<R>(c, B);
+    if constexpr (std::is_same_v<R, double>) {
+        HIPCHK(launch_widen(c->stream, d_img, b.x, (size_t)B * c->N));
+        ra.rin = b.x;
+    } else {
+        ra.rin = d_img;
+    }
+    ra.work = (C*)c->coils.ymc;
+    HIPCHK(anysize_coil_rows_in<R>(c->coils.any, c->stream, ra));
+    ColArgsT<R> ca = coil_cols<R>(c, c->coils.ymc, c->coils.ymc);
+    ca.y = d_noise; ca.y_per_slice = noise_mode != 0;
+    HIPCHK(anysize_cols<R>(c->coils.any, c->stream, true, MID_MASK_ADD, false, ca));
+    return PNP_OK;
+}
+
+template <typename R>
+static int synthesize_problem_mc(pnp_ctx* c, const char* who, const float* img, const R* noise, int noise_mode, const uint8_t* mask_bank,
+                                 const int32_t* mask_id, const int32_t* coil_id, int B, int K, int on_device) {
+    if (!img || !noise) { c->B = 0; return fail(PNP_E_ARG, "%s: img/noise is null", who); }
+    if (noise_mode < 0 || noise_mode > 2) { c->B = 0; return fail(PNP_E_ARG, "%s: noise_mode must be 0 ([H][W]), 1 ([C][H][W]) or 2 ([B][C][H][W]) (got %d)", who, noise_mode); }
+    int rc = begin_problem(c, mask_bank, mask_id, B, K, on_device);
+    if (rc == PNP_OK) rc = coil_begin(c, coil_id, B, on_device);
+    if (rc == PNP_OK) rc = synthesize_y_mc<R>(c, img, noise, noise_mode, B, on_device);
+    return coil_finish<R>(c, rc);
+}
+
+// pnp_set_coils: C = 0 clears.  Either way the uploaded problem is dropped.
+template <typename R>
+static int set_coils(pnp_ctx* c, const char* who, const R* sens, int C, int Ks, int on_device) {
+    using Cx = typename CxOf<R>::type;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->B = 0; c->prob = Problem{};
+    c->state_sliced = c->have_x = c->have_state = false;
+    coils_free(c);
+    if (C == 0) return PNP_OK;
+    if (!sens) return fail(PNP_E_ARG, "%s: sens is null", who);
+    Coils& k = c->coils;
+    const size_t BN = (size_t)c->Bmax * c->N, nblk = (size_t)cg_blocks(c->N);
+    const size_t work_bytes = coil_work_elems(c->Bmax, C, c->H, c->W) * sizeof(Cx), map_bytes = coil_map_elems(Ks, C, c->H, c->W) * sizeof(Cx);
+    struct Want { void** p; size_t bytes; const char* what; };
+    const Want wants[] = {
+        {&k.maps, map_bytes, "coil maps"}, {&k.work, work_bytes, "coil work array"}, {&k.ymc, work_bytes, "coil measurements"},
+        {&k.aty, BN * sizeof(Cx), "CG arrays"}, {&k.xh, BN * sizeof(Cx), "CG arrays"}, {&k.r, BN * sizeof(Cx), "CG arrays"},
+        {&k.p, BN * sizeof(Cx), "CG arrays"}, {&k.gp, BN * sizeof(Cx), "CG arrays"},
+        {(void**)&k.coil_id, (size_t)c->Bmax * sizeof(int32_t), "coil_id"}, {(void**)&k.mask_idx, (size_t)c->Bmax * C * sizeof(int32_t), "mask index"},
+        {(void**)&k.part_row, (size_t)c->Bmax * cg_row_partials(c->H) * sizeof(double), "CG partials"},
+        {(void**)&k.part_rr[0], c->Bmax * nblk * sizeof(double), "CG partials"}, {(void**)&k.part_rr[1], c->Bmax * nblk * sizeof(double), "CG partials"},
+        {(void**)&k.part_bb, c->Bmax * nblk * sizeof(double), "CG partials"},
+        {(void**)&k.scal, (size_t)c->Bmax * 4 * sizeof(double), "CG scalars"}, {(void**)&k.rel, (size_t)c->Bmax * sizeof(double), "CG residual"},
+    };
+    for (const Want& w : wants) {
+        const hipError_t e = hipMalloc(w.p, w.bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            *w.p = nullptr;
+            coils_free(c);
+            return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the %s: %zu bytes asked for (Bmax=%d, C=%d, %dx%d): %s",
+                        who, w.what, w.bytes, c->Bmax, C, c->H, c->W, hipGetErrorString(e));
+        }
+    }
+    HIPCHK(hipMemsetAsync(k.scal, 0, (size_t)c->Bmax * 4 * sizeof(double), c->stream));
+    if (c->any) k.any = c->any;
+    else {
+        hipError_t e = hipSuccess;
+        k.any = anysize_create(c->H, c->W, c->f64, &e);
+        if (!k.any) { coils_free(c); return fail(PNP_E_HIP, "%s: transform tables: %s", who, hipGetErrorString(e)); }
+        k.own_any = true;
+    }
+    k.C = C; k.Ks = Ks;                                   // from here on the context has coils
+    if (int rc = copy_in(c, k.maps, sens, map_bytes, on_device)) { coils_free(c); return rc; }
     return PNP_OK;
 }
 
@@ -525,6 +794,7 @@ static int run_wavelet_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R
 
 template <typename R>
 static int run_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
+    if (c->coils.C > 0) return run_coil_loop<R>(c, iters, cnc, pp, reo);
     if (c->wavelet != WV_NONE && iters > 0) return run_wavelet_loop<R>(c, iters, cnc, pp, reo);
     const Bufs<R> b = bufs<R>(c);
     const Path path = iters > 0 ? loop_path(c) : Path::generic;
@@ -769,6 +1039,7 @@ static int residuals_any(pnp_ctx* c, const char* who, const R* x, const R* z, co
 
 // What the next loop call runs (pnp_get_plan): the plans the engines themselves run by (loop_schedule.h).
 static LoopPlan loop_plan(const pnp_ctx* c) {
+    if (c->coils.C > 0) return {1, c->B, coil_iteration_launches(c->coils.cg_iters, c->wavelet != WV_NONE), false, 1, c->B};
     if (c->wavelet != WV_NONE) return {1, c->B, 5, false, 1, c->B};   // the data-consistency step (three launches on every path) + two prox launches
     switch (loop_path(c)) {
     case Path::generic: break;
@@ -976,6 +1247,7 @@ int pnp_ctx_destroy(pnp_ctx* c) {
     case Engine::fused512:  fused512_destroy(c->eng.f512); break;
     }
     slice256_destroy(c->eng.slice);
+    coils_free(c);
     anysize_destroy(c->any);
     void* ptrs[] = {c->y, c->work, c->z, c->w, c->x, c->mask_bank, c->mask_id, c->gt, c->acc, c->stage, c->ssim_part,
                     c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc, c->wv_coef};
@@ -1004,19 +1276,19 @@ int pnp_set_schedule(pnp_ctx* c, int queues, int mixed_launches, int chunk) {
 }
 
 int pnp_upload_problem(pnp_ctx* c, const float* y, const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
-    CTX(c); F32_ONLY(c); return upload_problem(c, __func__, y, mask_bank, mask_id, B, K, on_device);
+    CTX(c); F32_ONLY(c); NO_COILS(c, "pnp_upload_problem_mc"); return upload_problem(c, __func__, y, mask_bank, mask_id, B, K, on_device);
 }
 int pnp_upload_problem_f64(pnp_ctx* c, const double* y, const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
-    CTX(c); F64_ONLY(c); return upload_problem(c, __func__, y, mask_bank, mask_id, B, K, on_device);
+    CTX(c); F64_ONLY(c); NO_COILS(c, "pnp_upload_problem_mc_f64"); return upload_problem(c, __func__, y, mask_bank, mask_id, B, K, on_device);
 }
 
 int pnp_synthesize_problem(pnp_ctx* c, const float* img, const float* noise, int noise_per_slice,
                            const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
-    CTX(c); F32_ONLY(c); return synthesize_problem(c, __func__, img, noise, noise_per_slice, mask_bank, mask_id, B, K, on_device);
+    CTX(c); F32_ONLY(c); NO_COILS(c, "pnp_synthesize_problem_mc"); return synthesize_problem(c, __func__, img, noise, noise_per_slice, mask_bank, mask_id, B, K, on_device);
 }
 int pnp_synthesize_problem_f64(pnp_ctx* c, const float* img, const double* noise, int noise_per_slice,
                                const uint8_t* mask_bank, const int32_t* mask_id, int B, int K, int on_device) {
-    CTX(c); F64_ONLY(c); return synthesize_problem(c, __func__, img, noise, noise_per_slice, mask_bank, mask_id, B, K, on_device);
+    CTX(c); F64_ONLY(c); NO_COILS(c, "pnp_synthesize_problem_mc_f64"); return synthesize_problem(c, __func__, img, noise, noise_per_slice, mask_bank, mask_id, B, K, on_device);
 }
 
 int pnp_download_y(pnp_ctx* c, float* y, int on_device) { CTX(c); F32_ONLY(c); NEED_PROBLEM(c); return download_y(c, __func__, y, on_device); }
@@ -1107,6 +1379,7 @@ int pnp_dc_step(pnp_ctx* c, const float* z, const float* w, float* x, double reo
     Range r("pnp_dc_step");
     if (!z || !w || !x) return fail(PNP_E_ARG, "pnp_dc_step: null pointer");
     if (!(reo > 0.0)) return fail(PNP_E_ARG, "pnp_dc_step: reo must be > 0");
+    if (c->coils.C > 0) return coil_xstep<float>(c, z, w, x, reo);
     return dc_any<float>(c, z, w, x, dc_coeff<float>(reo));
 }
 
@@ -1182,6 +1455,13 @@ int pnp_fft2_inv(pnp_ctx* c, const float* in, float* out, int B) { CTX(c); F32_O
 int pnp_A(pnp_ctx* c, const float* x, float* k) {
     CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
     if (!x || !k) return fail(PNP_E_ARG, "pnp_A: null pointer");
+    if (c->coils.C > 0) {                              // k: [B][C][H][W]
+        CoilRowArgsT<float> ca = coil_rows<float>(c, c->B);
+        ca.rin = x; ca.work = (float2*)k;
+        HIPCHK(anysize_coil_rows_in<float>(c->coils.any, c->stream, ca));
+        HIPCHK(anysize_cols<float>(c->coils.any, c->stream, true, MID_MASK, false, coil_cols<float>(c, k, k)));
+        return PNP_OK;
+    }
     RowArgs ra{};
     ra.rin0 = x; ra.cout = (float2*)k; ra.scale = 1.0f; ra.nrows = c->B * c->H;
     HIPCHK(rows<float>(c, IN_REAL, false, EPI_COMPLEX, ra));
@@ -1194,6 +1474,7 @@ int pnp_A(pnp_ctx* c, const float* x, float* k) {
 int pnp_AH(pnp_ctx* c, const float* k, float* out) {
     CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
     if (!k || !out) return fail(PNP_E_ARG, "pnp_AH: null pointer");
+    if (c->coils.C > 0) return coil_AH<float>(c, k, out);
     ColArgs ca{};
     ca.in = (const float2*)k; ca.out = (float2*)out; ca.mask_bank = c->mask_bank; ca.mask_id = c->mask_id; ca.B = c->B;
     HIPCHK(cols<float>(c, false, MID_MASK, true, ca));
@@ -1206,6 +1487,7 @@ int pnp_AH(pnp_ctx* c, const float* k, float* out) {
 int pnp_Df(pnp_ctx* c, const float* x, float* out) {
     CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
     if (!x || !out) return fail(PNP_E_ARG, "pnp_Df: null pointer");
+    if (c->coils.C > 0) return fail(PNP_E_STATE, "pnp_Df: not available on a context with coils (pnp_set_coils); compose it from pnp_A and pnp_AH");
     RowArgs ra{};
     ra.rin0 = x; ra.cout = (float2*)out; ra.scale = 1.0f; ra.nrows = c->B * c->H;
     HIPCHK(rows<float>(c, IN_REAL, false, EPI_COMPLEX, ra));
@@ -1277,6 +1559,7 @@ int pnp_fft_plan(pnp_ctx* c, int axis, char* buf, int len) {
 
 const char* pnp_path_name(pnp_ctx* c) {
     if (!c) return "generic";
+    if (c->coils.C > 0) return "coils";
     switch (loop_path(c)) {
     case Path::generic: return "generic";
     case Path::slice:   return c->wavelet != WV_NONE ? "fused" : "slice";      // with a wavelet set the loops never run slice-resident
@@ -1318,5 +1601,66 @@ int pnp_dwt2_fwd(pnp_ctx* c, const float* in, float* out, int B) { CTX(c); F32_O
 int pnp_dwt2_inv(pnp_ctx* c, const float* in, float* out, int B) { CTX(c); F32_ONLY(c); return dwt2_any<float>(c, __func__, in, out, B, true); }
 int pnp_dwt2_fwd_f64(pnp_ctx* c, const double* in, double* out, int B) { CTX(c); F64_ONLY(c); return dwt2_any<double>(c, __func__, in, out, B, false); }
 int pnp_dwt2_inv_f64(pnp_ctx* c, const double* in, double* out, int B) { CTX(c); F64_ONLY(c); return dwt2_any<double>(c, __func__, in, out, B, true); }
+
+// ---- multi-coil (SENSE) data consistency ----
+
+int pnp_coils_check(int C, int Ks, int H, int W) {
+    switch (coil_check(C, Ks, H, W)) {
+    case COIL_OK:       return PNP_OK;
+    case COIL_BAD_C:    return fail(PNP_E_ARG, "coils: C must be 1..%d (got %d)", COIL_MAX_C, C);
+    case COIL_BAD_SETS: return fail(PNP_E_ARG, "coils: Ks must be >= 1 (got %d)", Ks);
+    default:            return fail(PNP_E_ARG, "coils: H, W must be in [128, 1024] (got %d x %d)", H, W);
+    }
+}
+
+static int set_coils_checked(pnp_ctx* c, const char* who, const void* sens, int C, int Ks, int on_device, bool f64) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", who);
+    if (C != 0) {
+        if (int rc = pnp_coils_check(C, Ks, c->H, c->W)) return rc;                  // before any device work
+        if (!sens) return fail(PNP_E_ARG, "%s: sens is null", who);
+    }
+    if (c->f64 != f64) return fail(PNP_E_STATE, f64 ? "%s: needs a context made by pnp_ctx_create_f64" : "%s: not available on an fp64 validation context", who);
+    HIPCHK(hipSetDevice(c->device));
+    return f64 ? set_coils<double>(c, who, (const double*)sens, C, Ks, on_device) : set_coils<float>(c, who, (const float*)sens, C, Ks, on_device);
+}
+int pnp_set_coils(pnp_ctx* c, const float* sens, int C, int Ks, int on_device) { return set_coils_checked(c, __func__, sens, C, Ks, on_device, false); }
+int pnp_set_coils_f64(pnp_ctx* c, const double* sens, int C, int Ks, int on_device) { return set_coils_checked(c, __func__, sens, C, Ks, on_device, true); }
+
+int pnp_set_cg(pnp_ctx* c, int iters) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
+    if (iters < 1 || iters > CG_MAX_ITERS) return fail(PNP_E_ARG, "pnp_set_cg: iters must be 1..%d (got %d)", CG_MAX_ITERS, iters);
+    c->coils.cg_iters = iters;
+    return PNP_OK;
+}
+
+int pnp_get_coils(pnp_ctx* c, int* C, int* Ks, int* cg_iters) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
+    if (C) *C = c->coils.C;
+    if (Ks) *Ks = c->coils.Ks;
+    if (cg_iters) *cg_iters = c->coils.cg_iters;
+    return PNP_OK;
+}
+
+int pnp_upload_problem_mc(pnp_ctx* c, const float* y, const uint8_t* mask_bank, const int32_t* mask_id, const int32_t* coil_id, int B, int K, int on_device) {
+    CTX(c); F32_ONLY(c); NEED_COILS(c); return upload_problem_mc<float>(c, __func__, y, mask_bank, mask_id, coil_id, B, K, on_device);
+}
+int pnp_upload_problem_mc_f64(pnp_ctx* c, const double* y, const uint8_t* mask_bank, const int32_t* mask_id, const int32_t* coil_id, int B, int K, int on_device) {
+    CTX(c); F64_ONLY(c); NEED_COILS(c); return upload_problem_mc<double>(c, __func__, y, mask_bank, mask_id, coil_id, B, K, on_device);
+}
+int pnp_synthesize_problem_mc(pnp_ctx* c, const float* img, const float* noise, int noise_mode, const uint8_t* mask_bank, const int32_t* mask_id,
+                              const int32_t* coil_id, int B, int K, int on_device) {
+    CTX(c); F32_ONLY(c); NEED_COILS(c); return synthesize_problem_mc<float>(c, __func__, img, noise, noise_mode, mask_bank, mask_id, coil_id, B, K, on_device);
+}
+int pnp_synthesize_problem_mc_f64(pnp_ctx* c, const float* img, const double* noise, int noise_mode, const uint8_t* mask_bank, const int32_t* mask_id,
+                                  const int32_t* coil_id, int B, int K, int on_device) {
+    CTX(c); F64_ONLY(c); NEED_COILS(c); return synthesize_problem_mc<double>(c, __func__, img, noise, noise_mode, mask_bank, mask_id, coil_id, B, K, on_device);
+}
+
+int pnp_cg_residual(pnp_ctx* c, double* rel) {
+    CTX(c); NEED_COILS(c); NEED_PROBLEM(c);
+    if (!rel) return fail(PNP_E_ARG, "pnp_cg_residual: rel is null");
+    if (!c->coils.have_rel) return fail(PNP_E_STATE, "pnp_cg_residual: no x-step has run on the uploaded problem");
+    return copy_out(c, rel, c->coils.rel, (size_t)c->B * sizeof(double), 0);
+}
 
 }  // extern "C"

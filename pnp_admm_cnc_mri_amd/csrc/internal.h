@@ -74,6 +74,43 @@ int        anysize_describe(const AnySize*, int axis /* 0 rows (W), 1 columns (H
 template <typename R> hipError_t anysize_rows(const AnySize*, hipStream_t s, RowIn in, bool inv, RowEpi epi, const RowArgsT<R>& a);
 template <typename R> hipError_t anysize_cols(const AnySize*, hipStream_t s, bool pre_fwd, ColMid mid, bool post_inv, const ColArgsT<R>& a);
 
+// multi-coil (SENSE) row roles of the any-size kernels (coil_plan.h): the coil-expanding forward rows and the coil-combining inverse rows
+template <typename R>
+struct CoilRowArgsT {
+    using C = typename CxOf<R>::type;
+    const C*       maps;      // [Ks][C][H][W]
+    const int32_t* coil_id;   // [B] or null (set 0)
+    int            ncoils, H;
+    C*             work;      // [B][C][H][W]: written by the expanding rows, read by the combining rows
+    const C*       cin;       // expanding rows: the image, complex [B][H][W] ...
+    const R*       rin;       // ... or real (cin null)
+    C*             cout;      // combining rows: sum_c conj(S_c) * scale * inverse rows [+ la2 * p]
+    const C*       p;         // combining rows: null (plain A^H), or the operand of G: la2 * p is added and Re<p, Gp> summed per row ...
+    double*        partial;   // ... into [B * H]
+    R              la2, scale;
+    int            nrows;     // B * H
+};
+template <typename R> hipError_t anysize_coil_rows_in(const AnySize*, hipStream_t s, const CoilRowArgsT<R>& a);
+template <typename R> hipError_t anysize_coil_rows_epi(const AnySize*, hipStream_t s, const CoilRowArgsT<R>& a);
+
+// multi-coil pointwise kernels and the batched conjugate-gradient updates (kernels_coils.hip; sums by coil_plan.h).  Complex arrays
+// [B][N] in the context's precision, partials and scalars in double; grid (cg_blocks(N), B).
+hipError_t launch_expand_ids(hipStream_t s, const int32_t* mask_id, int32_t* out, int B, int C);          // out[b * C + c] = mask_id[b]
+template <typename R> hipError_t launch_cg_begin(hipStream_t s, const R* z, const R* w, typename CxOf<R>::type* xh, int B, size_t N);
+template <typename R> hipError_t launch_cg_init(hipStream_t s, const typename CxOf<R>::type* aty, const typename CxOf<R>::type* xh,
+                                                const typename CxOf<R>::type* gp, typename CxOf<R>::type* r, typename CxOf<R>::type* p,
+                                                R la2, double* part_rr, double* part_bb, int B, size_t N);
+// alpha = <r,r> / Re<p,Gp> from the partials; x^ += alpha p, r -= alpha Gp, partials of the new <r,r>; x_out (last iteration): |Re x^|
+template <typename R> hipError_t launch_cg_xr(hipStream_t s, typename CxOf<R>::type* xh, typename CxOf<R>::type* r,
+                                              const typename CxOf<R>::type* p, const typename CxOf<R>::type* gp, const double* part_rr,
+                                              const double* part_pgp, double* part_rr_next, double* scal /*[B][4]: alpha, beta, rr, -*/,
+                                              R* x_out, int B, size_t N, int H);
+template <typename R> hipError_t launch_cg_p(hipStream_t s, const typename CxOf<R>::type* r, typename CxOf<R>::type* p, const double* part_rr,
+                                             const double* part_rr_next, double* scal, int B, size_t N);
+hipError_t launch_cg_residual(hipStream_t s, const double* part_rr, const double* part_bb, double* rel /*[B]*/, int B, size_t N);
+template <typename R> hipError_t launch_cabs(hipStream_t s, const typename CxOf<R>::type* in, R* out, size_t n);
+hipError_t launch_prox_f64(hipStream_t s, bool cnc, const double* x, double* z, double* w, ProxParamsT<double> p, size_t n);
+
 // pointwise
 hipError_t launch_prox(hipStream_t s, bool cnc, const float* x, float* z, float* w, ProxParams p, size_t n);
 hipError_t launch_combine(hipStream_t s, const float* z, const float* x, const float* w, const float* sden,

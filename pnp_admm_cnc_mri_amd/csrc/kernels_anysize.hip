@@ -15,6 +15,7 @@
 // Not a fast path: the iteration runs the three launches of the generic loop (rows, columns, rows) at any size.
 #include "internal.h"
 #include "anysize_plan.h"
+#include "coil_plan.h"
 #include "prox_ops.h"
 #include <string.h>
 #include <atomic>
@@ -173,6 +174,154 @@ static hipError_t any_rows_t(hipStream_t s, const AxisT<R>& t, const RowArgsT<R>
     hipLaunchKernelGGL((k_any_rows<IN, INV, EPI, R>), dim3(grid), dim3(ANY_THREADS), any_lds(t), s, a, t);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------
+// rows with coils (coil_plan.h): the two row roles of the multi-coil data consistency.  A workgroup owns G rows as k_any_rows does and
+// walks the C coils of each; beside the two ping-pong buffers it holds G * n values: the image rows (expanding) resp. the sums over
+// the coils (combining).  Every thread touches the same (line, k) elements in every pass, so that third array needs no barrier.
+// ------------------------------------------------------------------------------------------
+template <typename R> static size_t coil_lds(const AxisT<R>& t) { return any_lds(t) + sizeof(typename CxOf<R>::type) * (size_t)t.lines * t.plan.n; }
+// lines per workgroup of the coil rows: the third array counts against the same ANY_LDS_TARGET, so that as many workgroups share a compute
+// unit as with the plain rows (at n = 256 in float: 6 lines of 6160 B instead of 9 of 4112 B + 2048 B)
+template <typename R> static AxisT<R> coil_axis(AxisT<R> t) {
+    using C = typename CxOf<R>::type;
+    const size_t per_line = sizeof(C) * (2 * (size_t)t.pitch + (size_t)t.plan.n);
+    int g = (int)(ANY_LDS_TARGET / per_line);
+    if (g > t.lines) g = t.lines;
+    t.lines = g < 1 ? 1 : g;
+    return t;
+}
+
+// expanding rows, forward: work[b][c][h][:] = F_W(S_c[h][:] * image[b][h][:]), c = 0 .. C - 1 -- the image row is read once
+template <bool REAL, typename R>
+__global__ __launch_bounds__(ANY_THREADS) void k_any_rows_coil_in(CoilRowArgsT<R> p, AxisT<R> t) {
+    using C = typename CxOf<R>::type;
+    using anysize::mkc;
+    extern __shared__ __attribute__((aligned(16))) unsigned char any_smem[];
+    C* sA = reinterpret_cast<C*>(any_smem);
+    C* sB = sA + t.lines * t.pitch;
+    C* sP = sB + t.lines * t.pitch;
+    const int G = t.lines, n = t.plan.n, pitch = t.pitch, H = p.H;
+    const int row0 = blockIdx.x * G;
+    for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) {
+        const int g = i / n, row = row0 + g;
+        C v = mkc<C>(R(0), R(0));
+        if (row < p.nrows) {
+            const size_t e = (size_t)row * n + (i - g * n);
+            if (REAL) v = mkc<C>(p.rin[e], R(0)); else v = p.cin[e];
+        }
+        sP[i] = v;
+    }
+    for (int c = 0; c < p.ncoils; ++c) {
+        for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) {
+            const int g = i / n, k = i - g * n, row = row0 + g;
+            C v = mkc<C>(R(0), R(0));
+            if (row < p.nrows) {
+                const int b = coil_row_slice(row, H), h = coil_row_line(row, H);
+                v = anysize::cmul(sP[i], p.maps[coil_map_index(coil_set_of(p.coil_id, b), c, p.ncoils, h, k, H, n)]);
+            }
+            sA[g * pitch + k] = v;
+        }
+        __syncthreads();
+        const C* r = line_fft<false, R>(sA, sB, t);
+        for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) {
+            const int g = i / n, k = i - g * n, row = row0 + g;
+            if (row >= p.nrows) continue;
+            p.work[coil_work_index(coil_row_slice(row, H), c, p.ncoils, coil_row_line(row, H), k, H, n)] = r[g * pitch + k];
+        }
+        __syncthreads();
+    }
+}
+
+// combining rows, inverse: out[b][h][:] = sum_c conj(S_c[h][:]) * scale * F_W^-1(work[b][c][h][:]) [+ la2 * p[b][h][:]], coils in order;
+// with p the row's Re<p, out> goes to partial[row], summed in double by one wave (coil_plan.h, cg_wave_sum)
+template <typename R>
+__global__ __launch_bounds__(ANY_THREADS) void k_any_rows_coil_epi(CoilRowArgsT<R> p, AxisT<R> t) {
+    using C = typename CxOf<R>::type;
+    using anysize::mkc;
+    extern __shared__ __attribute__((aligned(16))) unsigned char any_smem[];
+    C* sA = reinterpret_cast<C*>(any_smem);
+    C* sB = sA + t.lines * t.pitch;
+    C* sAcc = sB + t.lines * t.pitch;
+    const int G = t.lines, n = t.plan.n, pitch = t.pitch, H = p.H;
+    const int row0 = blockIdx.x * G;
+    for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) sAcc[i] = mkc<C>(R(0), R(0));
+    for (int c = 0; c < p.ncoils; ++c) {
+        for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) {
+            const int g = i / n, k = i - g * n, row = row0 + g;
+            C v = mkc<C>(R(0), R(0));
+            if (row < p.nrows) v = p.work[coil_work_index(coil_row_slice(row, H), c, p.ncoils, coil_row_line(row, H), k, H, n)];
+            sA[g * pitch + k] = v;
+        }
+        __syncthreads();
+        const C* r = line_fft<true, R>(sA, sB, t);
+        for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) {
+            const int g = i / n, k = i - g * n, row = row0 + g;
+            if (row >= p.nrows) continue;
+            const int b = coil_row_slice(row, H), h = coil_row_line(row, H);
+            const C v = r[g * pitch + k];
+            const C sv = mkc<C>(v.x * p.scale, v.y * p.scale);
+            sAcc[i] = anysize::cadd(sAcc[i], anysize::cmulc(sv, p.maps[coil_map_index(coil_set_of(p.coil_id, b), c, p.ncoils, h, k, H, n)]));
+        }
+        __syncthreads();
+    }
+    double* prod = reinterpret_cast<double*>(any_smem);          // [G][n] doubles over sA (G * pitch complex: room enough); sA is idle now
+    for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) {
+        const int g = i / n, row = row0 + g;
+        double d = 0.0;
+        if (row < p.nrows) {
+            const size_t e = (size_t)row * n + (i - g * n);
+            C o = sAcc[i];
+            if (p.p) {
+                const C pv = p.p[e];
+                o = mkc<C>(fma_r(p.la2, pv.x, o.x), fma_r(p.la2, pv.y, o.y));
+                d = (double)pv.x * (double)o.x + (double)pv.y * (double)o.y;
+            }
+            p.cout[e] = o;
+        }
+        prod[i] = d;
+    }
+    if (!p.p) return;
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int g = wave; g < G; g += ANY_THREADS / 64) {
+        const int row = row0 + g;
+        double s = 0.0;
+        for (int k = lane; k < n; k += 64) s += prod[g * n + k];
+        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+        if (lane == 0 && row < p.nrows) p.partial[row] = s;
+    }
+}
+
+template <typename R> static AxisT<R> axis(const AnySize* A, int i);          // below, with the host side
+
+template <typename R>
+hipError_t anysize_coil_rows_in(const AnySize* A, hipStream_t s, const CoilRowArgsT<R>& a) {
+    if (!A || A->f64 != std::is_same<R, double>::value || a.ncoils < 1 || a.ncoils > COIL_MAX_C || a.H != A->plan[1].n) return hipErrorInvalidValue;
+    const AxisT<R> t = coil_axis(axis<R>(A, 0));
+    static std::atomic<bool> done[2][64] = {};
+    const void* fn = a.cin ? (const void*)k_any_rows_coil_in<false, R> : (const void*)k_any_rows_coil_in<true, R>;
+    if (hipError_t e = lds_opt_in(fn, done[a.cin ? 0 : 1], coil_lds(t))) return e;
+    const unsigned grid = (unsigned)((a.nrows + t.lines - 1) / t.lines);
+    if (a.cin) hipLaunchKernelGGL((k_any_rows_coil_in<false, R>), dim3(grid), dim3(ANY_THREADS), coil_lds(t), s, a, t);
+    else       hipLaunchKernelGGL((k_any_rows_coil_in<true, R>), dim3(grid), dim3(ANY_THREADS), coil_lds(t), s, a, t);
+    return hipGetLastError();
+}
+template hipError_t anysize_coil_rows_in<float>(const AnySize*, hipStream_t, const CoilRowArgsT<float>&);
+template hipError_t anysize_coil_rows_in<double>(const AnySize*, hipStream_t, const CoilRowArgsT<double>&);
+
+template <typename R>
+hipError_t anysize_coil_rows_epi(const AnySize* A, hipStream_t s, const CoilRowArgsT<R>& a) {
+    if (!A || A->f64 != std::is_same<R, double>::value || a.ncoils < 1 || a.ncoils > COIL_MAX_C || a.H != A->plan[1].n) return hipErrorInvalidValue;
+    const AxisT<R> t = coil_axis(axis<R>(A, 0));
+    static std::atomic<bool> done[64] = {};
+    if (hipError_t e = lds_opt_in((const void*)k_any_rows_coil_epi<R>, done, coil_lds(t))) return e;
+    const unsigned grid = (unsigned)((a.nrows + t.lines - 1) / t.lines);
+    hipLaunchKernelGGL((k_any_rows_coil_epi<R>), dim3(grid), dim3(ANY_THREADS), coil_lds(t), s, a, t);
+    return hipGetLastError();
+}
+template hipError_t anysize_coil_rows_epi<float>(const AnySize*, hipStream_t, const CoilRowArgsT<float>&);
+template hipError_t anysize_coil_rows_epi<double>(const AnySize*, hipStream_t, const CoilRowArgsT<double>&);
 
 // ------------------------------------------------------------------------------------------
 // columns: [optional forward] -> pointwise k-space op -> [optional inverse], the pointwise pass of k_cols
@@ -353,6 +502,7 @@ hipError_t anysize_cols(const AnySize* A, hipStream_t s, bool pre, ColMid mid, b
     if (!pre && post && mid == MID_NONE)      return any_cols_t<false, MID_NONE, true>(s, t, W, a);
     if (pre && post && mid == MID_BLEND)      return any_cols_t<true, MID_BLEND, true>(s, t, W, a);
     if (pre && !post && mid == MID_MASK)      return any_cols_t<true, MID_MASK, false>(s, t, W, a);
+    if (pre && post && mid == MID_MASK)       return any_cols_t<true, MID_MASK, true>(s, t, W, a);      // the coil columns of G
     if (!pre && post && mid == MID_MASK)      return any_cols_t<false, MID_MASK, true>(s, t, W, a);
     if (pre && post && mid == MID_RESID)      return any_cols_t<true, MID_RESID, true>(s, t, W, a);
     if (pre && !post && mid == MID_MASK_ADD)  return any_cols_t<true, MID_MASK_ADD, false>(s, t, W, a);

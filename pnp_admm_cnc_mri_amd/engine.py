@@ -44,6 +44,21 @@ def check_sparsity(wavelet, levels, H, W):
     return WAVELETS[wavelet]
 
 
+def check_coils(sens, H, W, cg_iters=3):
+    """ValueError unless `sens` is a valid set ([C,H,W]) or bank ([Ks,C,H,W]) of coil maps for H x W slices and cg_iters is 1..64
+    (pnp_coils_check: the library's own rule, no context and no device needed).  -> (C, Ks)."""
+    shape = np.shape(sens)
+    if len(shape) not in (3, 4) or tuple(shape[-2:]) != (int(H), int(W)):
+        raise ValueError('coils must be [C,H,W] or [Ks,C,H,W] with H x W = %d x %d (got shape %s)' % (H, W, tuple(shape)))
+    Cn, Ks = int(shape[-3]), (int(shape[0]) if len(shape) == 4 else 1)
+    L = _lib.lib()
+    if L.pnp_coils_check(Cn, Ks, int(H), int(W)) != 0:
+        raise ValueError(L.pnp_last_error().decode('utf-8', 'replace'))
+    if int(cg_iters) != cg_iters or not 1 <= int(cg_iters) <= 64:
+        raise ValueError('cg_iters must be an integer in 1..64 (got %r)' % (cg_iters,))
+    return Cn, Ks
+
+
 TRACE_FIELDS = ('r_pri', 'r_dual', 'x_norm', 'z_norm', 'w_norm', 'psnr', 're')      # PNP_TRACE_* of include/pnp_mri.h, in order
 
 
@@ -83,6 +98,7 @@ class Engine:
         self.B = 0
         self._real = np.float64 if self.f64 else np.float32
         self._cplx = np.complex128 if self.f64 else np.complex64
+        self.C = 0                                        # coils (set_coils); 0: none
 
     # -- lifetime -------------------------------------------------------------------------
     def close(self):
@@ -135,6 +151,48 @@ class Engine:
         _lib.check(self._L.pnp_get_sparsity(self._ctx, C.byref(wv), C.byref(lv)))
         return {v: k for k, v in WAVELETS.items()}[wv.value], lv.value
 
+    def set_coils(self, sens, cg_iters=3):
+        """Multi-coil (SENSE) data consistency (pnp_set_coils): sens [C,H,W] or a bank [Ks,C,H,W] of complex sensitivity maps (host array
+        or device tensor of the engine's complex type); None clears.  From then on y is [B,C,H,W], upload / synthesize take coil_id=,
+        and init_state, admm_l1, admm_cnc, dc_step, A, AH follow y_c = mask . fft2(S_c . x): the x-step is `cg_iters` iterations of
+        conjugate gradients (default 3: enough for maps normalised to sum_c |S_c|^2 = 1 at the presets' reo; UNNORMALISED MAPS OR A
+        LARGE reo -- the in-function default 2.75 -- NEED MORE, see cg_residual).  Drops the uploaded problem."""
+        if sens is None:
+            _lib.check(self._L.pnp_set_coils_f64(self._ctx, None, 0, 0, 0) if self.f64 else self._L.pnp_set_coils(self._ctx, None, 0, 0, 0))
+            self.C, self.B = 0, 0
+            return
+        Cn, Ks = check_coils(sens, self.H, self.W, cg_iters)
+        dev = _is_dev(sens)
+        if not dev:
+            sens = _host(sens, self._cplx)
+        _lib.check(self._L.pnp_set_cg(self._ctx, int(cg_iters)))
+        fn = self._L.pnp_set_coils_f64 if self.f64 else self._L.pnp_set_coils
+        _lib.check(fn(self._ctx, _ptr(sens), Cn, Ks, 1 if dev else 0))
+        self.C, self.Ks, self.B = Cn, Ks, 0
+
+    @property
+    def coils(self):
+        """{'C', 'Ks', 'cg_iters'} (pnp_get_coils); C = 0 without coils."""
+        c, k, it = C.c_int(0), C.c_int(0), C.c_int(0)
+        _lib.check(self._L.pnp_get_coils(self._ctx, C.byref(c), C.byref(k), C.byref(it)))
+        return {'C': c.value, 'Ks': k.value, 'cg_iters': it.value}
+
+    def cg_residual(self):
+        """||r|| / ||A^H y + La2 (z - w)|| of the most recent x-step, per slice [B] (pnp_cg_residual; synchronises)."""
+        rel = np.empty(self.B, np.float64)
+        _lib.check(self._L.pnp_cg_residual(self._ctx, rel.ctypes.data_as(_lib.c_double_p)))
+        return rel
+
+    def _coil_id(self, coil_id, B):
+        if not self.C:
+            if coil_id is not None:
+                raise ValueError('coil_id needs coils (set_coils)')
+            return None
+        cid = None if coil_id is None else _host(coil_id, np.int32)
+        if cid is not None and cid.shape != (B,):
+            raise ValueError('coil_id must have shape (B,)')
+        return cid
+
     @property
     def plan(self):
         """What the next loop call does for the uploaded batch: {'queues', 'chunk', 'launches_per_iteration'} (pnp_get_plan)."""
@@ -182,29 +240,49 @@ class Engine:
             raise ValueError('mask_id must have shape (B,)')
         return bank, mid
 
-    def upload(self, y, masks, mask_id=None):
-        """y: [B,H,W] complex (host; cast to complex64) -- S4:102's `y`; masks [K,H,W] or [H,W]."""
+    def upload(self, y, masks, mask_id=None, coil_id=None):
+        """y: [B,H,W] complex (host; cast to complex64) -- S4:102's `y`; masks [K,H,W] or [H,W].  With coils: y [B,C,H,W] (or [C,H,W]),
+        coil_id [B] into the bank of maps."""
         y = np.asarray(y)
-        if y.ndim == 2:
+        if y.ndim == (3 if self.C else 2):
             y = y[None]
         y = _host(y, self._cplx)
         B = y.shape[0]
-        if y.shape[1:] != (self.H, self.W):
-            raise ValueError('y shape %s does not match engine %dx%d' % (y.shape[1:], self.H, self.W))
+        want = (self.C, self.H, self.W) if self.C else (self.H, self.W)
+        if y.shape[1:] != want:
+            raise ValueError('y shape %s does not match engine %s' % (y.shape[1:], 'x'.join(map(str, want))))
         bank, mid = self._masks(masks, mask_id, B)
+        cid = self._coil_id(coil_id, B)
+        if self.C:
+            up = self._L.pnp_upload_problem_mc_f64 if self.f64 else self._L.pnp_upload_problem_mc
+            _lib.check(up(self._ctx, _ptr(y), _ptr(bank), _ptr(mid), _ptr(cid), B, bank.shape[0], 0))
+            self.B = B
+            return
         up = self._L.pnp_upload_problem_f64 if self.f64 else self._L.pnp_upload_problem
         _lib.check(up(self._ctx, _ptr(y), _ptr(bank), _ptr(mid), B, bank.shape[0], 0))
         self.B = B
 
-    def synthesize(self, img, noise, masks, mask_id=None):
+    def synthesize(self, img, noise, masks, mask_id=None, coil_id=None):
         """y = fft2(img)*mask + noise on the device (S4:102).  img [B,H,W] float; noise [H,W]
-        (shared, the reference's noises.mat) or [B,H,W] complex."""
+        (shared, the reference's noises.mat) or [B,H,W] complex.  With coils: y_c = fft2(S_c img)*mask + noise, noise [H,W],
+        [C,H,W] (shared by the slices) or [B,C,H,W]; coil_id [B] into the bank of maps."""
         img = np.asarray(img)
         if img.ndim == 2:
             img = img[None]
         img = _host(img, np.float32)                      # the reference's img_L is float32 in either precision
         B = img.shape[0]
         noise = _host(noise, self._cplx)
+        cid = self._coil_id(coil_id, B)
+        if self.C:
+            mode = {2: 0, 3: 1, 4: 2}.get(noise.ndim)
+            ok = {0: (self.H, self.W), 1: (self.C, self.H, self.W), 2: (B, self.C, self.H, self.W)}
+            if mode is None or noise.shape != ok[mode]:
+                raise ValueError('noise shape %s is none of [H,W], [C,H,W], [B,C,H,W] of this engine' % (noise.shape,))
+            bank, mid = self._masks(masks, mask_id, B)
+            fn = self._L.pnp_synthesize_problem_mc_f64 if self.f64 else self._L.pnp_synthesize_problem_mc
+            _lib.check(fn(self._ctx, _ptr(img), _ptr(noise), mode, _ptr(bank), _ptr(mid), _ptr(cid), B, bank.shape[0], 0))
+            self.B = B
+            return
         per = 1 if noise.ndim == 3 else 0
         if per and noise.shape[0] != B:
             raise ValueError('noise batch does not match images')
@@ -216,7 +294,7 @@ class Engine:
         self.B = B
 
     def download_y(self):
-        y = np.empty((self.B, self.H, self.W), self._cplx)
+        y = np.empty((self.B, self.C, self.H, self.W) if self.C else (self.B, self.H, self.W), self._cplx)
         fn = self._L.pnp_download_y_f64 if self.f64 else self._L.pnp_download_y
         _lib.check(fn(self._ctx, _ptr(y), 0))
         return y

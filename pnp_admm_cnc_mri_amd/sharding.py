@@ -71,14 +71,16 @@ def run_sharded(solve_shard, B_total, group=None, dst=0):
     return gather_slices(solve_shard(lo, hi), B_total, dst=dst, group=group)
 
 
-def solve_sharded(solver, mask, noises, images=None, y=None, mask_id=None, dst=0, group=None, gather_device=None,
+def solve_sharded(solver, mask, noises, images=None, y=None, mask_id=None, dst=0, group=None, gather_device=None, coil_id=None,
                   **solver_kwargs):
     """Run one of the entry points (ADMM_L1, ADMM_CNC, PNP_ADMM_*_D: anything with the
     `(…, mask, noises, images=, y=, mask_id=, **opts) -> out | (out, …)` shape, pre-bound with
     `functools.partial` when it takes leading model names) on this rank's contiguous block of slices
     and gather the reconstructions on `dst`.
 
-    Every rank passes the SAME full `images` / `y` / `mask_id`; returns an array [B_total, H, W] on `dst`
+    coil_id [B] (with coils= among the solver's keywords: a bank of coil maps, which every rank gets whole) is sliced with the shard as
+    mask_id is, and so is per-slice noise -- [B,H,W] without coils, [B,C,H,W] with them ([C,H,W] is shared by the slices).
+    Every rank passes the SAME full `images` / `y` / `mask_id` / `coil_id`; returns an array [B_total, H, W] on `dst`
     (float32; float64 when the solver is run with precision='f64'), None elsewhere.  With no process
     group it is a plain call.
     gather_device: torch device for the collective (default under nccl: the device the solver's result lies on -- see
@@ -104,7 +106,10 @@ def solve_sharded(solver, mask, noises, images=None, y=None, mask_id=None, dst=0
         kw['y'] = np.asarray(y)[lo:hi]
     if mask_id is not None:
         kw['mask_id'] = np.asarray(mask_id)[lo:hi]
-    if noises is not None and np.ndim(noises) == 3:       # per-slice k-space noise [B,H,W]: shard it with the slices
+    if coil_id is not None:
+        kw['coil_id'] = np.asarray(coil_id)[lo:hi]
+    per_slice_ndim = 3 if kw.get('coils') is None else 4
+    if noises is not None and np.ndim(noises) == per_slice_ndim:       # per-slice k-space noise [B,H,W] ([B,C,H,W] with coils): shard it with the slices
         noises = np.asarray(noises)[lo:hi]
     # The reconstructions stay on the device between the solver and the collective: `return_device=True` makes the entry point
     # hand back ONE [b,H,W] device tensor (no 22-slot list of host arrays), RCCL gathers it as it is, and the only device-to-host

@@ -33,6 +33,15 @@ bypass the file system through the extra keyword arguments
               thresholded (include/pnp_mri.h, "wavelet-domain sparsity").  NOT in the reference scripts, whose prox acts on the pixels;
               None (the default) is bit for bit what it was.  One extra log line names the transform
 
+    coils=None, coil_id=None, cg_iters=3   (all five solvers) multi-coil (SENSE) data consistency: coils [C,H,W] complex sensitivity maps,
+              or a bank [Ks,C,H,W] with coil_id [B] picking each slice's set.  The forward model becomes y_c = mask . fft2(S_c . x):
+              y= is [B,C,H,W], or images= are synthesised through the maps (noises [H,W], [C,H,W] or [B,C,H,W]); the x-update is
+              `cg_iters` iterations of conjugate gradients warm-started at z - w, the initial state |A^H y|; the z- and w-steps are
+              untouched.  3 iterations are enough for maps normalised to sum_c |S_c|^2 = 1 at the presets' reo (1e-7 from the converged
+              solve); UNNORMALISED MAPS OR A LARGE reo (the in-function default of ADMM_CNC, 2.75: condition number about 6.5) NEED
+              MORE -- info['cg_residual'] has ||r|| / ||rhs|| of the last x-step per slice.  NOT in the reference scripts; None (the
+              default) is bit for bit what it was.  One extra log line names C and cg_iters
+
 The PnP entry points (PNP_ADMM_L1_D, PNP_ADMM_CNC_D, PNP_ADMM_CNC_DnCNN) live in solvers_pnp.py.
 """
 import logging
@@ -42,7 +51,8 @@ from collections import OrderedDict
 import numpy as np
 
 from . import imageio
-from .engine import Engine, check_sparsity
+from ._lib import PnpError
+from .engine import Engine, check_coils, check_sparsity
 
 # CLI presets of the reference scripts (positional order differs per script!)
 PRESETS = {
@@ -99,7 +109,7 @@ class _Job:
 
     def __init__(self, mask, noises, tag, suffix, images=None, y=None, mask_id=None, testsets='testsets',
                  testset_name='Set1', results='results', save_E=None, device=None, log=None, ssim=None,
-                 psnr_fmt='{:.4f}', precision='f32'):
+                 psnr_fmt='{:.4f}', precision='f32', coils=None, coil_id=None, cg_iters=3):
         # psnr_fmt: S1:150 and S3:320 print the per-image PSNR with two decimals, S4:155 / S6:332 / S6:548 with four
         self.tag, self.suffix, self.psnr_fmt = tag, suffix, psnr_fmt
         if precision not in ('f32', 'f64'):
@@ -109,6 +119,12 @@ class _Job:
         self.mask_bank = mask[None] if mask.ndim == 2 else mask
         self.H, self.W = self.mask_bank.shape[1:]
         self.mask_id = None if mask_id is None else np.asarray(mask_id, np.int32)
+        self.coils, self.cg_iters = coils, cg_iters
+        self.coil_id = None if coil_id is None else np.asarray(coil_id, np.int32)
+        if coils is not None:
+            check_coils(coils, self.H, self.W, cg_iters)                         # before an engine is opened
+        elif coil_id is not None:
+            raise ValueError('coil_id= needs coils=')
         self.names = None
         self.from_files = images is None and y is None
         if self.from_files:
@@ -137,7 +153,7 @@ class _Job:
             self.gt_u8 = np.ascontiguousarray(images)
             self.img_L = imageio.requantise(self.gt_u8)                          # S4:91-94
         self.y = None if y is None else np.asarray(y)
-        if self.y is not None and self.y.ndim == 2:
+        if self.y is not None and self.y.ndim == (2 if coils is None else 3):
             self.y = self.y[None]
         self.B = len(self.gt_u8) if self.gt_u8 is not None else len(self.y)
         self.noises = None if noises is None else np.asarray(noises)
@@ -163,10 +179,16 @@ class _Job:
                     transform, int(levels)))
         if stream is not None:
             eng.set_stream(stream)
+        if self.coils is not None:
+            eng.set_coils(self.coils, self.cg_iters)
+            if self.log is not None:
+                self.log.info('multi-coil data consistency: {:d} coils, {:d} CG iterations per x-step (not in the reference scripts)'.format(
+                    eng.C, int(self.cg_iters)))
+        coil = {} if self.coils is None else {'coil_id': self.coil_id}
         if self.y is not None:
-            eng.upload(self.y, self.mask_bank, self.mask_id)
+            eng.upload(self.y, self.mask_bank, self.mask_id, **coil)
         else:
-            eng.synthesize(self.img_L, self.noises, self.mask_bank, self.mask_id)        # S4:102
+            eng.synthesize(self.img_L, self.noises, self.mask_bank, self.mask_id, **coil)        # S4:102
         eng.init_state()                                                                  # S4:103-109
         return eng
 
@@ -184,6 +206,13 @@ class _Job:
             if self.save_E:
                 x = x.reshape(self.B, self.H, self.W).cpu().numpy()
         info = OrderedDict(psnr=[], ssim=[], re=[])
+        if self.coils is not None:
+            try:
+                info['cg_residual'] = list(map(float, eng.cg_residual()))
+            except PnpError as e:                                                # iter_num = 0: no x-step has run
+                if e.code != -3:
+                    raise
+                info['cg_residual'] = []
         if self.gt_u8 is not None:
             psnr, re = eng.metrics(x_dev, self.gt_u8)                                     # device reductions
             info['psnr'], info['re'] = list(map(float, psnr)), list(map(float, re))
@@ -238,7 +267,7 @@ def _device_x(eng, job):
 
 def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
             results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
-            transform=None, levels=3, **ADMM_L1_opts):
+            transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, **ADMM_L1_opts):
     """ADMM with L1 prox on the MI355X engine.  Reference: "【1】ADMM_L1.py":29-169."""
     iter_num = ADMM_L1_opts.get('iter_num', 20)          # S1:35
     lambda1 = ADMM_L1_opts.get('lambda1', 0.04)          # S1:36
@@ -246,7 +275,7 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
     traced = trace_request(trace_every, tol, return_info)
     check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
     job = _Job(mask, noises, 'ADMM_L1', '_PDG L1', images, y, mask_id, testsets, testset_name, results, save_E, device,
-               psnr_fmt='{:.2f}', precision=precision)   # S1:150
+               psnr_fmt='{:.2f}', precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters)   # S1:150
     with job.open_engine(transform=transform, levels=levels) as eng:
         # S1:111-126, all slices, on device
         trace = eng.admm_l1(iter_num, lambda1, reo, trace_every, tol, job.gt_u8) if traced else eng.admm_l1(iter_num, lambda1, reo)
@@ -260,7 +289,7 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
 
 def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
              results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
-             transform=None, levels=3, **ADMM_CNC_opts):
+             transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, **ADMM_CNC_opts):
     """ADMM with the convex-non-convex z-step.  Reference: "【4】ADMM_CNC .py":31-174."""
     iter_num = ADMM_CNC_opts.get('iter_num', 4)          # S4:37
     alpha = ADMM_CNC_opts.get('alpha', 0.4)              # S4:38
@@ -270,7 +299,7 @@ def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets
     traced = trace_request(trace_every, tol, return_info)
     check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
     job = _Job(mask, noises, 'ADMM_CNC', '_ADMM CNC', images, y, mask_id, testsets, testset_name, results, save_E, device,
-               precision=precision)
+               precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters)
     with job.open_engine(transform=transform, levels=levels) as eng:
         # S4:115-132
         trace = (eng.admm_cnc(iter_num, alpha, lambda1, reo, b, trace_every, tol, job.gt_u8) if traced

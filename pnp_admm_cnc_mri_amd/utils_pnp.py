@@ -78,20 +78,34 @@ def idwt2(eng, c):
     return out
 
 
-def A(eng, x):
-    """A x = fft2(x) * mask for real x [B,H,W] with the engine's uploaded masks (S4:102)."""
+def _coils_of(eng, coils):
+    """coils=None: whatever the engine has; True / False: the caller's expectation, checked (an engine with coils returns and takes
+    [B,C,H,W] k-space: a silent mismatch would only show as a shape error far away).  -> the engine's coil count, 0 without"""
+    n = int(getattr(eng, 'C', 0))
+    if coils is not None and bool(coils) != (n > 0):
+        raise ValueError('coils=%r but the engine has %s' % (coils, '%d coils' % n if n else 'no coils (Engine.set_coils)'))
+    return n
+
+
+def A(eng, x, coils=None):
+    """A x = fft2(x) * mask for real x [B,H,W] with the engine's uploaded masks (S4:102).  On an engine with coils (Engine.set_coils;
+    coils=True insists on it): (A x)_c = fft2(S_c x) * mask, [B,C,H,W]."""
     torch = _torch()
     x = _prep(eng, x.float())
-    k = torch.empty(x.shape, dtype=torch.complex64, device=x.device)
+    n = _coils_of(eng, coils)
+    k = torch.empty((x.shape[0], n) + tuple(x.shape[1:]) if n else x.shape, dtype=torch.complex64, device=x.device)
     eng.A(x, torch.view_as_real(k))
     return k
 
 
-def AH(eng, k):
-    """A^H k = ifft2(k * mask) (utils/utils.py:54)."""
+def AH(eng, k, coils=None):
+    """A^H k = ifft2(k * mask) (utils/utils.py:54).  On an engine with coils: k [B,C,H,W] -> sum_c conj(S_c) ifft2(k_c * mask), [B,H,W]."""
     torch = _torch()
     k = _prep(eng, k.to(torch.complex64))
-    out = torch.empty_like(k)
+    n = _coils_of(eng, coils)
+    if n and (k.dim() != 4 or k.shape[1] != n):
+        raise ValueError('k must be [B,%d,H,W] on this engine (got %s)' % (n, tuple(k.shape)))
+    out = torch.empty((k.shape[0],) + tuple(k.shape[2:]), dtype=k.dtype, device=k.device) if n else torch.empty_like(k)
     eng.AH(torch.view_as_real(k), torch.view_as_real(out))
     return out
 

@@ -1,0 +1,235 @@
+"""CPU tests of the multi-coil (SENSE) data consistency (pnp_set_coils): the NumPy oracle itself (tests/multicoil_oracle.py) against the
+committed single-coil oracle, its operator identities and CG convergence; the binding and the argument checks through the real library;
+the index maps and summation orders of csrc/coil_plan.h through g++ (tests/host/coil_emulation.cpp, sanitizer flags of
+test_host_cores.py); and the sharding of coil_id over gloo."""
+import inspect
+import os
+import re
+import socket
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, rel_l2
+import multicoil_oracle as M
+from oracle import admm_oracle as O
+
+SRC = os.path.join(ROOT, 'tests', 'host', 'coil_emulation.cpp')
+SAN = ['-O1', '-g', '-std=c++17', '-fsanitize=address,undefined', '-fno-sanitize-recover=all']
+ENV = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
+SHAPES = [(128, 128), (140, 160), (131, 128), (256, 256)]
+
+
+# ---- the oracle against the committed oracle, and against itself -------------------------------------------------------------------
+
+@pytest.mark.parametrize('kind', ['l1', 'cnc'])
+def test_one_uniform_coil_is_the_committed_oracle(kind):
+    """C = 1, S = 1: ten iterations of the multi-coil oracle's loops equal oracle/admm_oracle.py's (pinned by the goldens) to 1e-12."""
+    H = W = 128
+    m = M.mask(1, H, W)
+    y = (np.fft.fft2(M.phantom(1, H, W)) + M.noise(1, 1, m, 4.0)[0]) * m
+    S = np.ones((1, H, W), np.complex128)
+    ref = O.admm_l1(y, m, 10) if kind == 'l1' else O.admm_cnc(y, m, 10)
+    assert rel_l2(M.admm(y[None], S, m, 10, kind), ref) <= 1e-12
+    # one CG iteration is already the closed form; the second divides 0 by 0 and must change nothing
+    aty, z, w = M.init_state(y[None], S, m)
+    x1, x2 = (M.x_step(z, w, aty, S, m, 0.05, k) for k in (1, 2))
+    assert rel_l2(x1, O.dc_step(z, w, y, m, 0.05)) <= 1e-12 and np.isfinite(x2).all() and rel_l2(x2, x1) <= 1e-12
+
+
+@pytest.mark.parametrize('H,W', SHAPES)
+def test_oracle_operator_identities(H, W):
+    """<A x, k> = N <x, A^H k> and the normal equations of the 30-iteration CG solution, to 1e-12."""
+    C = {128: 2, 140: 3, 131: 5, 256: 8}[H]
+    img, S, m, nz, y = M.problem(H + C, C, H, W)
+    assert np.abs((np.abs(S) ** 2).sum(0) - 1).max() <= 1e-12
+    rng = np.random.default_rng(H)
+    x = rng.standard_normal((H, W))
+    k = rng.standard_normal((C, H, W)) + 1j * rng.standard_normal((C, H, W))
+    lhs, rhs = np.vdot(M.A(x, S, m), k), H * W * np.vdot(x.astype(np.complex128), M.AH(k, S, m))
+    assert abs(lhs - rhs) <= 1e-12 * abs(lhs)
+    aty, z, w = M.init_state(y, S, m)
+    for reo in (0.05, 0.015):
+        xh, rel = M.cg_solve(aty, z - w, S, m, reo, 30)
+        assert rel_l2(M.G(xh, S, m, reo), aty + (z - w) / (2 * reo)) <= 1e-12 and rel <= 1e-12
+
+
+# relative distance from the converged solve after 1, 2, ... CG iterations (include/pnp_mri.h)
+TABLE = {0.05: (1.1e-4, 2.8e-6, 4.9e-8, 1.3e-9), 0.015: (1.1e-5, 8.6e-8, 4.7e-10)}
+
+
+@pytest.mark.parametrize('H,W', SHAPES)
+def test_oracle_cg_convergence_table(H, W):
+    """The convergence the header promises holds within a factor of 2 on the seeded inputs, at both presets' reo, C = 2 .. 8; and the
+    residual the library reports (||r|| / ||rhs||) tracks the distance."""
+    C = {128: 2, 140: 3, 131: 5, 256: 8}[H]
+    img, S, m, nz, y = M.problem(H + C, C, H, W)
+    aty, z, w = M.init_state(y, S, m)
+    for reo, want in TABLE.items():
+        ref, _ = M.cg_solve(aty, z - w, S, m, reo, 40)
+        for k, bar in enumerate(want, 1):
+            xh, rel = M.cg_solve(aty, z - w, S, m, reo, k)
+            d = rel_l2(xh, ref)
+            assert bar / 2 <= d <= bar * 2, (reo, k, d, bar)
+            assert d / 2 <= rel <= d * 2, (reo, k, rel, d)
+
+
+def test_three_cg_iterations_are_enough_for_the_loop():
+    """Ten ADMM_CNC iterations with cg_iters = 3 stay within 2 x 4.7e-7 of the same loop with a converged solve."""
+    img, S, m, nz, y = M.problem(130, 2, 128, 128)
+    assert rel_l2(M.admm(y, S, m, 10, 'cnc', cg_iters=3), M.admm(y, S, m, 10, 'cnc', cg_iters=30)) <= 2 * 4.7e-7
+
+
+# ---- ABI ----------------------------------------------------------------------------------------------------------------------------
+
+NEW = ('pnp_coils_check', 'pnp_set_coils', 'pnp_set_coils_f64', 'pnp_set_cg', 'pnp_get_coils', 'pnp_upload_problem_mc',
+       'pnp_upload_problem_mc_f64', 'pnp_synthesize_problem_mc', 'pnp_synthesize_problem_mc_f64', 'pnp_cg_residual')
+
+
+def test_binding_declares_the_coil_calls():
+    from pnp_admm_cnc_mri_amd import _lib
+    src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'pnp_mri.h')).read(), flags=re.S)
+    for name in NEW:
+        assert re.search(r'\b%s\s*\(' % name, src), name
+        assert name in _lib.SIGNATURES, name
+        assert hasattr(_lib.lib(), name), name
+    assert _lib.ABI_VERSION == 13 == int(re.search(r'#define PNP_ABI_VERSION\s+(\d+)', src).group(1)) == _lib.lib().pnp_abi_version()
+    import pnp_admm_cnc_mri_amd as P
+    for solver in (P.ADMM_L1, P.ADMM_CNC, P.PNP_ADMM_L1_D, P.PNP_ADMM_CNC_D, P.PNP_ADMM_CNC_DnCNN):
+        sig = inspect.signature(solver).parameters
+        assert sig['coils'].default is None and sig['coil_id'].default is None and sig['cg_iters'].default == 3, solver
+    assert 'coil_id' in inspect.signature(P.sharding.solve_sharded).parameters
+
+
+def test_coil_arguments_are_checked_without_a_device():
+    from pnp_admm_cnc_mri_amd import _lib
+    from pnp_admm_cnc_mri_amd.engine import check_coils
+    import pnp_admm_cnc_mri_amd as P
+    L = _lib.lib()
+    for C in (1, 3, 32):
+        for H, W in SHAPES + [(1024, 128)]:
+            assert L.pnp_coils_check(C, 1, H, W) == 0 and L.pnp_coils_check(C, 7, H, W) == 0
+    for C, Ks, H, W, word in ((0, 1, 128, 128, 'C must be'), (33, 1, 128, 128, 'C must be'), (-1, 1, 128, 128, 'C must be'),
+                              (2, 0, 128, 128, 'Ks must be'), (2, 1, 127, 128, '[128, 1024]'), (2, 1, 128, 1025, '[128, 1024]')):
+        assert L.pnp_coils_check(C, Ks, H, W) == -1, (C, Ks, H, W)          # PNP_E_ARG
+        assert word in L.pnp_last_error().decode()
+    # null contexts: codes, not crashes
+    assert L.pnp_set_coils(None, None, 2, 1, 0) == -1 and L.pnp_set_coils_f64(None, None, 0, 0, 0) == -1
+    assert L.pnp_set_cg(None, 3) == -1 and L.pnp_get_coils(None, None, None, None) == -1 and L.pnp_cg_residual(None, None) == -1
+    assert L.pnp_upload_problem_mc(None, None, None, None, None, 1, 1, 0) == -1
+    assert L.pnp_upload_problem_mc_f64(None, None, None, None, None, 1, 1, 0) == -1
+    assert L.pnp_synthesize_problem_mc(None, None, None, 0, None, None, None, 1, 1, 0) == -1
+    assert L.pnp_synthesize_problem_mc_f64(None, None, None, 0, None, None, None, 1, 1, 0) == -1
+    # the Python side refuses before an engine is opened
+    S = np.ones((2, 128, 128), np.complex64)
+    assert check_coils(S, 128, 128) == (2, 1) and check_coils(S[None], 128, 128) == (2, 1)
+    for bad, kw, word in ((np.ones((33, 128, 128)), {}, 'C must be'), (np.ones((2, 128, 130)), {}, 'coils must be'),
+                          (np.ones((128, 128)), {}, 'coils must be'), (S, {'cg_iters': 0}, 'cg_iters'), (S, {'cg_iters': 65}, 'cg_iters')):
+        with pytest.raises(ValueError, match=re.escape(word)):
+            P.ADMM_L1(np.ones((128, 128), np.uint8), None, y=np.zeros((1, 2, 128, 128), np.complex64), coils=bad, **kw)
+    with pytest.raises(ValueError, match='coil_id'):
+        P.ADMM_CNC(np.ones((128, 128), np.uint8), None, y=np.zeros((1, 128, 128), np.complex64), coil_id=[0])
+
+
+# ---- coil_plan.h under g++ with sanitizers -----------------------------------------------------------------------------------------
+
+@pytest.fixture(scope='module')
+def exe(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp('emu_coils') / 'coil_emulation')
+    subprocess.check_call(['g++'] + SAN + ['-o', out, SRC])
+    return out
+
+
+def _run(args):
+    r = subprocess.run(args, env=ENV, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 0 and b'runtime error' not in r.stderr and b'AddressSanitizer' not in r.stderr, (r.returncode, r.stderr.decode()[-1500:])
+    return r.stdout.decode()
+
+
+@pytest.mark.parametrize('H,W', [(128, 128), (131, 128), (140, 160), (1024, 128)])
+@pytest.mark.parametrize('C', [1, 3, 32])
+def test_plan_indices_stay_inside_arrays_of_the_plans_sizes(exe, H, W, C):
+    """Every index the coil kernels form -- [B][C][H][W] offsets, coil_id and expanded-mask lookups, the pointwise kernels' element map
+    and partial slots -- visits each element of an exactly-sized array once (B = 3 slices, a bank of 2 coil sets)."""
+    out = _run([exe, 'walk', str(H), str(W), str(C), '3', '2'])
+    assert out.split() == ['ok', str(H), str(W), str(C), 'blocks', str((H * W + 1023) // 1024), 'rows', str(H)]
+
+
+def test_plan_sums_and_launch_counts(exe):
+    """The two summation orders are exact on integers and within 1e-13 of long double on random data; alpha / beta are 0 for a zero or
+    non-finite ratio; an x-step is 5 + 5 cg_iters launches."""
+    assert _run([exe, 'sums']).strip() == 'ok sums'
+
+
+# ---- sharding ------------------------------------------------------------------------------------------------------------------------
+
+def _free_port():
+    s = socket.socket()
+    s.bind(('127.0.0.1', 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _recording_solver(mask, noises, images=None, y=None, mask_id=None, coils=None, coil_id=None, return_device=False, **opts):
+    """entry-point shape; the 'reconstruction' of slice n records what the shard was handed: pixel 0 its coil_id, pixel 1 its mask_id,
+    pixel 2 the first value of its y, pixel 3 of its noise, pixel 4 the number of coil sets it saw"""
+    import torch
+    out = np.zeros((len(y), 8, 8), np.float32)
+    assert len(coil_id) == len(y) == len(mask_id) and np.shape(noises)[0] == len(y)
+    for n in range(len(y)):
+        out[n].flat[:5] = (coil_id[n], mask_id[n], y[n].real.flat[0], np.asarray(noises)[n].real.flat[0], np.shape(coils)[0])
+    return torch.from_numpy(out)
+
+
+def _problem(B=5, C=2):
+    y = np.arange(B, dtype=np.float64)[:, None, None, None] + np.zeros((B, C, 8, 8), np.complex128)
+    noises = 100.0 + y
+    return np.ones((3, 8, 8)), noises, y, np.arange(B) % 3, (np.arange(B) * 2 + 1) % 4, np.ones((4, C, 8, 8), np.complex64)
+
+
+def _worker(rank, world, port, q):
+    import torch.distributed as dist
+    from pnp_admm_cnc_mri_amd import sharding
+    os.environ['MASTER_ADDR'] = '127.0.0.1'
+    os.environ['MASTER_PORT'] = str(port)
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    try:
+        masks, noises, y, mid, cid, S = _problem()
+        x = sharding.solve_sharded(_recording_solver, masks, noises, y=y, mask_id=mid, coil_id=cid, coils=S)
+        if rank == 0:
+            q.put(x)
+        else:
+            assert x is None
+        dist.monitored_barrier()                      # gloo-only, CPU: dist.barrier() probes for an accelerator and opens the GPU
+    finally:
+        dist.destroy_process_group()
+
+
+def test_solve_sharded_slices_coil_id_with_the_shard():
+    """Two ranks (3 + 2 slices): every slice is solved with ITS coil_id, mask_id, y and per-slice [B,C,H,W] noise, and every rank sees the
+    whole bank of maps; a shared [C,H,W] noise is not sliced."""
+    import torch.multiprocessing as mp
+    from pnp_admm_cnc_mri_amd import sharding
+    ctx = mp.get_context('spawn')
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = q.get(timeout=120)
+    for p in procs:
+        p.join(timeout=120)
+        assert p.exitcode == 0
+    masks, noises, y, mid, cid, S = _problem()
+    assert got.shape == (5, 8, 8)
+    for n in range(5):
+        assert tuple(got[n].flat[:5]) == (cid[n], mid[n], n, 100.0 + n, 4), (n, got[n].flat[:5])
+    seen = {}
+
+    def spy(mask, noises, **kw):
+        seen['noise'] = np.shape(noises)
+        return _recording_solver(mask, np.zeros((len(kw['y']),) + np.shape(noises)), **kw)
+    sharding.solve_sharded(spy, masks, noises[0], y=y, mask_id=mid, coil_id=cid, coils=S)
+    assert seen['noise'] == (2, 8, 8)

@@ -73,6 +73,30 @@ def combo(n, f64, across=1 << 30):
     return ('stockham' if smooth7(n) else 'bluestein', stockham_length(n), lines_per_wg(n, f64, across))
 
 
+def coil_lines_per_wg(n, f64):
+    """coil_axis of kernels_anysize.hip: the coil rows hold a third LDS array of n values per line beside the two buffers of pitch m + 1,
+    counted against the same 40 KiB; never more lines than the plain rows take."""
+    per_line = (16 if f64 else 8) * (2 * (stockham_length(n) + 1) + n)
+    return max(1, min(40 * 1024 // per_line, lines_per_wg(n, f64)))
+
+
+def coil_lds_bytes(n, f64):
+    """coil_lds of kernels_anysize.hip: the dynamic LDS of one coil-row workgroup."""
+    return (16 if f64 else 8) * coil_lines_per_wg(n, f64) * (2 * (stockham_length(n) + 1) + n)
+
+
+def coil_row_combo(n, f64):
+    """What shapes a coil row kernel along W: (kind, m if Bluestein else None, G)."""
+    kind = 'stockham' if smooth7(n) else 'bluestein'
+    return kind, stockham_length(n) if kind == 'bluestein' else None, coil_lines_per_wg(n, f64)
+
+
+# the first row length of every (kind, m, G) of the coil rows, worked out from coil_axis()'s rule; test_multicoil_host.py holds the
+# restatement above to it, test_gpu_multicoil_edges.py runs each length once
+COIL_ROW_FIRSTS = {False: (128, 129, 135, 144, 160, 175, 189, 216, 245, 255, 257, 288, 343, 432, 511, 513, 576, 864),
+                   True: (128, 129, 144, 175, 216, 255, 257, 288, 432, 513)}
+
+
 def shape_combos(H, W, f64):
     """(rows' combination, columns' combination) of a context, as anysize_create sets them."""
     return combo(W, f64), combo(H, f64, W)

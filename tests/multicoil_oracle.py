@@ -67,6 +67,19 @@ def noise(seed, C, m, std=1.0):
     return n * (m != 0)
 
 
+def noise_full(seed, shape, std=1.0):
+    """complex Gaussian noise on EVERY entry of an array of `shape` ([H,W], [C,H,W] or [B,C,H,W]), complex128: what the device synthesis
+    adds unmasked (y = m . fft2(S_c . img) + noise, the reference's y = fft2(img) * mask + noises)"""
+    rng = np.random.default_rng(4700 + seed)
+    return std * (rng.standard_normal(shape) + 1j * rng.standard_normal(shape))
+
+
+def disc(H, W, radius=0.42):
+    """1 inside the disc of `radius` * H around the centre, 0 outside: maps times this are rank-deficient there (G = La2 I)"""
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    return (((yy - H / 2) ** 2 + (xx - W / 2) ** 2) <= (radius * H) ** 2).astype(np.float64)
+
+
 # ---- operators ---------------------------------------------------------------------------------------------------------------------
 
 def A(x, S, m, dt=np.complex128):

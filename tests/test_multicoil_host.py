@@ -162,6 +162,27 @@ def test_plan_sums_and_launch_counts(exe):
     assert _run([exe, 'sums']).strip() == 'ok sums'
 
 
+# ---- the lines per workgroup and the LDS of the coil rows (coil_axis / coil_lds of kernels_anysize.hip, restated) -------------------
+
+def test_coil_row_rule_over_all_lengths():
+    """All 897 row lengths, float and double: at least one line per workgroup, the LDS within the 96 KiB the kernels opt in to, the
+    [G][n] doubles of the combining kernel's products inside the first buffer they overlay, the first length of every combination (the
+    restatement agrees with the list worked out from coil_axis()'s rule), and the largest LDS."""
+    import anysize_common as AC
+    for f64 in (False, True):
+        cbytes = 16 if f64 else 8
+        first = {}
+        for n in AC.LENGTHS:
+            kind, m, G = AC.coil_row_combo(n, f64)
+            assert G >= 1 and G == AC.coil_lines_per_wg(n, f64), n
+            assert AC.coil_lds_bytes(n, f64) <= 96 * 1024, n
+            assert 8 * G * n <= cbytes * G * (AC.stockham_length(n) + 1), n
+            first.setdefault((kind, m, G), n)
+        assert tuple(sorted(first.values())) == AC.COIL_ROW_FIRSTS[f64]
+        assert max((AC.coil_lds_bytes(n, f64), n) for n in AC.LENGTHS) == ((81936, 1023) if f64 else (40968, 1023))
+        assert {G for _, _, G in first} == set(range(1, 7 if f64 else 14))
+
+
 # ---- sharding ------------------------------------------------------------------------------------------------------------------------
 
 def _free_port():

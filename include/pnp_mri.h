@@ -30,6 +30,7 @@
 #ifndef PNP_MRI_H
 #define PNP_MRI_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -345,6 +346,49 @@ int pnp_synthesize_problem_mc_f64(pnp_ctx* ctx, const float* img, const double* 
  * 2 with a wavelet); pnp_Df fails with PNP_E_STATE.
  * pnp_cg_residual: ||r|| / ||A^H y + La2 v|| of the most recent x-step, per slice, rel [B] on the host (synchronises). */
 int pnp_cg_residual(pnp_ctx* ctx, double* rel);
+
+/* ---- coil mixing ahead of the multi-coil solve: noise prewhitening and coil compression (added after ABI 13, additive) ----
+ * NOT in the reference scripts.  Array data has 32 to 128 channels, the solve above takes at most 32 and costs time linear in C.  Both
+ * standard remedies are ONE operation: a C_out x C_in complex matrix M applied per k-space point to the measurements and per pixel to
+ * the maps.  The forward model is linear in the coil index, so with y' = M y and S' = M S it is again exactly y'_j = m . fft2(S'_j . x):
+ * nothing after pnp_set_coils changes, which is handed S' (C_out <= 32 virtual coils) and y'.
+ *   prewhitening   M_w = L^-1, L the lower Cholesky factor of the channels' noise covariance Psi (M_w Psi M_w^H = I)
+ *   compression    M_c [C_out][C_in]: the conjugated eigenvectors of the C_out largest eigenvalues of the Gram matrix
+ *                  R = sum_{p in calibration} mask(p) y(p) y(p)^H of the data (M_c M_c^H = I; eig_k / sum eig is virtual coil k's share of
+ *                  the calibration energy)
+ *   both           the Gram of the whitened data is M_w R M_w^H -- compress THAT, then M = M_c M_w.  The consumer multiplies these small
+ *                  matrices itself (host, C x C) and mixes the data ONCE, C_in -> C_out: no whitened intermediate is ever written.
+ * Calibration region (k-space un-shifted, DC at (0, 0)): rows 0 .. ceil(ncal / 2) - 1 and H - floor(ncal / 2) .. H - 1, columns by the same
+ * rule with W.  Limits: 1 <= C_in <= 128, 1 <= C_out <= min(C_in, 32), Ks >= 1, 4 <= ncal <= 64 (and <= min(H, W)), H and W in
+ * [128, 1024]; pnp_coilmix_check is that rule without a context or a device, anything else is PNP_E_ARG and pnp_last_error names the rule.
+ * The device entry points are stateless like the conv layers': caller-owned device arrays, any HIP stream, no allocation, no
+ * synchronisation, one launch.  Complex arrays are interleaved (re, im) in the precision of the entry point. */
+int pnp_coilmix_check(int C_in, int C_out, int Ks, int ncal, int H, int W);
+/* out[b][j][p] = sum_c m[set_id[b]][j][c] in[b][c][p]:  in [B][C_in][N], m [Ks][C_out][C_in] (device, the arrays' precision), set_id [B]
+ * on the device or null (set 0; the entries are NOT range-checked: that would synchronise), out [B][C_out][N].  Any N >= 1: the call does
+ * not know about H, W (measurements: N = H W; a bank of maps: B = Ks, set_id = 0 .. Ks - 1).  The coils are accumulated in the order
+ * c = 0 .. C_in - 1 with fused multiply-adds, per point: a slice alone and the same slice in a batch are bit-equal.  in and out must not
+ * overlap (PNP_E_ARG).  B <= 65535. */
+int pnp_coil_mix(void* hip_stream, const float* in_dev, const float* m_dev, const int32_t* set_id_dev, float* out_dev, int B, int C_in,
+                 int C_out, size_t N);
+int pnp_coil_mix_f64(void* hip_stream, const double* in_dev, const double* m_dev, const int32_t* set_id_dev, double* out_dev, int B, int C_in,
+                     int C_out, size_t N);
+/* gram[b][i][j] = sum_{p in calibration} mask_b(p) y[b][i][p] conj(y[b][j][p]):  y [B][C][H][W], mask_bank [K][H][W] and mask_id [B] (or
+ * null: mask 0; not range-checked) on the device, gram [B][C][C] complex DOUBLE.  Products and sums in double for both input precisions,
+ * in a fixed order that depends on (ncal, H, W) alone; both triangles are stored, gram[b][j][i] is bit for bit the conjugate of
+ * gram[b][i][j] and the diagonal's imaginary part is 0.  One matrix per SLICE: a consumer sums those of the slices that share a coil set
+ * (on the host, in slice order, when the result must not depend on how the batch was cut). */
+int pnp_coil_gram(void* hip_stream, const float* y_dev, const uint8_t* mask_bank_dev, const int32_t* mask_id_dev, double* gram_dev, int B,
+                  int C, int H, int W, int ncal);
+int pnp_coil_gram_f64(void* hip_stream, const double* y_dev, const uint8_t* mask_bank_dev, const int32_t* mask_id_dev, double* gram_dev, int B,
+                      int C, int H, int W, int ncal);
+/* Host, double, no device: m_out [C][C] = L^-1 of the Hermitian noise_cov [C][C] (its lower triangle is read), C <= 128.  A covariance
+ * that is not positive definite, or not finite, is PNP_E_ARG. */
+int pnp_coilmix_whiten(const double* noise_cov, int C, double* m_out);
+/* Host, double, no device: cyclic Jacobi on the Hermitian gram [C][C] ((gram + gram^H) / 2 is what is decomposed).  eig_out [C]: all
+ * eigenvalues, descending; m_out [C_out][C]: row j the conjugated eigenvector of eig_out[j], its phase fixed so that the eigenvector's
+ * entry of largest modulus is real and positive (on a tie the first such entry). */
+int pnp_coilmix_compress(const double* gram, int C, int C_out, double* m_out, double* eig_out);
 
 /* ---- optional HIP backend of the denoisers' plain conv stacks ------------------------------
  * The north star keeps the CNN forward pass in PyTorch-ROCm; these two entry points are the opt-in `Denoiser(backend='hip')`

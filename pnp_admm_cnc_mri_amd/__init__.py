@@ -6,7 +6,9 @@ PyTorch-ROCm only for the denoiser forward pass, device tensors and torch.distri
 """
 from .engine import Engine                                    # noqa: F401
 from .solvers import ADMM_L1, ADMM_CNC, PRESETS               # noqa: F401
-from . import utils_pnp                                       # noqa: F401
+from . import coilmix, utils_pnp                              # noqa: F401
+from .coilmix import whitening_matrix, calibration_gram, compression_matrix   # noqa: F401
+from .coilmix import mix as coil_mix, prepare as coil_prepare                  # noqa: F401
 
 
 def __getattr__(name):
@@ -20,4 +22,5 @@ def __getattr__(name):
 
 
 __all__ = ['Engine', 'ADMM_L1', 'ADMM_CNC', 'PNP_ADMM_L1_D', 'PNP_ADMM_CNC_D', 'PNP_ADMM_CNC_DnCNN', 'PRESETS',
-           'utils_pnp']
+           'utils_pnp', 'coilmix', 'whitening_matrix', 'calibration_gram', 'compression_matrix', 'coil_mix',
+           'coil_prepare']

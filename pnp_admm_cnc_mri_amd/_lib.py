@@ -121,6 +121,14 @@ SIGNATURES = {
     'pnp_synthesize_problem_mc': (C.c_int, [ctx_p, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
     'pnp_synthesize_problem_mc_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
     'pnp_cg_residual': (C.c_int, [ctx_p, c_double_p]),
+    # coil mixing ahead of the multi-coil solve: prewhitening and coil compression (added after ABI 13, additive)
+    'pnp_coilmix_check': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'pnp_coil_mix': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t]),
+    'pnp_coil_mix_f64': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t]),
+    'pnp_coil_gram': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'pnp_coil_gram_f64': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'pnp_coilmix_whiten': (C.c_int, [_vp, C.c_int, _vp]),
+    'pnp_coilmix_compress': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     'pnp_ssim': (C.c_int, [ctx_p, _vp, _vp, C.c_int, c_double_p]),
     'pnp_timer_start': (C.c_int, [ctx_p]),
     'pnp_timer_stop': (C.c_int, [ctx_p, c_float_p]),

@@ -4,6 +4,7 @@
 #include "internal.h"
 #include "wavelet_plan.h"
 #include "coil_plan.h"
+#include "coilmix_plan.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -1661,6 +1662,82 @@ int pnp_cg_residual(pnp_ctx* c, double* rel) {
     if (!rel) return fail(PNP_E_ARG, "pnp_cg_residual: rel is null");
     if (!c->coils.have_rel) return fail(PNP_E_STATE, "pnp_cg_residual: no x-step has run on the uploaded problem");
     return copy_out(c, rel, c->coils.rel, (size_t)c->B * sizeof(double), 0);
+}
+
+// ---- coil mixing ahead of the multi-coil solve: coilmix_plan.h, kernels_coilmix.hip.  No context: caller-owned device arrays ----
+
+int pnp_coilmix_check(int C_in, int C_out, int Ks, int ncal, int H, int W) {
+    switch (coilmix_check(C_in, C_out, Ks, ncal, H, W)) {
+    case COILMIX_OK:        return PNP_OK;
+    case COILMIX_BAD_IN:    return fail(PNP_E_ARG, "coil mixing: C_in must be 1..%d (got %d)", COILMIX_MAX_IN, C_in);
+    case COILMIX_BAD_OUT:   return fail(PNP_E_ARG, "coil mixing: C_out must be 1..min(C_in, %d) (got %d of %d)", COIL_MAX_C, C_out, C_in);
+    case COILMIX_BAD_SETS:  return fail(PNP_E_ARG, "coil mixing: Ks must be >= 1 (got %d)", Ks);
+    case COILMIX_BAD_NCAL:  return fail(PNP_E_ARG, "coil mixing: ncal must be %d..%d and <= min(H, W) (got %d at %d x %d)", COILMIX_NCAL_MIN,
+                                        COILMIX_NCAL_MAX, ncal, H, W);
+    default:                return fail(PNP_E_ARG, "coil mixing: H, W must be in [128, 1024] (got %d x %d)", H, W);
+    }
+}
+
+extern "C++" {
+template <typename R>
+static int coil_mix_any(const char* who, void* stream, const R* in, const R* m, const int32_t* set_id, R* out, int B, int C_in, int C_out, size_t N) {
+    if (!in || !m || !out) return fail(PNP_E_ARG, "%s: null pointer", who);
+    if (B < 1 || B > 65535) return fail(PNP_E_ARG, "%s: B must be 1..65535 (got %d)", who, B);
+    if (C_in < 1 || C_in > COILMIX_MAX_IN) return fail(PNP_E_ARG, "%s: C_in must be 1..%d (got %d)", who, COILMIX_MAX_IN, C_in);
+    if (C_out < 1 || C_out > C_in || C_out > COIL_MAX_C) return fail(PNP_E_ARG, "%s: C_out must be 1..min(C_in, %d) (got %d of %d)", who, COIL_MAX_C, C_out, C_in);
+    if (N < 1 || coilmix_mix_blocks(N, sizeof(R) == 8) > 0x7fffffffu) return fail(PNP_E_ARG, "%s: N must be >= 1 and make fewer than 2^31 workgroups (got %zu)", who, N);
+    if ((uintptr_t)in % (2 * sizeof(R)) || (uintptr_t)out % (2 * sizeof(R)) || (uintptr_t)m % (2 * sizeof(R)))
+        return fail(PNP_E_ARG, "%s: in, m and out must be aligned to one complex value", who);
+    const char *i0 = (const char*)in, *o0 = (const char*)out;
+    const size_t ib = (size_t)B * C_in * N * 2 * sizeof(R), ob = (size_t)B * C_out * N * 2 * sizeof(R);
+    if (i0 < o0 + ob && o0 < i0 + ib) return fail(PNP_E_ARG, "%s: in and out must not overlap", who);
+    HIPCHK(launch_coil_mix<R>((hipStream_t)stream, in, m, set_id, out, B, C_in, C_out, N));
+    return PNP_OK;
+}
+}  // extern "C++"
+int pnp_coil_mix(void* stream, const float* in, const float* m, const int32_t* set_id, float* out, int B, int C_in, int C_out, size_t N) {
+    return coil_mix_any<float>(__func__, stream, in, m, set_id, out, B, C_in, C_out, N);
+}
+int pnp_coil_mix_f64(void* stream, const double* in, const double* m, const int32_t* set_id, double* out, int B, int C_in, int C_out, size_t N) {
+    return coil_mix_any<double>(__func__, stream, in, m, set_id, out, B, C_in, C_out, N);
+}
+
+extern "C++" {
+template <typename R>
+static int coil_gram_any(const char* who, void* stream, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, double* gram, int B, int C,
+                         int H, int W, int ncal) {
+    if (!y || !mask_bank || !gram) return fail(PNP_E_ARG, "%s: null pointer", who);
+    if (B < 1 || B > 65535) return fail(PNP_E_ARG, "%s: B must be 1..65535 (got %d)", who, B);
+    if (int rc = pnp_coilmix_check(C, 1, 1, ncal, H, W)) return rc;
+    if ((uintptr_t)y % (2 * sizeof(R)) || (uintptr_t)gram % 16) return fail(PNP_E_ARG, "%s: y and gram must be aligned to one complex value", who);
+    HIPCHK(launch_coil_gram<R>((hipStream_t)stream, y, mask_bank, mask_id, gram, B, C, H, W, ncal));
+    return PNP_OK;
+}
+}  // extern "C++"
+int pnp_coil_gram(void* stream, const float* y, const uint8_t* mask_bank, const int32_t* mask_id, double* gram, int B, int C, int H, int W, int ncal) {
+    return coil_gram_any<float>(__func__, stream, y, mask_bank, mask_id, gram, B, C, H, W, ncal);
+}
+int pnp_coil_gram_f64(void* stream, const double* y, const uint8_t* mask_bank, const int32_t* mask_id, double* gram, int B, int C, int H, int W, int ncal) {
+    return coil_gram_any<double>(__func__, stream, y, mask_bank, mask_id, gram, B, C, H, W, ncal);
+}
+
+int pnp_coilmix_whiten(const double* noise_cov, int C, double* m_out) {
+    if (!noise_cov || !m_out || noise_cov == m_out) return fail(PNP_E_ARG, "pnp_coilmix_whiten: null or aliased pointers");
+    if (C < 1 || C > COILMIX_MAX_IN) return fail(PNP_E_ARG, "pnp_coilmix_whiten: C must be 1..%d (got %d)", COILMIX_MAX_IN, C);
+    if (!coilmix_all_finite(noise_cov, 2 * (size_t)C * C)) return fail(PNP_E_ARG, "pnp_coilmix_whiten: the covariance has a non-finite entry");
+    if (int at = coilmix_inv_chol(noise_cov, C, m_out))
+        return fail(PNP_E_ARG, "pnp_coilmix_whiten: the covariance is not positive definite (pivot %d of the Cholesky factor)", at - 1);
+    return PNP_OK;
+}
+
+int pnp_coilmix_compress(const double* gram, int C, int C_out, double* m_out, double* eig_out) {
+    if (!gram || !m_out || !eig_out) return fail(PNP_E_ARG, "pnp_coilmix_compress: null pointer");
+    if (C < 1 || C > COILMIX_MAX_IN) return fail(PNP_E_ARG, "pnp_coilmix_compress: C must be 1..%d (got %d)", COILMIX_MAX_IN, C);
+    if (C_out < 1 || C_out > C || C_out > COIL_MAX_C) return fail(PNP_E_ARG, "pnp_coilmix_compress: C_out must be 1..min(C, %d) (got %d of %d)", COIL_MAX_C, C_out, C);
+    if (!coilmix_all_finite(gram, 2 * (size_t)C * C)) return fail(PNP_E_ARG, "pnp_coilmix_compress: the Gram matrix has a non-finite entry");
+    std::vector<double> work(4 * (size_t)C * C);
+    if (coilmix_compress(gram, C, C_out, m_out, eig_out, work.data())) return fail(PNP_E_ARG, "pnp_coilmix_compress: the Jacobi sweeps did not converge");
+    return PNP_OK;
 }
 
 }  // extern "C"

@@ -111,6 +111,14 @@ hipError_t launch_cg_residual(hipStream_t s, const double* part_rr, const double
 template <typename R> hipError_t launch_cabs(hipStream_t s, const typename CxOf<R>::type* in, R* out, size_t n);
 hipError_t launch_prox_f64(hipStream_t s, bool cnc, const double* x, double* z, double* w, ProxParamsT<double> p, size_t n);
 
+// coil mixing ahead of the multi-coil solve (kernels_coilmix.hip, coilmix_plan.h): interleaved complex arrays in R, no context.
+// out[b][j][p] = sum_c m[set_id[b]][j][c] in[b][c][p] (in [B][C_in][N], m [Ks][C_out][C_in], out [B][C_out][N]; set_id null: set 0), and
+// the per-slice Gram matrices of the calibration region, gram [B][C][C] complex double
+template <typename R> hipError_t launch_coil_mix(hipStream_t s, const R* in, const R* m, const int32_t* set_id, R* out, int B, int C_in,
+                                                 int C_out, size_t N);
+template <typename R> hipError_t launch_coil_gram(hipStream_t s, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, double* gram,
+                                                  int B, int C, int H, int W, int ncal);
+
 // pointwise
 hipError_t launch_prox(hipStream_t s, bool cnc, const float* x, float* z, float* w, ProxParams p, size_t n);
 hipError_t launch_combine(hipStream_t s, const float* z, const float* x, const float* w, const float* sden,

@@ -41,6 +41,16 @@ bypass the file system through the extra keyword arguments
               solve); UNNORMALISED MAPS OR A LARGE reo (the in-function default of ADMM_CNC, 2.75: condition number about 6.5) NEED
               MORE -- info['cg_residual'] has ||r|| / ||rhs|| of the last x-step per slice.  NOT in the reference scripts; None (the
               default) is bit for bit what it was.  One extra log line names C and cg_iters
+    virtual_coils=None, noise_cov=None, calib=24   (all five solvers) coil mixing ahead of the solve (coilmix.py; include/pnp_mri.h, "coil
+              mixing"): noise_cov [C,C], the channels' noise covariance, prewhitens the data (M_w = L^-1 of its Cholesky factor);
+              virtual_coils = n keeps the n virtual coils that carry the most energy of the calib x calib lowest frequencies (SVD coil
+              compression: M_c from the Gram matrix of the slices that use a coil set, one matrix per set of the bank).  Both are one
+              matrix M = M_c M_w applied once to y and to the maps, after which the solve runs on n coils: `coils` may then have up to
+              128 channels, the limit of 32 and check_coils apply to the MIXED count, and the x-step costs n / C of what it did.  They need
+              coils= and measured y= (images= may still be given as the ground truth); noise_cov alone means n = C <= 32.  NOT in the
+              reference scripts; with all three at their defaults nothing is called and nothing changes.  One extra log line ("coil
+              mixing: 64 -> 8 virtual coils, 97.1 % of the calibration energy, prewhitened"); info['coil_mix'] = {M, eigvals, energy}.
+              Under sharding.solve_sharded every rank forms its matrices from the slices of its own shard
 
 The PnP entry points (PNP_ADMM_L1_D, PNP_ADMM_CNC_D, PNP_ADMM_CNC_DnCNN) live in solvers_pnp.py.
 """
@@ -50,7 +60,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import imageio
+from . import coilmix, imageio
 from ._lib import PnpError
 from .engine import Engine, check_coils, check_sparsity
 
@@ -109,7 +119,7 @@ class _Job:
 
     def __init__(self, mask, noises, tag, suffix, images=None, y=None, mask_id=None, testsets='testsets',
                  testset_name='Set1', results='results', save_E=None, device=None, log=None, ssim=None,
-                 psnr_fmt='{:.4f}', precision='f32', coils=None, coil_id=None, cg_iters=3):
+                 psnr_fmt='{:.4f}', precision='f32', coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24):
         # psnr_fmt: S1:150 and S3:320 print the per-image PSNR with two decimals, S4:155 / S6:332 / S6:548 with four
         self.tag, self.suffix, self.psnr_fmt = tag, suffix, psnr_fmt
         if precision not in ('f32', 'f64'):
@@ -121,7 +131,15 @@ class _Job:
         self.mask_id = None if mask_id is None else np.asarray(mask_id, np.int32)
         self.coils, self.cg_iters = coils, cg_iters
         self.coil_id = None if coil_id is None else np.asarray(coil_id, np.int32)
-        if coils is not None:
+        self.virtual_coils, self.noise_cov, self.calib, self.coil_mix = virtual_coils, noise_cov, calib, None
+        self.mixing = virtual_coils is not None or noise_cov is not None
+        if self.mixing:
+            if coils is None or y is None:
+                raise ValueError('virtual_coils= / noise_cov= mix MEASURED data: they need coils= and y= (the device synthesis from images= '
+                                 'is limited to 32 physical coils; images= may still be given as the ground truth)')
+            _, c_out, ks = coilmix.plan(coils, self.H, self.W, virtual_coils, noise_cov, calib)
+            check_coils(np.broadcast_to(np.int8(0), (ks, c_out, self.H, self.W)), self.H, self.W, cg_iters)   # the MIXED count; no engine yet
+        elif coils is not None:
             check_coils(coils, self.H, self.W, cg_iters)                         # before an engine is opened
         elif coil_id is not None:
             raise ValueError('coil_id= needs coils=')
@@ -171,6 +189,11 @@ class _Job:
         """stream: HIP stream handle every engine call is ordered on (PnP: torch's current stream),
         set BEFORE the first kernel so upload / synthesis / init and the loop share one queue.
         transform / levels: Engine.set_sparsity (ADMM_L1 / ADMM_CNC)."""
+        if self.mixing and self.coil_mix is None:                    # y' = M y, S' = M S: from here on the virtual coils are the coils
+            self.y, self.coils, self.coil_mix = coilmix.prepare(self.y, self.coils, self.mask_bank, self.mask_id, self.coil_id,
+                                                                self.virtual_coils, self.noise_cov, self.calib, self.precision, self.device)
+            if self.log is not None:
+                self.log.info(coilmix.describe(self.coil_mix))
         eng = Engine(self.H, self.W, Bmax=self.B, device=self.device, precision=self.precision)
         if transform is not None:
             eng.set_sparsity(transform, levels)
@@ -213,6 +236,8 @@ class _Job:
                 if e.code != -3:
                     raise
                 info['cg_residual'] = []
+        if self.coil_mix is not None:
+            info['coil_mix'] = {k: self.coil_mix[k] for k in ('M', 'eigvals', 'energy')}
         if self.gt_u8 is not None:
             psnr, re = eng.metrics(x_dev, self.gt_u8)                                     # device reductions
             info['psnr'], info['re'] = list(map(float, psnr)), list(map(float, re))
@@ -267,7 +292,7 @@ def _device_x(eng, job):
 
 def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
             results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
-            transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, **ADMM_L1_opts):
+            transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24, **ADMM_L1_opts):
     """ADMM with L1 prox on the MI355X engine.  Reference: "【1】ADMM_L1.py":29-169."""
     iter_num = ADMM_L1_opts.get('iter_num', 20)          # S1:35
     lambda1 = ADMM_L1_opts.get('lambda1', 0.04)          # S1:36
@@ -275,7 +300,8 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
     traced = trace_request(trace_every, tol, return_info)
     check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
     job = _Job(mask, noises, 'ADMM_L1', '_PDG L1', images, y, mask_id, testsets, testset_name, results, save_E, device,
-               psnr_fmt='{:.2f}', precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters)   # S1:150
+               psnr_fmt='{:.2f}', precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters, virtual_coils=virtual_coils,
+               noise_cov=noise_cov, calib=calib)   # S1:150
     with job.open_engine(transform=transform, levels=levels) as eng:
         # S1:111-126, all slices, on device
         trace = eng.admm_l1(iter_num, lambda1, reo, trace_every, tol, job.gt_u8) if traced else eng.admm_l1(iter_num, lambda1, reo)
@@ -289,7 +315,7 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
 
 def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
              results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
-             transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, **ADMM_CNC_opts):
+             transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24, **ADMM_CNC_opts):
     """ADMM with the convex-non-convex z-step.  Reference: "【4】ADMM_CNC .py":31-174."""
     iter_num = ADMM_CNC_opts.get('iter_num', 4)          # S4:37
     alpha = ADMM_CNC_opts.get('alpha', 0.4)              # S4:38
@@ -299,7 +325,8 @@ def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets
     traced = trace_request(trace_every, tol, return_info)
     check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
     job = _Job(mask, noises, 'ADMM_CNC', '_ADMM CNC', images, y, mask_id, testsets, testset_name, results, save_E, device,
-               precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters)
+               precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters, virtual_coils=virtual_coils, noise_cov=noise_cov,
+               calib=calib)
     with job.open_engine(transform=transform, levels=levels) as eng:
         # S4:115-132
         trace = (eng.admm_cnc(iter_num, alpha, lambda1, reo, b, trace_every, tol, job.gt_u8) if traced

@@ -110,6 +110,25 @@ def AH(eng, k, coils=None):
     return out
 
 
+def coil_mix(k, M, coil_id=None):
+    """out[b, j] = sum_c M[set(b), j, c] k[b, c]: prewhitening / coil compression of k-space [B,C,H,W] or of a bank of maps, on device
+    tensors or host arrays (coilmix.mix; no engine: pnp_coil_mix is stateless).  No counterpart in the reference."""
+    from . import coilmix
+    return coilmix.mix(k, M, coil_id)
+
+
+def whitening_matrix(noise_cov):
+    """M_w = L^-1 of the Cholesky factor of the channels' noise covariance (coilmix.whitening_matrix)."""
+    from . import coilmix
+    return coilmix.whitening_matrix(noise_cov)
+
+
+def compression_matrix(gram, n, whiten=None):
+    """(M, eigvals): the n leading virtual coils of a calibration Gram matrix, combined with M_w (coilmix.compression_matrix)."""
+    from . import coilmix
+    return coilmix.compression_matrix(gram, n, whiten)
+
+
 def Df(eng, x):
     """Df(x, mask, y) = A^H (A x - y) of utils/utils.py:50-55, with the engine's y and masks."""
     torch = _torch()

@@ -390,6 +390,45 @@ int pnp_coilmix_whiten(const double* noise_cov, int C, double* m_out);
  * entry of largest modulus is real and positive (on a tie the first such entry). */
 int pnp_coilmix_compress(const double* gram, int C, int C_out, double* m_out, double* eig_out);
 
+/* ---- coil sensitivity maps from the calibration region of k-space (added after ABI 13, additive) ----
+ * NOT in the reference scripts.  The solvers above need maps [C][H][W]; a scanner delivers k-space.  The estimator is the local
+ * dominant-eigenvector method (Walsh's adaptive combination) in matrix-free form on low-resolution coil images: no calibration-matrix
+ * SVD, no per-pixel eigendecomposition.  The solvers reconstruct a REAL non-negative image (x = |Re x^|), so the maps carry all of the
+ * phase.  One slice, y [C][H][W] un-shifted (DC at (0, 0)), mask [H][W], ncal, radius r, power_iters n, thresh tau:
+ *   1 window    calibration line i = 0 .. ncal - 1 of an axis of length n sits at line i (i < ceil(ncal / 2)) or n - ncal + i, its signed
+ *               frequency is f = i resp. i - ncal, its weight w(f) = cos^2(pi f / (ncal + 1)).  K_c = w_H (x) w_W . y_c on the ncal x ncal
+ *               region, 0 elsewhere.  EVERY point of the region must be sampled (mask != 0): otherwise PNP_E_ARG, and pnp_last_error names
+ *               the first missing point (lowest offset).  No silent zero-filling.
+ *   2 images    I_c = ifft2(K_c) with the context's own inverse transform (it carries 1 / (H W)).
+ *   3 vectors   the patch of pixel p: the (2r + 1)^2 pixels around it, offsets in row-major order (dy, dx) = (-r, -r) .. (r, r), wrapped
+ *               periodically on both axes.  v = I(p) / ||I(p)|| (e_0 when I(p) = 0); n times: g_q = sum_c conj(I_c(q)) v_c for every q of
+ *               the patch in order (coils in order), u = sum_q I(q) g_q (patch points in order), lambda = ||u||, v = u / lambda (v stays
+ *               when lambda = 0): power iteration on R(p) = sum_q I(q) I(q)^H, which is never formed.
+ *   4 phase     g = sum_c conj(v_c) I_c(p); v <- v g / |g| (unchanged when g = 0).  Then v^H I(p) >= 0: a real non-negative image is
+ *               consistent with the maps.
+ *   5 support   lambda_max = the slice's largest lambda; S(p) = v(p) where lambda(p) >= tau^2 lambda_max, else exactly +0 in every coil.
+ *               Inside the support sum_c |S_c|^2 = 1, the normalisation the x-step's 3 CG iterations assume; maps that vanish on a
+ *               region are what the multi-coil solve already handles.
+ * r = 0, n = 1 is S = I / ||I||, the classical low-resolution sum-of-squares maps; C = 1 is S = I / |I|.  Every sum is taken in an order
+ * that depends on (C, r, n) alone (csrc/coilmaps_plan.h states each): a slice alone is bit-equal to the slice in a batch.
+ * Limits, one message per rule (pnp_coilmaps_check: no context, no device): 1 <= C <= 32, ncal as for coil mixing, 0 <= radius <= 3,
+ * 1 <= power_iters <= 16, 0 <= thresh < 1, H and W in [128, 1024].
+ * pnp_coil_maps runs on `ctx` (any shape; the context's precision must be the entry point's) and on its stream, and touches neither the
+ * uploaded problem nor the state: y [B][C][H][W], mask_bank [K][H][W] with mask_id [B] (or null: mask 0; not range-checked), maps_out
+ * [B][C][H][W], lambda_out [B][H][W] or null -- all DEVICE arrays, interleaved complex.  The window kernel, the context's inverse
+ * transform over the B C pseudo-slices in chunks of at most Bmax, the eigenvector kernel and the support kernels; the context keeps one
+ * scratch array for min(B C, Bmax) pseudo-slices (at least C), allocated on first use -- a failure names the byte count.  maps_out must
+ * not overlap y (PNP_E_ARG); B <= 65535.  The call synchronises the stream once, at its end, to read the missing-point check back. */
+int pnp_coilmaps_check(int C, int ncal, int radius, int power_iters, double thresh, int H, int W);
+int pnp_coil_maps(pnp_ctx* ctx, const float* y_dev, const uint8_t* mask_bank_dev, const int32_t* mask_id_dev, float* maps_out_dev,
+                  float* lambda_out_dev, int B, int C, int ncal, int radius, int power_iters, double thresh);
+int pnp_coil_maps_f64(pnp_ctx* ctx, const double* y_dev, const uint8_t* mask_bank_dev, const int32_t* mask_id_dev, double* maps_out_dev,
+                      double* lambda_out_dev, int B, int C, int ncal, int radius, int power_iters, double thresh);
+/* MEASUREMENT, not product (profiles/coilmaps_rate.py): enable != 0 brackets the three stages of every later pnp_coil_maps call on ctx --
+ * window, inverse transform, eigenvectors with support -- by HIP events and synchronises after every pass; ms_out (or NULL) gets the three
+ * times accumulated since the previous call of this function, which also resets them.  Results are bit for bit the same either way. */
+int pnp_coil_maps_stage_times(pnp_ctx* ctx, int enable, float* ms_out);
+
 /* ---- optional HIP backend of the denoisers' plain conv stacks ------------------------------
  * The north star keeps the CNN forward pass in PyTorch-ROCm; these two entry points are the opt-in `Denoiser(backend='hip')`
  * for the 64 -> 64 channel conv3x3 (+ bias, + ReLU) body layers of FFDNet / DnCNN / FDnCNN (models/network_ffdnet.py:58-73,

@@ -6,7 +6,8 @@ PyTorch-ROCm only for the denoiser forward pass, device tensors and torch.distri
 """
 from .engine import Engine                                    # noqa: F401
 from .solvers import ADMM_L1, ADMM_CNC, PRESETS               # noqa: F401
-from . import coilmix, utils_pnp                              # noqa: F401
+from . import coilmaps, coilmix, utils_pnp                    # noqa: F401
+from .coilmaps import estimate as estimate_coil_maps          # noqa: F401
 from .coilmix import whitening_matrix, calibration_gram, compression_matrix   # noqa: F401
 from .coilmix import mix as coil_mix, prepare as coil_prepare                  # noqa: F401
 
@@ -22,5 +23,5 @@ def __getattr__(name):
 
 
 __all__ = ['Engine', 'ADMM_L1', 'ADMM_CNC', 'PNP_ADMM_L1_D', 'PNP_ADMM_CNC_D', 'PNP_ADMM_CNC_DnCNN', 'PRESETS',
-           'utils_pnp', 'coilmix', 'whitening_matrix', 'calibration_gram', 'compression_matrix', 'coil_mix',
+           'utils_pnp', 'coilmix', 'coilmaps', 'estimate_coil_maps', 'whitening_matrix', 'calibration_gram', 'compression_matrix', 'coil_mix',
            'coil_prepare']

@@ -129,6 +129,11 @@ SIGNATURES = {
     'pnp_coil_gram_f64': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'pnp_coilmix_whiten': (C.c_int, [_vp, C.c_int, _vp]),
     'pnp_coilmix_compress': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    # coil sensitivity maps from the calibration region (added after ABI 13, additive)
+    'pnp_coilmaps_check': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]),
+    'pnp_coil_maps': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
+    'pnp_coil_maps_f64': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
+    'pnp_coil_maps_stage_times': (C.c_int, [ctx_p, C.c_int, c_float_p]),
     'pnp_ssim': (C.c_int, [ctx_p, _vp, _vp, C.c_int, c_double_p]),
     'pnp_timer_start': (C.c_int, [ctx_p]),
     'pnp_timer_stop': (C.c_int, [ctx_p, c_float_p]),

@@ -227,11 +227,21 @@ def plan(coils, H, W, virtual_coils=None, noise_cov=None, calib=24):
     return Cin, int(Cout), Ks
 
 
+def plan_y(Cin, H, W, virtual_coils=None, noise_cov=None, calib=24):
+    """plan() for measurements without maps (coils='estimate': the maps are estimated from the mixed y).  -> (C_in, C_out)"""
+    Cout = Cin if virtual_coils is None else virtual_coils
+    check(Cin, Cout, 1, calib, H, W)
+    if noise_cov is not None and np.shape(noise_cov) != (Cin, Cin):
+        raise ValueError('noise_cov must be [C,C] = [%d,%d] (got shape %s)' % (Cin, Cin, tuple(np.shape(noise_cov))))
+    return int(Cin), int(Cout)
+
+
 def prepare(y, coils, mask, mask_id=None, coil_id=None, virtual_coils=None, noise_cov=None, calib=24, precision='f32', device=None,
             chunk_bytes=CHUNK_BYTES):
     """What the solvers do with virtual_coils= / noise_cov=: one matrix per coil set of the bank -- M_w from noise_cov, M_c from the Gram
     matrix of the calibration region (calib x calib) of the slices that use that set, M = M_c M_w -- applied once to y and to the maps.
     y [B,C,H,W] (host array or device tensor), coils [C,H,W] or [Ks,C,H,W], C <= 128; virtual_coils None: C_out = C (noise_cov alone).
+    coils None: only y is mixed, by ONE matrix from the Gram matrices of the whole batch (coil_id is ignored; coils' comes back None).
     -> (y' [B,C_out,H,W], coils' of coils' rank, info = {'M', 'eigvals', 'energy', 'C_in', 'C_out', 'whitened'}) in the precision's
     complex type; M [C_out,C] ([Ks,C_out,C] for a bank) complex128 is the matrix in double, as it came from the host routines."""
     if precision not in ('f32', 'f64'):
@@ -239,7 +249,12 @@ def prepare(y, coils, mask, mask_id=None, coil_id=None, virtual_coils=None, nois
     if virtual_coils is None and noise_cov is None:
         raise ValueError('nothing to do: give virtual_coils=, noise_cov= or both')
     H, W = (int(v) for v in np.shape(y)[-2:])
-    Cin, Cout, Ks = plan(coils, H, W, virtual_coils, noise_cov, calib)
+    if coils is None:                                                # the measurements alone (the maps are estimated from y' afterwards): one set
+        if np.ndim(y) != 4:
+            raise ValueError('y must be [B,C,H,W] (got shape %s)' % (tuple(np.shape(y)),))
+        Cin, Cout, Ks, coil_id = plan_y(np.shape(y)[1], H, W, virtual_coils, noise_cov, calib) + (1, None)
+    else:
+        Cin, Cout, Ks = plan(coils, H, W, virtual_coils, noise_cov, calib)
     if np.ndim(y) != 4 or np.shape(y)[1] != Cin:
         raise ValueError('y must be [B,%d,H,W] (got shape %s)' % (Cin, tuple(np.shape(y))))
     dt = np.complex128 if precision == 'f64' else np.complex64
@@ -248,9 +263,11 @@ def prepare(y, coils, mask, mask_id=None, coil_id=None, virtual_coils=None, nois
             raise ValueError("a device y must have the precision's complex type")
     elif np.asarray(y).dtype != dt:
         y = _Cast(np.asarray(y), dt)                                 # cast chunk by chunk, never the whole batch
-    bank = np.asarray(coils) if not _is_dev(coils) else coils
-    if len(np.shape(coils)) == 3:
-        bank = bank[None]
+    bank = None
+    if coils is not None:
+        bank = np.asarray(coils) if not _is_dev(coils) else coils
+        if len(np.shape(coils)) == 3:
+            bank = bank[None]
     Mw = None if noise_cov is None else whitening_matrix(noise_cov)
     if virtual_coils is not None:
         gram = calibration_gram(y, mask, mask_id, coil_id, Ks, calib, device, chunk_bytes)
@@ -259,13 +276,15 @@ def prepare(y, coils, mask, mask_id=None, coil_id=None, virtual_coils=None, nois
     else:
         M, eig, energy = np.stack([Mw] * Ks), None, [1.0] * Ks
     y2 = mix(y, M, coil_id if Ks > 1 or coil_id is not None else None, device, chunk_bytes)
-    if not _is_dev(bank) and bank.dtype != dt:
-        bank = bank.astype(dt)
-    S2 = mix(bank, M, np.arange(Ks, dtype=np.int32), device, chunk_bytes)
-    single = len(np.shape(coils)) == 3
+    S2 = None
+    if bank is not None:
+        if not _is_dev(bank) and bank.dtype != dt:
+            bank = bank.astype(dt)
+        S2 = mix(bank, M, np.arange(Ks, dtype=np.int32), device, chunk_bytes)
+    single = coils is None or len(np.shape(coils)) == 3
     info = dict(M=M[0] if single else M, eigvals=None if eig is None else (eig[0] if single else eig),
                 energy=energy[0] if single else energy, C_in=Cin, C_out=Cout, whitened=noise_cov is not None)
-    return y2, (S2[0] if single else S2), info
+    return y2, (None if S2 is None else S2[0] if single else S2), info
 
 
 class _Cast:

@@ -5,6 +5,7 @@
 #include "wavelet_plan.h"
 #include "coil_plan.h"
 #include "coilmix_plan.h"
+#include "coilmaps_plan.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -138,6 +139,11 @@ struct pnp_ctx {
     int wavelet = WV_NONE, wv_levels = 0;   // pnp_set_sparsity: the prox of the loops acts on the coefficients of this transform
     void* wv_coef = nullptr;          // [Bmax][H][W] real: the coefficients between the two prox launches (on first use)
     Coils coils;
+    void* cm_scratch = nullptr;       // pnp_coil_maps: low-resolution coil images, lambda, span maxima, missing points (coilmaps_scratch; on first use)
+    size_t cm_bytes = 0;
+    bool cm_timing = false;           // pnp_coil_maps_stage_times: every pass is bracketed by HIP events and synchronised
+    hipEvent_t cm_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float cm_ms[3] = {0.f, 0.f, 0.f}; // window, transform, eigenvectors + support: accumulated since the last read
 };
 
 // The context's buffers as the element type of its precision (R = float | double).
@@ -1251,10 +1257,11 @@ int pnp_ctx_destroy(pnp_ctx* c) {
     coils_free(c);
     anysize_destroy(c->any);
     void* ptrs[] = {c->y, c->work, c->z, c->w, c->x, c->mask_bank, c->mask_id, c->gt, c->acc, c->stage, c->ssim_part,
-                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc, c->wv_coef};
+                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc, c->wv_coef, c->cm_scratch};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
+    for (hipEvent_t e : c->cm_ev) if (e) (void)hipEventDestroy(e);
     delete c;
     return PNP_OK;
 }
@@ -1738,6 +1745,122 @@ int pnp_coilmix_compress(const double* gram, int C, int C_out, double* m_out, do
     std::vector<double> work(4 * (size_t)C * C);
     if (coilmix_compress(gram, C, C_out, m_out, eig_out, work.data())) return fail(PNP_E_ARG, "pnp_coilmix_compress: the Jacobi sweeps did not converge");
     return PNP_OK;
+}
+
+// ---- coil sensitivity maps from the calibration region: coilmaps_plan.h, kernels_coilmaps.hip.  On a context: its transforms, its stream ----
+
+int pnp_coilmaps_check(int C, int ncal, int radius, int power_iters, double thresh, int H, int W) {
+    switch (coilmaps_check(C, ncal, radius, power_iters, thresh, H, W)) {
+    case COILMAPS_OK:         return PNP_OK;
+    case COILMAPS_BAD_C:      return fail(PNP_E_ARG, "coil maps: C must be 1..%d (got %d)", COIL_MAX_C, C);
+    case COILMAPS_BAD_NCAL:   return fail(PNP_E_ARG, "coil maps: ncal must be %d..%d and <= min(H, W) (got %d at %d x %d)", COILMIX_NCAL_MIN,
+                                          COILMIX_NCAL_MAX, ncal, H, W);
+    case COILMAPS_BAD_RADIUS: return fail(PNP_E_ARG, "coil maps: radius must be 0..%d (got %d)", COILMAPS_MAX_RADIUS, radius);
+    case COILMAPS_BAD_ITERS:  return fail(PNP_E_ARG, "coil maps: power_iters must be 1..%d (got %d)", COILMAPS_MAX_ITERS, power_iters);
+    case COILMAPS_BAD_THRESH: return fail(PNP_E_ARG, "coil maps: thresh must be in [0, 1) (got %g)", thresh);
+    default:                  return fail(PNP_E_ARG, "coil maps: H, W must be in [128, 1024] (got %d x %d)", H, W);
+    }
+}
+
+extern "C++" {
+template <typename R>
+static int coil_maps_any(const char* who, pnp_ctx* c, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, R* maps, R* lambda, int B,
+                         int C, int ncal, int radius, int power_iters, double thresh) {
+    using Cx = typename CxOf<R>::type;
+    if (c->f64 != (sizeof(R) == 8))
+        return fail(PNP_E_STATE, sizeof(R) == 8 ? "%s: needs a context made by pnp_ctx_create_any_f64" : "%s: not available on an fp64 validation context", who);
+    if (!y || !mask_bank || !maps) return fail(PNP_E_ARG, "%s: null pointer", who);
+    if (B < 1 || B > 65535) return fail(PNP_E_ARG, "%s: B must be 1..65535 (got %d)", who, B);
+    if (int rc = pnp_coilmaps_check(C, ncal, radius, power_iters, thresh, c->H, c->W)) return rc;
+    if ((uintptr_t)y % sizeof(Cx) || (uintptr_t)maps % sizeof(Cx) || (lambda && (uintptr_t)lambda % sizeof(R)))
+        return fail(PNP_E_ARG, "%s: y and maps_out must be aligned to one complex value, lambda_out to one real", who);
+    const size_t N = c->N, bytes = (size_t)B * C * N * sizeof(Cx);
+    const char *y0 = (const char*)y, *m0 = (const char*)maps, *l0 = (const char*)lambda;
+    if (y0 < m0 + bytes && m0 < y0 + bytes) return fail(PNP_E_ARG, "%s: maps_out and y must not overlap", who);
+    if (lambda) {
+        const size_t lb = (size_t)B * N * sizeof(R);
+        if ((l0 < m0 + bytes && m0 < l0 + lb) || (l0 < y0 + bytes && y0 < l0 + lb)) return fail(PNP_E_ARG, "%s: lambda_out must not overlap y or maps_out", who);
+    }
+    const CoilmapsScratch lay = coilmaps_scratch(B, C, c->Bmax, N, c->f64);
+    if (c->cm_bytes < lay.bytes) {
+        HIPCHK(hipStreamSynchronize(c->stream));             // an earlier call on this stream may still read the old array
+        if (c->cm_scratch) (void)hipFree(c->cm_scratch);
+        c->cm_scratch = nullptr; c->cm_bytes = 0;
+        const hipError_t e = hipMalloc(&c->cm_scratch, lay.bytes);
+        if (e != hipSuccess) {
+            c->cm_scratch = nullptr;
+            return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the scratch array: %zu bytes asked for (B=%d, C=%d, Bmax=%d, %dx%d): %s",
+                        who, lay.bytes, B, C, c->Bmax, c->H, c->W, hipGetErrorString(e));
+        }
+        c->cm_bytes = lay.bytes;
+    }
+    char* base = (char*)c->cm_scratch;
+    Cx* img = (Cx*)(base + lay.img);
+    R* part = (R*)(base + lay.part);
+    int32_t* miss = (int32_t*)(base + lay.miss);
+    const int nb = coilmaps_pass_slices(B, C, c->Bmax);
+    const R tau2 = (R)(thresh * thresh);
+    for (int b0 = 0; b0 < B; b0 += nb) {
+        const int n = B - b0 < nb ? B - b0 : nb;             // slices of this pass: n C pseudo-slices
+        const R* yb = y + 2 * (size_t)b0 * C * N;
+        R* mb = maps + 2 * (size_t)b0 * C * N;
+        R* lam = lambda ? lambda + (size_t)b0 * N : (R*)(base + lay.lambda);
+        // the windowed region goes through maps_out: rows maps_out -> scratch, columns in place, the eigenvector kernel scratch -> maps_out
+        if (c->cm_timing) HIPCHK(hipEventRecord(c->cm_ev[0], c->stream));
+        HIPCHK(launch_calib_window<R>(c->stream, yb, mask_bank, mask_id ? mask_id + b0 : nullptr, mb, miss + b0, n, C, c->H, c->W, ncal));
+        if (c->cm_timing) HIPCHK(hipEventRecord(c->cm_ev[1], c->stream));
+        for (int s0 = 0; s0 < n * C; s0 += c->Bmax) {        // the transform in chunks of at most Bmax pseudo-slices
+            const int ns = n * C - s0 < c->Bmax ? n * C - s0 : c->Bmax;
+            RowArgsT<R> ra{};
+            ra.cin = (const Cx*)mb + (size_t)s0 * N; ra.cout = img + (size_t)s0 * N; ra.scale = R(1) / (R)N; ra.nrows = ns * c->H;
+            HIPCHK(rows<R>(c, IN_COMPLEX, true, EPI_COMPLEX, ra));
+            ColArgsT<R> ca{};
+            ca.in = img + (size_t)s0 * N; ca.out = img + (size_t)s0 * N; ca.B = ns;
+            HIPCHK(cols<R>(c, false, MID_NONE, true, ca));
+        }
+        if (c->cm_timing) HIPCHK(hipEventRecord(c->cm_ev[2], c->stream));
+        HIPCHK(launch_coil_eigmaps<R>(c->stream, (const R*)img, mb, lam, n, C, c->H, c->W, radius, power_iters));
+        HIPCHK(launch_coilmaps_support<R>(c->stream, lam, part, mb, n, C, N, tau2));
+        if (c->cm_timing) {
+            HIPCHK(hipEventRecord(c->cm_ev[3], c->stream));
+            HIPCHK(hipEventSynchronize(c->cm_ev[3]));
+            for (int k = 0; k < 3; ++k) {
+                float ms = 0.f;
+                HIPCHK(hipEventElapsedTime(&ms, c->cm_ev[k], c->cm_ev[k + 1]));
+                c->cm_ms[k] += ms;
+            }
+        }
+    }
+    std::vector<int32_t> host((size_t)B);
+    HIPCHK(hipMemcpyAsync(host.data(), miss, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int b = 0; b < B; ++b)
+        if (host[b] >= 0)
+            return fail(PNP_E_ARG, "%s: the mask of slice %d does not sample calibration point (%d, %d) of the %d x %d region: every point of it must be measured",
+                        who, b, host[b] / c->W, host[b] % c->W, ncal, ncal);
+    return PNP_OK;
+}
+}  // extern "C++"
+
+int pnp_coil_maps_stage_times(pnp_ctx* c, int enable, float* ms_out) {
+    CTX(c);
+    if (enable)
+        for (hipEvent_t& e : c->cm_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    if (ms_out) for (int k = 0; k < 3; ++k) ms_out[k] = c->cm_ms[k];
+    for (float& v : c->cm_ms) v = 0.f;
+    c->cm_timing = enable != 0;
+    return PNP_OK;
+}
+
+int pnp_coil_maps(pnp_ctx* c, const float* y, const uint8_t* mask_bank, const int32_t* mask_id, float* maps_out, float* lambda_out, int B, int C,
+                  int ncal, int radius, int power_iters, double thresh) {
+    CTX(c);
+    return coil_maps_any<float>(__func__, c, y, mask_bank, mask_id, maps_out, lambda_out, B, C, ncal, radius, power_iters, thresh);
+}
+int pnp_coil_maps_f64(pnp_ctx* c, const double* y, const uint8_t* mask_bank, const int32_t* mask_id, double* maps_out, double* lambda_out, int B,
+                      int C, int ncal, int radius, int power_iters, double thresh) {
+    CTX(c);
+    return coil_maps_any<double>(__func__, c, y, mask_bank, mask_id, maps_out, lambda_out, B, C, ncal, radius, power_iters, thresh);
 }
 
 }  // extern "C"

@@ -119,6 +119,15 @@ template <typename R> hipError_t launch_coil_mix(hipStream_t s, const R* in, con
 template <typename R> hipError_t launch_coil_gram(hipStream_t s, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, double* gram,
                                                   int B, int C, int H, int W, int ncal);
 
+// coil sensitivity maps from the calibration region (kernels_coilmaps.hip, coilmaps_plan.h): interleaved complex arrays in R.  The windowed
+// calibration region of B C pseudo-slices (+0 elsewhere) and the lowest offset of an unsampled calibration point per slice, miss [B] (-1:
+// none); the local dominant eigenvectors of the low-resolution coil images img [B][C][H][W] -> maps [B][C][H][W], lambda [B][H][W]; the
+// support: maps zeroed where lambda < tau2 * the slice's largest lambda (part: scratch of B * coilmaps_spans(N) values)
+template <typename R> hipError_t launch_calib_window(hipStream_t s, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, R* out,
+                                                     int32_t* miss, int B, int C, int H, int W, int ncal);
+template <typename R> hipError_t launch_coil_eigmaps(hipStream_t s, const R* img, R* maps, R* lambda, int B, int C, int H, int W, int r, int iters);
+template <typename R> hipError_t launch_coilmaps_support(hipStream_t s, const R* lambda, R* part, R* maps, int B, int C, size_t N, R tau2);
+
 // pointwise
 hipError_t launch_prox(hipStream_t s, bool cnc, const float* x, float* z, float* w, ProxParams p, size_t n);
 hipError_t launch_combine(hipStream_t s, const float* z, const float* x, const float* w, const float* sden,

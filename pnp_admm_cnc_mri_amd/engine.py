@@ -183,6 +183,22 @@ class Engine:
         _lib.check(self._L.pnp_cg_residual(self._ctx, rel.ctypes.data_as(_lib.c_double_p)))
         return rel
 
+    def coil_maps(self, y, mask_bank, mask_id, maps_out, lambda_out, B, Cn, calib=24, radius=2, power_iters=4, thresh=0.05):
+        """Sensitivity maps from the calibration region (pnp_coil_maps; coilmaps.estimate is the array-level entry): DEVICE tensors y
+        [B,C,H,W] and maps_out [B,C,H,W] of the engine's complex type, mask_bank [K,H,W] uint8, mask_id [B] int32 or None, lambda_out
+        [B,H,W] real or None.  Runs on the engine's stream with its transforms and synchronises at its end; the uploaded problem, the
+        state and the coils of the engine are not touched."""
+        fn = self._L.pnp_coil_maps_f64 if self.f64 else self._L.pnp_coil_maps
+        _lib.check(fn(self._ctx, _ptr(y), _ptr(mask_bank), _ptr(mask_id), _ptr(maps_out), _ptr(lambda_out), int(B), int(Cn), int(calib),
+                      int(radius), int(power_iters), float(thresh)))
+
+    def coil_maps_stage_times(self, enable=True):
+        """MEASUREMENT: the HIP-event times (ms) of coil_maps' three stages -- window, inverse transform, eigenvectors with support --
+        accumulated since the previous call of this method; enable: whether later calls are timed (pnp_coil_maps_stage_times)."""
+        ms = (C.c_float * 3)()
+        _lib.check(self._L.pnp_coil_maps_stage_times(self._ctx, 1 if enable else 0, ms))
+        return [float(v) for v in ms]
+
     def _coil_id(self, coil_id, B):
         if not self.C:
             if coil_id is not None:

@@ -52,6 +52,16 @@ bypass the file system through the extra keyword arguments
               mixing: 64 -> 8 virtual coils, 97.1 % of the calibration energy, prewhitened"); info['coil_mix'] = {M, eigvals, energy}.
               Under sharding.solve_sharded every rank forms its matrices from the slices of its own shard
 
+    coils='estimate', maps_radius=2, maps_power_iters=4, maps_thresh=0.05   (all five solvers) the maps are ESTIMATED from the calib x calib
+              calibration region of the measured y= (coilmaps.py; include/pnp_mri.h, "coil sensitivity maps from the calibration
+              region"): local dominant eigenvectors of low-resolution coil images over (2 maps_radius + 1)^2 patches by maps_power_iters
+              power steps, zero where the local eigenvalue is below maps_thresh^2 of the slice's largest.  One coil set per slice
+              (coil_id = arange(B); giving coil_id= is a ValueError); every point of the region must be sampled (ValueError naming the
+              first missing one); needs y=, images= may still be the ground truth.  With virtual_coils= / noise_cov= y is mixed first, by
+              ONE matrix from the Gram matrices of the whole batch, and the maps are estimated from the MIXED y: up to 128 physical
+              channels.  NOT in the reference scripts.  One extra log line; info['coil_maps'] = {calib, radius, power_iters, thresh,
+              support: the share of pixels kept per slice}
+
 The PnP entry points (PNP_ADMM_L1_D, PNP_ADMM_CNC_D, PNP_ADMM_CNC_DnCNN) live in solvers_pnp.py.
 """
 import logging
@@ -60,7 +70,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import coilmix, imageio
+from . import coilmaps, coilmix, imageio
 from ._lib import PnpError
 from .engine import Engine, check_coils, check_sparsity
 
@@ -119,7 +129,8 @@ class _Job:
 
     def __init__(self, mask, noises, tag, suffix, images=None, y=None, mask_id=None, testsets='testsets',
                  testset_name='Set1', results='results', save_E=None, device=None, log=None, ssim=None,
-                 psnr_fmt='{:.4f}', precision='f32', coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24):
+                 psnr_fmt='{:.4f}', precision='f32', coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
+                 maps_radius=2, maps_power_iters=4, maps_thresh=0.05):
         # psnr_fmt: S1:150 and S3:320 print the per-image PSNR with two decimals, S4:155 / S6:332 / S6:548 with four
         self.tag, self.suffix, self.psnr_fmt = tag, suffix, psnr_fmt
         if precision not in ('f32', 'f64'):
@@ -133,7 +144,24 @@ class _Job:
         self.coil_id = None if coil_id is None else np.asarray(coil_id, np.int32)
         self.virtual_coils, self.noise_cov, self.calib, self.coil_mix = virtual_coils, noise_cov, calib, None
         self.mixing = virtual_coils is not None or noise_cov is not None
-        if self.mixing:
+        self.estimate, self.coil_maps = isinstance(coils, str), None
+        if self.estimate:                                            # every check before an engine is opened
+            if coils != 'estimate':
+                raise ValueError("coils must be an array of sensitivity maps or 'estimate' (got %r)" % (coils,))
+            if y is None:
+                raise ValueError("coils='estimate' estimates the maps from MEASURED data: it needs y= [B,C,H,W] (images= may still be given "
+                                 'as the ground truth)')
+            if coil_id is not None:
+                raise ValueError("coils='estimate' builds one coil set per slice (coil_id = arange(B)): coil_id= cannot be given with it")
+            ys = tuple(np.shape(y))
+            if len(ys) not in (3, 4) or ys[-2:] != (self.H, self.W):
+                raise ValueError('y must be [B,C,H,W] (or [C,H,W]) with H x W = %d x %d (got shape %s)' % (self.H, self.W, ys))
+            c_out = coilmix.plan_y(ys[-3], self.H, self.W, virtual_coils, noise_cov, calib)[1] if self.mixing else int(ys[-3])
+            coilmaps.check(c_out, calib, maps_radius, maps_power_iters, maps_thresh, self.H, self.W)
+            check_coils(np.broadcast_to(np.int8(0), (1, c_out, self.H, self.W)), self.H, self.W, cg_iters)
+            coilmaps.check_region(self.mask_bank, self.mask_id, calib)
+            self.maps_opts = dict(calib=int(calib), radius=int(maps_radius), power_iters=int(maps_power_iters), thresh=float(maps_thresh))
+        elif self.mixing:
             if coils is None or y is None:
                 raise ValueError('virtual_coils= / noise_cov= mix MEASURED data: they need coils= and y= (the device synthesis from images= '
                                  'is limited to 32 physical coils; images= may still be given as the ground truth)')
@@ -189,7 +217,12 @@ class _Job:
         """stream: HIP stream handle every engine call is ordered on (PnP: torch's current stream),
         set BEFORE the first kernel so upload / synthesis / init and the loop share one queue.
         transform / levels: Engine.set_sparsity (ADMM_L1 / ADMM_CNC)."""
-        if self.mixing and self.coil_mix is None:                    # y' = M y, S' = M S: from here on the virtual coils are the coils
+        if self.mixing and self.estimate and self.coil_mix is None:  # y' = M y with ONE matrix for the batch; the maps come from y' below
+            self.y, _, self.coil_mix = coilmix.prepare(self.y, None, self.mask_bank, self.mask_id, None, self.virtual_coils, self.noise_cov,
+                                                       self.calib, self.precision, self.device)
+            if self.log is not None:
+                self.log.info(coilmix.describe(self.coil_mix))
+        elif self.mixing and self.coil_mix is None:                  # y' = M y, S' = M S: from here on the virtual coils are the coils
             self.y, self.coils, self.coil_mix = coilmix.prepare(self.y, self.coils, self.mask_bank, self.mask_id, self.coil_id,
                                                                 self.virtual_coils, self.noise_cov, self.calib, self.precision, self.device)
             if self.log is not None:
@@ -202,6 +235,12 @@ class _Job:
                     transform, int(levels)))
         if stream is not None:
             eng.set_stream(stream)
+        if self.estimate and self.coil_maps is None:                 # one coil set per slice, from the slice's own calibration region
+            self.coils = coilmaps.estimate(self.y, self.mask_bank, self.mask_id, precision=self.precision, engine=eng, **self.maps_opts)
+            self.coil_id = np.arange(self.B, dtype=np.int32)
+            self.coil_maps = dict(self.maps_opts, support=coilmaps.support_share(self.coils))
+            if self.log is not None:
+                self.log.info(coilmaps.describe(self.coil_maps))
         if self.coils is not None:
             eng.set_coils(self.coils, self.cg_iters)
             if self.log is not None:
@@ -238,6 +277,8 @@ class _Job:
                 info['cg_residual'] = []
         if self.coil_mix is not None:
             info['coil_mix'] = {k: self.coil_mix[k] for k in ('M', 'eigvals', 'energy')}
+        if self.coil_maps is not None:
+            info['coil_maps'] = dict(self.coil_maps)
         if self.gt_u8 is not None:
             psnr, re = eng.metrics(x_dev, self.gt_u8)                                     # device reductions
             info['psnr'], info['re'] = list(map(float, psnr)), list(map(float, re))
@@ -292,7 +333,8 @@ def _device_x(eng, job):
 
 def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
             results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
-            transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24, **ADMM_L1_opts):
+            transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
+            maps_radius=2, maps_power_iters=4, maps_thresh=0.05, **ADMM_L1_opts):
     """ADMM with L1 prox on the MI355X engine.  Reference: "【1】ADMM_L1.py":29-169."""
     iter_num = ADMM_L1_opts.get('iter_num', 20)          # S1:35
     lambda1 = ADMM_L1_opts.get('lambda1', 0.04)          # S1:36
@@ -301,7 +343,7 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
     check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
     job = _Job(mask, noises, 'ADMM_L1', '_PDG L1', images, y, mask_id, testsets, testset_name, results, save_E, device,
                psnr_fmt='{:.2f}', precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters, virtual_coils=virtual_coils,
-               noise_cov=noise_cov, calib=calib)   # S1:150
+               noise_cov=noise_cov, calib=calib, maps_radius=maps_radius, maps_power_iters=maps_power_iters, maps_thresh=maps_thresh)   # S1:150
     with job.open_engine(transform=transform, levels=levels) as eng:
         # S1:111-126, all slices, on device
         trace = eng.admm_l1(iter_num, lambda1, reo, trace_every, tol, job.gt_u8) if traced else eng.admm_l1(iter_num, lambda1, reo)
@@ -315,7 +357,8 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
 
 def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
              results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
-             transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24, **ADMM_CNC_opts):
+             transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
+             maps_radius=2, maps_power_iters=4, maps_thresh=0.05, **ADMM_CNC_opts):
     """ADMM with the convex-non-convex z-step.  Reference: "【4】ADMM_CNC .py":31-174."""
     iter_num = ADMM_CNC_opts.get('iter_num', 4)          # S4:37
     alpha = ADMM_CNC_opts.get('alpha', 0.4)              # S4:38
@@ -326,7 +369,7 @@ def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets
     check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
     job = _Job(mask, noises, 'ADMM_CNC', '_ADMM CNC', images, y, mask_id, testsets, testset_name, results, save_E, device,
                precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters, virtual_coils=virtual_coils, noise_cov=noise_cov,
-               calib=calib)
+               calib=calib, maps_radius=maps_radius, maps_power_iters=maps_power_iters, maps_thresh=maps_thresh)
     with job.open_engine(transform=transform, levels=levels) as eng:
         # S4:115-132
         trace = (eng.admm_cnc(iter_num, alpha, lambda1, reo, b, trace_every, tol, job.gt_u8) if traced

@@ -110,6 +110,13 @@ def AH(eng, k, coils=None):
     return out
 
 
+def estimate_coil_maps(y, mask, mask_id=None, calib=24, radius=2, power_iters=4, thresh=0.05, **kw):
+    """Sensitivity maps [B,C,H,W] from the calibration region of measured k-space y [B,C,H,W], one set per slice, on device tensors or host
+    arrays (coilmaps.estimate; engine=: an Engine to run on).  No counterpart in the reference."""
+    from . import coilmaps
+    return coilmaps.estimate(y, mask, mask_id, calib, radius, power_iters, thresh, **kw)
+
+
 def coil_mix(k, M, coil_id=None):
     """out[b, j] = sum_c M[set(b), j, c] k[b, c]: prewhitening / coil compression of k-space [B,C,H,W] or of a bank of maps, on device
     tensors or host arrays (coilmix.mix; no engine: pnp_coil_mix is stateless).  No counterpart in the reference."""

@@ -299,6 +299,35 @@ int pnp_dwt2_inv(pnp_ctx* ctx, const float* in_dev, float* out_dev, int B);
 int pnp_dwt2_fwd_f64(pnp_ctx* ctx, const double* in_dev, double* out_dev, int B);
 int pnp_dwt2_inv_f64(pnp_ctx* ctx, const double* in_dev, double* out_dev, int B);
 
+/* ---- cycle spinning for the wavelet prox (added after ABI 13, additive) ---------------------------
+ * The decimated transform above is not translation invariant: its prox leaves artefacts tied to the 2^levels grid.  Cycle spinning
+ * applies the prox in a circularly shifted frame, another shift every prox step, optionally averaging a few shifts per step.
+ * Shift s = (sy, sx), 0 <= sy, sx < 2^levels:  (R_s v)[i, j] = v[(i + sy) mod H, (j + sx) mod W];  Psi_s = Psi R_s.  The shifted prox step
+ * is the step above in that frame: x, z, w rolled by (-sy, -sx), the step, z+ and w+ rolled back -- done by addressing, the kernels,
+ * their two launches and their bytes are those of the unshifted step, and s = (0, 0) gives its bits.
+ * Schedule: a table shifts[n][2] (sy, sx), 1 <= n <= 4096, a group size per_prox = K, 1 <= K <= 16, n a multiple of K, and a cursor p
+ * that counts prox steps: step p uses entries (p mod (n / K)) K + j, j = 0 .. K - 1, then p += 1.  pnp_init_state and pnp_set_spin
+ * set p = 0, pnp_set_state leaves it, pnp_set_spin_cursor sets it: a run cut into calls stays bit-equal to one call.
+ * Averaging (K > 1): with z_j the z+ of shift j, all K from the same (x, z, w):  acc = z_0;  acc = acc + z_j, j = 1 .. K - 2, in order;
+ * z+ = (acc + z_(K-1)) r,  r = 1 / K rounded once to the context's precision;  w+ = (x + w) - z+.  K = 1 multiplies nothing.  A prox
+ * is 2 K launches; z and w are written by the last one only.  The first K > 1 allocates one more array of Bmax slices.
+ * The rules are decided by pnp_spin_check -- no context, no device; PNP_E_ARG with a message that names the rule: "n", "per_prox",
+ * "multiple", "range" -- which pnp_set_spin calls with the context's levels before any device work. */
+int pnp_spin_check(int levels, const int32_t* shifts, int n, int per_prox);
+/* n = 0 clears the setting (shifts_host is not read).  No wavelet set: PNP_E_STATE.  pnp_set_sparsity clears the setting (the valid
+ * range depends on levels).  With a setting, every wavelet prox of the context follows and advances the schedule: the loops, their
+ * _traced forms, the loops of a coil context, and pnp_prox_l1_dual / pnp_prox_cnc_dual.  pnp_get_plan / pnp_kernels_per_iteration
+ * report 3 + 2 K launches per iteration, 5 + 5 cg_iters + 2 K on a coil context. */
+int pnp_set_spin(pnp_ctx* ctx, const int32_t* shifts_host, int n, int per_prox);
+/* n = 0, per_prox = 1 without a setting; any pointer may be null */
+int pnp_get_spin(pnp_ctx* ctx, int* n, int* per_prox, int* cursor);
+/* cursor >= 0; PNP_E_STATE without a setting */
+int pnp_set_spin_cursor(pnp_ctx* ctx, int cursor);
+/* Psi_s (inverse = 0) / Psi_s^T (inverse != 0) alone, as pnp_dwt2_fwd / _inv (in_dev may equal out_dev); (sy, sx) outside
+ * [0, 2^levels) is PNP_E_ARG.  pnp_dwt2_fwd / _inv stay unshifted whatever the spin setting. */
+int pnp_dwt2_shifted(pnp_ctx* ctx, const float* in_dev, float* out_dev, int B, int inverse, int sy, int sx);
+int pnp_dwt2_shifted_f64(pnp_ctx* ctx, const double* in_dev, double* out_dev, int B, int inverse, int sy, int sx);
+
 /* ---- multi-coil (SENSE) data consistency (added after ABI 13, additive) --------------------------
  * Measurements from C receive coils with complex sensitivity maps S_c:  y_c = m . fft2(S_c . x),  c = 0 .. C - 1.  NOT in the reference
  * scripts, whose forward model is one coil of uniform sensitivity; without coils -- the default -- every entry point is bit for bit what

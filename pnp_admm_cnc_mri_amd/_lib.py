@@ -110,6 +110,13 @@ SIGNATURES = {
     'pnp_dwt2_inv': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
     'pnp_dwt2_fwd_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
     'pnp_dwt2_inv_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
+    # cycle spinning for the wavelet prox (added after ABI 13, additive)
+    'pnp_spin_check': (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int]),
+    'pnp_set_spin': (C.c_int, [ctx_p, C.POINTER(C.c_int32), C.c_int, C.c_int]),
+    'pnp_get_spin': (C.c_int, [ctx_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'pnp_set_spin_cursor': (C.c_int, [ctx_p, C.c_int]),
+    'pnp_dwt2_shifted': (C.c_int, [ctx_p, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'pnp_dwt2_shifted_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     # multi-coil (SENSE) data consistency (added after ABI 13, additive)
     'pnp_coils_check': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'pnp_set_coils': (C.c_int, [ctx_p, _vp, C.c_int, C.c_int, C.c_int]),

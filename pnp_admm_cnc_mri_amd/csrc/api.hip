@@ -7,6 +7,7 @@
 #include "coilmix_plan.h"
 #include "coilmaps_plan.h"
 
+#include <limits.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -138,6 +139,9 @@ struct pnp_ctx {
     Trace trace;
     int wavelet = WV_NONE, wv_levels = 0;   // pnp_set_sparsity: the prox of the loops acts on the coefficients of this transform
     void* wv_coef = nullptr;          // [Bmax][H][W] real: the coefficients between the two prox launches (on first use)
+    std::vector<int32_t> spin;        // pnp_set_spin: shifts[n][2] of the wavelet prox (empty: none) ...
+    int spin_k = 1, spin_p = 0;       // ... per_prox of them a step, and the cursor: prox steps since it was last set
+    void* wv_acc = nullptr;           // [Bmax][H][W] real: the sum of the shifts' z+ (by the first per_prox > 1)
     Coils coils;
     void* cm_scratch = nullptr;       // pnp_coil_maps: low-resolution coil images, lambda, span maxima, missing points (coilmaps_scratch; on first use)
     size_t cm_bytes = 0;
@@ -467,6 +471,7 @@ template <typename R> static int get_state(pnp_ctx* c, R* z, R* w, int on_device
 // ---- multi-coil (SENSE) data consistency: coil_plan.h, kernels_coils.hip, the coil row roles of kernels_anysize.hip ----
 
 static int wavelet_scratch(pnp_ctx* c);
+template <typename R> static int wavelet_prox_step(pnp_ctx* c, bool cnc, const R* x, R* z, R* w, const ProxParamsT<R>& pp);
 
 #define NO_COILS(c, mc) do { if ((c)->coils.C > 0) return fail(PNP_E_STATE, "%s: the context has coils (pnp_set_coils): use %s", __func__, mc); } while (0)
 #define NEED_COILS(c) do { if ((c)->coils.C == 0) return fail(PNP_E_STATE, "%s: the context has no coils (pnp_set_coils); without coils use the call without _mc", __func__); } while (0)
@@ -554,7 +559,7 @@ static int run_coil_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& 
     for (int i = 0; i < iters; ++i) {
         if (int rc = coil_xstep<R>(c, b.z, b.w, b.x, reo)) return rc;
         if (c->wavelet != WV_NONE) {
-            HIPCHK(launch_wavelet_prox<R>(c->stream, c->wavelet, c->wv_levels, cnc, b.x, b.z, b.w, (R*)c->wv_coef, pp, c->B, c->H, c->W));
+            if (int rc = wavelet_prox_step<R>(c, cnc, b.x, b.z, b.w, pp)) return rc;
         } else if constexpr (std::is_same_v<R, double>) {
             HIPCHK(launch_prox_f64(c->stream, cnc, b.x, b.z, b.w, pp, n));
         } else {
@@ -768,9 +773,27 @@ static int wavelet_scratch(pnp_ctx* c) {
     return PNP_OK;
 }
 
-// Psi / Psi^T on caller pointers.  A tile reads its neighbours' halo, so an in-place call goes through the context's scratch.
-template <typename R> static int dwt2_any(pnp_ctx* c, const char* who, const R* in, R* out, int B, bool inv) {
+// One wavelet prox of the context, wherever one runs (the loops, the coil loop, pnp_prox_*_dual): with a spin setting (pnp_set_spin) in
+// the frames of the schedule's current group of shifts, and the cursor moves on; without one the unshifted step.
+static int spin_per_prox(const pnp_ctx* c) { return c->spin.empty() ? 1 : c->spin_k; }
+template <typename R> static int wavelet_prox_step(pnp_ctx* c, bool cnc, const R* x, R* z, R* w, const ProxParamsT<R>& pp) {
+    if (c->spin.empty()) {
+        HIPCHK(launch_wavelet_prox<R>(c->stream, c->wavelet, c->wv_levels, cnc, x, z, w, (R*)c->wv_coef, pp, c->B, c->H, c->W));
+        return PNP_OK;
+    }
+    const int n = (int)(c->spin.size() / 2), K = c->spin_k, groups = n / K;
+    const int32_t* s = c->spin.data() + 2 * (size_t)wv_spin_first(c->spin_p, n, K);
+    HIPCHK(launch_wavelet_prox<R>(c->stream, c->wavelet, c->wv_levels, cnc, x, z, w, (R*)c->wv_coef, pp, c->B, c->H, c->W, s, K, (R*)c->wv_acc));
+    c->spin_p = c->spin_p == INT_MAX ? INT_MAX % groups + 1 : c->spin_p + 1;          // the same entries, within int
+    return PNP_OK;
+}
+
+// Psi / Psi^T on caller pointers, in the frame shifted by (sy, sx).  A tile reads its neighbours' halo, so an in-place call goes through
+// the context's scratch.
+template <typename R> static int dwt2_any(pnp_ctx* c, const char* who, const R* in, R* out, int B, bool inv, int sy = 0, int sx = 0) {
     if (c->wavelet == WV_NONE) return fail(PNP_E_STATE, "%s: no wavelet set (pnp_set_sparsity)", who);
+    if (!wv_shift_ok(c->wv_levels, sy, sx))
+        return fail(PNP_E_ARG, "%s: shift (%d, %d) out of range [0, %d) (2^levels)", who, sy, sx, 1 << c->wv_levels);
     if (!in || !out) return fail(PNP_E_ARG, "%s: null pointer", who);
     if (B < 1 || B > c->Bmax) return fail(PNP_E_ARG, "%s: B=%d out of range [1,%d]", who, B, c->Bmax);
     const size_t bytes = (size_t)B * c->N * sizeof(R);
@@ -778,7 +801,7 @@ template <typename R> static int dwt2_any(pnp_ctx* c, const char* who, const R* 
     if (pi != po && pi < po + bytes && po < pi + bytes) return fail(PNP_E_ARG, "%s: in and out overlap without being equal", who);
     R* dst = out;
     if (pi == po) { if (int rc = wavelet_scratch(c)) return rc; dst = (R*)c->wv_coef; }
-    HIPCHK(launch_dwt2<R>(c->stream, c->wavelet, c->wv_levels, inv, in, dst, B, c->H, c->W));
+    HIPCHK(launch_dwt2<R>(c->stream, c->wavelet, c->wv_levels, inv, in, dst, B, c->H, c->W, sy, sx));
     if (dst != out) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToDevice, c->stream));
     return PNP_OK;
 }
@@ -793,7 +816,7 @@ static int run_wavelet_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R
     const R cdc = dc_coeff<R>(reo);
     for (int i = 0; i < iters; ++i) {
         if (int rc = dc_any<R>(c, b.z, b.w, b.x, cdc)) return rc;
-        HIPCHK(launch_wavelet_prox<R>(c->stream, c->wavelet, c->wv_levels, cnc, b.x, b.z, b.w, (R*)c->wv_coef, pp, c->B, c->H, c->W));
+        if (int rc = wavelet_prox_step<R>(c, cnc, b.x, b.z, b.w, pp)) return rc;
     }
     c->have_x = true;
     return PNP_OK;
@@ -1046,8 +1069,10 @@ static int residuals_any(pnp_ctx* c, const char* who, const R* x, const R* z, co
 
 // What the next loop call runs (pnp_get_plan): the plans the engines themselves run by (loop_schedule.h).
 static LoopPlan loop_plan(const pnp_ctx* c) {
-    if (c->coils.C > 0) return {1, c->B, coil_iteration_launches(c->coils.cg_iters, c->wavelet != WV_NONE), false, 1, c->B};
-    if (c->wavelet != WV_NONE) return {1, c->B, 5, false, 1, c->B};   // the data-consistency step (three launches on every path) + two prox launches
+    // a wavelet prox is two launches per shift of its group (pnp_set_spin; one without)
+    const int spin_extra = c->wavelet != WV_NONE ? 2 * (spin_per_prox(c) - 1) : 0;
+    if (c->coils.C > 0) return {1, c->B, coil_iteration_launches(c->coils.cg_iters, c->wavelet != WV_NONE) + spin_extra, false, 1, c->B};
+    if (c->wavelet != WV_NONE) return {1, c->B, 5 + spin_extra, false, 1, c->B};   // the data-consistency step (three launches on every path) + the prox launches
     switch (loop_path(c)) {
     case Path::generic: break;
     case Path::slice:   return plan_slice(c->B, c->sched);         // one launch per RUN: the iterations are a loop inside it
@@ -1257,7 +1282,7 @@ int pnp_ctx_destroy(pnp_ctx* c) {
     coils_free(c);
     anysize_destroy(c->any);
     void* ptrs[] = {c->y, c->work, c->z, c->w, c->x, c->mask_bank, c->mask_id, c->gt, c->acc, c->stage, c->ssim_part,
-                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc, c->wv_coef, c->cm_scratch};
+                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc, c->wv_coef, c->wv_acc, c->cm_scratch};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1302,7 +1327,11 @@ int pnp_synthesize_problem_f64(pnp_ctx* c, const float* img, const double* noise
 int pnp_download_y(pnp_ctx* c, float* y, int on_device) { CTX(c); F32_ONLY(c); NEED_PROBLEM(c); return download_y(c, __func__, y, on_device); }
 int pnp_download_y_f64(pnp_ctx* c, double* y, int on_device) { CTX(c); F64_ONLY(c); NEED_PROBLEM(c); return download_y(c, __func__, y, on_device); }
 
-int pnp_init_state(pnp_ctx* c) { CTX(c); NEED_PROBLEM(c); return c->f64 ? init_state<double>(c) : init_state<float>(c); }
+int pnp_init_state(pnp_ctx* c) {
+    CTX(c); NEED_PROBLEM(c);
+    c->spin_p = 0;                    // a fresh run starts the spin schedule over (pnp_set_state does not)
+    return c->f64 ? init_state<double>(c) : init_state<float>(c);
+}
 
 int pnp_set_state(pnp_ctx* c, const float* z, const float* w, int on_device) { CTX(c); F32_ONLY(c); NEED_PROBLEM(c); return set_state(c, __func__, z, w, on_device); }
 int pnp_set_state_f64(pnp_ctx* c, const double* z, const double* w, int on_device) { CTX(c); F64_ONLY(c); NEED_PROBLEM(c); return set_state(c, __func__, z, w, on_device); }
@@ -1398,8 +1427,7 @@ static int wavelet_prox_dual(pnp_ctx* c, const char* who, bool cnc, const float*
     if ((px < pz + bytes && pz < px + bytes) || (px < pw + bytes && pw < px + bytes) || (pz < pw + bytes && pw < pz + bytes))
         return fail(PNP_E_ARG, "%s: x, z and w must not overlap with a wavelet set (tiles read their neighbours' halo)", who);
     if (int rc = wavelet_scratch(c)) return rc;
-    HIPCHK(launch_wavelet_prox<float>(c->stream, c->wavelet, c->wv_levels, cnc, x, z, w, (float*)c->wv_coef, p, c->B, c->H, c->W));
-    return PNP_OK;
+    return wavelet_prox_step<float>(c, cnc, x, z, w, p);
 }
 
 int pnp_prox_l1_dual(pnp_ctx* c, const float* x, float* z, float* w, double thr) {
@@ -1595,6 +1623,7 @@ int pnp_set_sparsity(pnp_ctx* c, int wavelet, int levels) {
     if (wavelet != PNP_WAVELET_NONE) if (int rc = wavelet_scratch(c)) return rc;
     c->wavelet = wavelet;
     c->wv_levels = wavelet == PNP_WAVELET_NONE ? 0 : levels;
+    c->spin.clear(); c->spin_k = 1; c->spin_p = 0;                                    // the valid shifts depend on levels
     return PNP_OK;
 }
 
@@ -1609,6 +1638,59 @@ int pnp_dwt2_fwd(pnp_ctx* c, const float* in, float* out, int B) { CTX(c); F32_O
 int pnp_dwt2_inv(pnp_ctx* c, const float* in, float* out, int B) { CTX(c); F32_ONLY(c); return dwt2_any<float>(c, __func__, in, out, B, true); }
 int pnp_dwt2_fwd_f64(pnp_ctx* c, const double* in, double* out, int B) { CTX(c); F64_ONLY(c); return dwt2_any<double>(c, __func__, in, out, B, false); }
 int pnp_dwt2_inv_f64(pnp_ctx* c, const double* in, double* out, int B) { CTX(c); F64_ONLY(c); return dwt2_any<double>(c, __func__, in, out, B, true); }
+
+// ---- cycle spinning for the wavelet prox (wavelet_plan.h, wv_spin_check) ----
+
+int pnp_spin_check(int levels, const int32_t* shifts, int n, int per_prox) {
+    switch (wv_spin_check(levels, shifts, n, per_prox)) {
+    case WV_SPIN_OK:           return PNP_OK;
+    case WV_SPIN_BAD_LEVELS:   return fail(PNP_E_ARG, "spin: levels must be 1..%d (got %d)", WV_MAX_LEVELS, levels);
+    case WV_SPIN_BAD_N:        return fail(PNP_E_ARG, "spin: n must be 1..%d with a table of n shifts (got %d%s)", WV_SPIN_MAX_N, n, shifts ? "" : ", null table");
+    case WV_SPIN_BAD_K:        return fail(PNP_E_ARG, "spin: per_prox must be 1..%d (got %d)", WV_SPIN_MAX_K, per_prox);
+    case WV_SPIN_BAD_MULTIPLE: return fail(PNP_E_ARG, "spin: the table length must be a multiple of the group size (got %d shifts, groups of %d)", n, per_prox);
+    default:
+        for (int i = 0; i < n; ++i)
+            if (!wv_shift_ok(levels, shifts[2 * i], shifts[2 * i + 1]))
+                return fail(PNP_E_ARG, "spin: shift %d = (%d, %d) out of range [0, %d) (2^levels)", i, shifts[2 * i], shifts[2 * i + 1], 1 << levels);
+        return fail(PNP_E_ARG, "spin: shift out of range");
+    }
+}
+
+int pnp_set_spin(pnp_ctx* c, const int32_t* shifts, int n, int per_prox) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
+    if (n == 0) { c->spin.clear(); c->spin_k = 1; c->spin_p = 0; return PNP_OK; }
+    if (c->wavelet == WV_NONE) return fail(PNP_E_STATE, "%s: no wavelet set (pnp_set_sparsity)", __func__);
+    if (int rc = pnp_spin_check(c->wv_levels, shifts, n, per_prox)) return rc;          // before any device work
+    CTX(c);
+    if (per_prox > 1 && !c->wv_acc) HIPCHK(hipMalloc(&c->wv_acc, (size_t)c->Bmax * c->N * (c->f64 ? sizeof(double) : sizeof(float))));
+    c->spin.assign(shifts, shifts + 2 * (size_t)n);
+    c->spin_k = per_prox;
+    c->spin_p = 0;
+    return PNP_OK;
+}
+
+int pnp_get_spin(pnp_ctx* c, int* n, int* per_prox, int* cursor) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
+    if (n) *n = (int)(c->spin.size() / 2);
+    if (per_prox) *per_prox = spin_per_prox(c);
+    if (cursor) *cursor = c->spin_p;
+    return PNP_OK;
+}
+
+int pnp_set_spin_cursor(pnp_ctx* c, int cursor) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
+    if (c->spin.empty()) return fail(PNP_E_STATE, "%s: no spin setting (pnp_set_spin)", __func__);
+    if (cursor < 0) return fail(PNP_E_ARG, "%s: cursor must be >= 0 (got %d)", __func__, cursor);
+    c->spin_p = cursor;
+    return PNP_OK;
+}
+
+int pnp_dwt2_shifted(pnp_ctx* c, const float* in, float* out, int B, int inverse, int sy, int sx) {
+    CTX(c); F32_ONLY(c); return dwt2_any<float>(c, __func__, in, out, B, inverse != 0, sy, sx);
+}
+int pnp_dwt2_shifted_f64(pnp_ctx* c, const double* in, double* out, int B, int inverse, int sy, int sx) {
+    CTX(c); F64_ONLY(c); return dwt2_any<double>(c, __func__, in, out, B, inverse != 0, sy, sx);
+}
 
 // ---- multi-coil (SENSE) data consistency ----
 

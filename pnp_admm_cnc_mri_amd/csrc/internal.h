@@ -149,9 +149,14 @@ hipError_t launch_residuals(hipStream_t s, const R* x, const R* z, const R* zp, 
 
 // wavelet-domain sparsity (kernels_wavelet.hip, wavelet_plan.h): Psi / Psi^T of B slices [H][W] (in != out: tiles read their neighbours'
 // halo), and the prox step z+ = Psi^T thresholded(Psi ...), w+ = (x + w) - z+ in place, through `coef`, scratch of B H W values
-template <typename R> hipError_t launch_dwt2(hipStream_t s, int wavelet, int levels, bool inv, const R* in, R* out, int B, int H, int W);
+// Cycle spinning: (sy, sx) in [0, 2^levels) is the frame's shift, by addressing alone.  The prox takes K >= 1 shifts [K][2] (host; null:
+// one unshifted step): K = 1 is the two launches in that frame; K > 1 runs them per shift, the syntheses summing z+ in `acc` (B H W values)
+// in the order of the table, and the last one writes z+ = (acc + z_(K-1)) (1 / K), w+ = (x + w) - z+ -- nothing else writes z or w.
+template <typename R> hipError_t launch_dwt2(hipStream_t s, int wavelet, int levels, bool inv, const R* in, R* out, int B, int H, int W,
+                                             int sy = 0, int sx = 0);
 template <typename R> hipError_t launch_wavelet_prox(hipStream_t s, int wavelet, int levels, bool cnc, const R* x, R* z, R* w, R* coef,
-                                                     const ProxParamsT<R>& p, int B, int H, int W);
+                                                     const ProxParamsT<R>& p, int B, int H, int W, const int* shifts = nullptr, int K = 1,
+                                                     R* acc = nullptr);
 
 // calibration (pnp_calibrate_stream): the slice-resident loop's access shape without its arithmetic, `passes` passes over `slices` slices of 256 KiB
 hipError_t launch_calibrate_stream(hipStream_t s, float* z, float* w, const float* y, int slices, int passes);

@@ -6,6 +6,9 @@
 //             through the same LDS, and the thread that wrote a coefficient of z combines it with that of x + w (same item -> same thread).
 //   k_wv_inv  synthesis + dual: reads the coefficient tile with its left / top halo, undoes all levels in LDS, writes z+ and
 //             w+ = (x + w) - z+ in place.
+// Cycle spinning (wavelet_plan.h): both kernels take the frame's shift (sy, sx) and apply it where they touch the image, nowhere else.  A
+// prox that averages K > 1 shifts is the two launches per shift; the synthesis of shift 0 stores its z+ into an accumulator, those of
+// shifts 1 .. K - 2 add theirs, the last one forms z+ = (acc + z_(K-1)) (1 / K) and w+ -- so z and w keep the old state for every analysis.
 // The work of every pass is wavelet_plan.h's item functions, one item per thread and step; tests/host/wavelet_emulation.cpp runs the
 // same functions on the host.  -ffp-contract=off (Makefile); products are chained by explicit fma.
 #include "internal.h"
@@ -26,11 +29,14 @@ struct WvArgs {
     R *z, *w;
     ProxParamsT<R> p;
     int H, W, L, tile, tiles_x, tiles_y;
+    int sy, sx;        // the frame's shift
+    R* acc;            // inv, averaging: the sum of the shifts' z+
+    R rk;              // inv, last of K > 1 shifts: 1 / K
 };
 
 template <typename R> __device__ __forceinline__ WvTile wv_tile_of_block(const WvArgs<R>& a) {
     const int per = a.tiles_x * a.tiles_y, b = blockIdx.x / per, rem = blockIdx.x - b * per, ty = rem / a.tiles_x, tx = rem - ty * a.tiles_x;
-    return WvTile{a.H, a.W, a.L, a.tile, ty * a.tile, tx * a.tile, (size_t)b * a.H * a.W};
+    return WvTile{a.H, a.W, a.L, a.tile, ty * a.tile, tx * a.tile, (size_t)b * a.H * a.W, a.sy, a.sx};
 }
 
 // what happens to a coefficient on its way out
@@ -93,7 +99,29 @@ template <typename R> struct EmitDual {             // z+ = v, w+ = (x + w) - z+
     }
 };
 
-template <typename R, bool DUAL, int T>
+// averaging K > 1 shifts: the first, the middle ones, the last
+template <typename R> struct EmitAccStore {
+    R* acc;
+    __device__ void operator()(size_t i, R v) const { acc[i] = v; }
+};
+template <typename R> struct EmitAccAdd {
+    R* acc;
+    __device__ void operator()(size_t i, R v) const { acc[i] = acc[i] + v; }
+};
+template <typename R> struct EmitAvgDual {          // z+ = (acc + v) (1 / K), w+ = (x + w) - z+
+    const R* x; const R* acc; R *z, *w; R rk;
+    __device__ void operator()(size_t i, R v) const {
+        const R u = x[i] + w[i];
+        const R zn = (acc[i] + v) * rk;
+        z[i] = zn;
+        w[i] = u - zn;
+    }
+};
+
+// what the synthesis does with a pixel
+enum { WV_OUT_IMAGE = 0, WV_OUT_DUAL = 1, WV_OUT_ACC_STORE = 2, WV_OUT_ACC_ADD = 3, WV_OUT_AVG_DUAL = 4 };
+
+template <typename R, int OUT, int T>
 __global__ __launch_bounds__(WV_THREADS) void k_wv_inv(const WvArgs<R> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char wv_smem[];
     const WvTile t = wv_tile_of_block(a);
@@ -103,8 +131,11 @@ __global__ __launch_bounds__(WV_THREADS) void k_wv_inv(const WvArgs<R> a) {
         for (int it = threadIdx.x, n = wv_inv_col_items(T, t, l); it < n; it += WV_THREADS) wv_inv_col_item<R, T>(it, l, t, a.in0, ll, colbuf);
         __syncthreads();
         for (int it = threadIdx.x, n = wv_inv_row_items(T, t, l); it < n; it += WV_THREADS) {
-            if constexpr (DUAL) wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitDual<R>{a.x, a.z, a.w});
-            else wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitImage<R>{a.out});
+            if constexpr (OUT == WV_OUT_IMAGE) wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitImage<R>{a.out});
+            if constexpr (OUT == WV_OUT_DUAL) wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitDual<R>{a.x, a.z, a.w});
+            if constexpr (OUT == WV_OUT_ACC_STORE) wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitAccStore<R>{a.acc});
+            if constexpr (OUT == WV_OUT_ACC_ADD) wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitAccAdd<R>{a.acc});
+            if constexpr (OUT == WV_OUT_AVG_DUAL) wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitAvgDual<R>{a.x, a.acc, a.z, a.w, a.rk});
         }
         __syncthreads();
     }
@@ -128,9 +159,9 @@ template <typename R, int PROX, int T> hipError_t wv_fwd_t(hipStream_t s, const 
     static bool attr_done[64] = {};
     return wv_launch(k_wv_fwd<R, PROX, T>, s, B * a.tiles_x * a.tiles_y, wv_fwd_lds_elems(T, a.L, a.tile) * sizeof(R), attr_done, a);
 }
-template <typename R, bool DUAL, int T> hipError_t wv_inv_t(hipStream_t s, const WvArgs<R>& a, int B) {
+template <typename R, int OUT, int T> hipError_t wv_inv_t(hipStream_t s, const WvArgs<R>& a, int B) {
     static bool attr_done[64] = {};
-    return wv_launch(k_wv_inv<R, DUAL, T>, s, B * a.tiles_x * a.tiles_y, wv_inv_lds_elems(T, a.tile) * sizeof(R), attr_done, a);
+    return wv_launch(k_wv_inv<R, OUT, T>, s, B * a.tiles_x * a.tiles_y, wv_inv_lds_elems(T, a.tile) * sizeof(R), attr_done, a);
 }
 
 template <typename R> WvArgs<R> wv_args(int wavelet, int levels, int H, int W) {
@@ -149,11 +180,11 @@ template <typename R, int PROX> hipError_t wv_fwd_p(hipStream_t s, int wavelet, 
     }
     return hipErrorInvalidValue;
 }
-template <typename R, bool DUAL> hipError_t wv_inv_p(hipStream_t s, int wavelet, const WvArgs<R>& a, int B) {
+template <typename R, int OUT> hipError_t wv_inv_p(hipStream_t s, int wavelet, const WvArgs<R>& a, int B) {
     switch (wavelet) {
-    case WV_HAAR: return wv_inv_t<R, DUAL, 2>(s, a, B);
-    case WV_DB2:  return wv_inv_t<R, DUAL, 4>(s, a, B);
-    case WV_DB4:  return wv_inv_t<R, DUAL, 8>(s, a, B);
+    case WV_HAAR: return wv_inv_t<R, OUT, 2>(s, a, B);
+    case WV_DB2:  return wv_inv_t<R, OUT, 4>(s, a, B);
+    case WV_DB4:  return wv_inv_t<R, OUT, 8>(s, a, B);
     }
     return hipErrorInvalidValue;
 }
@@ -161,28 +192,38 @@ template <typename R, bool DUAL> hipError_t wv_inv_p(hipStream_t s, int wavelet,
 }  // namespace
 
 template <typename R>
-hipError_t launch_dwt2(hipStream_t s, int wavelet, int levels, bool inv, const R* in, R* out, int B, int H, int W) {
-    if (wv_check(wavelet, levels, H, W) != WV_OK || B < 1) return hipErrorInvalidValue;
+hipError_t launch_dwt2(hipStream_t s, int wavelet, int levels, bool inv, const R* in, R* out, int B, int H, int W, int sy, int sx) {
+    if (wv_check(wavelet, levels, H, W) != WV_OK || B < 1 || !wv_shift_ok(levels, sy, sx)) return hipErrorInvalidValue;
     WvArgs<R> a = wv_args<R>(wavelet, levels, H, W);
-    a.in0 = in; a.out = out;
-    return inv ? wv_inv_p<R, false>(s, wavelet, a, B) : wv_fwd_p<R, 0>(s, wavelet, a, B);
+    a.in0 = in; a.out = out; a.sy = sy; a.sx = sx;
+    return inv ? wv_inv_p<R, WV_OUT_IMAGE>(s, wavelet, a, B) : wv_fwd_p<R, 0>(s, wavelet, a, B);
 }
 
 template <typename R>
 hipError_t launch_wavelet_prox(hipStream_t s, int wavelet, int levels, bool cnc, const R* x, R* z, R* w, R* coef, const ProxParamsT<R>& p,
-                               int B, int H, int W) {
-    if (wv_check(wavelet, levels, H, W) != WV_OK || B < 1) return hipErrorInvalidValue;
-    WvArgs<R> a = wv_args<R>(wavelet, levels, H, W);
-    a.in0 = x; a.in1 = w; a.zin = z; a.out = coef; a.p = p;
-    hipError_t e = cnc ? wv_fwd_p<R, 2>(s, wavelet, a, B) : wv_fwd_p<R, 1>(s, wavelet, a, B);
-    if (e != hipSuccess) return e;
-    a.in0 = coef; a.in1 = nullptr; a.zin = nullptr; a.out = nullptr; a.x = x; a.z = z; a.w = w;
-    return wv_inv_p<R, true>(s, wavelet, a, B);
+                               int B, int H, int W, const int* shifts, int K, R* acc) {
+    if (wv_check(wavelet, levels, H, W) != WV_OK || B < 1 || K < 1 || K > WV_SPIN_MAX_K || (K > 1 && (!shifts || !acc))) return hipErrorInvalidValue;
+    for (int j = 0; shifts && j < K; ++j) if (!wv_shift_ok(levels, shifts[2 * j], shifts[2 * j + 1])) return hipErrorInvalidValue;
+    for (int j = 0; j < K; ++j) {
+        WvArgs<R> a = wv_args<R>(wavelet, levels, H, W);
+        if (shifts) { a.sy = shifts[2 * j]; a.sx = shifts[2 * j + 1]; }
+        a.in0 = x; a.in1 = w; a.zin = z; a.out = coef; a.p = p;
+        hipError_t e = cnc ? wv_fwd_p<R, 2>(s, wavelet, a, B) : wv_fwd_p<R, 1>(s, wavelet, a, B);
+        if (e != hipSuccess) return e;
+        a.in0 = coef; a.in1 = nullptr; a.zin = nullptr; a.out = nullptr; a.x = x; a.z = z; a.w = w; a.acc = acc; a.rk = (R)(1.0 / K);
+        if (K == 1) e = wv_inv_p<R, WV_OUT_DUAL>(s, wavelet, a, B);
+        else if (j == K - 1) e = wv_inv_p<R, WV_OUT_AVG_DUAL>(s, wavelet, a, B);
+        else e = j == 0 ? wv_inv_p<R, WV_OUT_ACC_STORE>(s, wavelet, a, B) : wv_inv_p<R, WV_OUT_ACC_ADD>(s, wavelet, a, B);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
-template hipError_t launch_dwt2<float>(hipStream_t, int, int, bool, const float*, float*, int, int, int);
-template hipError_t launch_dwt2<double>(hipStream_t, int, int, bool, const double*, double*, int, int, int);
-template hipError_t launch_wavelet_prox<float>(hipStream_t, int, int, bool, const float*, float*, float*, float*, const ProxParamsT<float>&, int, int, int);
-template hipError_t launch_wavelet_prox<double>(hipStream_t, int, int, bool, const double*, double*, double*, double*, const ProxParamsT<double>&, int, int, int);
+template hipError_t launch_dwt2<float>(hipStream_t, int, int, bool, const float*, float*, int, int, int, int, int);
+template hipError_t launch_dwt2<double>(hipStream_t, int, int, bool, const double*, double*, int, int, int, int, int);
+template hipError_t launch_wavelet_prox<float>(hipStream_t, int, int, bool, const float*, float*, float*, float*, const ProxParamsT<float>&, int, int, int,
+                                               const int*, int, float*);
+template hipError_t launch_wavelet_prox<double>(hipStream_t, int, int, bool, const double*, double*, double*, double*, const ProxParamsT<double>&, int, int,
+                                                int, const int*, int, double*);
 
 }  // namespace pnp

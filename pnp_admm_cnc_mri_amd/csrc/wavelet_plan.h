@@ -19,6 +19,11 @@
 // Synthesis (wv_inv_*): the same tile of pixels; output m of a level needs the coefficients k = (m - n) / 2, n = m mod 2, .. < T, so a
 // left / top halo: level l is rebuilt on wv_inv_ext(l) = (tile >> l) + e_l samples per axis, e_0 = 0, e_(l+1) = ceil((e_l + T - 2) / 2)
 // (< T - 2).  colbuf [ext(l)][2 ext(l+1)] holds a column pass' result, ll [ext(l)]^2 the rebuilt LL band of level l >= 1.
+//
+// Cycle spinning (WvTile::sy, sx; wv_spin_check): the transform of the circularly shifted frame, Psi_s = Psi R_s with
+// (R_s v)[i, j] = v[(i + sy) mod H, (j + sx) mod W], 0 <= sy, sx < 2^L.  Only the two places that touch the image know of it -- level 0 of
+// the analysis row pass reads pixel (i + sy, j + sx), level 0 of the synthesis row pass emits to it; the coefficients stay in the Mallat
+// layout of the shifted frame, and tiles, items, LDS sizes and arithmetic are those of s = (0, 0).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -91,6 +96,8 @@ WV_HD inline int wv_wrap(int i, int M) {
     while (i < 0) i += M;
     return i;
 }
+// i modulo M for 0 <= i < 2 M: a pixel of the image moved by a shift (< 2^L <= M)
+WV_HD inline int wv_wrap_once(int i, int M) { return i >= M ? i - M : i; }
 // band test: is (y, x) of the Mallat layout a detail coefficient, i.e. outside the final LL band
 WV_HD constexpr bool wv_is_detail(int y, int x, int H, int W, int L) { return !(y < (H >> L) && x < (W >> L)); }
 
@@ -102,7 +109,23 @@ struct WvTile {
     int H, W, L, tile;
     int ty0, tx0;           // origin of the tile in pixels (multiples of tile)
     size_t base;            // offset of the slice: b * H * W
+    int sy = 0, sx = 0;     // cycle spinning: the frame's shift, pixel (i, j) of the frame is pixel (i + sy, j + sx) of the image (periodic)
 };
+
+// Argument check of pnp_set_spin / pnp_spin_check: a table shifts[n][2] used per_prox entries per prox step; 0 = valid, else which rule fails
+constexpr int WV_SPIN_MAX_N = 4096, WV_SPIN_MAX_K = 16;
+enum { WV_SPIN_OK = 0, WV_SPIN_BAD_LEVELS = 1, WV_SPIN_BAD_N = 2, WV_SPIN_BAD_K = 3, WV_SPIN_BAD_MULTIPLE = 4, WV_SPIN_BAD_RANGE = 5 };
+WV_HD constexpr bool wv_shift_ok(int levels, int sy, int sx) { return sy >= 0 && sx >= 0 && sy < (1 << levels) && sx < (1 << levels); }
+WV_HD inline int wv_spin_check(int levels, const int* shifts, int n, int per_prox) {
+    if (levels < 1 || levels > WV_MAX_LEVELS) return WV_SPIN_BAD_LEVELS;
+    if (n < 1 || n > WV_SPIN_MAX_N || !shifts) return WV_SPIN_BAD_N;
+    if (per_prox < 1 || per_prox > WV_SPIN_MAX_K) return WV_SPIN_BAD_K;
+    if (n % per_prox) return WV_SPIN_BAD_MULTIPLE;
+    for (int i = 0; i < n; ++i) if (!wv_shift_ok(levels, shifts[2 * i], shifts[2 * i + 1])) return WV_SPIN_BAD_RANGE;
+    return WV_SPIN_OK;
+}
+// the table entries of prox step `cursor`: first index of its group of per_prox entries
+WV_HD constexpr int wv_spin_first(int cursor, int n, int per_prox) { return (cursor % (n / per_prox)) * per_prox; }
 
 // ---- analysis: work items -------------------------------------------------------------------------------------------------------
 // Items of the row pass / the column pass of level l
@@ -110,7 +133,7 @@ WV_HD constexpr int wv_fwd_row_items(int T, const WvTile& t, int l) { return wv_
 WV_HD constexpr int wv_fwd_col_items(int T, const WvTile& t, int l) { return 2 * wv_fwd_ext(T, t.L, t.tile, l + 1) * wv_fwd_ext(T, t.L, t.tile, l + 1); }
 
 // Row pass of level l, item = (row r of the level's input, output column kx): a and d of that row into rowbuf [r][kx], [r][n_out + kx].
-// Level 0 reads the image: in0 (+ in1 when non-null: the sum is formed on the way in) with periodic wrap; level >= 1 reads ll.
+// Level 0 reads the image: in0 (+ in1 when non-null: the sum is formed on the way in) at the frame's shift with periodic wrap; level >= 1 reads ll.
 // Only what the column pass will read is computed: of the last level, and of every d, the part that lands inside the tile.
 template <typename R, int T>
 WV_HD inline void wv_fwd_row_item(int item, int l, const WvTile& t, const R* in0, const R* in1, const R* ll, R* rowbuf) {
@@ -121,9 +144,9 @@ WV_HD inline void wv_fwd_row_item(int item, int l, const WvTile& t, const R* in0
     if (!need_a) return;
     R s[T];
     if (l == 0) {
-        const size_t row = t.base + (size_t)wv_wrap(t.ty0 + r, t.H) * t.W;
+        const size_t row = t.base + (size_t)wv_wrap(t.ty0 + r + t.sy, t.H) * t.W;
         for (int n = 0; n < T; ++n) {
-            const size_t p = row + wv_wrap(t.tx0 + 2 * kx + n, t.W);
+            const size_t p = row + wv_wrap(t.tx0 + 2 * kx + n + t.sx, t.W);
             s[n] = in1 ? in0[p] + in1[p] : in0[p];
         }
     } else {
@@ -203,7 +226,7 @@ WV_HD inline void wv_inv_col_item(int item, int l, const WvTile& t, const R* coe
 }
 
 // Row pass that undoes the rows of level l + 1, item = (row iy, column ix of level l's local block): into ll for l >= 1; at l = 0 the
-// pixel leaves through emit(offset, value) when it lies inside the image.
+// pixel leaves through emit(offset, value) when it lies inside the image -- for its place in the image, the frame's shift away.
 template <typename R, int T, typename Emit>
 WV_HD inline void wv_inv_row_item(int item, int l, const WvTile& t, const R* colbuf, R* ll, Emit&& emit) {
     const int m_out = wv_inv_ext(T, t.tile, l), m_in = wv_inv_ext(T, t.tile, l + 1), e0 = wv_inv_halo(T, l), e1 = wv_inv_halo(T, l + 1);
@@ -212,7 +235,7 @@ WV_HD inline void wv_inv_row_item(int item, int l, const WvTile& t, const R* col
     const R v = wv_inv_taps<R, T>(ix - e0, e1, [&](int j) { return row[j]; }, [&](int j) { return row[m_in + j]; });
     if (l > 0) { ll[iy * m_out + ix] = v; return; }
     const int gy = t.ty0 + iy, gx = t.tx0 + ix;
-    if (gy < t.H && gx < t.W) emit(t.base + (size_t)gy * t.W + gx, v);
+    if (gy < t.H && gx < t.W) emit(t.base + (size_t)wv_wrap_once(gy + t.sy, t.H) * t.W + wv_wrap_once(gx + t.sx, t.W), v);
 }
 
 }  // namespace pnp

@@ -44,6 +44,42 @@ def check_sparsity(wavelet, levels, H, W):
     return WAVELETS[wavelet]
 
 
+def check_spin(shifts, levels, per_prox=1):
+    """ValueError unless `shifts` ([n, 2] integers (sy, sx)) and `per_prox` are a valid cycle-spinning schedule for a transform of
+    `levels` levels (pnp_spin_check: the library's own rule, no context and no device needed).  -> the table, [n, 2] int32."""
+    a = np.asarray(shifts)
+    if a.ndim != 2 or a.shape[1] != 2 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError('spin shifts must be an integer array [n, 2] of (sy, sx) (got shape %s, dtype %s)' % (a.shape, a.dtype))
+    if int(per_prox) != per_prox:
+        raise ValueError('per_prox must be an integer (got %r)' % (per_prox,))
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError('spin: shift out of range')
+    t = np.ascontiguousarray(a, dtype=np.int32)
+    L = _lib.lib()
+    if L.pnp_spin_check(int(levels), t.ctypes.data_as(C.POINTER(C.c_int32)), int(t.shape[0]), int(per_prox)) != 0:
+        raise ValueError(L.pnp_last_error().decode('utf-8', 'replace'))
+    return t
+
+
+def spin_table(spin, levels, iters, average=1, seed=0):
+    """The cycle-spinning table of a run of `iters` iterations that averages `average` shifts per prox (Engine.set_spin(table, average)):
+    'random' -> np.random.default_rng(seed).integers(0, 2**levels, size=(iters * average, 2)); an array-like [n, 2] is passed through
+    after checking (n a multiple of `average`, every shift in [0, 2**levels)); None -> None.  Always int32."""
+    if spin is None:
+        return None
+    if int(average) != average or not 1 <= int(average) <= 16:
+        raise ValueError('spin_average (per_prox) must be an integer in 1..16 (got %r)' % (average,))
+    if isinstance(spin, str):
+        if spin != 'random':
+            raise ValueError("spin must be None, 'random' or an array [n, 2] of shifts (got %r)" % (spin,))
+        if int(levels) != levels or not 1 <= int(levels) <= 4:
+            raise ValueError('levels must be 1..4 (got %r)' % (levels,))
+        if int(iters) * int(average) < 1:
+            return None                                   # nothing to schedule
+        spin = np.random.default_rng(seed).integers(0, 2 ** int(levels), size=(int(iters) * int(average), 2)).astype(np.int32)
+    return check_spin(spin, levels, average)
+
+
 def check_coils(sens, H, W, cg_iters=3):
     """ValueError unless `sens` is a valid set ([C,H,W]) or bank ([Ks,C,H,W]) of coil maps for H x W slices and cg_iters is 1..64
     (pnp_coils_check: the library's own rule, no context and no device needed).  -> (C, Ks)."""
@@ -150,6 +186,36 @@ class Engine:
         wv, lv = C.c_int(0), C.c_int(0)
         _lib.check(self._L.pnp_get_sparsity(self._ctx, C.byref(wv), C.byref(lv)))
         return {v: k for k, v in WAVELETS.items()}[wv.value], lv.value
+
+    def set_spin(self, shifts=None, per_prox=1):
+        """Cycle spinning for the wavelet prox (pnp_set_spin): `shifts` [n, 2] of (sy, sx) in [0, 2**levels), used `per_prox` per prox
+        step in table order (averaged when per_prox > 1), wrapping at the end; None clears.  Needs set_sparsity first, which also
+        clears it.  init_state and set_spin rewind the schedule, set_state does not (spin_cursor)."""
+        if shifts is None:
+            _lib.check(self._L.pnp_set_spin(self._ctx, None, 0, 1))
+            return
+        wavelet, levels = self.sparsity
+        # without a wavelet the library refuses the call (PNP_E_STATE); with one, a bad table is a ValueError that names the rule
+        t = check_spin(shifts, levels, per_prox) if wavelet is not None else np.ascontiguousarray(shifts, dtype=np.int32).reshape(-1, 2)
+        _lib.check(self._L.pnp_set_spin(self._ctx, t.ctypes.data_as(C.POINTER(C.c_int32)), int(t.shape[0]), int(per_prox)))
+
+    @property
+    def spin(self):
+        """{'n', 'per_prox'} of set_spin (pnp_get_spin); n = 0 without one."""
+        n, k = C.c_int(0), C.c_int(0)
+        _lib.check(self._L.pnp_get_spin(self._ctx, C.byref(n), C.byref(k), None))
+        return {'n': n.value, 'per_prox': k.value}
+
+    @property
+    def spin_cursor(self):
+        """Prox steps since the spin schedule was last rewound: the next one uses table group spin_cursor mod (n / per_prox)."""
+        p = C.c_int(0)
+        _lib.check(self._L.pnp_get_spin(self._ctx, None, None, C.byref(p)))
+        return p.value
+
+    @spin_cursor.setter
+    def spin_cursor(self, cursor):
+        _lib.check(self._L.pnp_set_spin_cursor(self._ctx, int(cursor)))
 
     def set_coils(self, sens, cg_iters=3):
         """Multi-coil (SENSE) data consistency (pnp_set_coils): sens [C,H,W] or a bank [Ks,C,H,W] of complex sensitivity maps (host array
@@ -439,15 +505,25 @@ class Engine:
     def ifft2(self, inp, out, B):
         _lib.check(self._L.pnp_fft2_inv(self._ctx, _ptr(inp), _ptr(out), int(B)))
 
-    def dwt2(self, inp, out, B):
-        """Psi of B real slices with the engine's sparsity setting (pnp_dwt2_fwd; device tensors of the engine's precision; inp may be out)."""
+    def dwt2(self, inp, out, B, shift=None):
+        """Psi of B real slices with the engine's sparsity setting (pnp_dwt2_fwd; device tensors of the engine's precision; inp may be out).
+        shift=(sy, sx): Psi_s, the transform of the frame shifted by it (pnp_dwt2_shifted); None: the call as it ever was."""
+        if shift is not None:
+            return self._dwt2_shifted(inp, out, B, 0, shift)
         fn = self._L.pnp_dwt2_fwd_f64 if self.f64 else self._L.pnp_dwt2_fwd
         _lib.check(fn(self._ctx, _ptr(inp), _ptr(out), int(B)))
 
-    def idwt2(self, inp, out, B):
-        """Psi^T (pnp_dwt2_inv)."""
+    def idwt2(self, inp, out, B, shift=None):
+        """Psi^T (pnp_dwt2_inv); shift=(sy, sx): Psi_s^T."""
+        if shift is not None:
+            return self._dwt2_shifted(inp, out, B, 1, shift)
         fn = self._L.pnp_dwt2_inv_f64 if self.f64 else self._L.pnp_dwt2_inv
         _lib.check(fn(self._ctx, _ptr(inp), _ptr(out), int(B)))
+
+    def _dwt2_shifted(self, inp, out, B, inverse, shift):
+        sy, sx = shift
+        fn = self._L.pnp_dwt2_shifted_f64 if self.f64 else self._L.pnp_dwt2_shifted
+        _lib.check(fn(self._ctx, _ptr(inp), _ptr(out), int(B), int(inverse), int(sy), int(sx)))
 
     def A(self, x, k):
         _lib.check(self._L.pnp_A(self._ctx, _ptr(x), _ptr(k)))

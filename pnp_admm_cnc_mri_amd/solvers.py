@@ -32,6 +32,12 @@ bypass the file system through the extra keyword arguments
               Psi^T soft(Psi v), the CNC pair of thresholds is applied coefficient-wise, the coarsest approximation band is never
               thresholded (include/pnp_mri.h, "wavelet-domain sparsity").  NOT in the reference scripts, whose prox acts on the pixels;
               None (the default) is bit for bit what it was.  One extra log line names the transform
+    spin=None, spin_average=1, spin_seed=0   (ADMM_L1 and ADMM_CNC only, with transform=) cycle spinning: the prox of every iteration acts
+              in a circularly shifted frame, which takes the artefacts of the decimated transform off the 2^levels grid (include/pnp_mri.h,
+              "cycle spinning").  spin='random': iter_num * spin_average shifts (sy, sx) drawn from [0, 2^levels) by
+              np.random.default_rng(spin_seed) (engine.spin_table); or an array [n, 2] of shifts, used in order and wrapping.
+              spin_average = K (1..16): every prox averages K consecutive shifts of the table, at 2 K launches instead of 2.  NOT in
+              the reference scripts; None (the default) calls nothing new.  One extra log line names the table and K
 
     coils=None, coil_id=None, cg_iters=3   (all five solvers) multi-coil (SENSE) data consistency: coils [C,H,W] complex sensitivity maps,
               or a bank [Ks,C,H,W] with coil_id [B] picking each slice's set.  The forward model becomes y_c = mask . fft2(S_c . x):
@@ -72,7 +78,7 @@ import numpy as np
 
 from . import coilmaps, coilmix, imageio
 from ._lib import PnpError
-from .engine import Engine, check_coils, check_sparsity
+from .engine import Engine, check_coils, check_sparsity, spin_table
 
 # CLI presets of the reference scripts (positional order differs per script!)
 PRESETS = {
@@ -213,10 +219,11 @@ class _Job:
             self.log.info(os.path.join(testsets, testset_name))
         self.testset_name = testset_name
 
-    def open_engine(self, stream=None, transform=None, levels=3):
+    def open_engine(self, stream=None, transform=None, levels=3, spin=None, spin_average=1):
         """stream: HIP stream handle every engine call is ordered on (PnP: torch's current stream),
         set BEFORE the first kernel so upload / synthesis / init and the loop share one queue.
-        transform / levels: Engine.set_sparsity (ADMM_L1 / ADMM_CNC)."""
+        transform / levels: Engine.set_sparsity (ADMM_L1 / ADMM_CNC); spin / spin_average: the table of spin_request and its group
+        size, Engine.set_spin."""
         if self.mixing and self.estimate and self.coil_mix is None:  # y' = M y with ONE matrix for the batch; the maps come from y' below
             self.y, _, self.coil_mix = coilmix.prepare(self.y, None, self.mask_bank, self.mask_id, None, self.virtual_coils, self.noise_cov,
                                                        self.calib, self.precision, self.device)
@@ -233,6 +240,11 @@ class _Job:
             if self.log is not None:
                 self.log.info('sparsity transform: {:s}, {:d} levels (periodic 2-D DWT; not in the reference scripts)'.format(
                     transform, int(levels)))
+        if spin is not None:
+            eng.set_spin(spin, spin_average)
+            if self.log is not None:
+                self.log.info('cycle spinning: {:d} shifts, {:d} averaged per prox (not in the reference scripts)'.format(
+                    len(spin), int(spin_average)))
         if stream is not None:
             eng.set_stream(stream)
         if self.estimate and self.coil_maps is None:                 # one coil set per slice, from the slice's own calibration region
@@ -314,6 +326,16 @@ def trace_request(trace_every, tol, return_info):
     return on
 
 
+def spin_request(spin, spin_average, spin_seed, transform, levels, iter_num):
+    """-> the table [n, 2] int32 of spin= / spin_average= / spin_seed= (engine.spin_table), or None; every rule is a ValueError here,
+    before an engine is opened."""
+    if spin is None:
+        return None
+    if transform is None:
+        raise ValueError('spin= shifts the frame of the wavelet prox: it needs transform=')
+    return spin_table(spin, levels, iter_num, spin_average, spin_seed)
+
+
 def log_early_stop(job, trace, iter_num, tol):
     """the one extra log line of a run that the stopping rule ended before iter_num"""
     if trace is not None and tol is not None and trace['iters_done'] < iter_num and job.log is not None:
@@ -334,17 +356,18 @@ def _device_x(eng, job):
 def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
             results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
             transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
-            maps_radius=2, maps_power_iters=4, maps_thresh=0.05, **ADMM_L1_opts):
+            maps_radius=2, maps_power_iters=4, maps_thresh=0.05, spin=None, spin_average=1, spin_seed=0, **ADMM_L1_opts):
     """ADMM with L1 prox on the MI355X engine.  Reference: "【1】ADMM_L1.py":29-169."""
     iter_num = ADMM_L1_opts.get('iter_num', 20)          # S1:35
     lambda1 = ADMM_L1_opts.get('lambda1', 0.04)          # S1:36
     reo = ADMM_L1_opts.get('reo', 0.04)                  # S1:37
     traced = trace_request(trace_every, tol, return_info)
     check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
+    shifts = spin_request(spin, spin_average, spin_seed, transform, levels, iter_num)
     job = _Job(mask, noises, 'ADMM_L1', '_PDG L1', images, y, mask_id, testsets, testset_name, results, save_E, device,
                psnr_fmt='{:.2f}', precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters, virtual_coils=virtual_coils,
                noise_cov=noise_cov, calib=calib, maps_radius=maps_radius, maps_power_iters=maps_power_iters, maps_thresh=maps_thresh)   # S1:150
-    with job.open_engine(transform=transform, levels=levels) as eng:
+    with job.open_engine(transform=transform, levels=levels, spin=shifts, spin_average=spin_average) as eng:
         # S1:111-126, all slices, on device
         trace = eng.admm_l1(iter_num, lambda1, reo, trace_every, tol, job.gt_u8) if traced else eng.admm_l1(iter_num, lambda1, reo)
         log_early_stop(job, trace, iter_num, tol)
@@ -358,7 +381,7 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
 def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
              results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
              transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
-             maps_radius=2, maps_power_iters=4, maps_thresh=0.05, **ADMM_CNC_opts):
+             maps_radius=2, maps_power_iters=4, maps_thresh=0.05, spin=None, spin_average=1, spin_seed=0, **ADMM_CNC_opts):
     """ADMM with the convex-non-convex z-step.  Reference: "【4】ADMM_CNC .py":31-174."""
     iter_num = ADMM_CNC_opts.get('iter_num', 4)          # S4:37
     alpha = ADMM_CNC_opts.get('alpha', 0.4)              # S4:38
@@ -367,10 +390,11 @@ def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets
     b = ADMM_CNC_opts.get('b', 1)                        # S4:41  (b is b^2 of the paper)
     traced = trace_request(trace_every, tol, return_info)
     check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
+    shifts = spin_request(spin, spin_average, spin_seed, transform, levels, iter_num)
     job = _Job(mask, noises, 'ADMM_CNC', '_ADMM CNC', images, y, mask_id, testsets, testset_name, results, save_E, device,
                precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters, virtual_coils=virtual_coils, noise_cov=noise_cov,
                calib=calib, maps_radius=maps_radius, maps_power_iters=maps_power_iters, maps_thresh=maps_thresh)
-    with job.open_engine(transform=transform, levels=levels) as eng:
+    with job.open_engine(transform=transform, levels=levels, spin=shifts, spin_average=spin_average) as eng:
         # S4:115-132
         trace = (eng.admm_cnc(iter_num, alpha, lambda1, reo, b, trace_every, tol, job.gt_u8) if traced
                  else eng.admm_cnc(iter_num, alpha, lambda1, reo, b))

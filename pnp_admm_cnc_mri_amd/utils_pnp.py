@@ -59,22 +59,23 @@ def ifft2(eng, k):
     return out
 
 
-def dwt2(eng, x):
+def dwt2(eng, x, shift=(0, 0)):
     """Psi x: the periodic 2-D DWT of the engine's sparsity setting (Engine.set_sparsity) of a real batch [B,H,W], Mallat layout.
+    shift=(sy, sx), each in [0, 2**levels): Psi_s x = Psi roll(x, (-sy, -sx)), the transform of the shifted frame (cycle spinning).
     No counterpart in the reference."""
     torch = _torch()
     x = _prep(eng, x.to(torch.float64 if eng.f64 else torch.float32))
     out = torch.empty_like(x)
-    eng.dwt2(x, out, x.shape[0])
+    eng.dwt2(x, out, x.shape[0], None if tuple(shift) == (0, 0) else shift)
     return out
 
 
-def idwt2(eng, c):
-    """Psi^T c, the inverse of dwt2."""
+def idwt2(eng, c, shift=(0, 0)):
+    """Psi^T c, the inverse of dwt2; with shift=(sy, sx) Psi_s^T c = roll(Psi^T c, (sy, sx))."""
     torch = _torch()
     c = _prep(eng, c.to(torch.float64 if eng.f64 else torch.float32))
     out = torch.empty_like(c)
-    eng.idwt2(c, out, c.shape[0])
+    eng.idwt2(c, out, c.shape[0], None if tuple(shift) == (0, 0) else shift)
     return out
 
 

@@ -458,6 +458,65 @@ int pnp_coil_maps_f64(pnp_ctx* ctx, const double* y_dev, const uint8_t* mask_ban
  * times accumulated since the previous call of this function, which also resets them.  Results are bit for bit the same either way. */
 int pnp_coil_maps_stage_times(pnp_ctx* ctx, int enable, float* ms_out);
 
+/* ---- ESPIRiT coil sensitivity maps: calibration kernels wider than one pixel (added after ABI 13, additive) ----
+ * NOT in the reference scripts.  The estimator above is local to a pixel of the low-resolution images; this one uses the correlations
+ * between neighbouring k-space samples and gives an eigenvalue ~ 1 test for where the maps are valid.  It needs neither a per-pixel
+ * eigendecomposition of stored matrices nor an image-sized transform of every calibration kernel.  One slice, y [C][H][W] un-shifted (DC
+ * at (0, 0)), ncal, kernel side k, power_iters n, sigma, crop, thresh tau:
+ *   1 block     the ncal x ncal calibration region (as above; EVERY point must be sampled, same PNP_E_ARG and message) re-ordered to
+ *               ascending signed frequency on both axes (a roll by ncal / 2): K [C][ncal][ncal].  Not windowed.
+ *   2 Gram      the (ncal - k + 1)^2 patch positions (i, j), not wrapped; row (i, j) of the calibration matrix A is K[c][i + a][j + b] at
+ *               column (c k + a) k + b (c slowest), N = C k^2 columns.  Gram = A^H A, [N][N] complex DOUBLE for both input precisions, the
+ *               positions summed in row-major order by one chain per entry, an order that depends on (ncal, k) alone; exactly Hermitian:
+ *               the lower triangle is the conjugate of the upper to the bit, the diagonal's imaginary part is +0.
+ *   3 space     (host, double, the cyclic Jacobi of pnp_coilmix_compress) eigenvalues e_j of Gram, s_j = sqrt(max(e_j, 0)); the signal
+ *               space keeps the eigenvectors with s_j >= sigma s_max (their number is the rank); P = V V^H over them, symmetrised.
+ *   4 kernels   (host, double) w_cc'(d) = (1 / k^2) sum_{a - a' = d} conj(P)[(c, a), (c', a')], d in [-(k - 1), k - 1]^2, stored
+ *               [C][C][2k-1][2k-1] with entry (dy + k - 1, dx + k - 1); the upper triangle c <= c' from the sum, the lower as
+ *               w_c'c(-d) = conj(w_cc'(d)).  Every k-space patch r of a signal in the calibration's span obeys conj(P) r = r; summed over
+ *               the patch positions that is the k-space convolution with w.  Rounded once to the per-pixel stage's precision.
+ *   5 operator  G_cc'(q) = sum_dy E_H(q_y, dy) [sum_dx w_cc'(dy, dx) E_W(q_x, dx)], E_n(q, d) = exp(+2 pi i ((q d) mod n) / n) formed in double
+ *               from the reduced integer and rounded once; the inner chain over dx ascending, the outer over dy ascending, fused
+ *               multiply-adds; the upper triangle is computed, the lower is its conjugate, the diagonal's imaginary part is +0.  The coil
+ *               images S(q) x(q) are eigenvectors of G(q) with eigenvalue 1.
+ *   6 vectors   v = I(q) / ||I(q)|| with I the windowed low-resolution images of the estimator above (e_0 where I = 0); n times: u = G v
+ *               (c' ascending), lambda = ||u||, v = u / lambda (v stays where lambda = 0); then the phase rule above, v^H I(q) >= 0.
+ *   7 support   S(q) = v(q) where lambda(q) >= crop AND ||I(q)|| >= tau max_q ||I(q)|| of the slice; elsewhere exactly +0 in every coil.
+ * Every order is a function of (C, k, n, ncal) alone (csrc/espirit_plan.h states each): a slice alone is bit-equal to the slice in a batch.
+ * Limits, one message per rule (pnp_espirit_check: no context, no device): 1 <= C <= 32, ncal as for coil mixing, 2 <= kernel <= 8,
+ * kernel <= ncal, C kernel^2 <= 128 (the size of the host Jacobi: more channels go through coil compression first), 1 <= power_iters <= 16,
+ * 0 < sigma < 1, 0 <= crop <= 1, 0 <= thresh < 1, H and W in [128, 1024].
+ * pnp_calib_patch_gram: step 2 alone, no context; y [B][C][H][W], mask_bank [K][H][W] with mask_id [B] (or null: mask 0), gram [B][N][N]
+ * complex double, all DEVICE arrays.  A calibration point the mask does not sample enters as +0 here; pnp_espirit_maps refuses such a mask.
+ * pnp_espirit_kernels: steps 3 and 4, HOST arrays, double: gram [N][N] -> w_out [C][C][2k-1][2k-1] complex, *rank_out, sing_out [N] (the
+ * s_j, descending).
+ * pnp_espirit_eigmaps: steps 5 and 6 alone on the caller's DEVICE arrays, on ctx's stream: lowres_images [B][C][H][W], w [B][C][C][2k-1][2k-1]
+ * in the context's precision -> maps_out [B][C][H][W] (the unit vectors, NO support applied), lambda_out [B][H][W].  Synchronises at its end.
+ * pnp_espirit_maps: the whole pipeline on ctx and its stream, the arrays as for pnp_coil_maps (lambda_out or null).  Per pass of as many
+ * slices as fit min(B C, Bmax) pseudo-slices: window and inverse transform, patch Gram, one read-back, the host stage for the slices of the
+ * pass on at most 16 threads (never the machine's CPU count), the per-pixel and support kernels.  The context keeps one scratch array,
+ * allocated on first use -- a failure names the byte count; the uploaded problem and the state are not touched.  maps_out must not overlap
+ * y (PNP_E_ARG); B <= 65535.  pnp_espirit_ranks: the rank of every slice of the most recent pnp_espirit_maps on ctx (rank_out [B], host). */
+int pnp_espirit_check(int C, int ncal, int kernel, int power_iters, double sigma, double crop, double thresh, int H, int W);
+int pnp_calib_patch_gram(void* hip_stream, const float* y_dev, const uint8_t* mask_bank_dev, const int32_t* mask_id_dev, double* gram_dev, int B,
+                         int C, int H, int W, int ncal, int kernel);
+int pnp_calib_patch_gram_f64(void* hip_stream, const double* y_dev, const uint8_t* mask_bank_dev, const int32_t* mask_id_dev, double* gram_dev,
+                             int B, int C, int H, int W, int ncal, int kernel);
+int pnp_espirit_kernels(const double* gram, int C, int kernel, double sigma, double* w_out, int* rank_out, double* sing_out);
+int pnp_espirit_eigmaps(pnp_ctx* ctx, const float* lowres_images_dev, const float* w_dev, float* maps_out_dev, float* lambda_out_dev, int B, int C,
+                        int kernel, int power_iters);
+int pnp_espirit_eigmaps_f64(pnp_ctx* ctx, const double* lowres_images_dev, const double* w_dev, double* maps_out_dev, double* lambda_out_dev, int B,
+                            int C, int kernel, int power_iters);
+int pnp_espirit_maps(pnp_ctx* ctx, const float* y_dev, const uint8_t* mask_bank_dev, const int32_t* mask_id_dev, float* maps_out_dev,
+                     float* lambda_out_dev, int B, int C, int ncal, int kernel, int power_iters, double sigma, double crop, double thresh);
+int pnp_espirit_maps_f64(pnp_ctx* ctx, const double* y_dev, const uint8_t* mask_bank_dev, const int32_t* mask_id_dev, double* maps_out_dev,
+                         double* lambda_out_dev, int B, int C, int ncal, int kernel, int power_iters, double sigma, double crop, double thresh);
+int pnp_espirit_ranks(pnp_ctx* ctx, int32_t* rank_out, int B);
+/* MEASUREMENT, not product (profiles/espirit_rate.py): enable != 0 times three stages of every later pnp_espirit_maps pass on ctx -- patch
+ * Gram with its read-back (HIP events), the host stage (host clock), per-pixel and support kernels (HIP events); ms_out (or NULL) gets the
+ * three times accumulated since the previous call of this function, which also resets them.  Results are the same bits either way. */
+int pnp_espirit_stage_times(pnp_ctx* ctx, int enable, float* ms_out);
+
 /* ---- optional HIP backend of the denoisers' plain conv stacks ------------------------------
  * The north star keeps the CNN forward pass in PyTorch-ROCm; these two entry points are the opt-in `Denoiser(backend='hip')`
  * for the 64 -> 64 channel conv3x3 (+ bias, + ReLU) body layers of FFDNet / DnCNN / FDnCNN (models/network_ffdnet.py:58-73,

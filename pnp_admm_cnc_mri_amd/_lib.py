@@ -141,6 +141,18 @@ SIGNATURES = {
     'pnp_coil_maps': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
     'pnp_coil_maps_f64': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
     'pnp_coil_maps_stage_times': (C.c_int, [ctx_p, C.c_int, c_float_p]),
+    # ESPIRiT coil maps (added after ABI 13, additive)
+    'pnp_espirit_check': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int]),
+    'pnp_calib_patch_gram': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'pnp_calib_patch_gram_f64': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'pnp_espirit_kernels': (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp, C.POINTER(C.c_int), _vp]),
+    'pnp_espirit_eigmaps': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'pnp_espirit_eigmaps_f64': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'pnp_espirit_maps': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]),
+    'pnp_espirit_maps_f64': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                       C.c_double]),
+    'pnp_espirit_ranks': (C.c_int, [ctx_p, _vp, C.c_int]),
+    'pnp_espirit_stage_times': (C.c_int, [ctx_p, C.c_int, c_float_p]),
     'pnp_ssim': (C.c_int, [ctx_p, _vp, _vp, C.c_int, c_double_p]),
     'pnp_timer_start': (C.c_int, [ctx_p]),
     'pnp_timer_stop': (C.c_int, [ctx_p, c_float_p]),

@@ -5,9 +5,14 @@ dominant-eigenvector method (Walsh's adaptive combination) in matrix-free form o
 frequencies under a cos^2 window, the library's own inverse transform, `power_iters` power steps on the (2 radius + 1)^2 patch around
 every pixel, a phase rule that leaves v^H I >= 0 (the solvers reconstruct a real non-negative image, so the maps carry all of the
 phase), and a support: maps are exactly 0 where the local eigenvalue is below thresh^2 of the slice's largest, and have
-sum_c |S_c|^2 = 1 everywhere else.  This module owns no numerics: all of it is pnp_coil_maps.
+sum_c |S_c|^2 = 1 everywhere else.  estimate(method='espirit') is the ESPIRiT estimator instead (include/pnp_mri.h, "ESPIRiT coil
+sensitivity maps"): the Gram matrix of the kernel x kernel patches of the calibration block, its signal space above sigma of the largest
+singular value, the per-pixel operator G(q) of the kernel autocorrelations, `power_iters` power steps on it from the same low-resolution
+images, the same phase rule, and the support where the eigenvalue is at least crop and the low-resolution image at least thresh of its
+largest.  This module owns no numerics: all of it is pnp_coil_maps / pnp_espirit_maps.
 
-    check(C, calib, radius, power_iters, thresh, H, W)      ValueError unless the sizes are valid (no device needed)
+    check(C, calib, radius, power_iters, thresh, H, W)      ValueError unless the sizes are valid (no device needed); method=, kernel=,
+                                                            sigma=, crop= for the ESPIRiT rules
     check_region(mask, mask_id, calib)                      ValueError unless every calibration point is sampled (host masks)
     estimate(y, mask, ...)                                  [B,C,H,W] maps, one set per slice
     describe(info)                                          the solvers' log line
@@ -21,8 +26,21 @@ from . import _lib
 from .coilmix import CHUNK_BYTES, _cdt, _chunks, _device, _err, _ids, _is_dev, _to_dev
 
 
-def check(Cn, calib, radius, power_iters, thresh, H, W):
-    """ValueError unless the sizes are valid for the map estimation (pnp_coilmaps_check: the library's own rule, no device needed)."""
+METHODS = ('walsh', 'espirit')
+
+
+def check(Cn, calib, radius, power_iters, thresh, H, W, method='walsh', kernel=4, sigma=0.02, crop=0.9):
+    """ValueError unless the sizes are valid for the map estimation (pnp_coilmaps_check or, for method='espirit', pnp_espirit_check: the
+    library's own rules, no device needed).  radius is not used by 'espirit', kernel / sigma / crop not by 'walsh'."""
+    if method not in METHODS:
+        raise ValueError("maps method must be 'walsh' or 'espirit' (got %r)" % (method,))
+    if method == 'espirit':
+        if any(int(v) != v for v in (Cn, calib, kernel, power_iters)):
+            raise ValueError('calib, maps_kernel and maps_power_iters must be integers')
+        if _lib.lib().pnp_espirit_check(int(Cn), int(calib), int(kernel), int(power_iters), float(sigma), float(crop), float(thresh), int(H),
+                                        int(W)) != 0:
+            raise _err()
+        return
     if any(int(v) != v for v in (Cn, calib, radius, power_iters)):
         raise ValueError('calib, maps_radius and maps_power_iters must be integers')
     if _lib.lib().pnp_coilmaps_check(int(Cn), int(calib), int(radius), int(power_iters), float(thresh), int(H), int(W)) != 0:
@@ -51,13 +69,17 @@ def check_region(mask, mask_id=None, calib=24):
 
 
 def estimate(y, mask, mask_id=None, calib=24, radius=2, power_iters=4, thresh=0.05, precision='f32', device=None, return_lambda=False,
-             engine=None, chunk_bytes=CHUNK_BYTES):
+             engine=None, chunk_bytes=CHUNK_BYTES, method='walsh', kernel=4, sigma=0.02, crop=0.9, return_rank=False):
     """Sensitivity maps of every slice from its own calibration region (pnp_coil_maps).  y [B,C,H,W] complex measurements (un-shifted, DC at
     [0, 0]): a contiguous device tensor of the precision's complex type (-> device tensors) or a host array (-> host arrays; chunks of
     slices of at most chunk_bytes go through the device).  mask [H,W] or a bank [K,H,W] with mask_id [B].  -> maps [B,C,H,W]: one coil set
     per slice, what the solvers take as coils= with coil_id=arange(B); return_lambda=True: (maps, lambda [B,H,W]), the local eigenvalue
     the support is cut from.  engine: an Engine of the same (H, W) and precision to run on (its uploaded problem and state are not
-    touched); None: one is opened for the call."""
+    touched); None: one is opened for the call.
+    method='espirit': the ESPIRiT estimator (pnp_espirit_maps) with kernel x kernel calibration patches, the signal space above sigma of
+    the largest singular value, and the support lambda >= crop and ||I|| >= thresh of the slice's largest; `radius` is IGNORED for it, and
+    return_lambda returns the eigenvalue of G(q), which is about 1 where the maps are valid.  return_rank=True appends the signal-space
+    rank of every slice, [B] int32 (None for 'walsh')."""
     import torch
     from .engine import Engine
     if precision not in ('f32', 'f64'):
@@ -65,7 +87,7 @@ def estimate(y, mask, mask_id=None, calib=24, radius=2, power_iters=4, thresh=0.
     if np.ndim(y) != 4:
         raise ValueError('y must be [B,C,H,W] (got shape %s)' % (tuple(np.shape(y)),))
     B, Cn, H, W = (int(v) for v in np.shape(y))
-    check(Cn, calib, radius, power_iters, thresh, H, W)
+    check(Cn, calib, radius, power_iters, thresh, H, W, method, kernel, sigma, crop)
     if B < 1:
         raise ValueError('y must have at least one slice')
     mask = np.asarray(mask)
@@ -90,6 +112,7 @@ def estimate(y, mask, mask_id=None, calib=24, radius=2, power_iters=4, thresh=0.
         try:
             bank_t = torch.from_numpy(bank).to(dev)
             maps = torch.empty((B, Cn, H, W), dtype=tdt, device=dev) if on_dev else np.empty((B, Cn, H, W), dt)
+            rank = np.zeros(B, np.int32) if method == 'espirit' else None
             lam = None if not return_lambda else (torch.empty((B, H, W), dtype=rdt, device=dev) if on_dev else np.empty((B, H, W), dt(0).real.dtype))
             for lo, hi in pieces:
                 y_t = _to_dev(y[lo:hi], dt, dev)
@@ -97,7 +120,10 @@ def estimate(y, mask, mask_id=None, calib=24, radius=2, power_iters=4, thresh=0.
                 m_t = maps[lo:hi] if on_dev else torch.empty((hi - lo, Cn, H, W), dtype=tdt, device=dev)
                 l_t = None if lam is None else (lam[lo:hi] if on_dev else torch.empty((hi - lo, H, W), dtype=rdt, device=dev))
                 torch.cuda.current_stream(dev).synchronize()         # the inputs are torch's; the call runs on the engine's stream
-                eng.coil_maps(y_t, bank_t, mid_t, m_t, l_t, hi - lo, Cn, calib, radius, power_iters, thresh)      # synchronises at its end
+                if method == 'espirit':
+                    rank[lo:hi] = eng.espirit_maps(y_t, bank_t, mid_t, m_t, l_t, hi - lo, Cn, calib, kernel, power_iters, sigma, crop, thresh)
+                else:
+                    eng.coil_maps(y_t, bank_t, mid_t, m_t, l_t, hi - lo, Cn, calib, radius, power_iters, thresh)  # synchronises at its end
                 if not on_dev:
                     maps[lo:hi] = m_t.cpu().numpy()
                     if lam is not None:
@@ -105,7 +131,10 @@ def estimate(y, mask, mask_id=None, calib=24, radius=2, power_iters=4, thresh=0.
         finally:
             if own:
                 eng.close()
-    return (maps, lam) if return_lambda else maps
+    out = (maps, lam) if return_lambda else (maps,)
+    if return_rank:
+        out = out + (rank,)
+    return out if len(out) > 1 else out[0]
 
 
 def support_share(maps):
@@ -119,6 +148,12 @@ def support_share(maps):
 def describe(info):
     """the solvers' log line"""
     s = np.atleast_1d(np.asarray(info['support'], np.float64))
+    if info.get('method', 'walsh') == 'espirit':
+        r = np.atleast_1d(np.asarray(info['rank']))
+        return ('coil maps estimated by ESPIRiT from the {:d} x {:d} calibration region: kernel {:d}, sigma {:g} (rank {:d} .. {:d}), {:d} '
+                'power iterations, crop {:g}, threshold {:g}, support {:.1f} % of the pixels (not in the reference scripts)').format(
+                    int(info['calib']), int(info['calib']), int(info['kernel']), float(info['sigma']), int(r.min()), int(r.max()),
+                    int(info['power_iters']), float(info['crop']), float(info['thresh']), 100.0 * float(s.mean()))
     return ('coil maps estimated from the {:d} x {:d} calibration region: radius {:d}, {:d} power iterations, threshold {:g}, support '
             '{:.1f} % of the pixels (not in the reference scripts)').format(int(info['calib']), int(info['calib']), int(info['radius']),
                                                                            int(info['power_iters']), float(info['thresh']), 100.0 * float(s.mean()))

@@ -6,6 +6,7 @@
 #include "coil_plan.h"
 #include "coilmix_plan.h"
 #include "coilmaps_plan.h"
+#include "espirit_plan.h"
 
 #include <limits.h>
 #include <math.h>
@@ -14,7 +15,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include <dlfcn.h>
+#include <chrono>
 #include <new>
+#include <thread>
 #include <type_traits>
 #include <vector>
 
@@ -147,6 +150,12 @@ struct pnp_ctx {
     size_t cm_bytes = 0;
     bool cm_timing = false;           // pnp_coil_maps_stage_times: every pass is bracketed by HIP events and synchronised
     hipEvent_t cm_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    void* es_scratch = nullptr;       // pnp_espirit_maps / pnp_espirit_eigmaps: espirit_scratch, on first use
+    size_t es_bytes = 0;
+    std::vector<int32_t> es_rank;     // the signal-space rank of every slice of the most recent pnp_espirit_maps (pnp_espirit_ranks)
+    bool es_timing = false;           // pnp_espirit_stage_times
+    float es_ms[3] = {0.f, 0.f, 0.f}; // patch Gram (with its read-back), host stage, per-pixel kernel with support
+    hipEvent_t es_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float cm_ms[3] = {0.f, 0.f, 0.f}; // window, transform, eigenvectors + support: accumulated since the last read
 };
 
@@ -1282,11 +1291,12 @@ int pnp_ctx_destroy(pnp_ctx* c) {
     coils_free(c);
     anysize_destroy(c->any);
     void* ptrs[] = {c->y, c->work, c->z, c->w, c->x, c->mask_bank, c->mask_id, c->gt, c->acc, c->stage, c->ssim_part,
-                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc, c->wv_coef, c->wv_acc, c->cm_scratch};
+                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc, c->wv_coef, c->wv_acc, c->cm_scratch, c->es_scratch};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->cm_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->es_ev) if (e) (void)hipEventDestroy(e);
     delete c;
     return PNP_OK;
 }
@@ -1943,6 +1953,259 @@ int pnp_coil_maps_f64(pnp_ctx* c, const double* y, const uint8_t* mask_bank, con
                       int C, int ncal, int radius, int power_iters, double thresh) {
     CTX(c);
     return coil_maps_any<double>(__func__, c, y, mask_bank, mask_id, maps_out, lambda_out, B, C, ncal, radius, power_iters, thresh);
+}
+
+// ---- ESPIRiT coil maps: espirit_plan.h, kernels_espirit.hip.  Patch Gram on the device, signal space and kernels on the host, pixels on the device ----
+
+int pnp_espirit_check(int C, int ncal, int kernel, int power_iters, double sigma, double crop, double thresh, int H, int W) {
+    switch (espirit_check(C, ncal, kernel, power_iters, sigma, crop, thresh, H, W)) {
+    case ESPIRIT_OK:               return PNP_OK;
+    case ESPIRIT_BAD_C:            return fail(PNP_E_ARG, "espirit: C must be 1..%d (got %d)", COIL_MAX_C, C);
+    case ESPIRIT_BAD_SHAPE:        return fail(PNP_E_ARG, "espirit: H, W must be in [128, 1024] (got %d x %d)", H, W);
+    case ESPIRIT_BAD_NCAL:         return fail(PNP_E_ARG, "espirit: ncal must be %d..%d and <= min(H, W) (got %d at %d x %d)", COILMIX_NCAL_MIN,
+                                               COILMIX_NCAL_MAX, ncal, H, W);
+    case ESPIRIT_BAD_KERNEL:       return fail(PNP_E_ARG, "espirit: kernel must be %d..%d (got %d)", ESPIRIT_MIN_KERNEL, ESPIRIT_MAX_KERNEL, kernel);
+    case ESPIRIT_KERNEL_OVER_NCAL: return fail(PNP_E_ARG, "espirit: kernel must be <= ncal (got %d with ncal %d)", kernel, ncal);
+    case ESPIRIT_BAD_SIZE:         return fail(PNP_E_ARG, "espirit: C * kernel^2 must be <= %d, the size of the host eigen-solver (got %d * %d^2 = %d): "
+                                               "compress the channels with virtual_coils= first", ESPIRIT_MAX_N, C, kernel, C * kernel * kernel);
+    case ESPIRIT_BAD_ITERS:        return fail(PNP_E_ARG, "espirit: power_iters must be 1..%d (got %d)", ESPIRIT_MAX_ITERS, power_iters);
+    case ESPIRIT_BAD_SIGMA:        return fail(PNP_E_ARG, "espirit: sigma must be in (0, 1) (got %g)", sigma);
+    case ESPIRIT_BAD_CROP:         return fail(PNP_E_ARG, "espirit: crop must be in [0, 1] (got %g)", crop);
+    default:                       return fail(PNP_E_ARG, "espirit: thresh must be in [0, 1) (got %g)", thresh);
+    }
+}
+
+extern "C++" {
+// the rules of espirit_check that the Gram stage alone depends on
+static int espirit_gram_rule(int C, int ncal, int kernel, int H, int W) { return pnp_espirit_check(C, ncal, kernel, 1, 0.5, 0.0, 0.0, H, W); }
+
+template <typename R>
+static int patch_gram_any(const char* who, void* stream, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, double* gram, int B, int C,
+                          int H, int W, int ncal, int kernel) {
+    if (!y || !mask_bank || !gram) return fail(PNP_E_ARG, "%s: null pointer", who);
+    if (B < 1 || B > 65535) return fail(PNP_E_ARG, "%s: B must be 1..65535 (got %d)", who, B);
+    if (int rc = espirit_gram_rule(C, ncal, kernel, H, W)) return rc;
+    if ((uintptr_t)y % (2 * sizeof(R)) || (uintptr_t)gram % 16) return fail(PNP_E_ARG, "%s: y and gram must be aligned to one complex value", who);
+    HIPCHK(launch_calib_patch_gram<R>((hipStream_t)stream, y, mask_bank, mask_id, gram, B, C, H, W, ncal, kernel));
+    return PNP_OK;
+}
+
+// the context's ESPIRiT scratch array, grown on demand
+static int espirit_reserve(const char* who, pnp_ctx* c, size_t bytes, int B, int C) {
+    if (c->es_bytes >= bytes) return PNP_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));             // an earlier call on this stream may still read the old array
+    if (c->es_scratch) (void)hipFree(c->es_scratch);
+    c->es_scratch = nullptr; c->es_bytes = 0;
+    const hipError_t e = hipMalloc(&c->es_scratch, bytes);
+    if (e != hipSuccess) {
+        c->es_scratch = nullptr;
+        return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the scratch array: %zu bytes asked for (B=%d, C=%d, Bmax=%d, %dx%d): %s",
+                    who, bytes, B, C, c->Bmax, c->H, c->W, hipGetErrorString(e));
+    }
+    c->es_bytes = bytes;
+    return PNP_OK;
+}
+
+// the phasor tables of the context's shape into the scratch array; the host copies live in `keep` until the caller has synchronised
+template <typename R>
+static int espirit_tables(pnp_ctx* c, const EspiritScratch& lay, int kernel, std::vector<R>& keep) {
+    const size_t D = (size_t)espirit_side(kernel), nh = 2 * (size_t)c->H * D, nw = 2 * (size_t)c->W * D;
+    keep.resize(nh + nw);
+    espirit_phasor_table<R>(c->H, kernel, keep.data());
+    espirit_phasor_table<R>(c->W, kernel, keep.data() + nh);
+    char* base = (char*)c->es_scratch;
+    HIPCHK(hipMemcpyAsync(base + lay.eh, keep.data(), nh * sizeof(R), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(base + lay.ew, keep.data() + nh, nw * sizeof(R), hipMemcpyHostToDevice, c->stream));
+    return PNP_OK;
+}
+
+template <typename R>
+static int espirit_eigmaps_any(const char* who, pnp_ctx* c, const R* img, const R* w, R* maps, R* lambda, int B, int C, int kernel, int power_iters) {
+    using Cx = typename CxOf<R>::type;
+    if (c->f64 != (sizeof(R) == 8))
+        return fail(PNP_E_STATE, sizeof(R) == 8 ? "%s: needs a context made by pnp_ctx_create_any_f64" : "%s: not available on an fp64 validation context", who);
+    if (!img || !w || !maps || !lambda) return fail(PNP_E_ARG, "%s: null pointer", who);
+    if (B < 1 || B > 65535) return fail(PNP_E_ARG, "%s: B must be 1..65535 (got %d)", who, B);
+    if (int rc = pnp_espirit_check(C, kernel > COILMIX_NCAL_MIN ? kernel : COILMIX_NCAL_MIN, kernel, power_iters, 0.5, 0.0, 0.0, c->H, c->W)) return rc;
+    if ((uintptr_t)img % sizeof(Cx) || (uintptr_t)maps % sizeof(Cx) || (uintptr_t)w % sizeof(Cx) || (uintptr_t)lambda % sizeof(R))
+        return fail(PNP_E_ARG, "%s: the complex arrays must be aligned to one complex value, lambda_out to one real", who);
+    const size_t N = c->N, bytes = (size_t)B * C * N * sizeof(Cx);
+    const char *i0 = (const char*)img, *m0 = (const char*)maps;
+    if (i0 < m0 + bytes && m0 < i0 + bytes) return fail(PNP_E_ARG, "%s: maps_out and the images must not overlap", who);
+    const EspiritScratch lay = espirit_scratch(B, B, C, kernel, c->H, c->W, c->f64, false);
+    if (int rc = espirit_reserve(who, c, lay.bytes, B, C)) return rc;
+    char* base = (char*)c->es_scratch;
+    std::vector<R> keep;
+    if (int rc = espirit_tables<R>(c, lay, kernel, keep)) return rc;
+    R* inorm = (R*)(base + lay.inorm);
+    HIPCHK(launch_espirit_maps<R>(c->stream, img, w, (const R*)(base + lay.eh), (const R*)(base + lay.ew), maps, lambda, inorm, B, C, c->H, c->W,
+                                  kernel, power_iters));
+    HIPCHK(hipStreamSynchronize(c->stream));             // the tables' host copies go out of scope
+    return PNP_OK;
+}
+
+template <typename R>
+static int espirit_maps_any(const char* who, pnp_ctx* c, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, R* maps, R* lambda, int B,
+                            int C, int ncal, int kernel, int power_iters, double sigma, double crop, double thresh) {
+    using Cx = typename CxOf<R>::type;
+    if (c->f64 != (sizeof(R) == 8))
+        return fail(PNP_E_STATE, sizeof(R) == 8 ? "%s: needs a context made by pnp_ctx_create_any_f64" : "%s: not available on an fp64 validation context", who);
+    if (!y || !mask_bank || !maps) return fail(PNP_E_ARG, "%s: null pointer", who);
+    if (B < 1 || B > 65535) return fail(PNP_E_ARG, "%s: B must be 1..65535 (got %d)", who, B);
+    if (int rc = pnp_espirit_check(C, ncal, kernel, power_iters, sigma, crop, thresh, c->H, c->W)) return rc;
+    if ((uintptr_t)y % sizeof(Cx) || (uintptr_t)maps % sizeof(Cx) || (lambda && (uintptr_t)lambda % sizeof(R)))
+        return fail(PNP_E_ARG, "%s: y and maps_out must be aligned to one complex value, lambda_out to one real", who);
+    const size_t N = c->N, bytes = (size_t)B * C * N * sizeof(Cx);
+    const char *y0 = (const char*)y, *m0 = (const char*)maps, *l0 = (const char*)lambda;
+    if (y0 < m0 + bytes && m0 < y0 + bytes) return fail(PNP_E_ARG, "%s: maps_out and y must not overlap", who);
+    if (lambda) {
+        const size_t lb = (size_t)B * N * sizeof(R);
+        if ((l0 < m0 + bytes && m0 < l0 + lb) || (l0 < y0 + bytes && y0 < l0 + lb)) return fail(PNP_E_ARG, "%s: lambda_out must not overlap y or maps_out", who);
+    }
+    const int nb = coilmaps_pass_slices(B, C, c->Bmax), n = espirit_columns(C, kernel);
+    const EspiritScratch lay = espirit_scratch(B, nb, C, kernel, c->H, c->W, c->f64, true);
+    if (int rc = espirit_reserve(who, c, lay.bytes, B, C)) return rc;
+    char* base = (char*)c->es_scratch;
+    Cx* img = (Cx*)(base + lay.img);
+    R* inorm = (R*)(base + lay.inorm);
+    R* part = (R*)(base + lay.part);
+    int32_t* miss = (int32_t*)(base + lay.miss);
+    double* gram = (double*)(base + lay.gram);
+    R* wdev = (R*)(base + lay.w);
+    std::vector<R> keep;
+    if (int rc = espirit_tables<R>(c, lay, kernel, keep)) return rc;
+    const size_t wn = espirit_w_count(C, kernel);
+    std::vector<double> hgram((size_t)nb * n * n * 2), hw64((size_t)ESPIRIT_HOST_THREADS * wn * 2),
+        work((size_t)ESPIRIT_HOST_THREADS * (espirit_work_doubles(n) + n));
+    std::vector<R> hw((size_t)nb * wn * 2);
+    std::vector<int32_t> hmiss((size_t)nb), rank((size_t)B, 0);
+    std::vector<int> status((size_t)nb);
+    for (int b0 = 0; b0 < B; b0 += nb) {
+        const int ns = B - b0 < nb ? B - b0 : nb;            // slices of this pass: ns C pseudo-slices
+        const R* yb = y + 2 * (size_t)b0 * C * N;
+        R* mb = maps + 2 * (size_t)b0 * C * N;
+        R* lam = lambda ? lambda + (size_t)b0 * N : (R*)(base + lay.lambda);
+        // the windowed region goes through maps_out: rows maps_out -> scratch, columns in place; the per-pixel kernel scratch -> maps_out
+        HIPCHK(launch_calib_window<R>(c->stream, yb, mask_bank, mask_id ? mask_id + b0 : nullptr, mb, miss + b0, ns, C, c->H, c->W, ncal));
+        for (int s0 = 0; s0 < ns * C; s0 += c->Bmax) {       // the transform in chunks of at most Bmax pseudo-slices
+            const int nsl = ns * C - s0 < c->Bmax ? ns * C - s0 : c->Bmax;
+            RowArgsT<R> ra{};
+            ra.cin = (const Cx*)mb + (size_t)s0 * N; ra.cout = img + (size_t)s0 * N; ra.scale = R(1) / (R)N; ra.nrows = nsl * c->H;
+            HIPCHK(rows<R>(c, IN_COMPLEX, true, EPI_COMPLEX, ra));
+            ColArgsT<R> ca{};
+            ca.in = img + (size_t)s0 * N; ca.out = img + (size_t)s0 * N; ca.B = nsl;
+            HIPCHK(cols<R>(c, false, MID_NONE, true, ca));
+        }
+        if (c->es_timing) HIPCHK(hipEventRecord(c->es_ev[0], c->stream));
+        HIPCHK(launch_calib_patch_gram<R>(c->stream, yb, mask_bank, mask_id ? mask_id + b0 : nullptr, gram, ns, C, c->H, c->W, ncal, kernel));
+        HIPCHK(hipMemcpyAsync(hgram.data(), gram, (size_t)ns * n * n * 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(hmiss.data(), miss + b0, (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (c->es_timing) HIPCHK(hipEventRecord(c->es_ev[1], c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (int b = 0; b < ns; ++b)
+            if (hmiss[b] >= 0)
+                return fail(PNP_E_ARG, "%s: the mask of slice %d does not sample calibration point (%d, %d) of the %d x %d region: every point of it must be measured",
+                            who, b0 + b, hmiss[b] / c->W, hmiss[b] % c->W, ncal, ncal);
+        if (!coilmix_all_finite(hgram.data(), (size_t)ns * n * n * 2)) return fail(PNP_E_ARG, "%s: the calibration region has a non-finite entry", who);
+        // the host stage: slice b of the pass on thread b % threads, every slice on its own arrays
+        const auto t0 = std::chrono::steady_clock::now();
+        const int threads = ns < ESPIRIT_HOST_THREADS ? ns : ESPIRIT_HOST_THREADS;
+        auto job = [&](int t) {
+            double* w64 = hw64.data() + (size_t)t * wn * 2;
+            double* wk = work.data() + (size_t)t * (espirit_work_doubles(n) + n);
+            for (int b = t; b < ns; b += threads) {
+                status[b] = espirit_kernels(hgram.data() + (size_t)b * n * n * 2, C, kernel, sigma, w64, &rank[b0 + b], wk + espirit_work_doubles(n), wk);
+                for (size_t i = 0; i < wn * 2; ++i) hw[(size_t)b * wn * 2 + i] = (R)w64[i];
+            }
+        };
+        if (threads == 1) job(0);
+        else {
+            std::vector<std::thread> pool;
+            for (int t = 1; t < threads; ++t) pool.emplace_back(job, t);
+            job(0);
+            for (std::thread& t : pool) t.join();
+        }
+        for (int b = 0; b < ns; ++b)
+            if (status[b]) return fail(PNP_E_ARG, "%s: the Jacobi sweeps did not converge on the Gram matrix of slice %d", who, b0 + b);
+        if (c->es_timing) c->es_ms[1] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        HIPCHK(hipMemcpyAsync(wdev, hw.data(), (size_t)ns * wn * 2 * sizeof(R), hipMemcpyHostToDevice, c->stream));
+        if (c->es_timing) HIPCHK(hipEventRecord(c->es_ev[2], c->stream));
+        HIPCHK(launch_espirit_maps<R>(c->stream, (const R*)img, wdev, (const R*)(base + lay.eh), (const R*)(base + lay.ew), mb, lam, inorm, ns, C,
+                                      c->H, c->W, kernel, power_iters));
+        HIPCHK(launch_espirit_support<R>(c->stream, lam, inorm, part, mb, ns, C, N, (R)crop, (R)thresh));
+        if (c->es_timing) HIPCHK(hipEventRecord(c->es_ev[3], c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));             // the next pass rewrites the host arrays the copies read
+        if (c->es_timing) {
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, c->es_ev[0], c->es_ev[1]));
+            c->es_ms[0] += ms;
+            HIPCHK(hipEventElapsedTime(&ms, c->es_ev[2], c->es_ev[3]));
+            c->es_ms[2] += ms;
+        }
+    }
+    c->es_rank = rank;
+    return PNP_OK;
+}
+}  // extern "C++"
+
+int pnp_calib_patch_gram(void* stream, const float* y, const uint8_t* mask_bank, const int32_t* mask_id, double* gram, int B, int C, int H, int W,
+                         int ncal, int kernel) {
+    return patch_gram_any<float>(__func__, stream, y, mask_bank, mask_id, gram, B, C, H, W, ncal, kernel);
+}
+int pnp_calib_patch_gram_f64(void* stream, const double* y, const uint8_t* mask_bank, const int32_t* mask_id, double* gram, int B, int C, int H,
+                             int W, int ncal, int kernel) {
+    return patch_gram_any<double>(__func__, stream, y, mask_bank, mask_id, gram, B, C, H, W, ncal, kernel);
+}
+
+int pnp_espirit_kernels(const double* gram, int C, int kernel, double sigma, double* w_out, int* rank_out, double* sing_out) {
+    if (!gram || !w_out || !rank_out || !sing_out) return fail(PNP_E_ARG, "pnp_espirit_kernels: null pointer");
+    if (int rc = pnp_espirit_check(C, kernel > COILMIX_NCAL_MIN ? kernel : COILMIX_NCAL_MIN, kernel, 1, sigma, 0.0, 0.0, 128, 128)) return rc;
+    const int n = espirit_columns(C, kernel);
+    if (!coilmix_all_finite(gram, 2 * (size_t)n * n)) return fail(PNP_E_ARG, "pnp_espirit_kernels: the Gram matrix has a non-finite entry");
+    std::vector<double> work(espirit_work_doubles(n));
+    if (espirit_kernels(gram, C, kernel, sigma, w_out, rank_out, sing_out, work.data()))
+        return fail(PNP_E_ARG, "pnp_espirit_kernels: the Jacobi sweeps did not converge");
+    return PNP_OK;
+}
+
+int pnp_espirit_eigmaps(pnp_ctx* c, const float* lowres_images, const float* w, float* maps_out, float* lambda_out, int B, int C, int kernel,
+                        int power_iters) {
+    CTX(c);
+    return espirit_eigmaps_any<float>(__func__, c, lowres_images, w, maps_out, lambda_out, B, C, kernel, power_iters);
+}
+int pnp_espirit_eigmaps_f64(pnp_ctx* c, const double* lowres_images, const double* w, double* maps_out, double* lambda_out, int B, int C, int kernel,
+                            int power_iters) {
+    CTX(c);
+    return espirit_eigmaps_any<double>(__func__, c, lowres_images, w, maps_out, lambda_out, B, C, kernel, power_iters);
+}
+
+int pnp_espirit_maps(pnp_ctx* c, const float* y, const uint8_t* mask_bank, const int32_t* mask_id, float* maps_out, float* lambda_out, int B, int C,
+                     int ncal, int kernel, int power_iters, double sigma, double crop, double thresh) {
+    CTX(c);
+    return espirit_maps_any<float>(__func__, c, y, mask_bank, mask_id, maps_out, lambda_out, B, C, ncal, kernel, power_iters, sigma, crop, thresh);
+}
+int pnp_espirit_maps_f64(pnp_ctx* c, const double* y, const uint8_t* mask_bank, const int32_t* mask_id, double* maps_out, double* lambda_out, int B,
+                         int C, int ncal, int kernel, int power_iters, double sigma, double crop, double thresh) {
+    CTX(c);
+    return espirit_maps_any<double>(__func__, c, y, mask_bank, mask_id, maps_out, lambda_out, B, C, ncal, kernel, power_iters, sigma, crop, thresh);
+}
+
+int pnp_espirit_ranks(pnp_ctx* c, int32_t* rank_out, int B) {
+    CTX(c);
+    if (!rank_out || B < 1 || (size_t)B != c->es_rank.size())
+        return fail(PNP_E_ARG, "pnp_espirit_ranks: rank_out must hold the %zu slices of the most recent pnp_espirit_maps (got %d)", c->es_rank.size(), B);
+    for (int b = 0; b < B; ++b) rank_out[b] = c->es_rank[b];
+    return PNP_OK;
+}
+
+int pnp_espirit_stage_times(pnp_ctx* c, int enable, float* ms_out) {
+    CTX(c);
+    if (enable)
+        for (hipEvent_t& e : c->es_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    if (ms_out) for (int k = 0; k < 3; ++k) ms_out[k] = c->es_ms[k];
+    for (float& v : c->es_ms) v = 0.f;
+    c->es_timing = enable != 0;
+    return PNP_OK;
 }
 
 }  // extern "C"

@@ -128,6 +128,17 @@ template <typename R> hipError_t launch_calib_window(hipStream_t s, const R* y, 
 template <typename R> hipError_t launch_coil_eigmaps(hipStream_t s, const R* img, R* maps, R* lambda, int B, int C, int H, int W, int r, int iters);
 template <typename R> hipError_t launch_coilmaps_support(hipStream_t s, const R* lambda, R* part, R* maps, int B, int C, size_t N, R tau2);
 
+// ESPIRiT coil maps (kernels_espirit.hip, espirit_plan.h).  The patch Gram matrices of the calibration block, gram [B][n][n] complex double,
+// n = C k^2; the per-pixel stage: img [B][C][H][W], w [B][C][C][D][D] (D = 2 k - 1), the phasor tables eh [H][D] and ew [W][D] -> the unit
+// vectors maps [B][C][H][W], lambda [B][H][W] and inorm [B][H][W] = ||I||; the support: maps zeroed where lambda < crop or inorm < tau *
+// the slice's largest inorm (part: scratch of B * coilmaps_spans(N) values)
+template <typename R> hipError_t launch_calib_patch_gram(hipStream_t s, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, double* gram,
+                                                         int B, int C, int H, int W, int ncal, int k);
+template <typename R> hipError_t launch_espirit_maps(hipStream_t s, const R* img, const R* w, const R* eh, const R* ew, R* maps, R* lambda,
+                                                     R* inorm, int B, int C, int H, int W, int k, int iters);
+template <typename R> hipError_t launch_espirit_support(hipStream_t s, const R* lambda, const R* inorm, R* part, R* maps, int B, int C, size_t N,
+                                                        R crop, R tau);
+
 // pointwise
 hipError_t launch_prox(hipStream_t s, bool cnc, const float* x, float* z, float* w, ProxParams p, size_t n);
 hipError_t launch_combine(hipStream_t s, const float* z, const float* x, const float* w, const float* sden,

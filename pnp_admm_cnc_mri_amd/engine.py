@@ -258,6 +258,31 @@ class Engine:
         _lib.check(fn(self._ctx, _ptr(y), _ptr(mask_bank), _ptr(mask_id), _ptr(maps_out), _ptr(lambda_out), int(B), int(Cn), int(calib),
                       int(radius), int(power_iters), float(thresh)))
 
+    def espirit_maps(self, y, mask_bank, mask_id, maps_out, lambda_out, B, Cn, calib=24, kernel=4, power_iters=4, sigma=0.02, crop=0.9,
+                     thresh=0.05):
+        """ESPIRiT sensitivity maps (pnp_espirit_maps; coilmaps.estimate(method='espirit') is the array-level entry): the arrays of
+        coil_maps.  Runs on the engine's stream with its transforms and synchronises; the uploaded problem, the state and the coils of the
+        engine are not touched.  -> the signal-space rank of every slice, [B] int32."""
+        fn = self._L.pnp_espirit_maps_f64 if self.f64 else self._L.pnp_espirit_maps
+        _lib.check(fn(self._ctx, _ptr(y), _ptr(mask_bank), _ptr(mask_id), _ptr(maps_out), _ptr(lambda_out), int(B), int(Cn), int(calib),
+                      int(kernel), int(power_iters), float(sigma), float(crop), float(thresh)))
+        rank = np.empty(int(B), np.int32)
+        _lib.check(self._L.pnp_espirit_ranks(self._ctx, rank.ctypes.data_as(C.c_void_p), int(B)))
+        return rank
+
+    def espirit_eigmaps(self, images, w, maps_out, lambda_out, B, Cn, kernel, power_iters):
+        """The per-pixel stage of the ESPIRiT estimator alone (pnp_espirit_eigmaps): DEVICE tensors images [B,C,H,W] (low-resolution coil
+        images), w [B,C,C,2k-1,2k-1] of the engine's complex type -> maps_out [B,C,H,W] (unit vectors, no support), lambda_out [B,H,W]."""
+        fn = self._L.pnp_espirit_eigmaps_f64 if self.f64 else self._L.pnp_espirit_eigmaps
+        _lib.check(fn(self._ctx, _ptr(images), _ptr(w), _ptr(maps_out), _ptr(lambda_out), int(B), int(Cn), int(kernel), int(power_iters)))
+
+    def espirit_stage_times(self, enable=True):
+        """MEASUREMENT: the times (ms) of espirit_maps' three stages -- patch Gram with its read-back, host eigen-solve, per-pixel kernel
+        with support -- accumulated since the previous call of this method (pnp_espirit_stage_times)."""
+        ms = (C.c_float * 3)()
+        _lib.check(self._L.pnp_espirit_stage_times(self._ctx, 1 if enable else 0, ms))
+        return [float(v) for v in ms]
+
     def coil_maps_stage_times(self, enable=True):
         """MEASUREMENT: the HIP-event times (ms) of coil_maps' three stages -- window, inverse transform, eigenvectors with support --
         accumulated since the previous call of this method; enable: whether later calls are timed (pnp_coil_maps_stage_times)."""

@@ -67,6 +67,12 @@ bypass the file system through the extra keyword arguments
               ONE matrix from the Gram matrices of the whole batch, and the maps are estimated from the MIXED y: up to 128 physical
               channels.  NOT in the reference scripts.  One extra log line; info['coil_maps'] = {calib, radius, power_iters, thresh,
               support: the share of pixels kept per slice}
+    maps_method='walsh', maps_kernel=4, maps_sigma=0.02, maps_crop=0.9   (all five solvers, with coils='estimate') maps_method='espirit'
+              estimates the maps by ESPIRiT instead (include/pnp_mri.h, "ESPIRiT coil sensitivity maps"): maps_kernel x maps_kernel
+              calibration patches, the signal space above maps_sigma of the largest singular value, maps_power_iters power steps on
+              the per-pixel operator, kept where its eigenvalue is >= maps_crop and the low-resolution image >= maps_thresh of its
+              largest; maps_radius is not used.  C maps_kernel^2 <= 128 (of the MIXED channels: virtual_coils= first).  info['coil_maps']
+              gains method, kernel, sigma, crop and rank (per slice).  The default, 'walsh', is bit for bit what it was
 
 The PnP entry points (PNP_ADMM_L1_D, PNP_ADMM_CNC_D, PNP_ADMM_CNC_DnCNN) live in solvers_pnp.py.
 """
@@ -136,7 +142,7 @@ class _Job:
     def __init__(self, mask, noises, tag, suffix, images=None, y=None, mask_id=None, testsets='testsets',
                  testset_name='Set1', results='results', save_E=None, device=None, log=None, ssim=None,
                  psnr_fmt='{:.4f}', precision='f32', coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
-                 maps_radius=2, maps_power_iters=4, maps_thresh=0.05):
+                 maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02, maps_crop=0.9):
         # psnr_fmt: S1:150 and S3:320 print the per-image PSNR with two decimals, S4:155 / S6:332 / S6:548 with four
         self.tag, self.suffix, self.psnr_fmt = tag, suffix, psnr_fmt
         if precision not in ('f32', 'f64'):
@@ -163,10 +169,13 @@ class _Job:
             if len(ys) not in (3, 4) or ys[-2:] != (self.H, self.W):
                 raise ValueError('y must be [B,C,H,W] (or [C,H,W]) with H x W = %d x %d (got shape %s)' % (self.H, self.W, ys))
             c_out = coilmix.plan_y(ys[-3], self.H, self.W, virtual_coils, noise_cov, calib)[1] if self.mixing else int(ys[-3])
-            coilmaps.check(c_out, calib, maps_radius, maps_power_iters, maps_thresh, self.H, self.W)
+            coilmaps.check(c_out, calib, maps_radius, maps_power_iters, maps_thresh, self.H, self.W, maps_method, maps_kernel, maps_sigma,
+                           maps_crop)
             check_coils(np.broadcast_to(np.int8(0), (1, c_out, self.H, self.W)), self.H, self.W, cg_iters)
             coilmaps.check_region(self.mask_bank, self.mask_id, calib)
             self.maps_opts = dict(calib=int(calib), radius=int(maps_radius), power_iters=int(maps_power_iters), thresh=float(maps_thresh))
+            if maps_method == 'espirit':                             # 'walsh', the default: the call and the info are what they were
+                self.maps_opts.update(method='espirit', kernel=int(maps_kernel), sigma=float(maps_sigma), crop=float(maps_crop))
         elif self.mixing:
             if coils is None or y is None:
                 raise ValueError('virtual_coils= / noise_cov= mix MEASURED data: they need coils= and y= (the device synthesis from images= '
@@ -248,9 +257,12 @@ class _Job:
         if stream is not None:
             eng.set_stream(stream)
         if self.estimate and self.coil_maps is None:                 # one coil set per slice, from the slice's own calibration region
-            self.coils = coilmaps.estimate(self.y, self.mask_bank, self.mask_id, precision=self.precision, engine=eng, **self.maps_opts)
+            self.coils, rank = coilmaps.estimate(self.y, self.mask_bank, self.mask_id, precision=self.precision, engine=eng, return_rank=True,
+                                                 **self.maps_opts)
             self.coil_id = np.arange(self.B, dtype=np.int32)
             self.coil_maps = dict(self.maps_opts, support=coilmaps.support_share(self.coils))
+            if rank is not None:
+                self.coil_maps['rank'] = [int(v) for v in rank]
             if self.log is not None:
                 self.log.info(coilmaps.describe(self.coil_maps))
         if self.coils is not None:
@@ -356,7 +368,8 @@ def _device_x(eng, job):
 def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
             results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
             transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
-            maps_radius=2, maps_power_iters=4, maps_thresh=0.05, spin=None, spin_average=1, spin_seed=0, **ADMM_L1_opts):
+            maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02,
+             maps_crop=0.9, spin=None, spin_average=1, spin_seed=0, **ADMM_L1_opts):
     """ADMM with L1 prox on the MI355X engine.  Reference: "【1】ADMM_L1.py":29-169."""
     iter_num = ADMM_L1_opts.get('iter_num', 20)          # S1:35
     lambda1 = ADMM_L1_opts.get('lambda1', 0.04)          # S1:36
@@ -366,7 +379,8 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
     shifts = spin_request(spin, spin_average, spin_seed, transform, levels, iter_num)
     job = _Job(mask, noises, 'ADMM_L1', '_PDG L1', images, y, mask_id, testsets, testset_name, results, save_E, device,
                psnr_fmt='{:.2f}', precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters, virtual_coils=virtual_coils,
-               noise_cov=noise_cov, calib=calib, maps_radius=maps_radius, maps_power_iters=maps_power_iters, maps_thresh=maps_thresh)   # S1:150
+               noise_cov=noise_cov, calib=calib, maps_radius=maps_radius, maps_power_iters=maps_power_iters, maps_thresh=maps_thresh,
+               maps_method=maps_method, maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop)   # S1:150
     with job.open_engine(transform=transform, levels=levels, spin=shifts, spin_average=spin_average) as eng:
         # S1:111-126, all slices, on device
         trace = eng.admm_l1(iter_num, lambda1, reo, trace_every, tol, job.gt_u8) if traced else eng.admm_l1(iter_num, lambda1, reo)
@@ -381,7 +395,8 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
 def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
              results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
              transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
-             maps_radius=2, maps_power_iters=4, maps_thresh=0.05, spin=None, spin_average=1, spin_seed=0, **ADMM_CNC_opts):
+             maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02,
+             maps_crop=0.9, spin=None, spin_average=1, spin_seed=0, **ADMM_CNC_opts):
     """ADMM with the convex-non-convex z-step.  Reference: "【4】ADMM_CNC .py":31-174."""
     iter_num = ADMM_CNC_opts.get('iter_num', 4)          # S4:37
     alpha = ADMM_CNC_opts.get('alpha', 0.4)              # S4:38
@@ -393,7 +408,8 @@ def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets
     shifts = spin_request(spin, spin_average, spin_seed, transform, levels, iter_num)
     job = _Job(mask, noises, 'ADMM_CNC', '_ADMM CNC', images, y, mask_id, testsets, testset_name, results, save_E, device,
                precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters, virtual_coils=virtual_coils, noise_cov=noise_cov,
-               calib=calib, maps_radius=maps_radius, maps_power_iters=maps_power_iters, maps_thresh=maps_thresh)
+               calib=calib, maps_radius=maps_radius, maps_power_iters=maps_power_iters, maps_thresh=maps_thresh,
+               maps_method=maps_method, maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop)
     with job.open_engine(transform=transform, levels=levels, spin=shifts, spin_average=spin_average) as eng:
         # S4:115-132
         trace = (eng.admm_cnc(iter_num, alpha, lambda1, reo, b, trace_every, tol, job.gt_u8) if traced

@@ -177,7 +177,7 @@ class _Tracer:
 def PNP_ADMM_CNC_D(model_name, mask, noises, images=None, y=None, mask_id=None, testsets='testsets',
                    testset_name='Set1', results='results', save_E=None, device=None, return_info=False,
                    model_zoo='model_zoo', model=None, cnn_batch=None, cnn_dtype=None, miopen_find='auto', cnn_backend='auto', cnn_graph=False, return_device=False,
-                   state0=None, iter_start=0, trace_every=0, tol=None, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24, maps_radius=2, maps_power_iters=4, maps_thresh=0.05, **PNP_ADMM_CNC_D_opts):
+                   state0=None, iter_start=0, trace_every=0, tol=None, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24, maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02, maps_crop=0.9, **PNP_ADMM_CNC_D_opts):
     """CNC ADMM with a CNN denoiser in place of both soft-thresholds.  Reference: S6:79-351."""
     import torch
     alpha = PNP_ADMM_CNC_D_opts.get('alpha', 0.4)          # S6:85-89
@@ -190,7 +190,8 @@ def PNP_ADMM_CNC_D(model_name, mask, noises, images=None, y=None, mask_id=None, 
     job = _Job(mask, noises, model_name, 'PNP_ADMM_CNC_D', images, y, mask_id, testsets, testset_name, results,
                save_E, device, coils=coils, coil_id=coil_id, cg_iters=cg_iters,
                virtual_coils=virtual_coils, noise_cov=noise_cov, calib=calib, maps_radius=maps_radius,
-               maps_power_iters=maps_power_iters, maps_thresh=maps_thresh)
+               maps_power_iters=maps_power_iters, maps_thresh=maps_thresh, maps_method=maps_method,
+               maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop)
     den = _load_model(model_name, model, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))   # x8 = False, S6:93
     with torch.cuda.device(dev), torch.no_grad(), job.open_engine(torch.cuda.current_stream(dev).cuda_stream) as eng:
         B, H, W = job.B, job.H, job.W
@@ -224,7 +225,7 @@ def PNP_ADMM_CNC_DnCNN(model_name1, model_name2, mask, noises, images=None, y=No
                        testsets='testsets', testset_name='Set1', results='results', save_E=None, device=None,
                        return_info=False, model_zoo='model_zoo', model=None, model2=None, cnn_batch=None,
                        cnn_dtype=None, faithful_model2_path=True, miopen_find='auto', cnn_backend='auto', cnn_graph=False, return_device=False,
-                       trace_every=0, tol=None, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24, maps_radius=2, maps_power_iters=4, maps_thresh=0.05, **opts):
+                       trace_every=0, tol=None, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24, maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02, maps_crop=0.9, **opts):
     """Two DnCNN-17 nets: s = D1(z), z = D2(t).  Reference: S6:372-567.
     `faithful_model2_path`: the reference loads model_path1 into BOTH nets (S6:435) although it logs
     path 2; True reproduces that, False loads model_name2's own weights."""
@@ -239,7 +240,8 @@ def PNP_ADMM_CNC_DnCNN(model_name1, model_name2, mask, noises, images=None, y=No
     job = _Job(mask, noises, model_name1 + '_' + model_name2, 'PNP_ADMM_CNC_DnCNN', images, y, mask_id, testsets,
                testset_name, results, save_E, device, coils=coils, coil_id=coil_id, cg_iters=cg_iters,
                virtual_coils=virtual_coils, noise_cov=noise_cov, calib=calib, maps_radius=maps_radius,
-               maps_power_iters=maps_power_iters, maps_thresh=maps_thresh)
+               maps_power_iters=maps_power_iters, maps_thresh=maps_thresh, maps_method=maps_method,
+               maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop)
     den1 = _load_model(model_name1, model, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))
     if faithful_model2_path and model2 is None:
         den2 = _load_model(model_name1, model, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))
@@ -272,7 +274,7 @@ def PNP_ADMM_CNC_DnCNN(model_name1, model_name2, mask, noises, images=None, y=No
 def PNP_ADMM_L1_D(model_name, mask, noises, images=None, y=None, mask_id=None, testsets='testsets',
                   testset_name='Set1', results='results', save_E=None, device=None, return_info=False,
                   model_zoo='model_zoo', model=None, cnn_batch=None, cnn_dtype=None, miopen_find='auto', cnn_backend='auto', cnn_graph=False, return_device=False,
-                  state0=None, iter_start=0, trace_every=0, tol=None, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24, maps_radius=2, maps_power_iters=4, maps_thresh=0.05, **PNP_ADMM_L1_D_opts):
+                  state0=None, iter_start=0, trace_every=0, tol=None, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24, maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02, maps_crop=0.9, **PNP_ADMM_L1_D_opts):
     """L1-ADMM with the CNN as the prox: z = D(x + w).  Reference: S3:77-337."""
     import torch
     iter_num = PNP_ADMM_L1_D_opts.get('iter_num', 20)      # S3:83-84
@@ -284,7 +286,8 @@ def PNP_ADMM_L1_D(model_name, mask, noises, images=None, y=None, mask_id=None, t
     job = _Job(mask, noises, model_name, '_' + model_name + '_PNP_ADMM_L1_D', images, y, mask_id, testsets,
                testset_name, results, save_E, device, psnr_fmt='{:.2f}', coils=coils, coil_id=coil_id, cg_iters=cg_iters,
                virtual_coils=virtual_coils, noise_cov=noise_cov, calib=calib, maps_radius=maps_radius,
-               maps_power_iters=maps_power_iters, maps_thresh=maps_thresh)            # file name S3:308, PSNR format S3:320
+               maps_power_iters=maps_power_iters, maps_thresh=maps_thresh, maps_method=maps_method,
+               maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop)            # file name S3:308, PSNR format S3:320
     den = _load_model(model_name, model, model_zoo, iter_num, noises, x8, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))
     with torch.cuda.device(dev), torch.no_grad(), job.open_engine(torch.cuda.current_stream(dev).cuda_stream) as eng:
         B, H, W = job.B, job.H, job.W

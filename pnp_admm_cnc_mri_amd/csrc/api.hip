@@ -113,6 +113,13 @@ struct Coils {
     bool own_any = false;
 };
 
+// The three stage times of a coil-map estimator (pnp_*_stage_times): ms accumulates since the last read, the events exist once enabled.
+struct StageTimer {
+    bool on = false;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float ms[3] = {0.f, 0.f, 0.f};
+};
+
 struct pnp_ctx {
     int device = 0, H = 0, W = 0, Bmax = 0;
     int B = 0, K = 0;                 // current problem (0 = none uploaded)
@@ -146,17 +153,11 @@ struct pnp_ctx {
     int spin_k = 1, spin_p = 0;       // ... per_prox of them a step, and the cursor: prox steps since it was last set
     void* wv_acc = nullptr;           // [Bmax][H][W] real: the sum of the shifts' z+ (by the first per_prox > 1)
     Coils coils;
-    void* cm_scratch = nullptr;       // pnp_coil_maps: low-resolution coil images, lambda, span maxima, missing points (coilmaps_scratch; on first use)
-    size_t cm_bytes = 0;
-    bool cm_timing = false;           // pnp_coil_maps_stage_times: every pass is bracketed by HIP events and synchronised
-    hipEvent_t cm_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    void* es_scratch = nullptr;       // pnp_espirit_maps / pnp_espirit_eigmaps: espirit_scratch, on first use
-    size_t es_bytes = 0;
+    void* maps_scratch = nullptr;     // the coil-map estimators' array, laid out by the call that runs (coilmaps_scratch, espirit_scratch); on first use
+    size_t maps_bytes = 0;
+    StageTimer cm_t;                  // pnp_coil_maps_stage_times: window, transform, eigenvectors + support; every pass is synchronised
+    StageTimer es_t;                  // pnp_espirit_stage_times: patch Gram (with its read-back), host stage, per-pixel kernel with support
     std::vector<int32_t> es_rank;     // the signal-space rank of every slice of the most recent pnp_espirit_maps (pnp_espirit_ranks)
-    bool es_timing = false;           // pnp_espirit_stage_times
-    float es_ms[3] = {0.f, 0.f, 0.f}; // patch Gram (with its read-back), host stage, per-pixel kernel with support
-    hipEvent_t es_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    float cm_ms[3] = {0.f, 0.f, 0.f}; // window, transform, eigenvectors + support: accumulated since the last read
 };
 
 // The context's buffers as the element type of its precision (R = float | double).
@@ -1291,12 +1292,12 @@ int pnp_ctx_destroy(pnp_ctx* c) {
     coils_free(c);
     anysize_destroy(c->any);
     void* ptrs[] = {c->y, c->work, c->z, c->w, c->x, c->mask_bank, c->mask_id, c->gt, c->acc, c->stage, c->ssim_part,
-                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc, c->wv_coef, c->wv_acc, c->cm_scratch, c->es_scratch};
+                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc, c->wv_coef, c->wv_acc, c->maps_scratch};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
-    for (hipEvent_t e : c->cm_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->es_ev) if (e) (void)hipEventDestroy(e);
+    for (StageTimer* t : {&c->cm_t, &c->es_t})
+        for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
     delete c;
     return PNP_OK;
 }
@@ -1483,16 +1484,32 @@ int pnp_dual_clamp(pnp_ctx* c, float* x, float* z, float* w) {
     return PNP_OK;
 }
 
+extern "C++" {
+// the 2-D transform of B <= Bmax slices, arguments unchecked: rows in -> out, columns in place, 1/N on the inverse
+template <typename R>
+static int fft2_run(pnp_ctx* c, const typename CxOf<R>::type* in, typename CxOf<R>::type* out, int B, bool inv) {
+    RowArgsT<R> ra{};
+    ra.cin = in; ra.cout = out; ra.scale = inv ? R(1) / (R)c->N : R(1); ra.nrows = B * c->H;
+    HIPCHK(rows<R>(c, IN_COMPLEX, inv, EPI_COMPLEX, ra));
+    ColArgsT<R> ca{};
+    ca.in = out; ca.out = out; ca.B = B;
+    HIPCHK(cols<R>(c, !inv, MID_NONE, inv, ca));
+    return PNP_OK;
+}
+
+// the inverse transform of `count` pseudo-slices, src -> dst, in chunks of at most Bmax
+template <typename R>
+static int ifft2_chunks(pnp_ctx* c, const typename CxOf<R>::type* src, typename CxOf<R>::type* dst, int count) {
+    for (int s0 = 0; s0 < count; s0 += c->Bmax)
+        if (int rc = fft2_run<R>(c, src + (size_t)s0 * c->N, dst + (size_t)s0 * c->N, count - s0 < c->Bmax ? count - s0 : c->Bmax, true)) return rc;
+    return PNP_OK;
+}
+}  // extern "C++"
+
 static int fft2_any(pnp_ctx* c, const float* in, float* out, int B, bool inv) {
     if (!in || !out) return fail(PNP_E_ARG, "fft2: null pointer");
     if (B < 1 || B > c->Bmax) return fail(PNP_E_ARG, "fft2: B=%d out of range [1,%d]", B, c->Bmax);
-    RowArgs ra{};
-    ra.cin = (const float2*)in; ra.cout = (float2*)out; ra.scale = inv ? 1.0f / (float)c->N : 1.0f; ra.nrows = B * c->H;
-    HIPCHK(rows<float>(c, IN_COMPLEX, inv, EPI_COMPLEX, ra));
-    ColArgs ca{};
-    ca.in = (const float2*)out; ca.out = (float2*)out; ca.B = B;
-    HIPCHK(cols<float>(c, !inv, MID_NONE, inv, ca));
-    return PNP_OK;
+    return fft2_run<float>(c, (const float2*)in, (float2*)out, B, inv);
 }
 
 int pnp_fft2_fwd(pnp_ctx* c, const float* in, float* out, int B) { CTX(c); F32_ONLY(c); return fft2_any(c, in, out, B, false); }
@@ -1854,16 +1871,19 @@ int pnp_coilmaps_check(int C, int ncal, int radius, int power_iters, double thre
     }
 }
 
+// ---- what pnp_coil_maps and pnp_espirit_maps share on the host: argument rules, scratch array, missing-point report, stage timers (the
+// calibration pass itself is launch_calib_window and ifft2_chunks) ----
 extern "C++" {
+// The pointer rules of both estimators (lambda may be null).  `rule` is the estimator's own pnp_*_check of its scalars, made by the caller:
+// it is reported where it always was, after the null and range rules and before alignment and overlap.
 template <typename R>
-static int coil_maps_any(const char* who, pnp_ctx* c, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, R* maps, R* lambda, int B,
-                         int C, int ncal, int radius, int power_iters, double thresh) {
+static int maps_args(const char* who, const pnp_ctx* c, const R* y, const uint8_t* mask_bank, const R* maps, const R* lambda, int B, int C, int rule) {
     using Cx = typename CxOf<R>::type;
     if (c->f64 != (sizeof(R) == 8))
         return fail(PNP_E_STATE, sizeof(R) == 8 ? "%s: needs a context made by pnp_ctx_create_any_f64" : "%s: not available on an fp64 validation context", who);
     if (!y || !mask_bank || !maps) return fail(PNP_E_ARG, "%s: null pointer", who);
     if (B < 1 || B > 65535) return fail(PNP_E_ARG, "%s: B must be 1..65535 (got %d)", who, B);
-    if (int rc = pnp_coilmaps_check(C, ncal, radius, power_iters, thresh, c->H, c->W)) return rc;
+    if (rule) return rule;
     if ((uintptr_t)y % sizeof(Cx) || (uintptr_t)maps % sizeof(Cx) || (lambda && (uintptr_t)lambda % sizeof(R)))
         return fail(PNP_E_ARG, "%s: y and maps_out must be aligned to one complex value, lambda_out to one real", who);
     const size_t N = c->N, bytes = (size_t)B * C * N * sizeof(Cx);
@@ -1873,20 +1893,53 @@ static int coil_maps_any(const char* who, pnp_ctx* c, const R* y, const uint8_t*
         const size_t lb = (size_t)B * N * sizeof(R);
         if ((l0 < m0 + bytes && m0 < l0 + lb) || (l0 < y0 + bytes && y0 < l0 + lb)) return fail(PNP_E_ARG, "%s: lambda_out must not overlap y or maps_out", who);
     }
-    const CoilmapsScratch lay = coilmaps_scratch(B, C, c->Bmax, N, c->f64);
-    if (c->cm_bytes < lay.bytes) {
-        HIPCHK(hipStreamSynchronize(c->stream));             // an earlier call on this stream may still read the old array
-        if (c->cm_scratch) (void)hipFree(c->cm_scratch);
-        c->cm_scratch = nullptr; c->cm_bytes = 0;
-        const hipError_t e = hipMalloc(&c->cm_scratch, lay.bytes);
-        if (e != hipSuccess) {
-            c->cm_scratch = nullptr;
-            return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the scratch array: %zu bytes asked for (B=%d, C=%d, Bmax=%d, %dx%d): %s",
-                        who, lay.bytes, B, C, c->Bmax, c->H, c->W, hipGetErrorString(e));
-        }
-        c->cm_bytes = lay.bytes;
+    return PNP_OK;
+}
+
+// the context's scratch array of the estimators, grown on demand
+static int maps_reserve(const char* who, pnp_ctx* c, size_t bytes, int B, int C) {
+    if (c->maps_bytes >= bytes) return PNP_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));             // an earlier call on this stream may still read the old array
+    if (c->maps_scratch) (void)hipFree(c->maps_scratch);
+    c->maps_scratch = nullptr; c->maps_bytes = 0;
+    const hipError_t e = hipMalloc(&c->maps_scratch, bytes);
+    if (e != hipSuccess) {
+        c->maps_scratch = nullptr;
+        return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the scratch array: %zu bytes asked for (B=%d, C=%d, Bmax=%d, %dx%d): %s",
+                    who, bytes, B, C, c->Bmax, c->H, c->W, hipGetErrorString(e));
     }
-    char* base = (char*)c->cm_scratch;
+    c->maps_bytes = bytes;
+    return PNP_OK;
+}
+
+// k_calib_window's report of slices b0 .. b0 + n - 1, read back to the host: the first slice whose mask has a hole in the region
+static int maps_missing(const char* who, const pnp_ctx* c, const int32_t* miss, int b0, int n, int ncal) {
+    for (int b = 0; b < n; ++b)
+        if (miss[b] >= 0)
+            return fail(PNP_E_ARG, "%s: the mask of slice %d does not sample calibration point (%d, %d) of the %d x %d region: every point of it must be measured",
+                        who, b0 + b, miss[b] / c->W, miss[b] % c->W, ncal, ncal);
+    return PNP_OK;
+}
+
+static int stage_times(StageTimer& t, int enable, float* ms_out) {
+    if (enable)
+        for (hipEvent_t& e : t.ev) if (!e) HIPCHK(hipEventCreate(&e));
+    if (ms_out) for (int k = 0; k < 3; ++k) ms_out[k] = t.ms[k];
+    for (float& v : t.ms) v = 0.f;
+    t.on = enable != 0;
+    return PNP_OK;
+}
+
+template <typename R>
+static int coil_maps_any(const char* who, pnp_ctx* c, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, R* maps, R* lambda, int B,
+                         int C, int ncal, int radius, int power_iters, double thresh) {
+    using Cx = typename CxOf<R>::type;
+    if (int rc = maps_args<R>(who, c, y, mask_bank, maps, lambda, B, C, pnp_coilmaps_check(C, ncal, radius, power_iters, thresh, c->H, c->W))) return rc;
+    const size_t N = c->N;
+    const CoilmapsScratch lay = coilmaps_scratch(B, C, c->Bmax, N, c->f64);
+    if (int rc = maps_reserve(who, c, lay.bytes, B, C)) return rc;
+    StageTimer& tm = c->cm_t;
+    char* base = (char*)c->maps_scratch;
     Cx* img = (Cx*)(base + lay.img);
     R* part = (R*)(base + lay.part);
     int32_t* miss = (int32_t*)(base + lay.miss);
@@ -1898,51 +1951,31 @@ static int coil_maps_any(const char* who, pnp_ctx* c, const R* y, const uint8_t*
         R* mb = maps + 2 * (size_t)b0 * C * N;
         R* lam = lambda ? lambda + (size_t)b0 * N : (R*)(base + lay.lambda);
         // the windowed region goes through maps_out: rows maps_out -> scratch, columns in place, the eigenvector kernel scratch -> maps_out
-        if (c->cm_timing) HIPCHK(hipEventRecord(c->cm_ev[0], c->stream));
+        if (tm.on) HIPCHK(hipEventRecord(tm.ev[0], c->stream));
         HIPCHK(launch_calib_window<R>(c->stream, yb, mask_bank, mask_id ? mask_id + b0 : nullptr, mb, miss + b0, n, C, c->H, c->W, ncal));
-        if (c->cm_timing) HIPCHK(hipEventRecord(c->cm_ev[1], c->stream));
-        for (int s0 = 0; s0 < n * C; s0 += c->Bmax) {        // the transform in chunks of at most Bmax pseudo-slices
-            const int ns = n * C - s0 < c->Bmax ? n * C - s0 : c->Bmax;
-            RowArgsT<R> ra{};
-            ra.cin = (const Cx*)mb + (size_t)s0 * N; ra.cout = img + (size_t)s0 * N; ra.scale = R(1) / (R)N; ra.nrows = ns * c->H;
-            HIPCHK(rows<R>(c, IN_COMPLEX, true, EPI_COMPLEX, ra));
-            ColArgsT<R> ca{};
-            ca.in = img + (size_t)s0 * N; ca.out = img + (size_t)s0 * N; ca.B = ns;
-            HIPCHK(cols<R>(c, false, MID_NONE, true, ca));
-        }
-        if (c->cm_timing) HIPCHK(hipEventRecord(c->cm_ev[2], c->stream));
+        if (tm.on) HIPCHK(hipEventRecord(tm.ev[1], c->stream));
+        if (int rc = ifft2_chunks<R>(c, (const Cx*)mb, img, n * C)) return rc;
+        if (tm.on) HIPCHK(hipEventRecord(tm.ev[2], c->stream));
         HIPCHK(launch_coil_eigmaps<R>(c->stream, (const R*)img, mb, lam, n, C, c->H, c->W, radius, power_iters));
-        HIPCHK(launch_coilmaps_support<R>(c->stream, lam, part, mb, n, C, N, tau2));
-        if (c->cm_timing) {
-            HIPCHK(hipEventRecord(c->cm_ev[3], c->stream));
-            HIPCHK(hipEventSynchronize(c->cm_ev[3]));
+        HIPCHK(launch_maps_support<R>(c->stream, nullptr, R(0), lam, tau2, part, mb, n, C, N));
+        if (tm.on) {
+            HIPCHK(hipEventRecord(tm.ev[3], c->stream));
+            HIPCHK(hipEventSynchronize(tm.ev[3]));
             for (int k = 0; k < 3; ++k) {
                 float ms = 0.f;
-                HIPCHK(hipEventElapsedTime(&ms, c->cm_ev[k], c->cm_ev[k + 1]));
-                c->cm_ms[k] += ms;
+                HIPCHK(hipEventElapsedTime(&ms, tm.ev[k], tm.ev[k + 1]));
+                tm.ms[k] += ms;
             }
         }
     }
     std::vector<int32_t> host((size_t)B);
     HIPCHK(hipMemcpyAsync(host.data(), miss, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    for (int b = 0; b < B; ++b)
-        if (host[b] >= 0)
-            return fail(PNP_E_ARG, "%s: the mask of slice %d does not sample calibration point (%d, %d) of the %d x %d region: every point of it must be measured",
-                        who, b, host[b] / c->W, host[b] % c->W, ncal, ncal);
-    return PNP_OK;
+    return maps_missing(who, c, host.data(), 0, B, ncal);
 }
 }  // extern "C++"
 
-int pnp_coil_maps_stage_times(pnp_ctx* c, int enable, float* ms_out) {
-    CTX(c);
-    if (enable)
-        for (hipEvent_t& e : c->cm_ev) if (!e) HIPCHK(hipEventCreate(&e));
-    if (ms_out) for (int k = 0; k < 3; ++k) ms_out[k] = c->cm_ms[k];
-    for (float& v : c->cm_ms) v = 0.f;
-    c->cm_timing = enable != 0;
-    return PNP_OK;
-}
+int pnp_coil_maps_stage_times(pnp_ctx* c, int enable, float* ms_out) { CTX(c); return stage_times(c->cm_t, enable, ms_out); }
 
 int pnp_coil_maps(pnp_ctx* c, const float* y, const uint8_t* mask_bank, const int32_t* mask_id, float* maps_out, float* lambda_out, int B, int C,
                   int ncal, int radius, int power_iters, double thresh) {
@@ -1990,22 +2023,6 @@ static int patch_gram_any(const char* who, void* stream, const R* y, const uint8
     return PNP_OK;
 }
 
-// the context's ESPIRiT scratch array, grown on demand
-static int espirit_reserve(const char* who, pnp_ctx* c, size_t bytes, int B, int C) {
-    if (c->es_bytes >= bytes) return PNP_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));             // an earlier call on this stream may still read the old array
-    if (c->es_scratch) (void)hipFree(c->es_scratch);
-    c->es_scratch = nullptr; c->es_bytes = 0;
-    const hipError_t e = hipMalloc(&c->es_scratch, bytes);
-    if (e != hipSuccess) {
-        c->es_scratch = nullptr;
-        return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the scratch array: %zu bytes asked for (B=%d, C=%d, Bmax=%d, %dx%d): %s",
-                    who, bytes, B, C, c->Bmax, c->H, c->W, hipGetErrorString(e));
-    }
-    c->es_bytes = bytes;
-    return PNP_OK;
-}
-
 // the phasor tables of the context's shape into the scratch array; the host copies live in `keep` until the caller has synchronised
 template <typename R>
 static int espirit_tables(pnp_ctx* c, const EspiritScratch& lay, int kernel, std::vector<R>& keep) {
@@ -2013,7 +2030,7 @@ static int espirit_tables(pnp_ctx* c, const EspiritScratch& lay, int kernel, std
     keep.resize(nh + nw);
     espirit_phasor_table<R>(c->H, kernel, keep.data());
     espirit_phasor_table<R>(c->W, kernel, keep.data() + nh);
-    char* base = (char*)c->es_scratch;
+    char* base = (char*)c->maps_scratch;
     HIPCHK(hipMemcpyAsync(base + lay.eh, keep.data(), nh * sizeof(R), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(base + lay.ew, keep.data() + nh, nw * sizeof(R), hipMemcpyHostToDevice, c->stream));
     return PNP_OK;
@@ -2033,8 +2050,8 @@ static int espirit_eigmaps_any(const char* who, pnp_ctx* c, const R* img, const 
     const char *i0 = (const char*)img, *m0 = (const char*)maps;
     if (i0 < m0 + bytes && m0 < i0 + bytes) return fail(PNP_E_ARG, "%s: maps_out and the images must not overlap", who);
     const EspiritScratch lay = espirit_scratch(B, B, C, kernel, c->H, c->W, c->f64, false);
-    if (int rc = espirit_reserve(who, c, lay.bytes, B, C)) return rc;
-    char* base = (char*)c->es_scratch;
+    if (int rc = maps_reserve(who, c, lay.bytes, B, C)) return rc;
+    char* base = (char*)c->maps_scratch;
     std::vector<R> keep;
     if (int rc = espirit_tables<R>(c, lay, kernel, keep)) return rc;
     R* inorm = (R*)(base + lay.inorm);
@@ -2048,24 +2065,14 @@ template <typename R>
 static int espirit_maps_any(const char* who, pnp_ctx* c, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, R* maps, R* lambda, int B,
                             int C, int ncal, int kernel, int power_iters, double sigma, double crop, double thresh) {
     using Cx = typename CxOf<R>::type;
-    if (c->f64 != (sizeof(R) == 8))
-        return fail(PNP_E_STATE, sizeof(R) == 8 ? "%s: needs a context made by pnp_ctx_create_any_f64" : "%s: not available on an fp64 validation context", who);
-    if (!y || !mask_bank || !maps) return fail(PNP_E_ARG, "%s: null pointer", who);
-    if (B < 1 || B > 65535) return fail(PNP_E_ARG, "%s: B must be 1..65535 (got %d)", who, B);
-    if (int rc = pnp_espirit_check(C, ncal, kernel, power_iters, sigma, crop, thresh, c->H, c->W)) return rc;
-    if ((uintptr_t)y % sizeof(Cx) || (uintptr_t)maps % sizeof(Cx) || (lambda && (uintptr_t)lambda % sizeof(R)))
-        return fail(PNP_E_ARG, "%s: y and maps_out must be aligned to one complex value, lambda_out to one real", who);
-    const size_t N = c->N, bytes = (size_t)B * C * N * sizeof(Cx);
-    const char *y0 = (const char*)y, *m0 = (const char*)maps, *l0 = (const char*)lambda;
-    if (y0 < m0 + bytes && m0 < y0 + bytes) return fail(PNP_E_ARG, "%s: maps_out and y must not overlap", who);
-    if (lambda) {
-        const size_t lb = (size_t)B * N * sizeof(R);
-        if ((l0 < m0 + bytes && m0 < l0 + lb) || (l0 < y0 + bytes && y0 < l0 + lb)) return fail(PNP_E_ARG, "%s: lambda_out must not overlap y or maps_out", who);
-    }
+    if (int rc = maps_args<R>(who, c, y, mask_bank, maps, lambda, B, C, pnp_espirit_check(C, ncal, kernel, power_iters, sigma, crop, thresh, c->H, c->W)))
+        return rc;
+    const size_t N = c->N;
     const int nb = coilmaps_pass_slices(B, C, c->Bmax), n = espirit_columns(C, kernel);
     const EspiritScratch lay = espirit_scratch(B, nb, C, kernel, c->H, c->W, c->f64, true);
-    if (int rc = espirit_reserve(who, c, lay.bytes, B, C)) return rc;
-    char* base = (char*)c->es_scratch;
+    if (int rc = maps_reserve(who, c, lay.bytes, B, C)) return rc;
+    StageTimer& tm = c->es_t;
+    char* base = (char*)c->maps_scratch;
     Cx* img = (Cx*)(base + lay.img);
     R* inorm = (R*)(base + lay.inorm);
     R* part = (R*)(base + lay.part);
@@ -2087,25 +2094,14 @@ static int espirit_maps_any(const char* who, pnp_ctx* c, const R* y, const uint8
         R* lam = lambda ? lambda + (size_t)b0 * N : (R*)(base + lay.lambda);
         // the windowed region goes through maps_out: rows maps_out -> scratch, columns in place; the per-pixel kernel scratch -> maps_out
         HIPCHK(launch_calib_window<R>(c->stream, yb, mask_bank, mask_id ? mask_id + b0 : nullptr, mb, miss + b0, ns, C, c->H, c->W, ncal));
-        for (int s0 = 0; s0 < ns * C; s0 += c->Bmax) {       // the transform in chunks of at most Bmax pseudo-slices
-            const int nsl = ns * C - s0 < c->Bmax ? ns * C - s0 : c->Bmax;
-            RowArgsT<R> ra{};
-            ra.cin = (const Cx*)mb + (size_t)s0 * N; ra.cout = img + (size_t)s0 * N; ra.scale = R(1) / (R)N; ra.nrows = nsl * c->H;
-            HIPCHK(rows<R>(c, IN_COMPLEX, true, EPI_COMPLEX, ra));
-            ColArgsT<R> ca{};
-            ca.in = img + (size_t)s0 * N; ca.out = img + (size_t)s0 * N; ca.B = nsl;
-            HIPCHK(cols<R>(c, false, MID_NONE, true, ca));
-        }
-        if (c->es_timing) HIPCHK(hipEventRecord(c->es_ev[0], c->stream));
+        if (int rc = ifft2_chunks<R>(c, (const Cx*)mb, img, ns * C)) return rc;
+        if (tm.on) HIPCHK(hipEventRecord(tm.ev[0], c->stream));
         HIPCHK(launch_calib_patch_gram<R>(c->stream, yb, mask_bank, mask_id ? mask_id + b0 : nullptr, gram, ns, C, c->H, c->W, ncal, kernel));
         HIPCHK(hipMemcpyAsync(hgram.data(), gram, (size_t)ns * n * n * 16, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(hmiss.data(), miss + b0, (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (c->es_timing) HIPCHK(hipEventRecord(c->es_ev[1], c->stream));
+        if (tm.on) HIPCHK(hipEventRecord(tm.ev[1], c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        for (int b = 0; b < ns; ++b)
-            if (hmiss[b] >= 0)
-                return fail(PNP_E_ARG, "%s: the mask of slice %d does not sample calibration point (%d, %d) of the %d x %d region: every point of it must be measured",
-                            who, b0 + b, hmiss[b] / c->W, hmiss[b] % c->W, ncal, ncal);
+        if (int rc = maps_missing(who, c, hmiss.data(), b0, ns, ncal)) return rc;
         if (!coilmix_all_finite(hgram.data(), (size_t)ns * n * n * 2)) return fail(PNP_E_ARG, "%s: the calibration region has a non-finite entry", who);
         // the host stage: slice b of the pass on thread b % threads, every slice on its own arrays
         const auto t0 = std::chrono::steady_clock::now();
@@ -2127,20 +2123,20 @@ static int espirit_maps_any(const char* who, pnp_ctx* c, const R* y, const uint8
         }
         for (int b = 0; b < ns; ++b)
             if (status[b]) return fail(PNP_E_ARG, "%s: the Jacobi sweeps did not converge on the Gram matrix of slice %d", who, b0 + b);
-        if (c->es_timing) c->es_ms[1] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (tm.on) tm.ms[1] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         HIPCHK(hipMemcpyAsync(wdev, hw.data(), (size_t)ns * wn * 2 * sizeof(R), hipMemcpyHostToDevice, c->stream));
-        if (c->es_timing) HIPCHK(hipEventRecord(c->es_ev[2], c->stream));
+        if (tm.on) HIPCHK(hipEventRecord(tm.ev[2], c->stream));
         HIPCHK(launch_espirit_maps<R>(c->stream, (const R*)img, wdev, (const R*)(base + lay.eh), (const R*)(base + lay.ew), mb, lam, inorm, ns, C,
                                       c->H, c->W, kernel, power_iters));
-        HIPCHK(launch_espirit_support<R>(c->stream, lam, inorm, part, mb, ns, C, N, (R)crop, (R)thresh));
-        if (c->es_timing) HIPCHK(hipEventRecord(c->es_ev[3], c->stream));
+        HIPCHK(launch_maps_support<R>(c->stream, lam, (R)crop, inorm, (R)thresh, part, mb, ns, C, N));
+        if (tm.on) HIPCHK(hipEventRecord(tm.ev[3], c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));             // the next pass rewrites the host arrays the copies read
-        if (c->es_timing) {
+        if (tm.on) {
             float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, c->es_ev[0], c->es_ev[1]));
-            c->es_ms[0] += ms;
-            HIPCHK(hipEventElapsedTime(&ms, c->es_ev[2], c->es_ev[3]));
-            c->es_ms[2] += ms;
+            HIPCHK(hipEventElapsedTime(&ms, tm.ev[0], tm.ev[1]));
+            tm.ms[0] += ms;
+            HIPCHK(hipEventElapsedTime(&ms, tm.ev[2], tm.ev[3]));
+            tm.ms[2] += ms;
         }
     }
     c->es_rank = rank;
@@ -2198,14 +2194,6 @@ int pnp_espirit_ranks(pnp_ctx* c, int32_t* rank_out, int B) {
     return PNP_OK;
 }
 
-int pnp_espirit_stage_times(pnp_ctx* c, int enable, float* ms_out) {
-    CTX(c);
-    if (enable)
-        for (hipEvent_t& e : c->es_ev) if (!e) HIPCHK(hipEventCreate(&e));
-    if (ms_out) for (int k = 0; k < 3; ++k) ms_out[k] = c->es_ms[k];
-    for (float& v : c->es_ms) v = 0.f;
-    c->es_timing = enable != 0;
-    return PNP_OK;
-}
+int pnp_espirit_stage_times(pnp_ctx* c, int enable, float* ms_out) { CTX(c); return stage_times(c->es_t, enable, ms_out); }
 
 }  // extern "C"

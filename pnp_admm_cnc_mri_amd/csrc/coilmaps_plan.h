@@ -31,7 +31,7 @@ namespace pnp {
 constexpr int COILMAPS_MAX_RADIUS = 3;        // 0 <= radius <= COILMAPS_MAX_RADIUS: patches of 1, 9, 25, 49 pixels
 constexpr int COILMAPS_MAX_ITERS = 16;        // 1 <= power_iters <= COILMAPS_MAX_ITERS
 constexpr int COILMAPS_WIN_THREADS = 256;     // k_calib_window: a thread owns 16 bytes of consecutive points (coilmix_points)
-constexpr int COILMAPS_SPAN = 4096;           // k_coilmaps_lmax / k_coilmaps_support: pixels of one slice per workgroup of 256 threads
+constexpr int COILMAPS_SPAN = 4096;           // k_maps_keymax / k_maps_support: pixels of one slice per workgroup of 256 threads
 constexpr int COILMAPS_SUP_THREADS = 256;
 constexpr size_t COILMAPS_LDS_SOFT = 64 * 1024;     // the tile is the largest whose staged coil images stay within this ...
 constexpr size_t COILMAPS_LDS_HARD = 128 * 1024;    // ... and where none does (C = 32 in double at radius 3) the smallest, within this

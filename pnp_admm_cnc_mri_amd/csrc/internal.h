@@ -1,6 +1,7 @@
 // Internal declarations shared by the translation units of libpnpmri.so (not part of the ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <stdint.h>
 #include <stdlib.h>
 #include "loop_schedule.h"
@@ -24,6 +25,20 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 template <typename R> struct CxOf;
 template <> struct CxOf<float>  { using type = float2; };
 template <> struct CxOf<double> { using type = double2; };
+
+// More than 64 KiB of dynamic LDS needs an opt-in per kernel and device: `done` is the launcher's own static std::atomic<bool>[64] of
+// that kernel instantiation.  Only a launch that needs it makes it, and it asks for `cap`, the bound of every configuration of the
+// kernel: the attribute is a cap, not an allocation, so one value serves every context on the device and a racing second opt-in writes
+// the same value.
+inline hipError_t lds_opt_in(const void* fn, std::atomic<bool>* done, size_t lds, size_t cap) {
+    if (lds <= 64 * 1024) return hipSuccess;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (done[dev].load(std::memory_order_acquire)) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
+    if (e == hipSuccess) done[dev].store(true, std::memory_order_release);
+    return e;
+}
 
 enum RowIn  { IN_COMPLEX = 0, IN_REAL = 1, IN_REAL_DIFF = 2 };
 enum RowEpi { EPI_COMPLEX = 0, EPI_ABS_REAL = 1, EPI_ABS_COMPLEX = 2, EPI_L1 = 3, EPI_CNC = 4 };
@@ -122,22 +137,22 @@ template <typename R> hipError_t launch_coil_gram(hipStream_t s, const R* y, con
 // coil sensitivity maps from the calibration region (kernels_coilmaps.hip, coilmaps_plan.h): interleaved complex arrays in R.  The windowed
 // calibration region of B C pseudo-slices (+0 elsewhere) and the lowest offset of an unsampled calibration point per slice, miss [B] (-1:
 // none); the local dominant eigenvectors of the low-resolution coil images img [B][C][H][W] -> maps [B][C][H][W], lambda [B][H][W]; the
-// support: maps zeroed where lambda < tau2 * the slice's largest lambda (part: scratch of B * coilmaps_spans(N) values)
+// support stage of both estimators: maps zeroed where gate < floor (gate null: no such rule) or key < frac * the slice's largest key (part:
+// scratch of B * coilmaps_spans(N) values).  Here key = lambda, frac = tau2 and no gate
 template <typename R> hipError_t launch_calib_window(hipStream_t s, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, R* out,
                                                      int32_t* miss, int B, int C, int H, int W, int ncal);
 template <typename R> hipError_t launch_coil_eigmaps(hipStream_t s, const R* img, R* maps, R* lambda, int B, int C, int H, int W, int r, int iters);
-template <typename R> hipError_t launch_coilmaps_support(hipStream_t s, const R* lambda, R* part, R* maps, int B, int C, size_t N, R tau2);
+template <typename R> hipError_t launch_maps_support(hipStream_t s, const R* gate, R floor, const R* key, R frac, R* part, R* maps, int B, int C,
+                                                     size_t N);
 
 // ESPIRiT coil maps (kernels_espirit.hip, espirit_plan.h).  The patch Gram matrices of the calibration block, gram [B][n][n] complex double,
 // n = C k^2; the per-pixel stage: img [B][C][H][W], w [B][C][C][D][D] (D = 2 k - 1), the phasor tables eh [H][D] and ew [W][D] -> the unit
-// vectors maps [B][C][H][W], lambda [B][H][W] and inorm [B][H][W] = ||I||; the support: maps zeroed where lambda < crop or inorm < tau *
-// the slice's largest inorm (part: scratch of B * coilmaps_spans(N) values)
+// vectors maps [B][C][H][W], lambda [B][H][W] and inorm [B][H][W] = ||I||; the support is launch_maps_support with gate = lambda, floor =
+// crop, key = inorm, frac = tau
 template <typename R> hipError_t launch_calib_patch_gram(hipStream_t s, const R* y, const uint8_t* mask_bank, const int32_t* mask_id, double* gram,
                                                          int B, int C, int H, int W, int ncal, int k);
 template <typename R> hipError_t launch_espirit_maps(hipStream_t s, const R* img, const R* w, const R* eh, const R* ew, R* maps, R* lambda,
                                                      R* inorm, int B, int C, int H, int W, int k, int iters);
-template <typename R> hipError_t launch_espirit_support(hipStream_t s, const R* lambda, const R* inorm, R* part, R* maps, int B, int C, size_t N,
-                                                        R crop, R tau);
 
 // pointwise
 hipError_t launch_prox(hipStream_t s, bool cnc, const float* x, float* z, float* w, ProxParams p, size_t n);

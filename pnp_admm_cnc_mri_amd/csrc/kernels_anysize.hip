@@ -153,23 +153,12 @@ __global__ __launch_bounds__(ANY_THREADS) void k_any_rows(RowArgsT<R> p, AxisT<R
     }
 }
 
-// More than 64 KiB of dynamic LDS needs an opt-in per kernel and device.  Only a launch that needs it makes it (a double Bluestein line,
-// 64 KiB + 32 B), and the opt-in asks for ANY_LDS_MAX, the bound of every configuration: the attribute is a cap, not an allocation,
-// so one value serves every context on the device and a racing second opt-in writes the same value.
-static hipError_t lds_opt_in(const void* fn, std::atomic<bool>* done, size_t lds) {
-    if (lds <= 64 * 1024) return hipSuccess;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (done[dev].load(std::memory_order_acquire)) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ANY_LDS_MAX);
-    if (e == hipSuccess) done[dev].store(true, std::memory_order_release);
-    return e;
-}
-
+// The LDS opt-in (internal.h) of the any-size kernels: only a double Bluestein line needs it (64 KiB + 32 B); ANY_LDS_MAX bounds every
+// configuration.
 template <int IN, bool INV, int EPI, typename R>
 static hipError_t any_rows_t(hipStream_t s, const AxisT<R>& t, const RowArgsT<R>& a) {
     static std::atomic<bool> done[64] = {};
-    if (hipError_t e = lds_opt_in((const void*)k_any_rows<IN, INV, EPI, R>, done, any_lds(t))) return e;
+    if (hipError_t e = lds_opt_in((const void*)k_any_rows<IN, INV, EPI, R>, done, any_lds(t), ANY_LDS_MAX)) return e;
     const unsigned grid = (unsigned)((a.nrows + t.lines - 1) / t.lines);
     hipLaunchKernelGGL((k_any_rows<IN, INV, EPI, R>), dim3(grid), dim3(ANY_THREADS), any_lds(t), s, a, t);
     return hipGetLastError();
@@ -301,7 +290,7 @@ hipError_t anysize_coil_rows_in(const AnySize* A, hipStream_t s, const CoilRowAr
     const AxisT<R> t = coil_axis(axis<R>(A, 0));
     static std::atomic<bool> done[2][64] = {};
     const void* fn = a.cin ? (const void*)k_any_rows_coil_in<false, R> : (const void*)k_any_rows_coil_in<true, R>;
-    if (hipError_t e = lds_opt_in(fn, done[a.cin ? 0 : 1], coil_lds(t))) return e;
+    if (hipError_t e = lds_opt_in(fn, done[a.cin ? 0 : 1], coil_lds(t), ANY_LDS_MAX)) return e;
     const unsigned grid = (unsigned)((a.nrows + t.lines - 1) / t.lines);
     if (a.cin) hipLaunchKernelGGL((k_any_rows_coil_in<false, R>), dim3(grid), dim3(ANY_THREADS), coil_lds(t), s, a, t);
     else       hipLaunchKernelGGL((k_any_rows_coil_in<true, R>), dim3(grid), dim3(ANY_THREADS), coil_lds(t), s, a, t);
@@ -315,7 +304,7 @@ hipError_t anysize_coil_rows_epi(const AnySize* A, hipStream_t s, const CoilRowA
     if (!A || A->f64 != std::is_same<R, double>::value || a.ncoils < 1 || a.ncoils > COIL_MAX_C || a.H != A->plan[1].n) return hipErrorInvalidValue;
     const AxisT<R> t = coil_axis(axis<R>(A, 0));
     static std::atomic<bool> done[64] = {};
-    if (hipError_t e = lds_opt_in((const void*)k_any_rows_coil_epi<R>, done, coil_lds(t))) return e;
+    if (hipError_t e = lds_opt_in((const void*)k_any_rows_coil_epi<R>, done, coil_lds(t), ANY_LDS_MAX)) return e;
     const unsigned grid = (unsigned)((a.nrows + t.lines - 1) / t.lines);
     hipLaunchKernelGGL((k_any_rows_coil_epi<R>), dim3(grid), dim3(ANY_THREADS), coil_lds(t), s, a, t);
     return hipGetLastError();
@@ -388,7 +377,7 @@ __global__ __launch_bounds__(ANY_THREADS) void k_any_cols(ColArgsT<R> p, AxisT<R
 template <bool PRE, int MID, bool POST, typename R>
 static hipError_t any_cols_t(hipStream_t s, const AxisT<R>& t, int W, const ColArgsT<R>& a) {
     static std::atomic<bool> done[64] = {};
-    if (hipError_t e = lds_opt_in((const void*)k_any_cols<PRE, MID, POST, R>, done, any_lds(t))) return e;
+    if (hipError_t e = lds_opt_in((const void*)k_any_cols<PRE, MID, POST, R>, done, any_lds(t), ANY_LDS_MAX)) return e;
     const unsigned grid = (unsigned)a.B * (unsigned)((W + t.lines - 1) / t.lines);
     hipLaunchKernelGGL((k_any_cols<PRE, MID, POST, R>), dim3(grid), dim3(ANY_THREADS), any_lds(t), s, a, t, W);
     return hipGetLastError();

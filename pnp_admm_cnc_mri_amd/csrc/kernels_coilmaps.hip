@@ -9,9 +9,9 @@
 //                       for all C coils in LDS as [pixel][coil] at a stride of an odd number of 16-byte slots; a thread keeps v and u (2 x CB
 //                       complex, CB = 4, 8, 16, 32) in registers for all iterations and reads a patch point's coils as consecutive 16-byte
 //                       slots.  16 (2r + 1)^2 C n flops per pixel; writes the unit vectors [B][C][H][W] and lambda [B][H][W].
-//   k_coilmaps_lmax     the maximum of lambda per span of COILMAPS_SPAN pixels, by a tree over the workgroup
-//   k_coilmaps_support  every workgroup of a slice recomputes the slice's maximum from the spans' partials and zeroes the vectors of its
-//                       span below tau2 * lambda_max
+//   k_maps_keymax       the maximum of the key (here lambda; ESPIRiT: inorm) per span of COILMAPS_SPAN pixels, by a tree over the workgroup
+//   k_maps_support      the support stage of both estimators: every workgroup of a slice recomputes the slice's maximum from the spans'
+//                       partials and zeroes the vectors of its span where key < frac * key_max or, with a gate array, gate < floor
 // Vector stores only, no atomics; no sum depends on the batch, on the tile or on a pixel's place in it.
 #include <atomic>
 #include "internal.h"
@@ -183,33 +183,34 @@ template <typename R> __device__ __forceinline__ R tree_max(R v, R* sh) {
 }
 
 template <typename R>
-__global__ __launch_bounds__(COILMAPS_SUP_THREADS) void k_coilmaps_lmax(const R* __restrict__ lambda, R* __restrict__ part, size_t N) {
+__global__ __launch_bounds__(COILMAPS_SUP_THREADS) void k_maps_keymax(const R* __restrict__ key, R* __restrict__ part, size_t N) {
     __shared__ R sh[COILMAPS_SUP_THREADS];
     const size_t lo = (size_t)blockIdx.x * COILMAPS_SPAN;
     const size_t hi = lo + COILMAPS_SPAN < N ? lo + COILMAPS_SPAN : N;
-    const R* l = lambda + (size_t)blockIdx.y * N;
-    R m = R(0);                                           // lambda is a norm: >= 0
+    const R* l = key + (size_t)blockIdx.y * N;
+    R m = R(0);                                           // the key is a norm: >= 0
     for (size_t p = lo + threadIdx.x; p < hi; p += COILMAPS_SUP_THREADS) if (l[p] > m) m = l[p];
     m = tree_max(m, sh);
     if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = m;
 }
 
 template <typename R>
-__global__ __launch_bounds__(COILMAPS_SUP_THREADS) void k_coilmaps_support(const R* __restrict__ lambda, const R* __restrict__ part,
-                                                                           typename CxOf<R>::type* __restrict__ maps, int Cn, size_t N, R tau2) {
+__global__ __launch_bounds__(COILMAPS_SUP_THREADS) void k_maps_support(const R* __restrict__ gate, R floor, const R* __restrict__ key, R frac,
+                                                                       const R* __restrict__ part, typename CxOf<R>::type* __restrict__ maps,
+                                                                       int Cn, size_t N) {
     using C = typename CxOf<R>::type;
     __shared__ R sh[COILMAPS_SUP_THREADS];
     const int b = blockIdx.y, spans = gridDim.x;
     R m = R(0);
     for (int j = threadIdx.x; j < spans; j += COILMAPS_SUP_THREADS) if (part[(size_t)b * spans + j] > m) m = part[(size_t)b * spans + j];
-    const R bar = tau2 * tree_max(m, sh);
+    const R bar = frac * tree_max(m, sh);
     const size_t lo = (size_t)blockIdx.x * COILMAPS_SPAN;
     const size_t hi = lo + COILMAPS_SPAN < N ? lo + COILMAPS_SPAN : N;
-    const R* l = lambda + (size_t)b * N;
+    const R* l = key + (size_t)b * N;
     C zero;
     zero.x = R(0); zero.y = R(0);
     for (size_t p = lo + threadIdx.x; p < hi; p += COILMAPS_SUP_THREADS) {
-        if (l[p] >= bar) continue;
+        if ((!gate || gate[(size_t)b * N + p] >= floor) && l[p] >= bar) continue;
         for (int c = 0; c < Cn; ++c) maps[((size_t)b * Cn + c) * N + p] = zero;
     }
 }
@@ -231,21 +232,11 @@ hipError_t launch_calib_window(hipStream_t s, const R* y, const uint8_t* mask_ba
     return hipGetLastError();
 }
 
-// More than 64 KiB of dynamic LDS needs an opt-in per kernel and device; the attribute is a cap, so COILMAPS_LDS_HARD serves every launch.
 template <typename R, int CB>
 static hipError_t eig_bucket(hipStream_t s, dim3 grid, CoilmapsTile t, size_t lds, const typename CxOf<R>::type* img,
                              typename CxOf<R>::type* maps, R* lambda, int Cn, int H, int W, int r, int iters) {
     static std::atomic<bool> done[64] = {};
-    if (lds > 64 * 1024) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        if (!done[dev].load(std::memory_order_acquire)) {
-            if (hipError_t e = hipFuncSetAttribute((const void*)k_coil_eigmaps<R, CB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)COILMAPS_LDS_HARD))
-                return e;
-            done[dev].store(true, std::memory_order_release);
-        }
-    }
+    if (hipError_t e = lds_opt_in((const void*)k_coil_eigmaps<R, CB>, done, lds, COILMAPS_LDS_HARD)) return e;
     hipLaunchKernelGGL((k_coil_eigmaps<R, CB>), grid, dim3((unsigned)(t.th * t.tw)), lds, s, img, maps, lambda, Cn, H, W, r, iters, t.th, t.tw);
     return hipGetLastError();
 }
@@ -268,19 +259,19 @@ hipError_t launch_coil_eigmaps(hipStream_t s, const R* img, R* maps, R* lambda, 
 }
 
 template <typename R>
-hipError_t launch_coilmaps_support(hipStream_t s, const R* lambda, R* part, R* maps, int B, int Cn, size_t N, R tau2) {
+hipError_t launch_maps_support(hipStream_t s, const R* gate, R floor, const R* key, R frac, R* part, R* maps, int B, int Cn, size_t N) {
     using C = typename CxOf<R>::type;
     const dim3 grid((unsigned)coilmaps_spans(N), (unsigned)B), blk(COILMAPS_SUP_THREADS);
-    hipLaunchKernelGGL(k_coilmaps_lmax<R>, grid, blk, 0, s, lambda, part, N);
+    hipLaunchKernelGGL(k_maps_keymax<R>, grid, blk, 0, s, key, part, N);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(k_coilmaps_support<R>, grid, blk, 0, s, lambda, (const R*)part, (C*)maps, Cn, N, tau2);
+    hipLaunchKernelGGL(k_maps_support<R>, grid, blk, 0, s, gate, floor, key, frac, (const R*)part, (C*)maps, Cn, N);
     return hipGetLastError();
 }
 
 #define COILMAPS_INST(R)                                                                                                                  \
     template hipError_t launch_calib_window<R>(hipStream_t, const R*, const uint8_t*, const int32_t*, R*, int32_t*, int, int, int, int, int); \
     template hipError_t launch_coil_eigmaps<R>(hipStream_t, const R*, R*, R*, int, int, int, int, int, int);                             \
-    template hipError_t launch_coilmaps_support<R>(hipStream_t, const R*, R*, R*, int, int, size_t, R);
+    template hipError_t launch_maps_support<R>(hipStream_t, const R*, R, const R*, R, R*, R*, int, int, size_t);
 COILMAPS_INST(float)
 COILMAPS_INST(double)
 #undef COILMAPS_INST

@@ -11,9 +11,7 @@
 //                       stored: row c of u = G v sits in a register pair while c' runs over the slab, the rows are unrolled (u [CB] in
 //                       registers, static indices: no scratch in any instance).  The phase rule is fused; writes the unit vectors
 //                       [B][C][H][W], lambda [B][H][W] and ||I|| [B][H][W].
-//   k_espirit_imax      the maximum of ||I|| per span of COILMAPS_SPAN pixels, by a tree over the workgroup (as k_coilmaps_lmax)
-//   k_espirit_support   every workgroup of a slice recomputes the slice's maximum from the spans' partials and zeroes the vectors of its
-//                       span where lambda < crop or ||I|| < tau * max
+// The support (lambda < crop or ||I|| < tau * max zeroed) is kernels_coilmaps.hip's k_maps_keymax / k_maps_support, gated on lambda.
 // Vector stores only, no atomics; no sum depends on the batch, on the tile or on a pixel's place in it.
 #include <atomic>
 #include "internal.h"
@@ -185,51 +183,6 @@ __global__ __launch_bounds__(256) void k_espirit_maps(const typename CxOf<R>::ty
     inorm[(size_t)b * N + p] = nrm;
 }
 
-// the maximum of the workgroup's values by a tree over its COILMAPS_SUP_THREADS threads; every thread gets it
-template <typename R> __device__ __forceinline__ R espirit_tree_max(R v, R* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = COILMAPS_SUP_THREADS / 2; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d && sh[threadIdx.x + d] > sh[threadIdx.x]) sh[threadIdx.x] = sh[threadIdx.x + d];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
-template <typename R>
-__global__ __launch_bounds__(COILMAPS_SUP_THREADS) void k_espirit_imax(const R* __restrict__ inorm, R* __restrict__ part, size_t N) {
-    __shared__ R sh[COILMAPS_SUP_THREADS];
-    const size_t lo = (size_t)blockIdx.x * COILMAPS_SPAN;
-    const size_t hi = lo + COILMAPS_SPAN < N ? lo + COILMAPS_SPAN : N;
-    const R* l = inorm + (size_t)blockIdx.y * N;
-    R m = R(0);                                           // a norm: >= 0
-    for (size_t p = lo + threadIdx.x; p < hi; p += COILMAPS_SUP_THREADS) if (l[p] > m) m = l[p];
-    m = espirit_tree_max(m, sh);
-    if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = m;
-}
-
-template <typename R>
-__global__ __launch_bounds__(COILMAPS_SUP_THREADS) void k_espirit_support(const R* __restrict__ lambda, const R* __restrict__ inorm,
-                                                                          const R* __restrict__ part, typename CxOf<R>::type* __restrict__ maps,
-                                                                          int Cn, size_t N, R crop, R tau) {
-    using C = typename CxOf<R>::type;
-    __shared__ R sh[COILMAPS_SUP_THREADS];
-    const int b = blockIdx.y, spans = gridDim.x;
-    R m = R(0);
-    for (int j = threadIdx.x; j < spans; j += COILMAPS_SUP_THREADS) if (part[(size_t)b * spans + j] > m) m = part[(size_t)b * spans + j];
-    const R bar = tau * espirit_tree_max(m, sh);
-    const size_t lo = (size_t)blockIdx.x * COILMAPS_SPAN;
-    const size_t hi = lo + COILMAPS_SPAN < N ? lo + COILMAPS_SPAN : N;
-    const R* l = lambda + (size_t)b * N;
-    const R* in = inorm + (size_t)b * N;
-    C zero;
-    zero.x = R(0); zero.y = R(0);
-    for (size_t p = lo + threadIdx.x; p < hi; p += COILMAPS_SUP_THREADS) {
-        if (l[p] >= crop && in[p] >= bar) continue;
-        for (int c = 0; c < Cn; ++c) maps[((size_t)b * Cn + c) * N + p] = zero;
-    }
-}
-
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 // the caller has checked espirit_check and that B fits a grid dimension
 template <typename R>
@@ -241,22 +194,12 @@ hipError_t launch_calib_patch_gram(hipStream_t s, const R* y, const uint8_t* mas
     return hipGetLastError();
 }
 
-// More than 64 KiB of dynamic LDS needs an opt-in per kernel and device; the attribute is a cap, so COILMAPS_LDS_HARD serves every launch.
 template <typename R, int CB>
 static hipError_t espirit_bucket(hipStream_t s, dim3 grid, CoilmapsTile t, size_t lds, const typename CxOf<R>::type* img,
                                  const typename CxOf<R>::type* w, const typename CxOf<R>::type* eh, const typename CxOf<R>::type* ew,
                                  typename CxOf<R>::type* maps, R* lambda, R* inorm, int Cn, int H, int W, int k, int iters) {
     static std::atomic<bool> done[64] = {};
-    if (lds > 64 * 1024) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        if (!done[dev].load(std::memory_order_acquire)) {
-            if (hipError_t e = hipFuncSetAttribute((const void*)k_espirit_maps<R, CB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)COILMAPS_LDS_HARD))
-                return e;
-            done[dev].store(true, std::memory_order_release);
-        }
-    }
+    if (hipError_t e = lds_opt_in((const void*)k_espirit_maps<R, CB>, done, lds, COILMAPS_LDS_HARD)) return e;
     hipLaunchKernelGGL((k_espirit_maps<R, CB>), grid, dim3((unsigned)(t.th * t.tw)), lds, s, img, w, eh, ew, maps, lambda, inorm, Cn, H, W, k, iters,
                        t.th, t.tw);
     return hipGetLastError();
@@ -282,20 +225,9 @@ hipError_t launch_espirit_maps(hipStream_t s, const R* img, const R* w, const R*
 #undef ESPIRIT_CASE
 }
 
-template <typename R>
-hipError_t launch_espirit_support(hipStream_t s, const R* lambda, const R* inorm, R* part, R* maps, int B, int Cn, size_t N, R crop, R tau) {
-    using C = typename CxOf<R>::type;
-    const dim3 grid((unsigned)coilmaps_spans(N), (unsigned)B), blk(COILMAPS_SUP_THREADS);
-    hipLaunchKernelGGL(k_espirit_imax<R>, grid, blk, 0, s, inorm, part, N);
-    if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(k_espirit_support<R>, grid, blk, 0, s, lambda, inorm, (const R*)part, (C*)maps, Cn, N, crop, tau);
-    return hipGetLastError();
-}
-
 #define ESPIRIT_INST(R)                                                                                                                     \
     template hipError_t launch_calib_patch_gram<R>(hipStream_t, const R*, const uint8_t*, const int32_t*, double*, int, int, int, int, int, int); \
-    template hipError_t launch_espirit_maps<R>(hipStream_t, const R*, const R*, const R*, const R*, R*, R*, R*, int, int, int, int, int, int); \
-    template hipError_t launch_espirit_support<R>(hipStream_t, const R*, const R*, R*, R*, int, int, size_t, R, R);
+    template hipError_t launch_espirit_maps<R>(hipStream_t, const R*, const R*, const R*, const R*, R*, R*, R*, int, int, int, int, int, int);
 ESPIRIT_INST(float)
 ESPIRIT_INST(double)
 #undef ESPIRIT_INST

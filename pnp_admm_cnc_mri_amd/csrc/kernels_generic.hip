@@ -274,15 +274,8 @@ static hipError_t launch_cols_t(hipStream_t s, int W, const ColArgsT<R>& a) {
     using C = typename CxOf<R>::type;
     constexpr int COLS = ColCfg<N, R>::COLS;
     const size_t lds = sizeof(C) * (2 * COLS * (N + 1) + N);
-    static bool attr_done[64] = {};         // >64 KiB dynamic LDS needs the opt-in once per kernel and device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_cols<N, PRE, MID, POST, R>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_done[dev] = true;
-    }
+    static std::atomic<bool> done[64] = {};
+    if (hipError_t e = lds_opt_in((const void*)k_cols<N, PRE, MID, POST, R>, done, lds, lds)) return e;
     hipLaunchKernelGGL((k_cols<N, PRE, MID, POST, R>), dim3(a.B * (W / COLS)), dim3(256), lds, s, a, W);
     return hipGetLastError();
 }
@@ -571,14 +564,8 @@ __global__ __launch_bounds__(512, 4) void k_cols32(ColArgsT<float> p, int W) {  
 template <bool PRE, int MID, bool POST>
 static hipError_t launch_cols32(hipStream_t s, int W, const ColArgsT<float>& a) {
     const size_t lds = sizeof(c32) * (16 * C32_P + 32 * 17);
-    static bool attr_done[64] = {};         // >64 KiB dynamic LDS needs the opt-in once per kernel and device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_cols32<PRE, MID, POST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_done[dev] = true;
-    }
+    static std::atomic<bool> done[64] = {};
+    if (hipError_t e = lds_opt_in((const void*)k_cols32<PRE, MID, POST>, done, lds, lds)) return e;
     hipLaunchKernelGGL((k_cols32<PRE, MID, POST>), dim3(a.B * (W / 16)), dim3(512), lds, s, a, W);
     return hipGetLastError();
 }

@@ -141,27 +141,20 @@ __global__ __launch_bounds__(WV_THREADS) void k_wv_inv(const WvArgs<R> a) {
     }
 }
 
-// >64 KiB dynamic LDS needs the opt-in once per kernel and device
-template <typename K, typename A> hipError_t wv_launch(K kernel, hipStream_t s, int blocks, size_t lds, bool* attr_done, const A& a) {
+template <typename K, typename A> hipError_t wv_launch(K kernel, hipStream_t s, int blocks, size_t lds, std::atomic<bool>* done, const A& a) {
     if (lds > WV_LDS_MAX) return hipErrorInvalidValue;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WV_LDS_MAX);
-        if (e != hipSuccess) return e;
-        attr_done[dev] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)kernel, done, lds, WV_LDS_MAX)) return e;
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(WV_THREADS), lds, s, a);
     return hipGetLastError();
 }
 
 template <typename R, int PROX, int T> hipError_t wv_fwd_t(hipStream_t s, const WvArgs<R>& a, int B) {
-    static bool attr_done[64] = {};
-    return wv_launch(k_wv_fwd<R, PROX, T>, s, B * a.tiles_x * a.tiles_y, wv_fwd_lds_elems(T, a.L, a.tile) * sizeof(R), attr_done, a);
+    static std::atomic<bool> done[64] = {};
+    return wv_launch(k_wv_fwd<R, PROX, T>, s, B * a.tiles_x * a.tiles_y, wv_fwd_lds_elems(T, a.L, a.tile) * sizeof(R), done, a);
 }
 template <typename R, int OUT, int T> hipError_t wv_inv_t(hipStream_t s, const WvArgs<R>& a, int B) {
-    static bool attr_done[64] = {};
-    return wv_launch(k_wv_inv<R, OUT, T>, s, B * a.tiles_x * a.tiles_y, wv_inv_lds_elems(T, a.tile) * sizeof(R), attr_done, a);
+    static std::atomic<bool> done[64] = {};
+    return wv_launch(k_wv_inv<R, OUT, T>, s, B * a.tiles_x * a.tiles_y, wv_inv_lds_elems(T, a.tile) * sizeof(R), done, a);
 }
 
 template <typename R> WvArgs<R> wv_args(int wavelet, int levels, int H, int W) {

@@ -469,3 +469,43 @@ def test_an_espirit_call_on_an_engine_leaves_no_state_behind():
     a, ia = solve('cnc', y, masks, coils='estimate', images=imgs)
     b, ib = solve('cnc', y, masks, coils='estimate', maps_method='walsh', images=imgs)
     assert np.array_equal(a, b) and ia['coil_maps'] == ib['coil_maps'] and 'method' not in ia['coil_maps']
+
+
+@pytest.mark.parametrize('precision', ['f32', 'f64'])
+@pytest.mark.parametrize('Bmax', [2, 4])
+def test_the_estimators_share_one_scratch_array(Bmax, precision):
+    """The context keeps ONE scratch array for pnp_coil_maps, pnp_espirit_maps and pnp_espirit_eigmaps, and each call lays it out anew.  On
+    one engine, in this order: Walsh without lambda_out (lambda lives in the array), ESPIRiT without lambda_out (the array grows),
+    espirit_eigmaps (another layout of it), Walsh with lambda_out -- every output is bit for bit that of the same call on a fresh engine.
+    128 x 128, C = 2, B = 3, calib 8, kernel 2.  Bmax = 2: three passes of one slice; Bmax = 4: a pass of two slices and one of one."""
+    import torch
+    from pnp_admm_cnc_mri_amd import Engine
+    Cn, k, n, H, W, ncal = 2, 2, 2, 128, 128, 8
+    masks, _, _, y = scene(Cn, H, W, ncal)
+    rng = np.random.default_rng(11)
+    D = 2 * k - 1
+    cplx = lambda *shape: dev((rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(cdt(precision)))
+    y_t, bank_t, mid_t, img_t, w_t = dev(y.astype(cdt(precision))), dev(masks), dev(MID), cplx(B, Cn, H, W), cplx(B, Cn, Cn, D, D)
+
+    def call(eng, which):
+        out = torch.full((B, Cn, H, W), float('nan'), dtype=y_t.dtype, device='cuda')
+        lam = torch.full((B, H, W), float('nan'), dtype=out.real.dtype, device='cuda')
+        if which == 'walsh':
+            eng.coil_maps(y_t, bank_t, mid_t, out, None, B, Cn, ncal)
+        elif which == 'espirit':
+            eng.espirit_maps(y_t, bank_t, mid_t, out, None, B, Cn, ncal, k, n, SIGMA, CROP, THRESH)
+        elif which == 'eigmaps':
+            eng.espirit_eigmaps(img_t, w_t, out, lam, B, Cn, k, n)
+        else:
+            eng.coil_maps(y_t, bank_t, mid_t, out, lam, B, Cn, ncal)
+        torch.cuda.synchronize()
+        return [out.cpu().numpy()] + ([] if which in ('walsh', 'espirit') else [lam.cpu().numpy()])
+
+    order = ['walsh', 'espirit', 'eigmaps', 'walsh_lambda']
+    with Engine(H, W, Bmax=Bmax, precision=precision) as eng:
+        shared = [call(eng, which) for which in order]
+    for which, got in zip(order, shared):
+        with Engine(H, W, Bmax=Bmax, precision=precision) as eng:
+            want = call(eng, which)
+        assert all(np.isfinite(a).all() for a in got), which
+        assert len(got) == len(want) and all(np.array_equal(a, b) for a, b in zip(got, want)), which

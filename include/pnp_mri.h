@@ -376,6 +376,63 @@ int pnp_synthesize_problem_mc_f64(pnp_ctx* ctx, const float* img, const double* 
  * pnp_cg_residual: ||r|| / ||A^H y + La2 v|| of the most recent x-step, per slice, rel [B] on the host (synchronises). */
 int pnp_cg_residual(pnp_ctx* ctx, double* rel);
 
+/* ---- complex-valued images on a coil context (added after ABI 13, additive) ----------------------
+ * The loops above return a real, non-negative image: x = |Re x^|, z0 = |A^H y|.  Measured multi-coil data has an image phase that the
+ * maps do not absorb (flow, off-resonance, a step at a tissue boundary); complex mode keeps it.  NOT in the reference scripts.  Opt-in per
+ * context (pnp_set_image); with the mode off -- the default -- nothing here is called and every result is bit for bit what it was.
+ * State: x, z, w are [B][H][W] interleaved complex in the context's precision.  z0 = A^H y (no modulus), w0 = 0.
+ * x-step:  G x^ = A^H y + La2 (z - w)  by the CG above, warm-started at x^ = z - w (complex);  x = x^ (no |Re .|).  The CG arithmetic, its
+ *   sums and pnp_cg_residual are those of the real mode.
+ * csoft(u, c), the prox of c |.| on a complex number:  m2 = u.re u.re + u.im u.im  (two rounded products, one sum, no fma),  m = sqrt(m2),
+ *   s = (m - c) / m  where m > c  and  s = 0  otherwise (m = 0 included);  csoft = (s u.re, s u.im).
+ * cclip(z, ib), the projection onto the disc of radius ib (= z - csoft(z, ib)):  z (ib / m)  where m > ib,  z otherwise;  m as above.
+ * L1 step:   u = x + w;  z+ = csoft(u, thr);  w+ = u - z+.                                    thr = reo lambda1
+ * CNC step:  u = x + w;  t = c1 z + c2 u + c3 cclip(z, ib), component-wise, each component fma(c1, z, fma(c2, u, c3 * clip));
+ *            z+ = csoft(t, thr);  w+ = u - z+.        thr = alpha reo lambda1, c1 = 1 - alpha, c2 = alpha, c3 = thr b, ib = 1 / b
+ *   With zero imaginary parts both are the real steps (soft, clip) up to the rounding of (m - c) / m and ib / m.
+ * Wavelet prox (pnp_set_sparsity):  Psi is real-linear and acts on the real and the imaginary part alike;  detail coefficients are
+ *   thresholded by csoft on the COMPLEX coefficient (L1: csoft(c_u, thr); CNC: the CNC step on the coefficients c_z, c_u), approximation
+ *   coefficients pass through (L1: c_u; CNC: c1 c_z + c2 c_u);  z+ = Psi^T of the result,  w+ = u - z+.  Two launches, as in real mode.
+ *   One setting does not fit the LDS on complex doubles -- db4 with 4 levels on an fp64 context -- and is PNP_E_ARG from whichever of
+ *   pnp_set_image / pnp_set_sparsity comes second; pnp_image_check(mode, wavelet, levels, f64) decides it without a context or a device.
+ *   That second call also allocates the [Bmax][H][W] complex coefficient array (PNP_E_NOMEM names the bytes): no loop allocates.
+ * pnp_set_image rules, the first broken one is named:  ctx null: PNP_E_ARG;  mode not PNP_IMAGE_REAL / PNP_IMAGE_COMPLEX: PNP_E_ARG;
+ *   complex mode on a context without coils: PNP_E_STATE (set them first: pnp_set_coils);  complex mode with a spin table set
+ *   (pnp_set_spin): PNP_E_STATE.  The call drops the uploaded problem, as pnp_set_coils does; the first complex one allocates three
+ *   [Bmax][H][W] complex arrays (PNP_E_NOMEM names the bytes).  pnp_set_coils -- clearing or setting -- returns the context to real mode.
+ * In complex mode
+ *   pnp_init_state, pnp_admm_l1_run, pnp_admm_cnc_run follow the mathematics above; pnp_get_plan reports the same launch counts as in
+ *     real mode (the complex steps are launch for launch the real ones); pnp_path_name stays "coils"; pnp_metrics / pnp_ssim with
+ *     x_dev = null score |x|;
+ *   the real state calls (pnp_set_state, pnp_get_state), pnp_download_x, pnp_dc_step, pnp_prox_l1_dual, pnp_prox_cnc_dual and their _f64
+ *     forms return PNP_E_STATE and name their _cx counterpart;
+ *   pnp_admm_l1_run_traced, pnp_admm_cnc_run_traced, pnp_residuals[_f64] and pnp_set_spin return PNP_E_STATE ("not available in complex
+ *     image mode").
+ * The _cx calls mirror their real namesakes on interleaved complex arrays (float: 2 floats per pixel) and return PNP_E_STATE in real
+ * mode.  EVERY complex array a caller hands to a _cx call on device pointers (pnp_dc_step_cx, pnp_prox_*_dual_cx, pnp_A_cx) must be
+ * aligned to one complex value, 2 sizeof(real) = 8 bytes in float and 16 in double (PNP_E_ARG otherwise); pnp_prox_*_dual_cx without a
+ * wavelet asks for 16 bytes in either precision (the kernel moves 16 bytes per access), with one x, z, w must not overlap.  pnp_A_cx: x [B][H][W] complex -> k [B][C][H][W], float only, like pnp_A.  pnp_synthesize_problem_mc
+ * stays real-input: complex mode is for uploaded y. */
+#define PNP_IMAGE_REAL    0
+#define PNP_IMAGE_COMPLEX 1
+int pnp_image_check(int mode, int wavelet, int levels, int f64);
+int pnp_set_image(pnp_ctx* ctx, int mode);
+int pnp_get_image(pnp_ctx* ctx, int* mode);
+int pnp_set_state_cx(pnp_ctx* ctx, const float* z, const float* w, int on_device);
+int pnp_set_state_cx_f64(pnp_ctx* ctx, const double* z, const double* w, int on_device);
+int pnp_get_state_cx(pnp_ctx* ctx, float* z, float* w, int on_device);
+int pnp_get_state_cx_f64(pnp_ctx* ctx, double* z, double* w, int on_device);
+int pnp_download_x_cx(pnp_ctx* ctx, float* x, int on_device);
+int pnp_download_x_cx_f64(pnp_ctx* ctx, double* x, int on_device);
+int pnp_dc_step_cx(pnp_ctx* ctx, const float* z_dev, const float* w_dev, float* x_dev, double reo);
+int pnp_dc_step_cx_f64(pnp_ctx* ctx, const double* z_dev, const double* w_dev, double* x_dev, double reo);
+int pnp_prox_l1_dual_cx(pnp_ctx* ctx, const float* x_dev, float* z_dev, float* w_dev, double thr);
+int pnp_prox_l1_dual_cx_f64(pnp_ctx* ctx, const double* x_dev, double* z_dev, double* w_dev, double thr);
+int pnp_prox_cnc_dual_cx(pnp_ctx* ctx, const float* x_dev, float* z_dev, float* w_dev, double alpha, double lambda1, double reo, double b);
+int pnp_prox_cnc_dual_cx_f64(pnp_ctx* ctx, const double* x_dev, double* z_dev, double* w_dev, double alpha, double lambda1, double reo,
+                             double b);
+int pnp_A_cx(pnp_ctx* ctx, const float* x_dev, float* k_dev);
+
 /* ---- coil mixing ahead of the multi-coil solve: noise prewhitening and coil compression (added after ABI 13, additive) ----
  * NOT in the reference scripts.  Array data has 32 to 128 channels, the solve above takes at most 32 and costs time linear in C.  Both
  * standard remedies are ONE operation: a C_out x C_in complex matrix M applied per k-space point to the measurements and per pixel to

@@ -128,6 +128,23 @@ SIGNATURES = {
     'pnp_synthesize_problem_mc': (C.c_int, [ctx_p, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
     'pnp_synthesize_problem_mc_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
     'pnp_cg_residual': (C.c_int, [ctx_p, c_double_p]),
+    # complex-valued images on a coil context (added after ABI 13, additive)
+    'pnp_image_check': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'pnp_set_image': (C.c_int, [ctx_p, C.c_int]),
+    'pnp_get_image': (C.c_int, [ctx_p, C.POINTER(C.c_int)]),
+    'pnp_set_state_cx': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
+    'pnp_set_state_cx_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
+    'pnp_get_state_cx': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
+    'pnp_get_state_cx_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int]),
+    'pnp_download_x_cx': (C.c_int, [ctx_p, _vp, C.c_int]),
+    'pnp_download_x_cx_f64': (C.c_int, [ctx_p, _vp, C.c_int]),
+    'pnp_dc_step_cx': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_double]),
+    'pnp_dc_step_cx_f64': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_double]),
+    'pnp_prox_l1_dual_cx': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_double]),
+    'pnp_prox_l1_dual_cx_f64': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_double]),
+    'pnp_prox_cnc_dual_cx': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double]),
+    'pnp_prox_cnc_dual_cx_f64': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double]),
+    'pnp_A_cx': (C.c_int, [ctx_p, _vp, _vp]),
     # coil mixing ahead of the multi-coil solve: prewhitening and coil compression (added after ABI 13, additive)
     'pnp_coilmix_check': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'pnp_coil_mix': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t]),

@@ -111,6 +111,10 @@ struct Coils {
     bool have_rel = false;            // an x-step has run on the current problem
     AnySize* any = nullptr;           // the transforms of a coil context: the any-size kernels at every shape (the context's own, or made here)
     bool own_any = false;
+    // complex-valued images (pnp_set_image): the state of the loops is complex and lives here, beside the real z / w / x of the context
+    int image = PNP_IMAGE_REAL;
+    void *zc = nullptr, *wc = nullptr, *xc = nullptr;      // [Bmax][H][W] complex, allocated by pnp_set_image(PNP_IMAGE_COMPLEX)
+    void* wv_coef = nullptr;          // [Bmax][H][W] complex: the coefficients between the two launches of the complex wavelet prox (on first use)
 };
 
 // The three stage times of a coil-map estimator (pnp_*_stage_times): ms accumulates since the last read, the events exist once enabled.
@@ -436,6 +440,14 @@ template <typename R> static int download_x(pnp_ctx* c, const char* who, R* x, i
 template <typename R> static int init_state(pnp_ctx* c) {
     const Bufs<R> b = bufs<R>(c);
     c->state_sliced = false;                           // both arrays are rewritten below, in natural order
+    if (c->coils.C > 0 && c->coils.image == PNP_IMAGE_COMPLEX) {      // complex images: z = A^H y, no modulus; w = 0
+        const size_t bytes = (size_t)c->B * c->N * sizeof(typename CxOf<R>::type);
+        HIPCHK(hipMemcpyAsync(c->coils.zc, c->coils.aty, bytes, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(c->coils.wc, 0, bytes, c->stream));
+        c->have_x = false;
+        c->have_state = true;
+        return PNP_OK;
+    }
     if (c->coils.C > 0) {                              // z = |A^H y|, w = 0
         HIPCHK(launch_cabs<R>(c->stream, (const typename CxOf<R>::type*)c->coils.aty, b.z, (size_t)c->B * c->N));
         HIPCHK(hipMemsetAsync(b.w, 0, (size_t)c->B * c->N * sizeof(R), c->stream));
@@ -489,7 +501,7 @@ template <typename R> static int wavelet_prox_step(pnp_ctx* c, bool cnc, const R
 static void coils_free(pnp_ctx* c) {
     Coils& k = c->coils;
     void* ptrs[] = {k.maps, k.coil_id, k.mask_idx, k.work, k.ymc, k.aty, k.xh, k.r, k.p, k.gp, k.part_row, k.part_rr[0], k.part_rr[1],
-                    k.part_bb, k.scal, k.rel};
+                    k.part_bb, k.scal, k.rel, k.zc, k.wc, k.xc, k.wv_coef};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (k.own_any) anysize_destroy(k.any);
     const int iters = k.cg_iters;
@@ -536,20 +548,23 @@ template <typename R> static int coil_G(pnp_ctx* c, const void* p, void* gp, R l
 
 // The x-step: cg_iters iterations of CG on G x^ = aty + La2 (z - w), warm-started at z - w; x = |Re x^|.  cg_launches(cg_iters) launches,
 // no host synchronisation: every scalar stays on the device (kernels_coils.hip).
-template <typename R> static int coil_xstep(pnp_ctx* c, const R* z, const R* w, R* x, double reo) {
+// CX (complex images, pnp_set_image): z, w, x are complex and x = x^; the launches between the two ends are the same.
+template <typename R, bool CX = false>
+static int coil_xstep(pnp_ctx* c, const CoilState<R, CX>* z, const CoilState<R, CX>* w, CoilState<R, CX>* x, double reo) {
     using C = typename CxOf<R>::type;
     Coils& k = c->coils;
     const R la2 = (R)(1.0 / 2.0 / reo);
     const int B = c->B, iters = k.cg_iters;
     C *xh = (C*)k.xh, *r = (C*)k.r, *p = (C*)k.p, *gp = (C*)k.gp;
-    HIPCHK(launch_cg_begin<R>(c->stream, z, w, xh, B, c->N));
+    HIPCHK((launch_cg_begin<R, CX>(c->stream, z, w, xh, B, c->N)));
     if (int rc = coil_G<R>(c, xh, gp, la2)) return rc;
     HIPCHK(launch_cg_init<R>(c->stream, (const C*)k.aty, xh, gp, r, p, la2, k.part_rr[0], k.part_bb, B, c->N));
     int cur = 0;
     for (int i = 0; i < iters; ++i) {
         const bool last = i == iters - 1;
         if (int rc = coil_G<R>(c, p, gp, la2)) return rc;
-        HIPCHK(launch_cg_xr<R>(c->stream, xh, r, p, gp, k.part_rr[cur], k.part_row, k.part_rr[cur ^ 1], k.scal, last ? x : (R*)nullptr, B, c->N, c->H));
+        HIPCHK((launch_cg_xr<R, CX>(c->stream, xh, r, p, gp, k.part_rr[cur], k.part_row, k.part_rr[cur ^ 1], k.scal,
+                                    last ? x : (CoilState<R, CX>*)nullptr, B, c->N, c->H)));
         if (!last) HIPCHK(launch_cg_p<R>(c->stream, r, p, k.part_rr[cur], k.part_rr[cur ^ 1], k.scal, B, c->N));
         cur ^= 1;
     }
@@ -558,10 +573,108 @@ template <typename R> static int coil_xstep(pnp_ctx* c, const R* z, const R* w, 
     return PNP_OK;
 }
 
+// ---- complex-valued images (pnp_set_image; kernels_complex.hip): the coil loop on the complex state of Coils ----
+
+static bool cx_mode(const pnp_ctx* c) { return c->coils.image == PNP_IMAGE_COMPLEX; }
+#define REAL_IMAGE(c, cx) do { if (cx_mode(c)) return fail(PNP_E_STATE, "%s: the context is in complex image mode (pnp_set_image): use %s", __func__, cx); } while (0)
+#define NOT_IN_COMPLEX(c) do { if (cx_mode(c)) return fail(PNP_E_STATE, "%s: not available in complex image mode (pnp_set_image)", __func__); } while (0)
+#define NEED_COMPLEX(c) do { if (!cx_mode(c)) return fail(PNP_E_STATE, "%s: needs complex image mode (pnp_set_image); in real mode use the call without _cx", __func__); } while (0)
+
+// The coefficient array of the complex wavelet prox: allocated where the setting is made -- by pnp_set_image or pnp_set_sparsity,
+// whichever comes second -- so that no loop and no step-wise call allocates.
+static int cx_wavelet_scratch(pnp_ctx* c, const char* who) {
+    if (c->coils.wv_coef) return PNP_OK;
+    const size_t bytes = (size_t)c->Bmax * c->N * 2 * (c->f64 ? sizeof(double) : sizeof(float));
+    const hipError_t e = hipMalloc(&c->coils.wv_coef, bytes);
+    if (e == hipSuccess) return PNP_OK;
+    (void)hipGetLastError();
+    c->coils.wv_coef = nullptr;
+    return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the complex wavelet coefficients: %zu bytes asked for (Bmax=%d, %dx%d): %s",
+                who, bytes, c->Bmax, c->H, c->W, hipGetErrorString(e));
+}
+
+// every complex array a caller hands in is read and written as 2 sizeof(R)-byte values (float2 / double2; the pixel prox: 16 bytes)
+template <typename R> static int cx_aligned(const char* who, const void* a, const void* b = nullptr, const void* c = nullptr, size_t to = 2 * sizeof(R)) {
+    if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & (to - 1)) == 0) return PNP_OK;
+    return fail(PNP_E_ARG, "%s: complex arrays must be %zu-byte aligned", who, to);
+}
+
+// one z / w step on complex arrays: the pixel prox (one launch) or the wavelet prox of the context's sparsity setting (two)
+template <typename R>
+static int prox_step_cx(pnp_ctx* c, bool cnc, const typename CxOf<R>::type* x, typename CxOf<R>::type* z, typename CxOf<R>::type* w,
+                        const ProxParamsT<R>& pp) {
+    using C = typename CxOf<R>::type;
+    if (c->wavelet == WV_NONE) {
+        HIPCHK(launch_prox_cx<R>(c->stream, cnc, x, z, w, pp, (size_t)c->B * c->N));
+        return PNP_OK;
+    }
+    if (!c->coils.wv_coef) return fail(PNP_E_STATE, "complex wavelet prox: no coefficient array (pnp_set_image / pnp_set_sparsity allocate it)");
+    HIPCHK(launch_wavelet_prox_cx<R>(c->stream, c->wavelet, c->wv_levels, cnc, x, z, w, (C*)c->coils.wv_coef, pp, c->B, c->H, c->W));
+    return PNP_OK;
+}
+
+template <typename R>
+static int run_coil_loop_cx(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
+    using C = typename CxOf<R>::type;
+    C *z = (C*)c->coils.zc, *w = (C*)c->coils.wc, *x = (C*)c->coils.xc;
+    if (iters == 0) HIPCHK(hipMemcpyAsync(x, z, (size_t)c->B * c->N * sizeof(C), hipMemcpyDeviceToDevice, c->stream));
+    for (int i = 0; i < iters; ++i) {
+        if (int rc = coil_xstep<R, true>(c, z, w, x, reo)) return rc;
+        if (int rc = prox_step_cx<R>(c, cnc, x, z, w, pp)) return rc;
+    }
+    c->have_x = true;
+    return PNP_OK;
+}
+
+template <typename R> static int set_state_cx(pnp_ctx* c, const char* who, const R* z, const R* w, int on_device) {
+    const size_t bytes = (size_t)c->B * c->N * 2 * sizeof(R);
+    if (!(z && w) && !c->have_state) return undefined_state(who);                 // one of the two kept: it must be defined
+    if (z) if (int rc = copy_in(c, c->coils.zc, z, bytes, on_device)) return rc;
+    if (w) if (int rc = copy_in(c, c->coils.wc, w, bytes, on_device)) return rc;
+    c->have_x = false;
+    if (z && w) c->have_state = true;
+    return PNP_OK;
+}
+template <typename R> static int get_state_cx(pnp_ctx* c, R* z, R* w, int on_device) {
+    const size_t bytes = (size_t)c->B * c->N * 2 * sizeof(R);
+    if (z) if (int rc = copy_out(c, z, c->coils.zc, bytes, on_device)) return rc;
+    if (w) if (int rc = copy_out(c, w, c->coils.wc, bytes, on_device)) return rc;
+    return PNP_OK;
+}
+template <typename R> static int download_x_cx(pnp_ctx* c, const char* who, R* x, int on_device) {
+    if (!x) return fail(PNP_E_ARG, "%s: null", who);
+    if (!c->have_x) return fail(PNP_E_STATE, "%s: no iteration has been run since the state was set", who);
+    return copy_out(c, x, c->coils.xc, (size_t)c->B * c->N * 2 * sizeof(R), on_device);
+}
+template <typename R> static int dc_step_cx(pnp_ctx* c, const char* who, const R* z, const R* w, R* x, double reo) {
+    using C = typename CxOf<R>::type;
+    if (!z || !w || !x) return fail(PNP_E_ARG, "%s: null pointer", who);
+    if (!(reo > 0.0)) return fail(PNP_E_ARG, "%s: reo must be > 0", who);
+    if (int rc = cx_aligned<R>(who, z, w, x)) return rc;
+    return coil_xstep<R, true>(c, (const C*)z, (const C*)w, (C*)x, reo);
+}
+// the step-wise prox on caller pointers (complex, interleaved): 16-byte aligned for the pixel prox, 2 sizeof(R) and not overlapping for
+// the wavelet prox
+template <typename R> static int prox_dual_cx(pnp_ctx* c, const char* who, bool cnc, const R* x, R* z, R* w, const ProxParamsT<R>& pp) {
+    using C = typename CxOf<R>::type;
+    if (!x || !z || !w) return fail(PNP_E_ARG, "%s: null pointer", who);
+    if (c->wavelet == WV_NONE) {
+        if (int rc = cx_aligned<R>(who, x, z, w, 16)) return rc;
+    } else {
+        if (int rc = cx_aligned<R>(who, x, z, w)) return rc;
+        const size_t bytes = (size_t)c->B * c->N * sizeof(C);
+        const char *px = (const char*)x, *pz = (const char*)z, *pw = (const char*)w;
+        if ((px < pz + bytes && pz < px + bytes) || (px < pw + bytes && pw < px + bytes) || (pz < pw + bytes && pw < pz + bytes))
+            return fail(PNP_E_ARG, "%s: x, z and w must not overlap with a wavelet set (tiles read their neighbours' halo)", who);
+    }
+    return prox_step_cx<R>(c, cnc, (const C*)x, (C*)z, (C*)w, pp);
+}
+
 // the loops of a coil context: per iteration the x-step and the pixel prox (one launch) or the wavelet prox (two), on the state in
 // natural order; every iteration stands alone, so a run cut anywhere (the trace's legs) is bit-equal to the uncut run
 template <typename R>
 static int run_coil_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
+    if (cx_mode(c)) return run_coil_loop_cx<R>(c, iters, cnc, pp, reo);
     const Bufs<R> b = bufs<R>(c);
     const size_t n = (size_t)c->B * c->N;
     if (c->wavelet != WV_NONE && iters > 0) if (int rc = wavelet_scratch(c)) return rc;
@@ -1105,6 +1218,8 @@ static int metric_inputs(pnp_ctx* c, const char* who, const X*& x, const uint8_t
     if (!x) {
         if (!c->have_x) return fail(PNP_E_STATE, "%s: x_dev is null and the ctx holds no x yet", who);
         x = bufs<X>(c).x;
+        // complex images: the metrics are taken on |x|, formed into the context's real x (unused in complex mode)
+        if (cx_mode(c)) HIPCHK(launch_cabs<X>(c->stream, (const typename CxOf<X>::type*)c->coils.xc, bufs<X>(c).x, (size_t)c->B * c->N));
     }
     if (!gt_on_device) {
         if (!c->gt) HIPCHK(hipMalloc((void**)&c->gt, (size_t)c->Bmax * c->N));
@@ -1344,11 +1459,11 @@ int pnp_init_state(pnp_ctx* c) {
     return c->f64 ? init_state<double>(c) : init_state<float>(c);
 }
 
-int pnp_set_state(pnp_ctx* c, const float* z, const float* w, int on_device) { CTX(c); F32_ONLY(c); NEED_PROBLEM(c); return set_state(c, __func__, z, w, on_device); }
-int pnp_set_state_f64(pnp_ctx* c, const double* z, const double* w, int on_device) { CTX(c); F64_ONLY(c); NEED_PROBLEM(c); return set_state(c, __func__, z, w, on_device); }
+int pnp_set_state(pnp_ctx* c, const float* z, const float* w, int on_device) { CTX(c); REAL_IMAGE(c, "pnp_set_state_cx"); F32_ONLY(c); NEED_PROBLEM(c); return set_state(c, __func__, z, w, on_device); }
+int pnp_set_state_f64(pnp_ctx* c, const double* z, const double* w, int on_device) { CTX(c); REAL_IMAGE(c, "pnp_set_state_cx_f64"); F64_ONLY(c); NEED_PROBLEM(c); return set_state(c, __func__, z, w, on_device); }
 
-int pnp_get_state(pnp_ctx* c, float* z, float* w, int on_device) { CTX(c); F32_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c); return get_state(c, z, w, on_device); }
-int pnp_get_state_f64(pnp_ctx* c, double* z, double* w, int on_device) { CTX(c); F64_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c); return get_state(c, z, w, on_device); }
+int pnp_get_state(pnp_ctx* c, float* z, float* w, int on_device) { CTX(c); REAL_IMAGE(c, "pnp_get_state_cx"); F32_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c); return get_state(c, z, w, on_device); }
+int pnp_get_state_f64(pnp_ctx* c, double* z, double* w, int on_device) { CTX(c); REAL_IMAGE(c, "pnp_get_state_cx_f64"); F64_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c); return get_state(c, z, w, on_device); }
 
 // soft(a, thr) is evaluated as a - med3(a, -thr, thr) on the fast paths, which equals the reference's
 // fmax(|a| - thr, 0) * sign(a) (S1:18-19) for thr >= 0 only; the reference's own parameters are all positive.
@@ -1380,7 +1495,7 @@ int pnp_admm_cnc_run(pnp_ctx* c, int iters, double alpha, double lambda1, double
 
 int pnp_admm_l1_run_traced(pnp_ctx* c, int iters, double lambda1, double reo, int every, double tol, const uint8_t* gt, int gt_on_device,
                            int* checks, int* iters_done) {
-    CTX(c); NEED_PROBLEM(c); NEED_STATE(c);
+    CTX(c); NOT_IN_COMPLEX(c); NEED_PROBLEM(c); NEED_STATE(c);
     Range r("pnp_admm_l1_run_traced");
     if (int rv = check_thresholds(__func__, 0.0, lambda1, reo)) return rv;
     if (iters < 0) return fail(PNP_E_ARG, "%s: iters must be >= 0", __func__);
@@ -1390,7 +1505,7 @@ int pnp_admm_l1_run_traced(pnp_ctx* c, int iters, double lambda1, double reo, in
 
 int pnp_admm_cnc_run_traced(pnp_ctx* c, int iters, double alpha, double lambda1, double reo, double b, int every, double tol,
                             const uint8_t* gt, int gt_on_device, int* checks, int* iters_done) {
-    CTX(c); NEED_PROBLEM(c); NEED_STATE(c);
+    CTX(c); NOT_IN_COMPLEX(c); NEED_PROBLEM(c); NEED_STATE(c);
     Range r("pnp_admm_cnc_run_traced");
     if (!(b > 0.0)) return fail(PNP_E_ARG, "%s: b must be > 0", __func__);
     if (int rv = check_thresholds(__func__, alpha, lambda1, reo)) return rv;
@@ -1410,20 +1525,20 @@ int pnp_trace_read(pnp_ctx* c, int32_t* iters, double* values, int32_t* converge
 
 int pnp_residuals(pnp_ctx* c, const float* x, const float* z, const float* zprev, const float* w, const uint8_t* gt, int gt_on_device,
                   int quantise, double* out, int out_on_device) {
-    CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
+    CTX(c); NOT_IN_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c);
     return residuals_any<float>(c, __func__, x, z, zprev, w, gt, gt_on_device, quantise, out, out_on_device);
 }
 int pnp_residuals_f64(pnp_ctx* c, const double* x, const double* z, const double* zprev, const double* w, const uint8_t* gt, int gt_on_device,
                       int quantise, double* out, int out_on_device) {
-    CTX(c); F64_ONLY(c); NEED_PROBLEM(c);
+    CTX(c); NOT_IN_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c);
     return residuals_any<double>(c, __func__, x, z, zprev, w, gt, gt_on_device, quantise, out, out_on_device);
 }
 
-int pnp_download_x(pnp_ctx* c, float* x, int on_device) { CTX(c); F32_ONLY(c); NEED_PROBLEM(c); return download_x(c, __func__, x, on_device); }
-int pnp_download_x_f64(pnp_ctx* c, double* x, int on_device) { CTX(c); F64_ONLY(c); NEED_PROBLEM(c); return download_x(c, __func__, x, on_device); }
+int pnp_download_x(pnp_ctx* c, float* x, int on_device) { CTX(c); REAL_IMAGE(c, "pnp_download_x_cx"); F32_ONLY(c); NEED_PROBLEM(c); return download_x(c, __func__, x, on_device); }
+int pnp_download_x_f64(pnp_ctx* c, double* x, int on_device) { CTX(c); REAL_IMAGE(c, "pnp_download_x_cx_f64"); F64_ONLY(c); NEED_PROBLEM(c); return download_x(c, __func__, x, on_device); }
 
 int pnp_dc_step(pnp_ctx* c, const float* z, const float* w, float* x, double reo) {
-    CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
+    CTX(c); REAL_IMAGE(c, "pnp_dc_step_cx"); F32_ONLY(c); NEED_PROBLEM(c);
     Range r("pnp_dc_step");
     if (!z || !w || !x) return fail(PNP_E_ARG, "pnp_dc_step: null pointer");
     if (!(reo > 0.0)) return fail(PNP_E_ARG, "pnp_dc_step: reo must be > 0");
@@ -1442,7 +1557,7 @@ static int wavelet_prox_dual(pnp_ctx* c, const char* who, bool cnc, const float*
 }
 
 int pnp_prox_l1_dual(pnp_ctx* c, const float* x, float* z, float* w, double thr) {
-    CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
+    CTX(c); REAL_IMAGE(c, "pnp_prox_l1_dual_cx"); F32_ONLY(c); NEED_PROBLEM(c);
     if (!x || !z || !w) return fail(PNP_E_ARG, "pnp_prox_l1_dual: null pointer");
     if (!(thr >= 0.0)) return fail(PNP_E_ARG, "pnp_prox_l1_dual: thr must be >= 0");
     ProxParams p{}; p.thr = (float)thr;
@@ -1452,7 +1567,7 @@ int pnp_prox_l1_dual(pnp_ctx* c, const float* x, float* z, float* w, double thr)
 }
 
 int pnp_prox_cnc_dual(pnp_ctx* c, const float* x, float* z, float* w, double alpha, double lambda1, double reo, double b) {
-    CTX(c); F32_ONLY(c); NEED_PROBLEM(c);
+    CTX(c); REAL_IMAGE(c, "pnp_prox_cnc_dual_cx"); F32_ONLY(c); NEED_PROBLEM(c);
     if (!x || !z || !w) return fail(PNP_E_ARG, "pnp_prox_cnc_dual: null pointer");
     if (!(b > 0.0)) return fail(PNP_E_ARG, "pnp_prox_cnc_dual: b must be > 0");
     if (int rv = check_thresholds("pnp_prox_cnc_dual", alpha, lambda1, reo)) return rv;
@@ -1646,8 +1761,10 @@ int pnp_sparsity_check(int wavelet, int levels, int H, int W) {
 int pnp_set_sparsity(pnp_ctx* c, int wavelet, int levels) {
     if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
     if (int rc = pnp_sparsity_check(wavelet, levels, c->H, c->W)) return rc;         // before any device work
+    if (cx_mode(c)) if (int rc = pnp_image_check(PNP_IMAGE_COMPLEX, wavelet, levels, c->f64)) return rc;
     CTX(c);
     if (wavelet != PNP_WAVELET_NONE) if (int rc = wavelet_scratch(c)) return rc;
+    if (wavelet != PNP_WAVELET_NONE && cx_mode(c)) if (int rc = cx_wavelet_scratch(c, __func__)) return rc;
     c->wavelet = wavelet;
     c->wv_levels = wavelet == PNP_WAVELET_NONE ? 0 : levels;
     c->spin.clear(); c->spin_k = 1; c->spin_p = 0;                                    // the valid shifts depend on levels
@@ -1686,6 +1803,7 @@ int pnp_spin_check(int levels, const int32_t* shifts, int n, int per_prox) {
 int pnp_set_spin(pnp_ctx* c, const int32_t* shifts, int n, int per_prox) {
     if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
     if (n == 0) { c->spin.clear(); c->spin_k = 1; c->spin_p = 0; return PNP_OK; }
+    NOT_IN_COMPLEX(c);
     if (c->wavelet == WV_NONE) return fail(PNP_E_STATE, "%s: no wavelet set (pnp_set_sparsity)", __func__);
     if (int rc = pnp_spin_check(c->wv_levels, shifts, n, per_prox)) return rc;          // before any device work
     CTX(c);
@@ -1778,6 +1896,110 @@ int pnp_cg_residual(pnp_ctx* c, double* rel) {
     if (!rel) return fail(PNP_E_ARG, "pnp_cg_residual: rel is null");
     if (!c->coils.have_rel) return fail(PNP_E_STATE, "pnp_cg_residual: no x-step has run on the uploaded problem");
     return copy_out(c, rel, c->coils.rel, (size_t)c->B * sizeof(double), 0);
+}
+
+// ---- complex-valued images on a coil context: kernels_complex.hip, the CX roles of kernels_coils.hip ----
+
+int pnp_image_check(int mode, int wavelet, int levels, int f64) {
+    if (mode != PNP_IMAGE_REAL && mode != PNP_IMAGE_COMPLEX)
+        return fail(PNP_E_ARG, "image: mode must be PNP_IMAGE_REAL (0) or PNP_IMAGE_COMPLEX (1) (got %d)", mode);
+    if (mode == PNP_IMAGE_COMPLEX && wavelet != PNP_WAVELET_NONE && wv_taps(wavelet) != 0 && levels >= 1 && levels <= WV_MAX_LEVELS &&
+        !wavelet_cx_fits(wavelet, levels, f64 != 0))
+        return fail(PNP_E_ARG, "image: with complex images the tile of this wavelet at %d levels does not fit the LDS in %s", levels, f64 ? "double" : "float");
+    return PNP_OK;
+}
+
+int pnp_set_image(pnp_ctx* c, int mode) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
+    if (int rc = pnp_image_check(mode, PNP_WAVELET_NONE, 0, 0)) return rc;
+    if (mode == PNP_IMAGE_COMPLEX) {
+        if (c->coils.C == 0) return fail(PNP_E_STATE, "%s: complex images need a context with coils (pnp_set_coils)", __func__);
+        if (!c->spin.empty()) return fail(PNP_E_STATE, "%s: complex images do not run with a spin table (clear it with pnp_set_spin(ctx, NULL, 0, 1))", __func__);
+        if (int rc = pnp_image_check(mode, c->wavelet, c->wv_levels, c->f64)) return rc;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->B = 0; c->prob = Problem{};                        // the uploaded problem is dropped, as by pnp_set_coils
+    c->state_sliced = c->have_x = c->have_state = false;
+    c->coils.have_rel = false;
+    Coils& k = c->coils;
+    if (mode == PNP_IMAGE_COMPLEX && !k.zc) {
+        const size_t bytes = (size_t)c->Bmax * c->N * 2 * (c->f64 ? sizeof(double) : sizeof(float));
+        void** want[] = {&k.zc, &k.wc, &k.xc};
+        for (void** p : want) {
+            const hipError_t e = hipMalloc(p, bytes);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                *p = nullptr;
+                for (void** q : want) { if (*q) (void)hipFree(*q); *q = nullptr; }
+                return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the complex state: %zu bytes asked for (Bmax=%d, %dx%d): %s",
+                            __func__, bytes, c->Bmax, c->H, c->W, hipGetErrorString(e));
+            }
+        }
+    }
+    if (mode == PNP_IMAGE_COMPLEX && c->wavelet != WV_NONE) if (int rc = cx_wavelet_scratch(c, __func__)) return rc;
+    k.image = mode;
+    return PNP_OK;
+}
+
+int pnp_get_image(pnp_ctx* c, int* mode) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
+    if (mode) *mode = c->coils.image;
+    return PNP_OK;
+}
+
+int pnp_set_state_cx(pnp_ctx* c, const float* z, const float* w, int on_device) { CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c); return set_state_cx(c, __func__, z, w, on_device); }
+int pnp_set_state_cx_f64(pnp_ctx* c, const double* z, const double* w, int on_device) { CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c); return set_state_cx(c, __func__, z, w, on_device); }
+int pnp_get_state_cx(pnp_ctx* c, float* z, float* w, int on_device) { CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c); return get_state_cx(c, z, w, on_device); }
+int pnp_get_state_cx_f64(pnp_ctx* c, double* z, double* w, int on_device) { CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c); return get_state_cx(c, z, w, on_device); }
+int pnp_download_x_cx(pnp_ctx* c, float* x, int on_device) { CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c); return download_x_cx(c, __func__, x, on_device); }
+int pnp_download_x_cx_f64(pnp_ctx* c, double* x, int on_device) { CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c); return download_x_cx(c, __func__, x, on_device); }
+
+int pnp_dc_step_cx(pnp_ctx* c, const float* z, const float* w, float* x, double reo) {
+    CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c);
+    Range r("pnp_dc_step_cx");
+    return dc_step_cx<float>(c, __func__, z, w, x, reo);
+}
+int pnp_dc_step_cx_f64(pnp_ctx* c, const double* z, const double* w, double* x, double reo) {
+    CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c);
+    Range r("pnp_dc_step_cx_f64");
+    return dc_step_cx<double>(c, __func__, z, w, x, reo);
+}
+
+int pnp_prox_l1_dual_cx(pnp_ctx* c, const float* x, float* z, float* w, double thr) {
+    CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c);
+    if (!(thr >= 0.0)) return fail(PNP_E_ARG, "%s: thr must be >= 0", __func__);
+    ProxParams p{}; p.thr = (float)thr;
+    return prox_dual_cx<float>(c, __func__, false, x, z, w, p);
+}
+int pnp_prox_l1_dual_cx_f64(pnp_ctx* c, const double* x, double* z, double* w, double thr) {
+    CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c);
+    if (!(thr >= 0.0)) return fail(PNP_E_ARG, "%s: thr must be >= 0", __func__);
+    ProxParamsT<double> p{}; p.thr = thr;
+    return prox_dual_cx<double>(c, __func__, false, x, z, w, p);
+}
+int pnp_prox_cnc_dual_cx(pnp_ctx* c, const float* x, float* z, float* w, double alpha, double lambda1, double reo, double b) {
+    CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c);
+    if (!(b > 0.0)) return fail(PNP_E_ARG, "%s: b must be > 0", __func__);
+    if (int rv = check_thresholds(__func__, alpha, lambda1, reo)) return rv;
+    return prox_dual_cx<float>(c, __func__, true, x, z, w, prox_cnc<float>(alpha, lambda1, reo, b));
+}
+int pnp_prox_cnc_dual_cx_f64(pnp_ctx* c, const double* x, double* z, double* w, double alpha, double lambda1, double reo, double b) {
+    CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c);
+    if (!(b > 0.0)) return fail(PNP_E_ARG, "%s: b must be > 0", __func__);
+    if (int rv = check_thresholds(__func__, alpha, lambda1, reo)) return rv;
+    return prox_dual_cx<double>(c, __func__, true, x, z, w, prox_cnc<double>(alpha, lambda1, reo, b));
+}
+
+int pnp_A_cx(pnp_ctx* c, const float* x, float* k) {        // x: [B][H][W] complex, k: [B][C][H][W]
+    CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c);
+    if (!x || !k) return fail(PNP_E_ARG, "%s: null pointer", __func__);
+    if (int rc = cx_aligned<float>(__func__, x, k)) return rc;
+    CoilRowArgsT<float> ca = coil_rows<float>(c, c->B);
+    ca.cin = (const float2*)x; ca.work = (float2*)k;
+    HIPCHK(anysize_coil_rows_in<float>(c->coils.any, c->stream, ca));
+    HIPCHK(anysize_cols<float>(c->coils.any, c->stream, true, MID_MASK, false, coil_cols<float>(c, k, k)));
+    return PNP_OK;
 }
 
 // ---- coil mixing ahead of the multi-coil solve: coilmix_plan.h, kernels_coilmix.hip.  No context: caller-owned device arrays ----

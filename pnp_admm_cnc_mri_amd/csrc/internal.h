@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <type_traits>
 #include <stdint.h>
 #include <stdlib.h>
 #include "loop_schedule.h"
@@ -111,20 +112,34 @@ template <typename R> hipError_t anysize_coil_rows_epi(const AnySize*, hipStream
 // multi-coil pointwise kernels and the batched conjugate-gradient updates (kernels_coils.hip; sums by coil_plan.h).  Complex arrays
 // [B][N] in the context's precision, partials and scalars in double; grid (cg_blocks(N), B).
 hipError_t launch_expand_ids(hipStream_t s, const int32_t* mask_id, int32_t* out, int B, int C);          // out[b * C + c] = mask_id[b]
-template <typename R> hipError_t launch_cg_begin(hipStream_t s, const R* z, const R* w, typename CxOf<R>::type* xh, int B, size_t N);
+// the state arrays z, w, x of a coil context: real, or complex with pnp_set_image(PNP_IMAGE_COMPLEX) (the CX roles)
+template <typename R, bool CX> using CoilState = typename std::conditional<CX, typename CxOf<R>::type, R>::type;
+template <typename R, bool CX = false>
+hipError_t launch_cg_begin(hipStream_t s, const CoilState<R, CX>* z, const CoilState<R, CX>* w, typename CxOf<R>::type* xh, int B, size_t N);
 template <typename R> hipError_t launch_cg_init(hipStream_t s, const typename CxOf<R>::type* aty, const typename CxOf<R>::type* xh,
                                                 const typename CxOf<R>::type* gp, typename CxOf<R>::type* r, typename CxOf<R>::type* p,
                                                 R la2, double* part_rr, double* part_bb, int B, size_t N);
-// alpha = <r,r> / Re<p,Gp> from the partials; x^ += alpha p, r -= alpha Gp, partials of the new <r,r>; x_out (last iteration): |Re x^|
-template <typename R> hipError_t launch_cg_xr(hipStream_t s, typename CxOf<R>::type* xh, typename CxOf<R>::type* r,
+// alpha = <r,r> / Re<p,Gp> from the partials; x^ += alpha p, r -= alpha Gp, partials of the new <r,r>; x_out (last iteration): |Re x^|, CX: x^
+template <typename R, bool CX = false> hipError_t launch_cg_xr(hipStream_t s, typename CxOf<R>::type* xh, typename CxOf<R>::type* r,
                                               const typename CxOf<R>::type* p, const typename CxOf<R>::type* gp, const double* part_rr,
                                               const double* part_pgp, double* part_rr_next, double* scal /*[B][4]: alpha, beta, rr, -*/,
-                                              R* x_out, int B, size_t N, int H);
+                                              CoilState<R, CX>* x_out, int B, size_t N, int H);
 template <typename R> hipError_t launch_cg_p(hipStream_t s, const typename CxOf<R>::type* r, typename CxOf<R>::type* p, const double* part_rr,
                                              const double* part_rr_next, double* scal, int B, size_t N);
 hipError_t launch_cg_residual(hipStream_t s, const double* part_rr, const double* part_bb, double* rel /*[B]*/, int B, size_t N);
 template <typename R> hipError_t launch_cabs(hipStream_t s, const typename CxOf<R>::type* in, R* out, size_t n);
 hipError_t launch_prox_f64(hipStream_t s, bool cnc, const double* x, double* z, double* w, ProxParamsT<double> p, size_t n);
+
+// complex-valued images on a coil context (kernels_complex.hip): the z / w step on complex arrays [n] resp. [B][H][W], interleaved, in the
+// context's precision.  launch_prox_cx: 16-byte accesses, so x, z, w must be 16-byte aligned (hipErrorInvalidValue otherwise).
+// launch_wavelet_prox_cx: two launches, coef [B][H][W] complex scratch; wavelet_cx_fits: whether the setting's tile fits the LDS
+template <typename R>
+hipError_t launch_prox_cx(hipStream_t s, bool cnc, const typename CxOf<R>::type* x, typename CxOf<R>::type* z, typename CxOf<R>::type* w,
+                          const ProxParamsT<R>& p, size_t n);
+template <typename R>
+hipError_t launch_wavelet_prox_cx(hipStream_t s, int wavelet, int levels, bool cnc, const typename CxOf<R>::type* x, typename CxOf<R>::type* z,
+                                  typename CxOf<R>::type* w, typename CxOf<R>::type* coef, const ProxParamsT<R>& p, int B, int H, int W);
+bool wavelet_cx_fits(int wavelet, int levels, bool f64);
 
 // coil mixing ahead of the multi-coil solve (kernels_coilmix.hip, coilmix_plan.h): interleaved complex arrays in R, no context.
 // out[b][j][p] = sum_c m[set_id[b]][j][c] in[b][c][p] (in [B][C_in][N], m [Ks][C_out][C_in], out [B][C_out][N]; set_id null: set 0), and

@@ -5,6 +5,7 @@
 // pseudo-slices, coil-combining rows, which also leave the row partials of Re<p, Gp>).  The kernels here are the rest of a CG iteration:
 //   k_cg_init  r0 = aty + La2 v - G v, p0 = r0, partials of <r0, r0> and of ||aty + La2 v||^2
 //   k_cg_xr    alpha = <r, r> / Re<p, Gp>;  x^ += alpha p;  r -= alpha Gp;  partials of the new <r, r>;  last iteration: x = |Re x^|
+//              (complex images, pnp_set_image: x = x^, and k_cg_begin reads a complex z - w; the CX roles of both kernels)
 //   k_cg_p     beta = <r+, r+> / <r, r>;  p = r+ + beta p
 // Every scalar is formed on the device, by EVERY workgroup of a slice for itself from the slice's partials (a few hundred doubles, in the
 // fixed order of coil_plan.h): no atomics, no host round trip, and nothing that depends on the batch or on a slice's place in it.
@@ -47,12 +48,18 @@ __global__ __launch_bounds__(256) void k_expand_ids(const int32_t* mask_id, int3
     if (s < n) out[s] = mask_id[coil_pseudo_slice(s, C)];
 }
 
-template <typename R>
-__global__ __launch_bounds__(CG_THREADS) void k_cg_begin(const R* z, const R* w, typename CxOf<R>::type* xh, size_t N) {
+// CX: the state is complex (pnp_set_image): z - w keeps its imaginary part
+template <typename R, bool CX>
+__global__ __launch_bounds__(CG_THREADS) void k_cg_begin(const CoilState<R, CX>* z, const CoilState<R, CX>* w, typename CxOf<R>::type* xh, size_t N) {
     const size_t base = (size_t)blockIdx.y * N, lo = (size_t)blockIdx.x * CG_SPAN;
     for (size_t i = lo + threadIdx.x; i < lo + CG_SPAN && i < N; i += CG_THREADS) {
         typename CxOf<R>::type v;
-        v.x = z[base + i] - w[base + i]; v.y = R(0);
+        if constexpr (CX) {
+            const typename CxOf<R>::type zv = z[base + i], wv = w[base + i];
+            v.x = zv.x - wv.x; v.y = zv.y - wv.y;
+        } else {
+            v.x = z[base + i] - w[base + i]; v.y = R(0);
+        }
         xh[base + i] = v;
     }
 }
@@ -83,10 +90,11 @@ __global__ __launch_bounds__(CG_THREADS) void k_cg_init(const typename CxOf<R>::
     }
 }
 
-template <typename R>
+// CX: the last iteration stores x = x^ (complex) instead of |Re x^|
+template <typename R, bool CX>
 __global__ __launch_bounds__(CG_THREADS) void k_cg_xr(typename CxOf<R>::type* xh, typename CxOf<R>::type* r, const typename CxOf<R>::type* p,
                                                       const typename CxOf<R>::type* gp, const double* part_rr, const double* part_pgp,
-                                                      double* part_rr_next, double* scal, R* x_out, size_t N, int H) {
+                                                      double* part_rr_next, double* scal, CoilState<R, CX>* x_out, size_t N, int H) {
     using C = typename CxOf<R>::type;
     __shared__ double sh[CG_THREADS];
     const int b = blockIdx.y, nblk = gridDim.x;
@@ -103,7 +111,8 @@ __global__ __launch_bounds__(CG_THREADS) void k_cg_xr(typename CxOf<R>::type* xh
         rv.x = fma_r(-a, gv.x, rv.x); rv.y = fma_r(-a, gv.y, rv.y);
         xh[base + i] = xv;
         r[base + i] = rv;
-        if (x_out) x_out[base + i] = fabs(xv.x);
+        if constexpr (CX) { if (x_out) x_out[base + i] = xv; }
+        else              { if (x_out) x_out[base + i] = fabs(xv.x); }
         rn += (double)rv.x * (double)rv.x + (double)rv.y * (double)rv.y;
     }
     const double srn = block_sum_own(rn, sh);
@@ -168,8 +177,9 @@ hipError_t launch_expand_ids(hipStream_t s, const int32_t* mask_id, int32_t* out
     return hipGetLastError();
 }
 
-template <typename R> hipError_t launch_cg_begin(hipStream_t s, const R* z, const R* w, typename CxOf<R>::type* xh, int B, size_t N) {
-    hipLaunchKernelGGL(k_cg_begin<R>, cg_grid(B, N), dim3(CG_THREADS), 0, s, z, w, xh, N);
+template <typename R, bool CX>
+hipError_t launch_cg_begin(hipStream_t s, const CoilState<R, CX>* z, const CoilState<R, CX>* w, typename CxOf<R>::type* xh, int B, size_t N) {
+    hipLaunchKernelGGL((k_cg_begin<R, CX>), cg_grid(B, N), dim3(CG_THREADS), 0, s, z, w, xh, N);
     return hipGetLastError();
 }
 template <typename R>
@@ -178,11 +188,11 @@ hipError_t launch_cg_init(hipStream_t s, const typename CxOf<R>::type* aty, cons
     hipLaunchKernelGGL(k_cg_init<R>, cg_grid(B, N), dim3(CG_THREADS), 0, s, aty, xh, gp, r, p, la2, part_rr, part_bb, N);
     return hipGetLastError();
 }
-template <typename R>
+template <typename R, bool CX>
 hipError_t launch_cg_xr(hipStream_t s, typename CxOf<R>::type* xh, typename CxOf<R>::type* r, const typename CxOf<R>::type* p,
                         const typename CxOf<R>::type* gp, const double* part_rr, const double* part_pgp, double* part_rr_next, double* scal,
-                        R* x_out, int B, size_t N, int H) {
-    hipLaunchKernelGGL(k_cg_xr<R>, cg_grid(B, N), dim3(CG_THREADS), 0, s, xh, r, p, gp, part_rr, part_pgp, part_rr_next, scal, x_out, N, H);
+                        CoilState<R, CX>* x_out, int B, size_t N, int H) {
+    hipLaunchKernelGGL((k_cg_xr<R, CX>), cg_grid(B, N), dim3(CG_THREADS), 0, s, xh, r, p, gp, part_rr, part_pgp, part_rr_next, scal, x_out, N, H);
     return hipGetLastError();
 }
 template <typename R>
@@ -206,11 +216,14 @@ hipError_t launch_prox_f64(hipStream_t s, bool cnc, const double* x, double* z, 
 }
 
 #define COIL_INST(R)                                                                                                                        \
-    template hipError_t launch_cg_begin<R>(hipStream_t, const R*, const R*, CxOf<R>::type*, int, size_t);                                   \
+    template hipError_t launch_cg_begin<R, false>(hipStream_t, const R*, const R*, CxOf<R>::type*, int, size_t);                            \
+    template hipError_t launch_cg_begin<R, true>(hipStream_t, const CxOf<R>::type*, const CxOf<R>::type*, CxOf<R>::type*, int, size_t);     \
+    template hipError_t launch_cg_xr<R, true>(hipStream_t, CxOf<R>::type*, CxOf<R>::type*, const CxOf<R>::type*, const CxOf<R>::type*,      \
+                                              const double*, const double*, double*, double*, CxOf<R>::type*, int, size_t, int);            \
     template hipError_t launch_cg_init<R>(hipStream_t, const CxOf<R>::type*, const CxOf<R>::type*, const CxOf<R>::type*, CxOf<R>::type*,    \
                                           CxOf<R>::type*, R, double*, double*, int, size_t);                                                \
-    template hipError_t launch_cg_xr<R>(hipStream_t, CxOf<R>::type*, CxOf<R>::type*, const CxOf<R>::type*, const CxOf<R>::type*,            \
-                                        const double*, const double*, double*, double*, R*, int, size_t, int);                              \
+    template hipError_t launch_cg_xr<R, false>(hipStream_t, CxOf<R>::type*, CxOf<R>::type*, const CxOf<R>::type*, const CxOf<R>::type*,     \
+                                               const double*, const double*, double*, double*, R*, int, size_t, int);                       \
     template hipError_t launch_cg_p<R>(hipStream_t, const CxOf<R>::type*, CxOf<R>::type*, const double*, const double*, double*, int, size_t); \
     template hipError_t launch_cabs<R>(hipStream_t, const CxOf<R>::type*, R*, size_t);
 COIL_INST(float)

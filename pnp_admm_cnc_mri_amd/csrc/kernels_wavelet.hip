@@ -14,30 +14,11 @@
 #include "internal.h"
 #include "prox_ops.h"
 #include "wavelet_plan.h"
+#include "wavelet_kernels.h"
 
 namespace pnp {
 
 namespace {
-
-template <typename R>
-struct WvArgs {
-    const R* in0;      // fwd: image (NONE), x (L1, CNC);   inv: coefficients
-    const R* in1;      // fwd: null (NONE), w
-    const R* zin;      // fwd CNC: z
-    R* out;            // fwd: coefficients;   inv NONE: image
-    const R* x;        // inv with dual: x, w (read), z, w (written)
-    R *z, *w;
-    ProxParamsT<R> p;
-    int H, W, L, tile, tiles_x, tiles_y;
-    int sy, sx;        // the frame's shift
-    R* acc;            // inv, averaging: the sum of the shifts' z+
-    R rk;              // inv, last of K > 1 shifts: 1 / K
-};
-
-template <typename R> __device__ __forceinline__ WvTile wv_tile_of_block(const WvArgs<R>& a) {
-    const int per = a.tiles_x * a.tiles_y, b = blockIdx.x / per, rem = blockIdx.x - b * per, ty = rem / a.tiles_x, tx = rem - ty * a.tiles_x;
-    return WvTile{a.H, a.W, a.L, a.tile, ty * a.tile, tx * a.tile, (size_t)b * a.H * a.W, a.sy, a.sx};
-}
 
 // what happens to a coefficient on its way out
 template <typename R> struct EmitStore {            // Psi alone; CNC: the raw coefficients of z
@@ -60,16 +41,6 @@ template <typename R> struct EmitCnc {              // v = coefficient of x + w;
         }
     }
 };
-
-template <typename R, int T, typename Emit>
-__device__ __forceinline__ void wv_fwd_image(const WvTile& t, const R* in0, const R* in1, R* rowbuf, R* ll, Emit emit) {
-    for (int l = 0; l < t.L; ++l) {
-        for (int it = threadIdx.x, n = wv_fwd_row_items(T, t, l); it < n; it += WV_THREADS) wv_fwd_row_item<R, T>(it, l, t, in0, in1, ll, rowbuf);
-        __syncthreads();
-        for (int it = threadIdx.x, n = wv_fwd_col_items(T, t, l); it < n; it += WV_THREADS) wv_fwd_col_item<R, T>(it, l, t, rowbuf, ll, emit);
-        __syncthreads();
-    }
-}
 
 // PROX: 0 none, 1 L1, 2 CNC
 template <typename R, int PROX, int T>
@@ -127,25 +98,11 @@ __global__ __launch_bounds__(WV_THREADS) void k_wv_inv(const WvArgs<R> a) {
     const WvTile t = wv_tile_of_block(a);
     R* colbuf = (R*)wv_smem;
     R* ll = colbuf + wv_inv_colbuf_elems(T, a.tile);
-    for (int l = a.L - 1; l >= 0; --l) {
-        for (int it = threadIdx.x, n = wv_inv_col_items(T, t, l); it < n; it += WV_THREADS) wv_inv_col_item<R, T>(it, l, t, a.in0, ll, colbuf);
-        __syncthreads();
-        for (int it = threadIdx.x, n = wv_inv_row_items(T, t, l); it < n; it += WV_THREADS) {
-            if constexpr (OUT == WV_OUT_IMAGE) wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitImage<R>{a.out});
-            if constexpr (OUT == WV_OUT_DUAL) wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitDual<R>{a.x, a.z, a.w});
-            if constexpr (OUT == WV_OUT_ACC_STORE) wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitAccStore<R>{a.acc});
-            if constexpr (OUT == WV_OUT_ACC_ADD) wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitAccAdd<R>{a.acc});
-            if constexpr (OUT == WV_OUT_AVG_DUAL) wv_inv_row_item<R, T>(it, l, t, colbuf, ll, EmitAvgDual<R>{a.x, a.acc, a.z, a.w, a.rk});
-        }
-        __syncthreads();
-    }
-}
-
-template <typename K, typename A> hipError_t wv_launch(K kernel, hipStream_t s, int blocks, size_t lds, std::atomic<bool>* done, const A& a) {
-    if (lds > WV_LDS_MAX) return hipErrorInvalidValue;
-    if (hipError_t e = lds_opt_in((const void*)kernel, done, lds, WV_LDS_MAX)) return e;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(WV_THREADS), lds, s, a);
-    return hipGetLastError();
+    if constexpr (OUT == WV_OUT_IMAGE) wv_inv_image<R, T>(t, a.L, a.in0, colbuf, ll, [&] { return EmitImage<R>{a.out}; });
+    if constexpr (OUT == WV_OUT_DUAL) wv_inv_image<R, T>(t, a.L, a.in0, colbuf, ll, [&] { return EmitDual<R>{a.x, a.z, a.w}; });
+    if constexpr (OUT == WV_OUT_ACC_STORE) wv_inv_image<R, T>(t, a.L, a.in0, colbuf, ll, [&] { return EmitAccStore<R>{a.acc}; });
+    if constexpr (OUT == WV_OUT_ACC_ADD) wv_inv_image<R, T>(t, a.L, a.in0, colbuf, ll, [&] { return EmitAccAdd<R>{a.acc}; });
+    if constexpr (OUT == WV_OUT_AVG_DUAL) wv_inv_image<R, T>(t, a.L, a.in0, colbuf, ll, [&] { return EmitAvgDual<R>{a.x, a.acc, a.z, a.w, a.rk}; });
 }
 
 template <typename R, int PROX, int T> hipError_t wv_fwd_t(hipStream_t s, const WvArgs<R>& a, int B) {
@@ -155,14 +112,6 @@ template <typename R, int PROX, int T> hipError_t wv_fwd_t(hipStream_t s, const 
 template <typename R, int OUT, int T> hipError_t wv_inv_t(hipStream_t s, const WvArgs<R>& a, int B) {
     static std::atomic<bool> done[64] = {};
     return wv_launch(k_wv_inv<R, OUT, T>, s, B * a.tiles_x * a.tiles_y, wv_inv_lds_elems(T, a.tile) * sizeof(R), done, a);
-}
-
-template <typename R> WvArgs<R> wv_args(int wavelet, int levels, int H, int W) {
-    WvArgs<R> a{};
-    const int T = wv_taps(wavelet);
-    a.H = H; a.W = W; a.L = levels; a.tile = wv_tile(T, levels);
-    a.tiles_x = wv_tiles(W, a.tile); a.tiles_y = wv_tiles(H, a.tile);
-    return a;
 }
 
 template <typename R, int PROX> hipError_t wv_fwd_p(hipStream_t s, int wavelet, const WvArgs<R>& a, int B) {

@@ -28,6 +28,7 @@ def _host(a, dtype):
 
 
 WAVELETS = {None: 0, 'haar': 1, 'db2': 2, 'db4': 3}                                    # PNP_WAVELET_* of include/pnp_mri.h
+IMAGE_MODES = {'real': 0, 'complex': 1}                                                # PNP_IMAGE_* of include/pnp_mri.h
 
 
 def check_sparsity(wavelet, levels, H, W):
@@ -42,6 +43,17 @@ def check_sparsity(wavelet, levels, H, W):
         if L.pnp_sparsity_check(WAVELETS[wavelet], int(levels), int(H), int(W)) != 0:
             raise ValueError(L.pnp_last_error().decode('utf-8', 'replace'))
     return WAVELETS[wavelet]
+
+
+def check_image(mode, wavelet=None, levels=3, precision='f32'):
+    """ValueError unless the image mode runs with this sparsity setting and precision (pnp_image_check: the library's own rule, no
+    context and no device needed -- db4 with 4 levels does not fit the LDS on complex doubles).  -> the PNP_IMAGE_* code."""
+    if mode not in IMAGE_MODES:
+        raise ValueError("image must be 'real' or 'complex' (got %r)" % (mode,))
+    L = _lib.lib()
+    if L.pnp_image_check(IMAGE_MODES[mode], WAVELETS.get(wavelet, 0), int(levels) if wavelet is not None else 0, 1 if precision == 'f64' else 0) != 0:
+        raise ValueError(L.pnp_last_error().decode('utf-8', 'replace'))
+    return IMAGE_MODES[mode]
 
 
 def check_spin(shifts, levels, per_prox=1):
@@ -135,6 +147,7 @@ class Engine:
         self._real = np.float64 if self.f64 else np.float32
         self._cplx = np.complex128 if self.f64 else np.complex64
         self.C = 0                                        # coils (set_coils); 0: none
+        self._cx = False                                  # complex image mode (set_image_mode)
 
     # -- lifetime -------------------------------------------------------------------------
     def close(self):
@@ -225,7 +238,7 @@ class Engine:
         LARGE reo -- the in-function default 2.75 -- NEED MORE, see cg_residual).  Drops the uploaded problem."""
         if sens is None:
             _lib.check(self._L.pnp_set_coils_f64(self._ctx, None, 0, 0, 0) if self.f64 else self._L.pnp_set_coils(self._ctx, None, 0, 0, 0))
-            self.C, self.B = 0, 0
+            self.C, self.B, self._cx = 0, 0, False
             return
         Cn, Ks = check_coils(sens, self.H, self.W, cg_iters)
         dev = _is_dev(sens)
@@ -234,7 +247,28 @@ class Engine:
         _lib.check(self._L.pnp_set_cg(self._ctx, int(cg_iters)))
         fn = self._L.pnp_set_coils_f64 if self.f64 else self._L.pnp_set_coils
         _lib.check(fn(self._ctx, _ptr(sens), Cn, Ks, 1 if dev else 0))
-        self.C, self.Ks, self.B = Cn, Ks, 0
+        self.C, self.Ks, self.B, self._cx = Cn, Ks, 0, False
+
+    def set_image_mode(self, mode='real'):
+        """'complex': the loops of a coil engine keep the image phase (pnp_set_image) -- x, z, w are complex [B,H,W], z0 = A^H y,
+        x = x^ of the CG x-step, the prox thresholds the modulus; init_state, admm_l1, admm_cnc, x, set_state, get_state, dc_step,
+        prox_*_dual, A and the metrics follow.  Needs coils (set_coils, which also returns the engine to 'real') and no spin table; no
+        trace, no residuals.  Drops the uploaded problem.  'real': as ever."""
+        if mode not in IMAGE_MODES:
+            raise ValueError("image must be 'real' or 'complex' (got %r)" % (mode,))
+        _lib.check(self._L.pnp_set_image(self._ctx, IMAGE_MODES[mode]))
+        self._cx, self.B = mode == 'complex', 0
+
+    @property
+    def image_mode(self):
+        """'real' or 'complex' (pnp_get_image)"""
+        m = C.c_int(0)
+        _lib.check(self._L.pnp_get_image(self._ctx, C.byref(m)))
+        return {v: k for k, v in IMAGE_MODES.items()}[m.value]
+
+    def _fn(self, name):
+        """the entry point `name` of the engine's image mode and precision: pnp_<name>[_cx][_f64]"""
+        return getattr(self._L, 'pnp_' + name + ('_cx' if self._cx else '') + ('_f64' if self.f64 else ''))
 
     @property
     def coils(self):
@@ -414,21 +448,23 @@ class Engine:
         _lib.check(self._L.pnp_prepare_loops(self._ctx))
 
     def set_state(self, z=None, w=None):
-        zz = None if z is None else (z if _is_dev(z) else _host(z, self._real))
-        ww = None if w is None else (w if _is_dev(w) else _host(w, self._real))
+        """z, w [B,H,W]: real, or complex in complex image mode (set_image_mode)"""
+        dt = self._cplx if self._cx else self._real
+        zz = None if z is None else (z if _is_dev(z) else _host(z, dt))
+        ww = None if w is None else (w if _is_dev(w) else _host(w, dt))
         dev = 1 if (_is_dev(z) or _is_dev(w)) else 0
-        fn = self._L.pnp_set_state_f64 if self.f64 else self._L.pnp_set_state
+        fn = self._fn('set_state')
         _lib.check(fn(self._ctx, _ptr(zz), _ptr(ww), dev))
 
     def get_state(self, z_out=None, w_out=None):
         """-> (z, w) as host arrays, or copied device-to-device into the given device tensors."""
-        fn = self._L.pnp_get_state_f64 if self.f64 else self._L.pnp_get_state
+        fn = self._fn('get_state')
         if z_out is not None or w_out is not None:
             if not all(o is None or _is_dev(o) for o in (z_out, w_out)):
                 raise TypeError('get_state outputs must be device tensors')
             _lib.check(fn(self._ctx, _ptr(z_out), _ptr(w_out), 1))
             return z_out, w_out
-        z = np.empty((self.B, self.H, self.W), self._real)
+        z = np.empty((self.B, self.H, self.W), self._cplx if self._cx else self._real)
         w = np.empty_like(z)
         _lib.check(fn(self._ctx, _ptr(z), _ptr(w), 0))
         return z, w
@@ -478,24 +514,29 @@ class Engine:
         return trace
 
     def x(self, out=None):
-        fn = self._L.pnp_download_x_f64 if self.f64 else self._L.pnp_download_x
+        """the x of the last loop, [B,H,W]: real, or complex in complex image mode"""
+        fn = self._fn('download_x')
         if out is not None and _is_dev(out):
             _lib.check(fn(self._ctx, _ptr(out), 1))
             return out
-        x = np.empty((self.B, self.H, self.W), self._real)
+        x = np.empty((self.B, self.H, self.W), self._cplx if self._cx else self._real)
         _lib.check(fn(self._ctx, _ptr(x), 0))
         return x
 
     # -- step-wise operators on device tensors (PnP path) ---------------------------------
+    # In complex image mode dc_step, prox_l1_dual and prox_cnc_dual take complex device tensors of the engine's precision (the _cx calls,
+    # which exist in float and double); in real mode they are the float32 calls they ever were.
     def dc_step(self, z, w, x, reo):
-        _lib.check(self._L.pnp_dc_step(self._ctx, _ptr(z), _ptr(w), _ptr(x), float(reo)))
+        fn = self._fn('dc_step') if self._cx else self._L.pnp_dc_step
+        _lib.check(fn(self._ctx, _ptr(z), _ptr(w), _ptr(x), float(reo)))
 
     def prox_l1_dual(self, x, z, w, thr):
-        _lib.check(self._L.pnp_prox_l1_dual(self._ctx, _ptr(x), _ptr(z), _ptr(w), float(thr)))
+        fn = self._fn('prox_l1_dual') if self._cx else self._L.pnp_prox_l1_dual
+        _lib.check(fn(self._ctx, _ptr(x), _ptr(z), _ptr(w), float(thr)))
 
     def prox_cnc_dual(self, x, z, w, alpha, lambda1, reo, b):
-        _lib.check(self._L.pnp_prox_cnc_dual(self._ctx, _ptr(x), _ptr(z), _ptr(w), float(alpha), float(lambda1),
-                                             float(reo), float(b)))
+        fn = self._fn('prox_cnc_dual') if self._cx else self._L.pnp_prox_cnc_dual
+        _lib.check(fn(self._ctx, _ptr(x), _ptr(z), _ptr(w), float(alpha), float(lambda1), float(reo), float(b)))
 
     def cnc_combine(self, z, x, w, s, t, alpha, lambda1, reo, b):
         _lib.check(self._L.pnp_cnc_combine(self._ctx, _ptr(z), _ptr(x), _ptr(w), _ptr(s), _ptr(t), float(alpha),
@@ -551,7 +592,8 @@ class Engine:
         _lib.check(fn(self._ctx, _ptr(inp), _ptr(out), int(B), int(inverse), int(sy), int(sx)))
 
     def A(self, x, k):
-        _lib.check(self._L.pnp_A(self._ctx, _ptr(x), _ptr(k)))
+        """x real [B,H,W]; in complex image mode x complex [B,H,W] (pnp_A_cx)"""
+        _lib.check((self._L.pnp_A_cx if self._cx else self._L.pnp_A)(self._ctx, _ptr(x), _ptr(k)))
 
     def AH(self, k, out):
         _lib.check(self._L.pnp_AH(self._ctx, _ptr(k), _ptr(out)))

@@ -33,9 +33,13 @@ def gather_slices(x_local, B_total, dst=0, group=None):
     The root receives into ONE [world * bmax, H, W] tensor whose per-rank views are the gather
     list, so even shards (the benchmark's and every power-of-two job's case) need no second copy
     of the result: the tensor returned IS the receive buffer.  Uneven shards are padded to the
-    largest shard for the collective and compacted on the root."""
+    largest shard for the collective and compacted on the root.  A complex tensor (image='complex') travels as its real view
+    [b_r, H, W, 2] -- dist.gather takes no complex dtype -- and comes back complex on the root."""
     import torch
     import torch.distributed as dist
+    if x_local.is_complex():
+        out = gather_slices(torch.view_as_real(x_local.contiguous()), B_total, dst=dst, group=group)
+        return None if out is None else torch.view_as_complex(out.contiguous())
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)                       # position inside `group`: which shard this rank holds
     # `dst` is a GLOBAL rank (what dist.gather takes), so compare it with the global rank
@@ -81,7 +85,7 @@ def solve_sharded(solver, mask, noises, images=None, y=None, mask_id=None, dst=0
     coil_id [B] (with coils= among the solver's keywords: a bank of coil maps, which every rank gets whole) is sliced with the shard as
     mask_id is, and so is per-slice noise -- [B,H,W] without coils, [B,C,H,W] with them ([C,H,W] is shared by the slices).
     Every rank passes the SAME full `images` / `y` / `mask_id` / `coil_id`; returns an array [B_total, H, W] on `dst`
-    (float32; float64 when the solver is run with precision='f64'), None elsewhere.  With no process
+    (float32; float64 when the solver is run with precision='f64'; complex64 / complex128 with image='complex'), None elsewhere.  With no process
     group it is a plain call.
     gather_device: torch device for the collective (default under nccl: the device the solver's result lies on -- see
     collective_device; cpu under gloo).  Solver contract: called as solver(mask, noises, images=/y=/mask_id= slices, **opts,
@@ -115,6 +119,9 @@ def solve_sharded(solver, mask, noises, images=None, y=None, mask_id=None, dst=0
     # hand back ONE [b,H,W] device tensor (no 22-slot list of host arrays), RCCL gathers it as it is, and the only device-to-host
     # copy of the job is the root's, of the gathered result (config 4: 128 MiB per rank stay off PCIe in both directions).
     tdt = torch.float64 if real is np.float64 else torch.float32
+    if kw.get('image') == 'complex':                      # ADMM_L1 / ADMM_CNC with image='complex': the gathered array is complex
+        real = np.complex128 if real is np.float64 else np.complex64
+        tdt = torch.complex128 if real is np.complex128 else torch.complex64
     if hi > lo:
         # solver contract: `return_device=True` -> ONE [b,H,W] tensor (every entry point of this package); a solver whose signature has
         # neither that keyword nor **opts is called without it and may return the reference's list of host arrays
@@ -126,6 +133,9 @@ def solve_sharded(solver, mask, noises, images=None, y=None, mask_id=None, dst=0
             x_local = torch.from_numpy(np.stack([np.asarray(out[n], dtype=real) for n in range(hi - lo)]))
         if tuple(x_local.shape[:1]) != (hi - lo,):
             raise TypeError('solve_sharded: the solver returned %s for a shard of %d slices' % (tuple(x_local.shape), hi - lo))
+        if x_local.is_complex() and not tdt.is_complex:   # e.g. image='complex' bound with functools.partial: a cast would drop the phase
+            raise TypeError("solve_sharded: the solver returned a complex result but image='complex' is not among solve_sharded's "
+                            'keywords (every rank, also one with an empty shard, must know the dtype of the gather): pass it there')
         if x_local.dtype != tdt:                          # one dtype on every rank (empty shards send zeros of `tdt`): mixed dtypes hang a gather
             x_local = x_local.to(tdt)
     else:

@@ -74,6 +74,15 @@ bypass the file system through the extra keyword arguments
               largest; maps_radius is not used.  C maps_kernel^2 <= 128 (of the MIXED channels: virtual_coils= first).  info['coil_maps']
               gains method, kernel, sigma, crop and rank (per slice).  The default, 'walsh', is bit for bit what it was
 
+    image='real'   (ADMM_L1 and ADMM_CNC only) 'complex': the reconstruction keeps the image phase (include/pnp_mri.h, "complex-valued
+              images"): x, z, w are complex, z0 = A^H y without the modulus, the x-step returns x^ itself instead of |Re x^|, and the prox
+              thresholds the MODULUS of a pixel (or, with transform=, of a wavelet coefficient of the complex image).  Needs coils= (an
+              array or 'estimate', with or without virtual_coils= / noise_cov=) and measured y=; spin=, trace_every= and tol= are refused
+              with it (ValueError before an engine is opened).  `out` then holds complex128 [H,W] arrays (return_device=True: one complex
+              tensor), PSNR / SSIM / RE are taken on |x| when images= is given, info['image'] = 'complex'.  NOT in the reference scripts,
+              which reconstruct a real PNG; 'real' (the default) calls nothing new and is bit for bit what it was.  One extra log line.
+              The three PnP entry points do not have the keyword: their denoisers are real
+
 The PnP entry points (PNP_ADMM_L1_D, PNP_ADMM_CNC_D, PNP_ADMM_CNC_DnCNN) live in solvers_pnp.py.
 """
 import logging
@@ -84,7 +93,7 @@ import numpy as np
 
 from . import coilmaps, coilmix, imageio
 from ._lib import PnpError
-from .engine import Engine, check_coils, check_sparsity, spin_table
+from .engine import Engine, check_coils, check_image, check_sparsity, spin_table
 
 # CLI presets of the reference scripts (positional order differs per script!)
 PRESETS = {
@@ -142,12 +151,20 @@ class _Job:
     def __init__(self, mask, noises, tag, suffix, images=None, y=None, mask_id=None, testsets='testsets',
                  testset_name='Set1', results='results', save_E=None, device=None, log=None, ssim=None,
                  psnr_fmt='{:.4f}', precision='f32', coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
-                 maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02, maps_crop=0.9):
+                 maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02, maps_crop=0.9,
+                 image='real'):
         # psnr_fmt: S1:150 and S3:320 print the per-image PSNR with two decimals, S4:155 / S6:332 / S6:548 with four
         self.tag, self.suffix, self.psnr_fmt = tag, suffix, psnr_fmt
         if precision not in ('f32', 'f64'):
             raise ValueError("precision must be 'f32' or 'f64'")
         self.precision = precision
+        self.image = image
+        if image == 'complex':                                       # every check before an engine is opened (image_request has the rest)
+            if coils is None:
+                raise ValueError("image='complex' runs on the multi-coil path: it needs coils= (an array of maps or 'estimate')")
+            if y is None:
+                raise ValueError("image='complex' reconstructs MEASURED data: it needs y= [B,C,H,W] (the synthesis from images= is "
+                                 'real-input; images= may still be given as the ground truth of |x|)')
         mask = np.asarray(mask)
         self.mask_bank = mask[None] if mask.ndim == 2 else mask
         self.H, self.W = self.mask_bank.shape[1:]
@@ -270,6 +287,10 @@ class _Job:
             if self.log is not None:
                 self.log.info('multi-coil data consistency: {:d} coils, {:d} CG iterations per x-step (not in the reference scripts)'.format(
                     eng.C, int(self.cg_iters)))
+        if self.image == 'complex':                                  # after set_coils, which returns the engine to real mode
+            eng.set_image_mode('complex')
+            if self.log is not None:
+                self.log.info('complex-valued image: the phase is kept, the prox thresholds the modulus (not in the reference scripts)')
         coil = {} if self.coils is None else {'coil_id': self.coil_id}
         if self.y is not None:
             eng.upload(self.y, self.mask_bank, self.mask_id, **coil)
@@ -286,12 +307,14 @@ class _Job:
         if isinstance(x, np.ndarray):
             out = [A] * max(22, self.B)
             for n in range(self.B):
-                out[n] = x[n].astype(np.float64)
+                out[n] = x[n].astype(np.complex128 if np.iscomplexobj(x) else np.float64)
         else:
             out = x                                                  # return_device=True: the device tensor [B,H,W] itself
             if self.save_E:
                 x = x.reshape(self.B, self.H, self.W).cpu().numpy()
         info = OrderedDict(psnr=[], ssim=[], re=[])
+        if self.image == 'complex':
+            info['image'] = 'complex'
         if self.coils is not None:
             try:
                 info['cg_residual'] = list(map(float, eng.cg_residual()))
@@ -322,7 +345,7 @@ class _Job:
             os.makedirs(self.E_path, exist_ok=True)
             for n in range(self.B):
                 stem = os.path.splitext(self.names[n])[0] if self.names else '%04d' % n
-                imageio.imsave_gray(x[n] * 255, os.path.join(self.E_path, stem + self.suffix + '.png'))
+                imageio.imsave_gray(np.abs(x[n]) * 255, os.path.join(self.E_path, stem + self.suffix + '.png'))
         return out, psnr1, info
 
 
@@ -336,6 +359,18 @@ def trace_request(trace_every, tol, return_info):
     if tol is not None and not float(tol) > 0:
         raise ValueError('tol must be > 0 (got %r)' % (tol,))
     return on
+
+
+def image_request(image, spin, trace_every, tol, transform=None, levels=3, precision='f32'):
+    """the rules of image= that need no _Job; every one is a ValueError here, before an engine is opened"""
+    if image not in ('real', 'complex'):
+        raise ValueError("image must be 'real' or 'complex' (got %r)" % (image,))
+    if image == 'complex':
+        if spin is not None:
+            raise ValueError("image='complex' does not run with spin= (cycle spinning is not built for complex images)")
+        if trace_every or tol is not None:
+            raise ValueError("image='complex' does not run with trace_every= / tol= (the trace is not built for complex images)")
+        check_image('complex', transform, levels, precision)
 
 
 def spin_request(spin, spin_average, spin_seed, transform, levels, iter_num):
@@ -358,8 +393,9 @@ def log_early_stop(job, trace, iter_num, tol):
 def _device_x(eng, job):
     """the ctx's x copied device-to-device into a torch tensor that outlives the engine"""
     import torch
-    xt = torch.empty((job.B, job.H, job.W), dtype=torch.float64 if job.precision == 'f64' else torch.float32,
-                     device=torch.device('cuda', job.device))
+    f64 = job.precision == 'f64'
+    dt = (torch.complex128 if f64 else torch.complex64) if job.image == 'complex' else (torch.float64 if f64 else torch.float32)
+    xt = torch.empty((job.B, job.H, job.W), dtype=dt, device=torch.device('cuda', job.device))
     eng.x(out=xt)
     eng.sync()
     return xt
@@ -369,18 +405,19 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
             results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
             transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
             maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02,
-             maps_crop=0.9, spin=None, spin_average=1, spin_seed=0, **ADMM_L1_opts):
+             maps_crop=0.9, spin=None, spin_average=1, spin_seed=0, image='real', **ADMM_L1_opts):
     """ADMM with L1 prox on the MI355X engine.  Reference: "【1】ADMM_L1.py":29-169."""
     iter_num = ADMM_L1_opts.get('iter_num', 20)          # S1:35
     lambda1 = ADMM_L1_opts.get('lambda1', 0.04)          # S1:36
     reo = ADMM_L1_opts.get('reo', 0.04)                  # S1:37
     traced = trace_request(trace_every, tol, return_info)
     check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
+    image_request(image, spin, trace_every, tol, transform, levels, precision)
     shifts = spin_request(spin, spin_average, spin_seed, transform, levels, iter_num)
     job = _Job(mask, noises, 'ADMM_L1', '_PDG L1', images, y, mask_id, testsets, testset_name, results, save_E, device,
                psnr_fmt='{:.2f}', precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters, virtual_coils=virtual_coils,
                noise_cov=noise_cov, calib=calib, maps_radius=maps_radius, maps_power_iters=maps_power_iters, maps_thresh=maps_thresh,
-               maps_method=maps_method, maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop)   # S1:150
+               maps_method=maps_method, maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop, image=image)   # S1:150
     with job.open_engine(transform=transform, levels=levels, spin=shifts, spin_average=spin_average) as eng:
         # S1:111-126, all slices, on device
         trace = eng.admm_l1(iter_num, lambda1, reo, trace_every, tol, job.gt_u8) if traced else eng.admm_l1(iter_num, lambda1, reo)
@@ -396,7 +433,7 @@ def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets
              results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
              transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
              maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02,
-             maps_crop=0.9, spin=None, spin_average=1, spin_seed=0, **ADMM_CNC_opts):
+             maps_crop=0.9, spin=None, spin_average=1, spin_seed=0, image='real', **ADMM_CNC_opts):
     """ADMM with the convex-non-convex z-step.  Reference: "【4】ADMM_CNC .py":31-174."""
     iter_num = ADMM_CNC_opts.get('iter_num', 4)          # S4:37
     alpha = ADMM_CNC_opts.get('alpha', 0.4)              # S4:38
@@ -405,11 +442,12 @@ def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets
     b = ADMM_CNC_opts.get('b', 1)                        # S4:41  (b is b^2 of the paper)
     traced = trace_request(trace_every, tol, return_info)
     check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
+    image_request(image, spin, trace_every, tol, transform, levels, precision)
     shifts = spin_request(spin, spin_average, spin_seed, transform, levels, iter_num)
     job = _Job(mask, noises, 'ADMM_CNC', '_ADMM CNC', images, y, mask_id, testsets, testset_name, results, save_E, device,
                precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters, virtual_coils=virtual_coils, noise_cov=noise_cov,
                calib=calib, maps_radius=maps_radius, maps_power_iters=maps_power_iters, maps_thresh=maps_thresh,
-               maps_method=maps_method, maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop)
+               maps_method=maps_method, maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop, image=image)
     with job.open_engine(transform=transform, levels=levels, spin=shifts, spin_average=spin_average) as eng:
         # S4:115-132
         trace = (eng.admm_cnc(iter_num, alpha, lambda1, reo, b, trace_every, tol, job.gt_u8) if traced

@@ -90,12 +90,16 @@ def _coils_of(eng, coils):
 
 def A(eng, x, coils=None):
     """A x = fft2(x) * mask for real x [B,H,W] with the engine's uploaded masks (S4:102).  On an engine with coils (Engine.set_coils;
-    coils=True insists on it): (A x)_c = fft2(S_c x) * mask, [B,C,H,W]."""
+    coils=True insists on it): (A x)_c = fft2(S_c x) * mask, [B,C,H,W].  On an engine in complex image mode (Engine.set_image_mode) x is
+    a complex batch [B,H,W]."""
     torch = _torch()
-    x = _prep(eng, x.float())
+    cx = getattr(eng, 'image_mode', 'real') == 'complex'
+    if x.is_complex() and not cx:
+        raise ValueError("A takes a complex image only on an engine in complex image mode (Engine.set_image_mode('complex'))")
+    x = _prep(eng, x.to(torch.complex64) if cx else x.float())
     n = _coils_of(eng, coils)
     k = torch.empty((x.shape[0], n) + tuple(x.shape[1:]) if n else x.shape, dtype=torch.complex64, device=x.device)
-    eng.A(x, torch.view_as_real(k))
+    eng.A(torch.view_as_real(x) if cx else x, torch.view_as_real(k))
     return k
 
 

@@ -111,10 +111,6 @@ struct Coils {
     bool have_rel = false;            // an x-step has run on the current problem
     AnySize* any = nullptr;           // the transforms of a coil context: the any-size kernels at every shape (the context's own, or made here)
     bool own_any = false;
-    // complex-valued images (pnp_set_image): the state of the loops is complex and lives here, beside the real z / w / x of the context
-    int image = PNP_IMAGE_REAL;
-    void *zc = nullptr, *wc = nullptr, *xc = nullptr;      // [Bmax][H][W] complex, allocated by pnp_set_image(PNP_IMAGE_COMPLEX)
-    void* wv_coef = nullptr;          // [Bmax][H][W] complex: the coefficients between the two launches of the complex wavelet prox (on first use)
 };
 
 // The three stage times of a coil-map estimator (pnp_*_stage_times): ms accumulates since the last read, the events exist once enabled.
@@ -136,7 +132,10 @@ struct pnp_ctx {
     bool state_sliced = false;       // z / w are in the slice-resident kernel's order (slice_layout.h, sl_state_index)
     void* y = nullptr;                // [Bmax][H][W] complex, in the context's precision (bufs<R>)
     void* work = nullptr;             // [Bmax][H][W] complex transform intermediate
+    // the state of the loops (state<R, CX>): real, and beside it the complex one of a coil context with complex-valued images
     void *z = nullptr, *w = nullptr, *x = nullptr;     // [Bmax][H][W] real
+    int image = PNP_IMAGE_REAL;       // pnp_set_image; back to real, and the complex arrays freed, with the coils (coils_free)
+    void *zc = nullptr, *wc = nullptr, *xc = nullptr;  // [Bmax][H][W] complex, allocated by pnp_set_image(PNP_IMAGE_COMPLEX)
     uint8_t* mask_bank = nullptr;     // [Kcap][H][W]
     int Kcap = 0;
     int32_t* mask_id = nullptr;       // [Bmax]
@@ -153,6 +152,7 @@ struct pnp_ctx {
     Trace trace;
     int wavelet = WV_NONE, wv_levels = 0;   // pnp_set_sparsity: the prox of the loops acts on the coefficients of this transform
     void* wv_coef = nullptr;          // [Bmax][H][W] real: the coefficients between the two prox launches (on first use)
+    void* wv_coef_cx = nullptr;       // [Bmax][H][W] complex: the same of the complex prox (by pnp_set_image / pnp_set_sparsity, whichever comes second)
     std::vector<int32_t> spin;        // pnp_set_spin: shifts[n][2] of the wavelet prox (empty: none) ...
     int spin_k = 1, spin_p = 0;       // ... per_prox of them a step, and the cursor: prox steps since it was last set
     void* wv_acc = nullptr;           // [Bmax][H][W] real: the sum of the shifts' z+ (by the first per_prox > 1)
@@ -174,6 +174,16 @@ template <typename R> static Bufs<R> bufs(const pnp_ctx* c) {
     using C = typename CxOf<R>::type;
     return {(C*)c->y, (C*)c->work, (R*)c->z, (R*)c->w, (R*)c->x};
 }
+// The state of the loops and the wavelet prox's coefficient array as their element type: R, or with CX (complex-valued images) the complex of R.
+template <typename R, bool CX> struct State {
+    CoilState<R, CX> *z, *w, *x, *wv_coef;
+};
+template <typename R, bool CX> static State<R, CX> state(const pnp_ctx* c) {
+    using T = CoilState<R, CX>;
+    if constexpr (CX) return {(T*)c->zc, (T*)c->wc, (T*)c->xc, (T*)c->wv_coef_cx};
+    else return {(T*)c->z, (T*)c->w, (T*)c->x, (T*)c->wv_coef};
+}
+static bool cx_mode(const pnp_ctx* c) { return c->image == PNP_IMAGE_COMPLEX; }
 
 static bool supported(int n) { return n == 256 || n == 512; }
 
@@ -253,6 +263,23 @@ static int copy_out(pnp_ctx* c, void* dst, const void* src, size_t bytes, int on
     HIPCHK(hipMemcpyAsync(dst, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     if (!on_device) HIPCHK(hipStreamSynchronize(c->stream));
     return PNP_OK;
+}
+
+// hipMalloc with a report: on failure the HIP error is cleared, *p is null and the message names the array, the bytes asked for and the
+// caller's sizes (`sizes`: printf-style, as in "Bmax=%d, %dx%d")
+__attribute__((format(printf, 5, 6)))
+static int alloc_or_fail(void** p, size_t bytes, const char* who, const char* what, const char* sizes, ...) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return PNP_OK;
+    (void)hipGetLastError();
+    *p = nullptr;
+    char tail[128];
+    va_list ap;
+    va_start(ap, sizes);
+    vsnprintf(tail, sizeof(tail), sizes, ap);
+    va_end(ap);
+    return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the %s: %zu bytes asked for (%s): %s", who, what, bytes, tail,
+                hipGetErrorString(e));
 }
 
 // ---- the problem lifecycle: begin_problem, y written, finish_problem ----
@@ -430,27 +457,32 @@ template <typename R> static int download_y(pnp_ctx* c, const char* who, R* y, i
     return copy_out(c, y, c->y, (size_t)c->B * c->N * 2 * sizeof(R), on_device);
 }
 
-template <typename R> static int download_x(pnp_ctx* c, const char* who, R* x, int on_device) {
+// The state surface (pnp_set_state / pnp_get_state / pnp_download_x and their _cx forms) on the arrays of state<R, CX>; the caller's arrays
+// are R (CX: interleaved).  A coil context never holds a sliced state, so state_order does nothing there.
+template <typename R, bool CX = false> static int download_x(pnp_ctx* c, const char* who, R* x, int on_device) {
+    const State<R, CX> s = state<R, CX>(c);
     if (!x) return fail(PNP_E_ARG, "%s: null", who);
     if (!c->have_x) return fail(PNP_E_STATE, "%s: no iteration has been run since the state was set", who);
-    return copy_out(c, x, c->x, (size_t)c->B * c->N * sizeof(R), on_device);
+    return copy_out(c, x, s.x, (size_t)c->B * c->N * sizeof(*s.x), on_device);
+}
+
+// the initial state of a coil context: z = |A^H y| (CX: A^H y itself, no modulus), w = 0
+template <typename R, bool CX> static int coil_init_state(pnp_ctx* c) {
+    using C = typename CxOf<R>::type;
+    const State<R, CX> s = state<R, CX>(c);
+    const size_t n = (size_t)c->B * c->N;
+    if constexpr (CX) HIPCHK(hipMemcpyAsync(s.z, c->coils.aty, n * sizeof(C), hipMemcpyDeviceToDevice, c->stream));
+    else HIPCHK(launch_cabs<R>(c->stream, (const C*)c->coils.aty, s.z, n));
+    HIPCHK(hipMemsetAsync(s.w, 0, n * sizeof(*s.w), c->stream));
+    return PNP_OK;
 }
 
 // z = |ifft2(y)|, w = 0
 template <typename R> static int init_state(pnp_ctx* c) {
     const Bufs<R> b = bufs<R>(c);
     c->state_sliced = false;                           // both arrays are rewritten below, in natural order
-    if (c->coils.C > 0 && c->coils.image == PNP_IMAGE_COMPLEX) {      // complex images: z = A^H y, no modulus; w = 0
-        const size_t bytes = (size_t)c->B * c->N * sizeof(typename CxOf<R>::type);
-        HIPCHK(hipMemcpyAsync(c->coils.zc, c->coils.aty, bytes, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipMemsetAsync(c->coils.wc, 0, bytes, c->stream));
-        c->have_x = false;
-        c->have_state = true;
-        return PNP_OK;
-    }
-    if (c->coils.C > 0) {                              // z = |A^H y|, w = 0
-        HIPCHK(launch_cabs<R>(c->stream, (const typename CxOf<R>::type*)c->coils.aty, b.z, (size_t)c->B * c->N));
-        HIPCHK(hipMemsetAsync(b.w, 0, (size_t)c->B * c->N * sizeof(R), c->stream));
+    if (c->coils.C > 0) {
+        if (int rc = cx_mode(c) ? coil_init_state<R, true>(c) : coil_init_state<R, false>(c)) return rc;
         c->have_x = false;
         c->have_state = true;
         return PNP_OK;
@@ -467,33 +499,32 @@ template <typename R> static int init_state(pnp_ctx* c) {
     return PNP_OK;
 }
 
-template <typename R> static int set_state(pnp_ctx* c, const char* who, const R* z, const R* w, int on_device) {
-    const size_t bytes = (size_t)c->B * c->N * sizeof(R);
+template <typename R, bool CX = false> static int set_state(pnp_ctx* c, const char* who, const R* z, const R* w, int on_device) {
+    const State<R, CX> s = state<R, CX>(c);
+    const size_t bytes = (size_t)c->B * c->N * sizeof(*s.z);
     int rc;
     if (z && w) c->state_sliced = false;               // both replaced: nothing to convert
     else if (!c->have_state) return undefined_state(who);                         // one of the two kept: it must be defined
     else if ((rc = state_order<R>(c, false))) return rc;
-    if (z) { rc = copy_in(c, c->z, z, bytes, on_device); if (rc) return rc; }
-    if (w) { rc = copy_in(c, c->w, w, bytes, on_device); if (rc) return rc; }
+    if (z) { rc = copy_in(c, s.z, z, bytes, on_device); if (rc) return rc; }
+    if (w) { rc = copy_in(c, s.w, w, bytes, on_device); if (rc) return rc; }
     c->have_x = false;
     if (z && w) c->have_state = true;
     return PNP_OK;
 }
 
-template <typename R> static int get_state(pnp_ctx* c, R* z, R* w, int on_device) {
-    const size_t bytes = (size_t)c->B * c->N * sizeof(R);
+template <typename R, bool CX = false> static int get_state(pnp_ctx* c, R* z, R* w, int on_device) {
+    const State<R, CX> s = state<R, CX>(c);
+    const size_t bytes = (size_t)c->B * c->N * sizeof(*s.z);
     int rc;
     if ((rc = state_order<R>(c, false))) return rc;
-    if (z) { rc = copy_out(c, z, c->z, bytes, on_device); if (rc) return rc; }
-    if (w) { rc = copy_out(c, w, c->w, bytes, on_device); if (rc) return rc; }
+    if (z) { rc = copy_out(c, z, s.z, bytes, on_device); if (rc) return rc; }
+    if (w) { rc = copy_out(c, w, s.w, bytes, on_device); if (rc) return rc; }
     return PNP_OK;
 }
 
 
 // ---- multi-coil (SENSE) data consistency: coil_plan.h, kernels_coils.hip, the coil row roles of kernels_anysize.hip ----
-
-static int wavelet_scratch(pnp_ctx* c);
-template <typename R> static int wavelet_prox_step(pnp_ctx* c, bool cnc, const R* x, R* z, R* w, const ProxParamsT<R>& pp);
 
 #define NO_COILS(c, mc) do { if ((c)->coils.C > 0) return fail(PNP_E_STATE, "%s: the context has coils (pnp_set_coils): use %s", __func__, mc); } while (0)
 #define NEED_COILS(c) do { if ((c)->coils.C == 0) return fail(PNP_E_STATE, "%s: the context has no coils (pnp_set_coils); without coils use the call without _mc", __func__); } while (0)
@@ -501,12 +532,14 @@ template <typename R> static int wavelet_prox_step(pnp_ctx* c, bool cnc, const R
 static void coils_free(pnp_ctx* c) {
     Coils& k = c->coils;
     void* ptrs[] = {k.maps, k.coil_id, k.mask_idx, k.work, k.ymc, k.aty, k.xh, k.r, k.p, k.gp, k.part_row, k.part_rr[0], k.part_rr[1],
-                    k.part_bb, k.scal, k.rel, k.zc, k.wc, k.xc, k.wv_coef};
+                    k.part_bb, k.scal, k.rel, c->zc, c->wc, c->xc, c->wv_coef_cx};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (k.own_any) anysize_destroy(k.any);
     const int iters = k.cg_iters;
     k = Coils{};
     k.cg_iters = iters;
+    c->zc = c->wc = c->xc = c->wv_coef_cx = nullptr;     // complex-valued images go with the coils
+    c->image = PNP_IMAGE_REAL;
 }
 
 template <typename R> static CoilRowArgsT<R> coil_rows(const pnp_ctx* c, int B) {
@@ -573,124 +606,16 @@ static int coil_xstep(pnp_ctx* c, const CoilState<R, CX>* z, const CoilState<R, 
     return PNP_OK;
 }
 
-// ---- complex-valued images (pnp_set_image; kernels_complex.hip): the coil loop on the complex state of Coils ----
+// ---- complex-valued images (pnp_set_image; kernels_complex.hip): the guards of the entry points ----
 
-static bool cx_mode(const pnp_ctx* c) { return c->coils.image == PNP_IMAGE_COMPLEX; }
 #define REAL_IMAGE(c, cx) do { if (cx_mode(c)) return fail(PNP_E_STATE, "%s: the context is in complex image mode (pnp_set_image): use %s", __func__, cx); } while (0)
 #define NOT_IN_COMPLEX(c) do { if (cx_mode(c)) return fail(PNP_E_STATE, "%s: not available in complex image mode (pnp_set_image)", __func__); } while (0)
 #define NEED_COMPLEX(c) do { if (!cx_mode(c)) return fail(PNP_E_STATE, "%s: needs complex image mode (pnp_set_image); in real mode use the call without _cx", __func__); } while (0)
-
-// The coefficient array of the complex wavelet prox: allocated where the setting is made -- by pnp_set_image or pnp_set_sparsity,
-// whichever comes second -- so that no loop and no step-wise call allocates.
-static int cx_wavelet_scratch(pnp_ctx* c, const char* who) {
-    if (c->coils.wv_coef) return PNP_OK;
-    const size_t bytes = (size_t)c->Bmax * c->N * 2 * (c->f64 ? sizeof(double) : sizeof(float));
-    const hipError_t e = hipMalloc(&c->coils.wv_coef, bytes);
-    if (e == hipSuccess) return PNP_OK;
-    (void)hipGetLastError();
-    c->coils.wv_coef = nullptr;
-    return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the complex wavelet coefficients: %zu bytes asked for (Bmax=%d, %dx%d): %s",
-                who, bytes, c->Bmax, c->H, c->W, hipGetErrorString(e));
-}
 
 // every complex array a caller hands in is read and written as 2 sizeof(R)-byte values (float2 / double2; the pixel prox: 16 bytes)
 template <typename R> static int cx_aligned(const char* who, const void* a, const void* b = nullptr, const void* c = nullptr, size_t to = 2 * sizeof(R)) {
     if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & (to - 1)) == 0) return PNP_OK;
     return fail(PNP_E_ARG, "%s: complex arrays must be %zu-byte aligned", who, to);
-}
-
-// one z / w step on complex arrays: the pixel prox (one launch) or the wavelet prox of the context's sparsity setting (two)
-template <typename R>
-static int prox_step_cx(pnp_ctx* c, bool cnc, const typename CxOf<R>::type* x, typename CxOf<R>::type* z, typename CxOf<R>::type* w,
-                        const ProxParamsT<R>& pp) {
-    using C = typename CxOf<R>::type;
-    if (c->wavelet == WV_NONE) {
-        HIPCHK(launch_prox_cx<R>(c->stream, cnc, x, z, w, pp, (size_t)c->B * c->N));
-        return PNP_OK;
-    }
-    if (!c->coils.wv_coef) return fail(PNP_E_STATE, "complex wavelet prox: no coefficient array (pnp_set_image / pnp_set_sparsity allocate it)");
-    HIPCHK(launch_wavelet_prox_cx<R>(c->stream, c->wavelet, c->wv_levels, cnc, x, z, w, (C*)c->coils.wv_coef, pp, c->B, c->H, c->W));
-    return PNP_OK;
-}
-
-template <typename R>
-static int run_coil_loop_cx(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
-    using C = typename CxOf<R>::type;
-    C *z = (C*)c->coils.zc, *w = (C*)c->coils.wc, *x = (C*)c->coils.xc;
-    if (iters == 0) HIPCHK(hipMemcpyAsync(x, z, (size_t)c->B * c->N * sizeof(C), hipMemcpyDeviceToDevice, c->stream));
-    for (int i = 0; i < iters; ++i) {
-        if (int rc = coil_xstep<R, true>(c, z, w, x, reo)) return rc;
-        if (int rc = prox_step_cx<R>(c, cnc, x, z, w, pp)) return rc;
-    }
-    c->have_x = true;
-    return PNP_OK;
-}
-
-template <typename R> static int set_state_cx(pnp_ctx* c, const char* who, const R* z, const R* w, int on_device) {
-    const size_t bytes = (size_t)c->B * c->N * 2 * sizeof(R);
-    if (!(z && w) && !c->have_state) return undefined_state(who);                 // one of the two kept: it must be defined
-    if (z) if (int rc = copy_in(c, c->coils.zc, z, bytes, on_device)) return rc;
-    if (w) if (int rc = copy_in(c, c->coils.wc, w, bytes, on_device)) return rc;
-    c->have_x = false;
-    if (z && w) c->have_state = true;
-    return PNP_OK;
-}
-template <typename R> static int get_state_cx(pnp_ctx* c, R* z, R* w, int on_device) {
-    const size_t bytes = (size_t)c->B * c->N * 2 * sizeof(R);
-    if (z) if (int rc = copy_out(c, z, c->coils.zc, bytes, on_device)) return rc;
-    if (w) if (int rc = copy_out(c, w, c->coils.wc, bytes, on_device)) return rc;
-    return PNP_OK;
-}
-template <typename R> static int download_x_cx(pnp_ctx* c, const char* who, R* x, int on_device) {
-    if (!x) return fail(PNP_E_ARG, "%s: null", who);
-    if (!c->have_x) return fail(PNP_E_STATE, "%s: no iteration has been run since the state was set", who);
-    return copy_out(c, x, c->coils.xc, (size_t)c->B * c->N * 2 * sizeof(R), on_device);
-}
-template <typename R> static int dc_step_cx(pnp_ctx* c, const char* who, const R* z, const R* w, R* x, double reo) {
-    using C = typename CxOf<R>::type;
-    if (!z || !w || !x) return fail(PNP_E_ARG, "%s: null pointer", who);
-    if (!(reo > 0.0)) return fail(PNP_E_ARG, "%s: reo must be > 0", who);
-    if (int rc = cx_aligned<R>(who, z, w, x)) return rc;
-    return coil_xstep<R, true>(c, (const C*)z, (const C*)w, (C*)x, reo);
-}
-// the step-wise prox on caller pointers (complex, interleaved): 16-byte aligned for the pixel prox, 2 sizeof(R) and not overlapping for
-// the wavelet prox
-template <typename R> static int prox_dual_cx(pnp_ctx* c, const char* who, bool cnc, const R* x, R* z, R* w, const ProxParamsT<R>& pp) {
-    using C = typename CxOf<R>::type;
-    if (!x || !z || !w) return fail(PNP_E_ARG, "%s: null pointer", who);
-    if (c->wavelet == WV_NONE) {
-        if (int rc = cx_aligned<R>(who, x, z, w, 16)) return rc;
-    } else {
-        if (int rc = cx_aligned<R>(who, x, z, w)) return rc;
-        const size_t bytes = (size_t)c->B * c->N * sizeof(C);
-        const char *px = (const char*)x, *pz = (const char*)z, *pw = (const char*)w;
-        if ((px < pz + bytes && pz < px + bytes) || (px < pw + bytes && pw < px + bytes) || (pz < pw + bytes && pw < pz + bytes))
-            return fail(PNP_E_ARG, "%s: x, z and w must not overlap with a wavelet set (tiles read their neighbours' halo)", who);
-    }
-    return prox_step_cx<R>(c, cnc, (const C*)x, (C*)z, (C*)w, pp);
-}
-
-// the loops of a coil context: per iteration the x-step and the pixel prox (one launch) or the wavelet prox (two), on the state in
-// natural order; every iteration stands alone, so a run cut anywhere (the trace's legs) is bit-equal to the uncut run
-template <typename R>
-static int run_coil_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
-    if (cx_mode(c)) return run_coil_loop_cx<R>(c, iters, cnc, pp, reo);
-    const Bufs<R> b = bufs<R>(c);
-    const size_t n = (size_t)c->B * c->N;
-    if (c->wavelet != WV_NONE && iters > 0) if (int rc = wavelet_scratch(c)) return rc;
-    if (iters == 0) HIPCHK(hipMemcpyAsync(b.x, b.z, n * sizeof(R), hipMemcpyDeviceToDevice, c->stream));
-    for (int i = 0; i < iters; ++i) {
-        if (int rc = coil_xstep<R>(c, b.z, b.w, b.x, reo)) return rc;
-        if (c->wavelet != WV_NONE) {
-            if (int rc = wavelet_prox_step<R>(c, cnc, b.x, b.z, b.w, pp)) return rc;
-        } else if constexpr (std::is_same_v<R, double>) {
-            HIPCHK(launch_prox_f64(c->stream, cnc, b.x, b.z, b.w, pp, n));
-        } else {
-            HIPCHK(launch_prox(c->stream, cnc, b.x, b.z, b.w, pp, n));
-        }
-    }
-    c->have_x = true;
-    return PNP_OK;
 }
 
 // after begin_problem on a coil context: the coil set of every slice, the expanded mask index
@@ -810,16 +735,8 @@ static int set_coils(pnp_ctx* c, const char* who, const R* sens, int C, int Ks, 
         {(void**)&k.part_bb, c->Bmax * nblk * sizeof(double), "CG partials"},
         {(void**)&k.scal, (size_t)c->Bmax * 4 * sizeof(double), "CG scalars"}, {(void**)&k.rel, (size_t)c->Bmax * sizeof(double), "CG residual"},
     };
-    for (const Want& w : wants) {
-        const hipError_t e = hipMalloc(w.p, w.bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            *w.p = nullptr;
-            coils_free(c);
-            return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the %s: %zu bytes asked for (Bmax=%d, C=%d, %dx%d): %s",
-                        who, w.what, w.bytes, c->Bmax, C, c->H, c->W, hipGetErrorString(e));
-        }
-    }
+    for (const Want& w : wants)
+        if (int rc = alloc_or_fail(w.p, w.bytes, who, w.what, "Bmax=%d, C=%d, %dx%d", c->Bmax, C, c->H, c->W)) { coils_free(c); return rc; }
     HIPCHK(hipMemsetAsync(k.scal, 0, (size_t)c->Bmax * 4 * sizeof(double), c->stream));
     if (c->any) k.any = c->any;
     else {
@@ -891,8 +808,14 @@ template <typename R> static int dc_any(pnp_ctx* c, const R* z, const R* w, R* x
 
 // ---- wavelet-domain sparsity (pnp_set_sparsity; wavelet_plan.h, kernels_wavelet.hip) ----
 
-static int wavelet_scratch(pnp_ctx* c) {
-    if (!c->wv_coef) HIPCHK(hipMalloc(&c->wv_coef, (size_t)c->Bmax * c->N * (c->f64 ? sizeof(double) : sizeof(float))));
+// The coefficient array of the wavelet prox, real or (cx) complex.  Both are allocated where the setting is made -- the real one by
+// pnp_set_sparsity, the complex one by pnp_set_image or pnp_set_sparsity, whichever comes second -- so that no loop and no step-wise
+// call allocates; a failure of the complex one is reported in the name of that call, `who`.
+static int wavelet_scratch(pnp_ctx* c, bool cx = false, const char* who = "") {
+    if (cx ? c->wv_coef_cx : c->wv_coef) return PNP_OK;
+    if (cx) return alloc_or_fail(&c->wv_coef_cx, (size_t)c->Bmax * c->N * 2 * (c->f64 ? sizeof(double) : sizeof(float)), who,
+                                 "complex wavelet coefficients", "Bmax=%d, %dx%d", c->Bmax, c->H, c->W);
+    HIPCHK(hipMalloc(&c->wv_coef, (size_t)c->Bmax * c->N * (c->f64 ? sizeof(double) : sizeof(float))));
     return PNP_OK;
 }
 
@@ -908,6 +831,29 @@ template <typename R> static int wavelet_prox_step(pnp_ctx* c, bool cnc, const R
     const int32_t* s = c->spin.data() + 2 * (size_t)wv_spin_first(c->spin_p, n, K);
     HIPCHK(launch_wavelet_prox<R>(c->stream, c->wavelet, c->wv_levels, cnc, x, z, w, (R*)c->wv_coef, pp, c->B, c->H, c->W, s, K, (R*)c->wv_acc));
     c->spin_p = c->spin_p == INT_MAX ? INT_MAX % groups + 1 : c->spin_p + 1;          // the same entries, within int
+    return PNP_OK;
+}
+
+// One z / w step of the loops and the step-wise calls, on real or (CX) complex arrays in natural order: the pixel prox (one launch) or the
+// wavelet prox of the context's sparsity setting (two; in real mode by the spin schedule).  Which launcher serves which type ends here.
+template <typename R, bool CX>
+static int prox_step(pnp_ctx* c, bool cnc, const CoilState<R, CX>* x, CoilState<R, CX>* z, CoilState<R, CX>* w, const ProxParamsT<R>& pp) {
+    const size_t n = (size_t)c->B * c->N;
+    if constexpr (CX) {
+        if (c->wavelet == WV_NONE) {
+            HIPCHK(launch_prox_cx<R>(c->stream, cnc, x, z, w, pp, n));
+            return PNP_OK;
+        }
+        if (!c->wv_coef_cx) return fail(PNP_E_STATE, "complex wavelet prox: no coefficient array (pnp_set_image / pnp_set_sparsity allocate it)");
+        HIPCHK(launch_wavelet_prox_cx<R>(c->stream, c->wavelet, c->wv_levels, cnc, x, z, w, state<R, true>(c).wv_coef, pp, c->B, c->H, c->W));
+    } else if (c->wavelet != WV_NONE) {
+        if (int rc = wavelet_scratch(c)) return rc;
+        return wavelet_prox_step<R>(c, cnc, x, z, w, pp);
+    } else if constexpr (std::is_same_v<R, double>) {
+        HIPCHK(launch_prox_f64(c->stream, cnc, x, z, w, pp, n));
+    } else {
+        HIPCHK(launch_prox(c->stream, cnc, x, z, w, pp, n));
+    }
     return PNP_OK;
 }
 
@@ -935,11 +881,52 @@ template <typename R>
 static int run_wavelet_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
     const Bufs<R> b = bufs<R>(c);
     if (int rc = state_order<R>(c, false)) return rc;
-    if (int rc = wavelet_scratch(c)) return rc;
     const R cdc = dc_coeff<R>(reo);
     for (int i = 0; i < iters; ++i) {
         if (int rc = dc_any<R>(c, b.z, b.w, b.x, cdc)) return rc;
-        if (int rc = wavelet_prox_step<R>(c, cnc, b.x, b.z, b.w, pp)) return rc;
+        if (int rc = prox_step<R, false>(c, cnc, b.x, b.z, b.w, pp)) return rc;
+    }
+    c->have_x = true;
+    return PNP_OK;
+}
+
+// The step-wise calls on caller pointers in natural order (CX: complex, interleaved).  pnp_dc_step[_cx]: one x-step; without coils the
+// data-consistency step of the context's own kernels (dc_any).
+template <typename R, bool CX> static int dc_step(pnp_ctx* c, const char* who, const R* z, const R* w, R* x, double reo) {
+    using T = CoilState<R, CX>;
+    if (!z || !w || !x) return fail(PNP_E_ARG, "%s: null pointer", who);
+    if (!(reo > 0.0)) return fail(PNP_E_ARG, "%s: reo must be > 0", who);
+    if constexpr (CX) {
+        if (int rc = cx_aligned<R>(who, z, w, x)) return rc;
+    } else {
+        if (c->coils.C == 0) return dc_any<R>(c, z, w, x, dc_coeff<R>(reo));
+    }
+    return coil_xstep<R, CX>(c, (const T*)z, (const T*)w, (T*)x, reo);
+}
+// pnp_prox_*_dual[_cx]: one prox step.  Complex arrays: 16-byte aligned for the pixel prox, 2 sizeof(R) for the wavelet prox; with a wavelet
+// set the three arrays must not overlap.
+template <typename R, bool CX> static int prox_dual(pnp_ctx* c, const char* who, bool cnc, const R* x, R* z, R* w, const ProxParamsT<R>& pp) {
+    using T = CoilState<R, CX>;
+    if (!x || !z || !w) return fail(PNP_E_ARG, "%s: null pointer", who);
+    if constexpr (CX) if (int rc = cx_aligned<R>(who, x, z, w, c->wavelet == WV_NONE ? 16 : 2 * sizeof(R))) return rc;
+    if (c->wavelet != WV_NONE) {
+        const size_t bytes = (size_t)c->B * c->N * sizeof(T);
+        const char *px = (const char*)x, *pz = (const char*)z, *pw = (const char*)w;
+        if ((px < pz + bytes && pz < px + bytes) || (px < pw + bytes && pw < px + bytes) || (pz < pw + bytes && pw < pz + bytes))
+            return fail(PNP_E_ARG, "%s: x, z and w must not overlap with a wavelet set (tiles read their neighbours' halo)", who);
+    }
+    return prox_step<R, CX>(c, cnc, (const T*)x, (T*)z, (T*)w, pp);
+}
+
+// the loops of a coil context: per iteration the x-step and the prox step, on the state in natural order; every iteration stands alone,
+// so a run cut anywhere (the trace's legs) is bit-equal to the uncut run
+template <typename R, bool CX>
+static int run_coil_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
+    const State<R, CX> s = state<R, CX>(c);
+    if (iters == 0) HIPCHK(hipMemcpyAsync(s.x, s.z, (size_t)c->B * c->N * sizeof(*s.x), hipMemcpyDeviceToDevice, c->stream));
+    for (int i = 0; i < iters; ++i) {
+        if (int rc = coil_xstep<R, CX>(c, s.z, s.w, s.x, reo)) return rc;
+        if (int rc = prox_step<R, CX>(c, cnc, s.x, s.z, s.w, pp)) return rc;
     }
     c->have_x = true;
     return PNP_OK;
@@ -947,7 +934,7 @@ static int run_wavelet_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R
 
 template <typename R>
 static int run_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
-    if (c->coils.C > 0) return run_coil_loop<R>(c, iters, cnc, pp, reo);
+    if (c->coils.C > 0) return cx_mode(c) ? run_coil_loop<R, true>(c, iters, cnc, pp, reo) : run_coil_loop<R, false>(c, iters, cnc, pp, reo);
     if (c->wavelet != WV_NONE && iters > 0) return run_wavelet_loop<R>(c, iters, cnc, pp, reo);
     const Bufs<R> b = bufs<R>(c);
     const Path path = iters > 0 ? loop_path(c) : Path::generic;
@@ -1219,7 +1206,7 @@ static int metric_inputs(pnp_ctx* c, const char* who, const X*& x, const uint8_t
         if (!c->have_x) return fail(PNP_E_STATE, "%s: x_dev is null and the ctx holds no x yet", who);
         x = bufs<X>(c).x;
         // complex images: the metrics are taken on |x|, formed into the context's real x (unused in complex mode)
-        if (cx_mode(c)) HIPCHK(launch_cabs<X>(c->stream, (const typename CxOf<X>::type*)c->coils.xc, bufs<X>(c).x, (size_t)c->B * c->N));
+        if (cx_mode(c)) HIPCHK(launch_cabs<X>(c->stream, state<X, true>(c).x, bufs<X>(c).x, (size_t)c->B * c->N));
     }
     if (!gt_on_device) {
         if (!c->gt) HIPCHK(hipMalloc((void**)&c->gt, (size_t)c->Bmax * c->N));
@@ -1473,6 +1460,11 @@ static int check_thresholds(const char* who, double alpha, double lambda1, doubl
     if (!(reo > 0.0)) return fail(PNP_E_ARG, "%s: reo must be > 0 (got %g)", who, reo);
     return PNP_OK;
 }
+// the scalars of a CNC call: b first, as every such call has checked them
+static int check_cnc(const char* who, double alpha, double lambda1, double reo, double b) {
+    if (!(b > 0.0)) return fail(PNP_E_ARG, "%s: b must be > 0", who);
+    return check_thresholds(who, alpha, lambda1, reo);
+}
 
 int pnp_admm_l1_run(pnp_ctx* c, int iters, double lambda1, double reo) {
     CTX(c); NEED_PROBLEM(c); NEED_STATE(c);
@@ -1486,8 +1478,7 @@ int pnp_admm_l1_run(pnp_ctx* c, int iters, double lambda1, double reo) {
 int pnp_admm_cnc_run(pnp_ctx* c, int iters, double alpha, double lambda1, double reo, double b) {
     CTX(c); NEED_PROBLEM(c); NEED_STATE(c);
     Range r("pnp_admm_cnc_run");
-    if (!(b > 0.0)) return fail(PNP_E_ARG, "pnp_admm_cnc_run: b must be > 0");
-    if (int rv = check_thresholds(__func__, alpha, lambda1, reo)) return rv;
+    if (int rv = check_cnc(__func__, alpha, lambda1, reo, b)) return rv;
     if (iters < 0) return fail(PNP_E_ARG, "%s: iters must be >= 0", __func__);
     return c->f64 ? run_loop(c, iters, true, prox_cnc<double>(alpha, lambda1, reo, b), reo)
                   : run_loop(c, iters, true, prox_cnc<float>(alpha, lambda1, reo, b), reo);
@@ -1507,8 +1498,7 @@ int pnp_admm_cnc_run_traced(pnp_ctx* c, int iters, double alpha, double lambda1,
                             const uint8_t* gt, int gt_on_device, int* checks, int* iters_done) {
     CTX(c); NOT_IN_COMPLEX(c); NEED_PROBLEM(c); NEED_STATE(c);
     Range r("pnp_admm_cnc_run_traced");
-    if (!(b > 0.0)) return fail(PNP_E_ARG, "%s: b must be > 0", __func__);
-    if (int rv = check_thresholds(__func__, alpha, lambda1, reo)) return rv;
+    if (int rv = check_cnc(__func__, alpha, lambda1, reo, b)) return rv;
     if (iters < 0) return fail(PNP_E_ARG, "%s: iters must be >= 0", __func__);
     return c->f64 ? run_traced<double>(c, __func__, iters, true, prox_cnc<double>(alpha, lambda1, reo, b), reo, every, tol, gt, gt_on_device, checks, iters_done)
                   : run_traced<float>(c, __func__, iters, true, prox_cnc<float>(alpha, lambda1, reo, b), reo, every, tol, gt, gt_on_device, checks, iters_done);
@@ -1540,40 +1530,23 @@ int pnp_download_x_f64(pnp_ctx* c, double* x, int on_device) { CTX(c); REAL_IMAG
 int pnp_dc_step(pnp_ctx* c, const float* z, const float* w, float* x, double reo) {
     CTX(c); REAL_IMAGE(c, "pnp_dc_step_cx"); F32_ONLY(c); NEED_PROBLEM(c);
     Range r("pnp_dc_step");
-    if (!z || !w || !x) return fail(PNP_E_ARG, "pnp_dc_step: null pointer");
-    if (!(reo > 0.0)) return fail(PNP_E_ARG, "pnp_dc_step: reo must be > 0");
-    if (c->coils.C > 0) return coil_xstep<float>(c, z, w, x, reo);
-    return dc_any<float>(c, z, w, x, dc_coeff<float>(reo));
+    return dc_step<float, false>(c, __func__, z, w, x, reo);
 }
 
-// the step-wise prox with a wavelet set: the two launches of kernels_wavelet.hip on caller pointers
-static int wavelet_prox_dual(pnp_ctx* c, const char* who, bool cnc, const float* x, float* z, float* w, const ProxParams& p) {
-    const size_t bytes = (size_t)c->B * c->N * sizeof(float);
-    const char *px = (const char*)x, *pz = (const char*)z, *pw = (const char*)w;
-    if ((px < pz + bytes && pz < px + bytes) || (px < pw + bytes && pw < px + bytes) || (pz < pw + bytes && pw < pz + bytes))
-        return fail(PNP_E_ARG, "%s: x, z and w must not overlap with a wavelet set (tiles read their neighbours' halo)", who);
-    if (int rc = wavelet_scratch(c)) return rc;
-    return wavelet_prox_step<float>(c, cnc, x, z, w, p);
-}
-
+// The real prox calls name a null pointer before a bad scalar, the _cx calls after it (prox_dual): that check stays here, in its place.
 int pnp_prox_l1_dual(pnp_ctx* c, const float* x, float* z, float* w, double thr) {
     CTX(c); REAL_IMAGE(c, "pnp_prox_l1_dual_cx"); F32_ONLY(c); NEED_PROBLEM(c);
-    if (!x || !z || !w) return fail(PNP_E_ARG, "pnp_prox_l1_dual: null pointer");
-    if (!(thr >= 0.0)) return fail(PNP_E_ARG, "pnp_prox_l1_dual: thr must be >= 0");
+    if (!x || !z || !w) return fail(PNP_E_ARG, "%s: null pointer", __func__);
+    if (!(thr >= 0.0)) return fail(PNP_E_ARG, "%s: thr must be >= 0", __func__);
     ProxParams p{}; p.thr = (float)thr;
-    if (c->wavelet != WV_NONE) return wavelet_prox_dual(c, __func__, false, x, z, w, p);
-    HIPCHK(launch_prox(c->stream, false, x, z, w, p, (size_t)c->B * c->N));
-    return PNP_OK;
+    return prox_dual<float, false>(c, __func__, false, x, z, w, p);
 }
 
 int pnp_prox_cnc_dual(pnp_ctx* c, const float* x, float* z, float* w, double alpha, double lambda1, double reo, double b) {
     CTX(c); REAL_IMAGE(c, "pnp_prox_cnc_dual_cx"); F32_ONLY(c); NEED_PROBLEM(c);
-    if (!x || !z || !w) return fail(PNP_E_ARG, "pnp_prox_cnc_dual: null pointer");
-    if (!(b > 0.0)) return fail(PNP_E_ARG, "pnp_prox_cnc_dual: b must be > 0");
-    if (int rv = check_thresholds("pnp_prox_cnc_dual", alpha, lambda1, reo)) return rv;
-    if (c->wavelet != WV_NONE) return wavelet_prox_dual(c, __func__, true, x, z, w, prox_cnc<float>(alpha, lambda1, reo, b));
-    HIPCHK(launch_prox(c->stream, true, x, z, w, prox_cnc<float>(alpha, lambda1, reo, b), (size_t)c->B * c->N));
-    return PNP_OK;
+    if (!x || !z || !w) return fail(PNP_E_ARG, "%s: null pointer", __func__);
+    if (int rv = check_cnc(__func__, alpha, lambda1, reo, b)) return rv;
+    return prox_dual<float, false>(c, __func__, true, x, z, w, prox_cnc<float>(alpha, lambda1, reo, b));
 }
 
 int pnp_cnc_combine(pnp_ctx* c, const float* z, const float* x, const float* w, const float* s, float* t,
@@ -1764,7 +1737,7 @@ int pnp_set_sparsity(pnp_ctx* c, int wavelet, int levels) {
     if (cx_mode(c)) if (int rc = pnp_image_check(PNP_IMAGE_COMPLEX, wavelet, levels, c->f64)) return rc;
     CTX(c);
     if (wavelet != PNP_WAVELET_NONE) if (int rc = wavelet_scratch(c)) return rc;
-    if (wavelet != PNP_WAVELET_NONE && cx_mode(c)) if (int rc = cx_wavelet_scratch(c, __func__)) return rc;
+    if (wavelet != PNP_WAVELET_NONE && cx_mode(c)) if (int rc = wavelet_scratch(c, true, __func__)) return rc;
     c->wavelet = wavelet;
     c->wv_levels = wavelet == PNP_WAVELET_NONE ? 0 : levels;
     c->spin.clear(); c->spin_k = 1; c->spin_p = 0;                                    // the valid shifts depend on levels
@@ -1922,73 +1895,65 @@ int pnp_set_image(pnp_ctx* c, int mode) {
     c->B = 0; c->prob = Problem{};                        // the uploaded problem is dropped, as by pnp_set_coils
     c->state_sliced = c->have_x = c->have_state = false;
     c->coils.have_rel = false;
-    Coils& k = c->coils;
-    if (mode == PNP_IMAGE_COMPLEX && !k.zc) {
+    if (mode == PNP_IMAGE_COMPLEX && !c->zc) {
         const size_t bytes = (size_t)c->Bmax * c->N * 2 * (c->f64 ? sizeof(double) : sizeof(float));
-        void** want[] = {&k.zc, &k.wc, &k.xc};
-        for (void** p : want) {
-            const hipError_t e = hipMalloc(p, bytes);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                *p = nullptr;
+        void** want[] = {&c->zc, &c->wc, &c->xc};
+        for (void** p : want)
+            if (int rc = alloc_or_fail(p, bytes, __func__, "complex state", "Bmax=%d, %dx%d", c->Bmax, c->H, c->W)) {
                 for (void** q : want) { if (*q) (void)hipFree(*q); *q = nullptr; }
-                return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the complex state: %zu bytes asked for (Bmax=%d, %dx%d): %s",
-                            __func__, bytes, c->Bmax, c->H, c->W, hipGetErrorString(e));
+                return rc;
             }
-        }
     }
-    if (mode == PNP_IMAGE_COMPLEX && c->wavelet != WV_NONE) if (int rc = cx_wavelet_scratch(c, __func__)) return rc;
-    k.image = mode;
+    if (mode == PNP_IMAGE_COMPLEX && c->wavelet != WV_NONE) if (int rc = wavelet_scratch(c, true, __func__)) return rc;
+    c->image = mode;
     return PNP_OK;
 }
 
 int pnp_get_image(pnp_ctx* c, int* mode) {
     if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
-    if (mode) *mode = c->coils.image;
+    if (mode) *mode = c->image;
     return PNP_OK;
 }
 
-int pnp_set_state_cx(pnp_ctx* c, const float* z, const float* w, int on_device) { CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c); return set_state_cx(c, __func__, z, w, on_device); }
-int pnp_set_state_cx_f64(pnp_ctx* c, const double* z, const double* w, int on_device) { CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c); return set_state_cx(c, __func__, z, w, on_device); }
-int pnp_get_state_cx(pnp_ctx* c, float* z, float* w, int on_device) { CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c); return get_state_cx(c, z, w, on_device); }
-int pnp_get_state_cx_f64(pnp_ctx* c, double* z, double* w, int on_device) { CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c); return get_state_cx(c, z, w, on_device); }
-int pnp_download_x_cx(pnp_ctx* c, float* x, int on_device) { CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c); return download_x_cx(c, __func__, x, on_device); }
-int pnp_download_x_cx_f64(pnp_ctx* c, double* x, int on_device) { CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c); return download_x_cx(c, __func__, x, on_device); }
+int pnp_set_state_cx(pnp_ctx* c, const float* z, const float* w, int on_device) { CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c); return set_state<float, true>(c, __func__, z, w, on_device); }
+int pnp_set_state_cx_f64(pnp_ctx* c, const double* z, const double* w, int on_device) { CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c); return set_state<double, true>(c, __func__, z, w, on_device); }
+int pnp_get_state_cx(pnp_ctx* c, float* z, float* w, int on_device) { CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c); return get_state<float, true>(c, z, w, on_device); }
+int pnp_get_state_cx_f64(pnp_ctx* c, double* z, double* w, int on_device) { CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c); NEED_STATE(c); return get_state<double, true>(c, z, w, on_device); }
+int pnp_download_x_cx(pnp_ctx* c, float* x, int on_device) { CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c); return download_x<float, true>(c, __func__, x, on_device); }
+int pnp_download_x_cx_f64(pnp_ctx* c, double* x, int on_device) { CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c); return download_x<double, true>(c, __func__, x, on_device); }
 
 int pnp_dc_step_cx(pnp_ctx* c, const float* z, const float* w, float* x, double reo) {
     CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c);
     Range r("pnp_dc_step_cx");
-    return dc_step_cx<float>(c, __func__, z, w, x, reo);
+    return dc_step<float, true>(c, __func__, z, w, x, reo);
 }
 int pnp_dc_step_cx_f64(pnp_ctx* c, const double* z, const double* w, double* x, double reo) {
     CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c);
     Range r("pnp_dc_step_cx_f64");
-    return dc_step_cx<double>(c, __func__, z, w, x, reo);
+    return dc_step<double, true>(c, __func__, z, w, x, reo);
 }
 
 int pnp_prox_l1_dual_cx(pnp_ctx* c, const float* x, float* z, float* w, double thr) {
     CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c);
     if (!(thr >= 0.0)) return fail(PNP_E_ARG, "%s: thr must be >= 0", __func__);
     ProxParams p{}; p.thr = (float)thr;
-    return prox_dual_cx<float>(c, __func__, false, x, z, w, p);
+    return prox_dual<float, true>(c, __func__, false, x, z, w, p);
 }
 int pnp_prox_l1_dual_cx_f64(pnp_ctx* c, const double* x, double* z, double* w, double thr) {
     CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c);
     if (!(thr >= 0.0)) return fail(PNP_E_ARG, "%s: thr must be >= 0", __func__);
     ProxParamsT<double> p{}; p.thr = thr;
-    return prox_dual_cx<double>(c, __func__, false, x, z, w, p);
+    return prox_dual<double, true>(c, __func__, false, x, z, w, p);
 }
 int pnp_prox_cnc_dual_cx(pnp_ctx* c, const float* x, float* z, float* w, double alpha, double lambda1, double reo, double b) {
     CTX(c); NEED_COMPLEX(c); F32_ONLY(c); NEED_PROBLEM(c);
-    if (!(b > 0.0)) return fail(PNP_E_ARG, "%s: b must be > 0", __func__);
-    if (int rv = check_thresholds(__func__, alpha, lambda1, reo)) return rv;
-    return prox_dual_cx<float>(c, __func__, true, x, z, w, prox_cnc<float>(alpha, lambda1, reo, b));
+    if (int rv = check_cnc(__func__, alpha, lambda1, reo, b)) return rv;
+    return prox_dual<float, true>(c, __func__, true, x, z, w, prox_cnc<float>(alpha, lambda1, reo, b));
 }
 int pnp_prox_cnc_dual_cx_f64(pnp_ctx* c, const double* x, double* z, double* w, double alpha, double lambda1, double reo, double b) {
     CTX(c); NEED_COMPLEX(c); F64_ONLY(c); NEED_PROBLEM(c);
-    if (!(b > 0.0)) return fail(PNP_E_ARG, "%s: b must be > 0", __func__);
-    if (int rv = check_thresholds(__func__, alpha, lambda1, reo)) return rv;
-    return prox_dual_cx<double>(c, __func__, true, x, z, w, prox_cnc<double>(alpha, lambda1, reo, b));
+    if (int rv = check_cnc(__func__, alpha, lambda1, reo, b)) return rv;
+    return prox_dual<double, true>(c, __func__, true, x, z, w, prox_cnc<double>(alpha, lambda1, reo, b));
 }
 
 int pnp_A_cx(pnp_ctx* c, const float* x, float* k) {        // x: [B][H][W] complex, k: [B][C][H][W]
@@ -2124,12 +2089,7 @@ static int maps_reserve(const char* who, pnp_ctx* c, size_t bytes, int B, int C)
     HIPCHK(hipStreamSynchronize(c->stream));             // an earlier call on this stream may still read the old array
     if (c->maps_scratch) (void)hipFree(c->maps_scratch);
     c->maps_scratch = nullptr; c->maps_bytes = 0;
-    const hipError_t e = hipMalloc(&c->maps_scratch, bytes);
-    if (e != hipSuccess) {
-        c->maps_scratch = nullptr;
-        return fail(e == hipErrorOutOfMemory ? PNP_E_NOMEM : PNP_E_HIP, "%s: cannot allocate the scratch array: %zu bytes asked for (B=%d, C=%d, Bmax=%d, %dx%d): %s",
-                    who, bytes, B, C, c->Bmax, c->H, c->W, hipGetErrorString(e));
-    }
+    if (int rc = alloc_or_fail(&c->maps_scratch, bytes, who, "scratch array", "B=%d, C=%d, Bmax=%d, %dx%d", B, C, c->Bmax, c->H, c->W)) return rc;
     c->maps_bytes = bytes;
     return PNP_OK;
 }

@@ -270,6 +270,15 @@ class Engine:
         """the entry point `name` of the engine's image mode and precision: pnp_<name>[_cx][_f64]"""
         return getattr(self._L, 'pnp_' + name + ('_cx' if self._cx else '') + ('_f64' if self.f64 else ''))
 
+    def _step_fn(self, name):
+        """the step-wise entry point `name`: in complex image mode of the engine's precision, in real mode the float32 call"""
+        return self._fn(name) if self._cx else getattr(self._L, 'pnp_' + name)
+
+    @property
+    def _state_dtype(self):
+        """the element type of z, w, x on the host: complex in complex image mode"""
+        return self._cplx if self._cx else self._real
+
     @property
     def coils(self):
         """{'C', 'Ks', 'cg_iters'} (pnp_get_coils); C = 0 without coils."""
@@ -449,7 +458,7 @@ class Engine:
 
     def set_state(self, z=None, w=None):
         """z, w [B,H,W]: real, or complex in complex image mode (set_image_mode)"""
-        dt = self._cplx if self._cx else self._real
+        dt = self._state_dtype
         zz = None if z is None else (z if _is_dev(z) else _host(z, dt))
         ww = None if w is None else (w if _is_dev(w) else _host(w, dt))
         dev = 1 if (_is_dev(z) or _is_dev(w)) else 0
@@ -464,7 +473,7 @@ class Engine:
                 raise TypeError('get_state outputs must be device tensors')
             _lib.check(fn(self._ctx, _ptr(z_out), _ptr(w_out), 1))
             return z_out, w_out
-        z = np.empty((self.B, self.H, self.W), self._cplx if self._cx else self._real)
+        z = np.empty((self.B, self.H, self.W), self._state_dtype)
         w = np.empty_like(z)
         _lib.check(fn(self._ctx, _ptr(z), _ptr(w), 0))
         return z, w
@@ -519,7 +528,7 @@ class Engine:
         if out is not None and _is_dev(out):
             _lib.check(fn(self._ctx, _ptr(out), 1))
             return out
-        x = np.empty((self.B, self.H, self.W), self._cplx if self._cx else self._real)
+        x = np.empty((self.B, self.H, self.W), self._state_dtype)
         _lib.check(fn(self._ctx, _ptr(x), 0))
         return x
 
@@ -527,15 +536,15 @@ class Engine:
     # In complex image mode dc_step, prox_l1_dual and prox_cnc_dual take complex device tensors of the engine's precision (the _cx calls,
     # which exist in float and double); in real mode they are the float32 calls they ever were.
     def dc_step(self, z, w, x, reo):
-        fn = self._fn('dc_step') if self._cx else self._L.pnp_dc_step
+        fn = self._step_fn('dc_step')
         _lib.check(fn(self._ctx, _ptr(z), _ptr(w), _ptr(x), float(reo)))
 
     def prox_l1_dual(self, x, z, w, thr):
-        fn = self._fn('prox_l1_dual') if self._cx else self._L.pnp_prox_l1_dual
+        fn = self._step_fn('prox_l1_dual')
         _lib.check(fn(self._ctx, _ptr(x), _ptr(z), _ptr(w), float(thr)))
 
     def prox_cnc_dual(self, x, z, w, alpha, lambda1, reo, b):
-        fn = self._fn('prox_cnc_dual') if self._cx else self._L.pnp_prox_cnc_dual
+        fn = self._step_fn('prox_cnc_dual')
         _lib.check(fn(self._ctx, _ptr(x), _ptr(z), _ptr(w), float(alpha), float(lambda1), float(reo), float(b)))
 
     def cnc_combine(self, z, x, w, s, t, alpha, lambda1, reo, b):

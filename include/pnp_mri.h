@@ -173,6 +173,8 @@ int pnp_download_x(pnp_ctx* ctx, float* x, int on_device);
  *   X = fft2(z - w); X[mask] = (La2*X[mask] + y[mask])/(1+La2), La2 = 1/(2 reo);
  *   x = |Re ifft2(X)|.      z, w, x: [B][H][W] float32 device pointers (x may alias neither). */
 int pnp_dc_step(pnp_ctx* ctx, const float* z_dev, const float* w_dev, float* x_dev, double reo);
+/* The five pointwise calls below (pnp_prox_l1_dual, pnp_prox_cnc_dual, pnp_cnc_combine, pnp_add, pnp_dual_clamp) accept any float
+ * pointer: arrays that are all aligned to 16 bytes take the vector path, others a slower scalar one with the same results. */
 /* z = soft(x + w, thr); w = w + x - z                                           (S1:123,126) */
 int pnp_prox_l1_dual(pnp_ctx* ctx, const float* x_dev, float* z_dev, float* w_dev, double thr);
 /* CNC z-update + dual update                                                 (S4:127-129,132) */

@@ -15,6 +15,8 @@
 #include "fft16.h"
 #include "prox_ops.h"
 #include <math.h>
+#include <stdint.h>
+#include <initializer_list>
 
 namespace pnp {
 
@@ -687,27 +689,37 @@ static inline unsigned pw_grid(size_t n4) {
     return (unsigned)(g < 2048 ? (g ? g : 1) : 2048);
 }
 
+// The float4 body needs every array on a 16-byte boundary; the C ABI promises only float alignment.  One pointer off that boundary:
+// n4 = 0, the scalar tail loop covers [0, n) with 4-byte accesses, and the grid is sized from n (same 2048-block cap).
+struct PwShape { size_t n4; unsigned grid; };
+static inline PwShape pw_shape(size_t n, std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* q : ptrs) bits |= (uintptr_t)q;
+    if (bits & 15) return { 0, pw_grid(n) };
+    return { n / 4, pw_grid(n / 4) };
+}
+
 hipError_t launch_prox(hipStream_t s, bool cnc, const float* x, float* z, float* w, ProxParams p, size_t n) {
-    const size_t n4 = n / 4;
-    if (cnc) hipLaunchKernelGGL(k_prox<true>, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)x, (float4*)z, (float4*)w, p, n4, n);
-    else     hipLaunchKernelGGL(k_prox<false>, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)x, (float4*)z, (float4*)w, p, n4, n);
+    const PwShape g = pw_shape(n, { x, z, w });
+    if (cnc) hipLaunchKernelGGL(k_prox<true>, dim3(g.grid), dim3(256), 0, s, (const float4*)x, (float4*)z, (float4*)w, p, g.n4, n);
+    else     hipLaunchKernelGGL(k_prox<false>, dim3(g.grid), dim3(256), 0, s, (const float4*)x, (float4*)z, (float4*)w, p, g.n4, n);
     return hipGetLastError();
 }
 hipError_t launch_combine(hipStream_t s, const float* z, const float* x, const float* w, const float* sd, float* t,
                           float c1, float c2, float c3, size_t n) {
-    const size_t n4 = n / 4;
-    hipLaunchKernelGGL(k_combine, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)z, (const float4*)x,
-                       (const float4*)w, (const float4*)sd, (float4*)t, c1, c2, c3, n4, n);
+    const PwShape g = pw_shape(n, { z, x, w, sd, t });
+    hipLaunchKernelGGL(k_combine, dim3(g.grid), dim3(256), 0, s, (const float4*)z, (const float4*)x,
+                       (const float4*)w, (const float4*)sd, (float4*)t, c1, c2, c3, g.n4, n);
     return hipGetLastError();
 }
 hipError_t launch_add(hipStream_t s, const float* a, const float* b, float* o, size_t n) {
-    const size_t n4 = n / 4;
-    hipLaunchKernelGGL(k_add, dim3(pw_grid(n4)), dim3(256), 0, s, (const float4*)a, (const float4*)b, (float4*)o, n4, n);
+    const PwShape g = pw_shape(n, { a, b, o });
+    hipLaunchKernelGGL(k_add, dim3(g.grid), dim3(256), 0, s, (const float4*)a, (const float4*)b, (float4*)o, g.n4, n);
     return hipGetLastError();
 }
 hipError_t launch_dual_clamp(hipStream_t s, float* x, float* z, float* w, size_t n) {
-    const size_t n4 = n / 4;
-    hipLaunchKernelGGL(k_dual_clamp, dim3(pw_grid(n4)), dim3(256), 0, s, (float4*)x, (float4*)z, (float4*)w, n4, n);
+    const PwShape g = pw_shape(n, { x, z, w });
+    hipLaunchKernelGGL(k_dual_clamp, dim3(g.grid), dim3(256), 0, s, (float4*)x, (float4*)z, (float4*)w, g.n4, n);
     return hipGetLastError();
 }
 

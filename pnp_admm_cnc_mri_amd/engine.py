@@ -140,7 +140,7 @@ class Engine:
         self._L = _lib.lib()
         self._ctx = _lib.ctx_p()
         self.f64 = precision == 'f64'
-        create = self._L.pnp_ctx_create_any_f64 if self.f64 else self._L.pnp_ctx_create_any      # H, W in [128, 1024]
+        create = self._prec_fn('ctx_create_any')      # H, W in [128, 1024]
         _lib.check(create(int(device), int(H), int(W), int(Bmax), C.byref(self._ctx)))
         self.H, self.W, self.Bmax, self.device = int(H), int(W), int(Bmax), int(device)
         self.B = 0
@@ -237,7 +237,7 @@ class Engine:
         conjugate gradients (default 3: enough for maps normalised to sum_c |S_c|^2 = 1 at the presets' reo; UNNORMALISED MAPS OR A
         LARGE reo -- the in-function default 2.75 -- NEED MORE, see cg_residual).  Drops the uploaded problem."""
         if sens is None:
-            _lib.check(self._L.pnp_set_coils_f64(self._ctx, None, 0, 0, 0) if self.f64 else self._L.pnp_set_coils(self._ctx, None, 0, 0, 0))
+            _lib.check(self._prec_fn('set_coils')(self._ctx, None, 0, 0, 0))
             self.C, self.B, self._cx = 0, 0, False
             return
         Cn, Ks = check_coils(sens, self.H, self.W, cg_iters)
@@ -245,7 +245,7 @@ class Engine:
         if not dev:
             sens = _host(sens, self._cplx)
         _lib.check(self._L.pnp_set_cg(self._ctx, int(cg_iters)))
-        fn = self._L.pnp_set_coils_f64 if self.f64 else self._L.pnp_set_coils
+        fn = self._prec_fn('set_coils')
         _lib.check(fn(self._ctx, _ptr(sens), Cn, Ks, 1 if dev else 0))
         self.C, self.Ks, self.B, self._cx = Cn, Ks, 0, False
 
@@ -266,9 +266,13 @@ class Engine:
         _lib.check(self._L.pnp_get_image(self._ctx, C.byref(m)))
         return {v: k for k, v in IMAGE_MODES.items()}[m.value]
 
+    def _prec_fn(self, name):
+        """the entry point `name` of the engine's precision, whatever the image mode: pnp_<name>[_f64]"""
+        return getattr(self._L, 'pnp_' + name + ('_f64' if self.f64 else ''))
+
     def _fn(self, name):
         """the entry point `name` of the engine's image mode and precision: pnp_<name>[_cx][_f64]"""
-        return getattr(self._L, 'pnp_' + name + ('_cx' if self._cx else '') + ('_f64' if self.f64 else ''))
+        return self._prec_fn(name + ('_cx' if self._cx else ''))
 
     def _step_fn(self, name):
         """the step-wise entry point `name`: in complex image mode of the engine's precision, in real mode the float32 call"""
@@ -297,7 +301,7 @@ class Engine:
         [B,C,H,W] and maps_out [B,C,H,W] of the engine's complex type, mask_bank [K,H,W] uint8, mask_id [B] int32 or None, lambda_out
         [B,H,W] real or None.  Runs on the engine's stream with its transforms and synchronises at its end; the uploaded problem, the
         state and the coils of the engine are not touched."""
-        fn = self._L.pnp_coil_maps_f64 if self.f64 else self._L.pnp_coil_maps
+        fn = self._prec_fn('coil_maps')
         _lib.check(fn(self._ctx, _ptr(y), _ptr(mask_bank), _ptr(mask_id), _ptr(maps_out), _ptr(lambda_out), int(B), int(Cn), int(calib),
                       int(radius), int(power_iters), float(thresh)))
 
@@ -306,7 +310,7 @@ class Engine:
         """ESPIRiT sensitivity maps (pnp_espirit_maps; coilmaps.estimate(method='espirit') is the array-level entry): the arrays of
         coil_maps.  Runs on the engine's stream with its transforms and synchronises; the uploaded problem, the state and the coils of the
         engine are not touched.  -> the signal-space rank of every slice, [B] int32."""
-        fn = self._L.pnp_espirit_maps_f64 if self.f64 else self._L.pnp_espirit_maps
+        fn = self._prec_fn('espirit_maps')
         _lib.check(fn(self._ctx, _ptr(y), _ptr(mask_bank), _ptr(mask_id), _ptr(maps_out), _ptr(lambda_out), int(B), int(Cn), int(calib),
                       int(kernel), int(power_iters), float(sigma), float(crop), float(thresh)))
         rank = np.empty(int(B), np.int32)
@@ -316,7 +320,7 @@ class Engine:
     def espirit_eigmaps(self, images, w, maps_out, lambda_out, B, Cn, kernel, power_iters):
         """The per-pixel stage of the ESPIRiT estimator alone (pnp_espirit_eigmaps): DEVICE tensors images [B,C,H,W] (low-resolution coil
         images), w [B,C,C,2k-1,2k-1] of the engine's complex type -> maps_out [B,C,H,W] (unit vectors, no support), lambda_out [B,H,W]."""
-        fn = self._L.pnp_espirit_eigmaps_f64 if self.f64 else self._L.pnp_espirit_eigmaps
+        fn = self._prec_fn('espirit_eigmaps')
         _lib.check(fn(self._ctx, _ptr(images), _ptr(w), _ptr(maps_out), _ptr(lambda_out), int(B), int(Cn), int(kernel), int(power_iters)))
 
     def espirit_stage_times(self, enable=True):
@@ -404,11 +408,11 @@ class Engine:
         bank, mid = self._masks(masks, mask_id, B)
         cid = self._coil_id(coil_id, B)
         if self.C:
-            up = self._L.pnp_upload_problem_mc_f64 if self.f64 else self._L.pnp_upload_problem_mc
+            up = self._prec_fn('upload_problem_mc')
             _lib.check(up(self._ctx, _ptr(y), _ptr(bank), _ptr(mid), _ptr(cid), B, bank.shape[0], 0))
             self.B = B
             return
-        up = self._L.pnp_upload_problem_f64 if self.f64 else self._L.pnp_upload_problem
+        up = self._prec_fn('upload_problem')
         _lib.check(up(self._ctx, _ptr(y), _ptr(bank), _ptr(mid), B, bank.shape[0], 0))
         self.B = B
 
@@ -429,7 +433,7 @@ class Engine:
             if mode is None or noise.shape != ok[mode]:
                 raise ValueError('noise shape %s is none of [H,W], [C,H,W], [B,C,H,W] of this engine' % (noise.shape,))
             bank, mid = self._masks(masks, mask_id, B)
-            fn = self._L.pnp_synthesize_problem_mc_f64 if self.f64 else self._L.pnp_synthesize_problem_mc
+            fn = self._prec_fn('synthesize_problem_mc')
             _lib.check(fn(self._ctx, _ptr(img), _ptr(noise), mode, _ptr(bank), _ptr(mid), _ptr(cid), B, bank.shape[0], 0))
             self.B = B
             return
@@ -439,13 +443,13 @@ class Engine:
         if noise.shape[-2:] != (self.H, self.W):
             raise ValueError('noise shape %s does not match engine %dx%d' % (noise.shape[-2:], self.H, self.W))
         bank, mid = self._masks(masks, mask_id, B)
-        fn = self._L.pnp_synthesize_problem_f64 if self.f64 else self._L.pnp_synthesize_problem
+        fn = self._prec_fn('synthesize_problem')
         _lib.check(fn(self._ctx, _ptr(img), _ptr(noise), per, _ptr(bank), _ptr(mid), B, bank.shape[0], 0))
         self.B = B
 
     def download_y(self):
         y = np.empty((self.B, self.C, self.H, self.W) if self.C else (self.B, self.H, self.W), self._cplx)
-        fn = self._L.pnp_download_y_f64 if self.f64 else self._L.pnp_download_y
+        fn = self._prec_fn('download_y')
         _lib.check(fn(self._ctx, _ptr(y), 0))
         return y
 
@@ -564,7 +568,7 @@ class Engine:
         the engine's stream and returned -- or None: a host array, after a synchronisation."""
         if gt is not None and not _is_dev(gt):
             gt = _host(gt, np.uint8)
-        fn = self._L.pnp_residuals_f64 if self.f64 else self._L.pnp_residuals
+        fn = self._prec_fn('residuals')
         dev = out is not None
         if dev and not _is_dev(out):
             raise TypeError('residuals: out must be a device tensor (or None for a host array)')
@@ -585,19 +589,19 @@ class Engine:
         shift=(sy, sx): Psi_s, the transform of the frame shifted by it (pnp_dwt2_shifted); None: the call as it ever was."""
         if shift is not None:
             return self._dwt2_shifted(inp, out, B, 0, shift)
-        fn = self._L.pnp_dwt2_fwd_f64 if self.f64 else self._L.pnp_dwt2_fwd
+        fn = self._prec_fn('dwt2_fwd')
         _lib.check(fn(self._ctx, _ptr(inp), _ptr(out), int(B)))
 
     def idwt2(self, inp, out, B, shift=None):
         """Psi^T (pnp_dwt2_inv); shift=(sy, sx): Psi_s^T."""
         if shift is not None:
             return self._dwt2_shifted(inp, out, B, 1, shift)
-        fn = self._L.pnp_dwt2_inv_f64 if self.f64 else self._L.pnp_dwt2_inv
+        fn = self._prec_fn('dwt2_inv')
         _lib.check(fn(self._ctx, _ptr(inp), _ptr(out), int(B)))
 
     def _dwt2_shifted(self, inp, out, B, inverse, shift):
         sy, sx = shift
-        fn = self._L.pnp_dwt2_shifted_f64 if self.f64 else self._L.pnp_dwt2_shifted
+        fn = self._prec_fn('dwt2_shifted')
         _lib.check(fn(self._ctx, _ptr(inp), _ptr(out), int(B), int(inverse), int(sy), int(sx)))
 
     def A(self, x, k):
@@ -616,7 +620,7 @@ class Engine:
         gt = _host(gt_u8, np.uint8)
         psnr = np.empty(self.B, np.float64)
         re = np.empty(self.B, np.float64)
-        fn = self._L.pnp_metrics_f64 if self.f64 else self._L.pnp_metrics
+        fn = self._prec_fn('metrics')
         _lib.check(fn(self._ctx, _ptr(x_dev), _ptr(gt), 0,
                       psnr.ctypes.data_as(_lib.c_double_p), re.ctypes.data_as(_lib.c_double_p)))
         return psnr, re
@@ -625,6 +629,6 @@ class Engine:
         """-> ssim[B] of img_E = x*255 against uint8 ground truth (utils/utils_image.py:570-615), on device."""
         gt = _host(gt_u8, np.uint8)
         out = np.empty(self.B, np.float64)
-        fn = self._L.pnp_ssim_f64 if self.f64 else self._L.pnp_ssim
+        fn = self._prec_fn('ssim')
         _lib.check(fn(self._ctx, _ptr(x_dev), _ptr(gt), 0, out.ctypes.data_as(_lib.c_double_p)))
         return out

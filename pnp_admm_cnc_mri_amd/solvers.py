@@ -88,6 +88,7 @@ The PnP entry points (PNP_ADMM_L1_D, PNP_ADMM_CNC_D, PNP_ADMM_CNC_DnCNN) live in
 import logging
 import os
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -100,6 +101,16 @@ PRESETS = {
     'ADMM_L1': dict(iter_num=50, lambda1=0.1, reo=0.015),                         # S1:171
     'ADMM_CNC': dict(alpha=0.45, iter_num=50, lambda1=0.5, reo=0.05, b=64),       # S4:176
 }
+
+# The coil keywords of all five entry points (the docstring above has what they mean).  An entry point takes its keywords ONCE, as
+# `call = SimpleNamespace(**locals())`; its driver (_solve here, solvers_pnp._solve_pnp) hands _Job these thirteen as one namespace.
+COIL_KEYS = ('coils', 'coil_id', 'cg_iters', 'virtual_coils', 'noise_cov', 'calib', 'maps_radius', 'maps_power_iters', 'maps_thresh',
+             'maps_method', 'maps_kernel', 'maps_sigma', 'maps_crop')
+
+
+def coil_options(call):
+    """the COIL_KEYS of an entry point's keywords `call`, as the namespace _Job takes"""
+    return SimpleNamespace(**{k: getattr(call, k) for k in COIL_KEYS})
 
 
 def logger_info(logger_name, log_path):
@@ -148,19 +159,28 @@ class _Job:
     """Everything around the hot loop that ADMM_L1 / ADMM_CNC / the PnP solvers share:
     inputs (S4:83-109), outputs and metrics (S4:138-172)."""
 
-    def __init__(self, mask, noises, tag, suffix, images=None, y=None, mask_id=None, testsets='testsets',
+    def __init__(self, mask, noises, tag, suffix, coil, images=None, y=None, mask_id=None, testsets='testsets',
                  testset_name='Set1', results='results', save_E=None, device=None, log=None, ssim=None,
-                 psnr_fmt='{:.4f}', precision='f32', coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
-                 maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02, maps_crop=0.9,
-                 image='real'):
+                 psnr_fmt='{:.4f}', precision='f32', image='real'):
+        """coil: the COIL_KEYS of the call (coil_options)"""
         # psnr_fmt: S1:150 and S3:320 print the per-image PSNR with two decimals, S4:155 / S6:332 / S6:548 with four
         self.tag, self.suffix, self.psnr_fmt = tag, suffix, psnr_fmt
         if precision not in ('f32', 'f64'):
             raise ValueError("precision must be 'f32' or 'f64'")
-        self.precision = precision
-        self.image = image
-        if image == 'complex':                                       # every check before an engine is opened (image_request has the rest)
-            if coils is None:
+        self.precision, self.image, self.testset_name = precision, image, testset_name
+        self._check_options(coil, image, mask, mask_id, y)
+        name, L_path = testset_name + '_dn_' + tag, os.path.join(testsets, testset_name)
+        self._load(images, y, L_path, os.path.join(results, name), save_E)
+        self.noises = None if noises is None else np.asarray(noises)
+        self.device = resolve_device(device)
+        self.ssim = True if ssim is None else ssim
+        self._open_log(log, name, L_path)
+
+    def _check_options(self, c, image, mask, mask_id, y):
+        """The coil and image rules that need the mask's size (image_request has the rest of image=): every one a ValueError before an
+        engine is opened.  Leaves the mask bank, the coil options and what they ask for (mixing, estimate, maps_opts) on the job."""
+        if image == 'complex':
+            if c.coils is None:
                 raise ValueError("image='complex' runs on the multi-coil path: it needs coils= (an array of maps or 'estimate')")
             if y is None:
                 raise ValueError("image='complex' reconstructs MEASURED data: it needs y= [B,C,H,W] (the synthesis from images= is "
@@ -169,45 +189,50 @@ class _Job:
         self.mask_bank = mask[None] if mask.ndim == 2 else mask
         self.H, self.W = self.mask_bank.shape[1:]
         self.mask_id = None if mask_id is None else np.asarray(mask_id, np.int32)
-        self.coils, self.cg_iters = coils, cg_iters
-        self.coil_id = None if coil_id is None else np.asarray(coil_id, np.int32)
-        self.virtual_coils, self.noise_cov, self.calib, self.coil_mix = virtual_coils, noise_cov, calib, None
-        self.mixing = virtual_coils is not None or noise_cov is not None
-        self.estimate, self.coil_maps = isinstance(coils, str), None
-        if self.estimate:                                            # every check before an engine is opened
-            if coils != 'estimate':
-                raise ValueError("coils must be an array of sensitivity maps or 'estimate' (got %r)" % (coils,))
+        self.coils, self.cg_iters = c.coils, c.cg_iters
+        self.coil_id = None if c.coil_id is None else np.asarray(c.coil_id, np.int32)
+        self.virtual_coils, self.noise_cov, self.calib, self.coil_mix = c.virtual_coils, c.noise_cov, c.calib, None
+        self.mixing = c.virtual_coils is not None or c.noise_cov is not None
+        self.estimate, self.coil_maps = isinstance(c.coils, str), None
+        if self.estimate:
+            if c.coils != 'estimate':
+                raise ValueError("coils must be an array of sensitivity maps or 'estimate' (got %r)" % (c.coils,))
             if y is None:
                 raise ValueError("coils='estimate' estimates the maps from MEASURED data: it needs y= [B,C,H,W] (images= may still be given "
                                  'as the ground truth)')
-            if coil_id is not None:
+            if c.coil_id is not None:
                 raise ValueError("coils='estimate' builds one coil set per slice (coil_id = arange(B)): coil_id= cannot be given with it")
             ys = tuple(np.shape(y))
             if len(ys) not in (3, 4) or ys[-2:] != (self.H, self.W):
                 raise ValueError('y must be [B,C,H,W] (or [C,H,W]) with H x W = %d x %d (got shape %s)' % (self.H, self.W, ys))
-            c_out = coilmix.plan_y(ys[-3], self.H, self.W, virtual_coils, noise_cov, calib)[1] if self.mixing else int(ys[-3])
-            coilmaps.check(c_out, calib, maps_radius, maps_power_iters, maps_thresh, self.H, self.W, maps_method, maps_kernel, maps_sigma,
-                           maps_crop)
-            check_coils(np.broadcast_to(np.int8(0), (1, c_out, self.H, self.W)), self.H, self.W, cg_iters)
-            coilmaps.check_region(self.mask_bank, self.mask_id, calib)
-            self.maps_opts = dict(calib=int(calib), radius=int(maps_radius), power_iters=int(maps_power_iters), thresh=float(maps_thresh))
-            if maps_method == 'espirit':                             # 'walsh', the default: the call and the info are what they were
-                self.maps_opts.update(method='espirit', kernel=int(maps_kernel), sigma=float(maps_sigma), crop=float(maps_crop))
+            c_out = coilmix.plan_y(ys[-3], self.H, self.W, c.virtual_coils, c.noise_cov, c.calib)[1] if self.mixing else int(ys[-3])
+            coilmaps.check(c_out, c.calib, c.maps_radius, c.maps_power_iters, c.maps_thresh, self.H, self.W, c.maps_method, c.maps_kernel,
+                           c.maps_sigma, c.maps_crop)
+            check_coils(np.broadcast_to(np.int8(0), (1, c_out, self.H, self.W)), self.H, self.W, c.cg_iters)
+            coilmaps.check_region(self.mask_bank, self.mask_id, c.calib)
+            self.maps_opts = dict(calib=int(c.calib), radius=int(c.maps_radius), power_iters=int(c.maps_power_iters),
+                                  thresh=float(c.maps_thresh))
+            if c.maps_method == 'espirit':                           # 'walsh', the default: the call and the info are what they were
+                self.maps_opts.update(method='espirit', kernel=int(c.maps_kernel), sigma=float(c.maps_sigma), crop=float(c.maps_crop))
         elif self.mixing:
-            if coils is None or y is None:
+            if c.coils is None or y is None:
                 raise ValueError('virtual_coils= / noise_cov= mix MEASURED data: they need coils= and y= (the device synthesis from images= '
                                  'is limited to 32 physical coils; images= may still be given as the ground truth)')
-            _, c_out, ks = coilmix.plan(coils, self.H, self.W, virtual_coils, noise_cov, calib)
-            check_coils(np.broadcast_to(np.int8(0), (ks, c_out, self.H, self.W)), self.H, self.W, cg_iters)   # the MIXED count; no engine yet
-        elif coils is not None:
-            check_coils(coils, self.H, self.W, cg_iters)                         # before an engine is opened
-        elif coil_id is not None:
+            _, c_out, ks = coilmix.plan(c.coils, self.H, self.W, c.virtual_coils, c.noise_cov, c.calib)
+            check_coils(np.broadcast_to(np.int8(0), (ks, c_out, self.H, self.W)), self.H, self.W, c.cg_iters)   # the MIXED count
+        elif c.coils is not None:
+            check_coils(c.coils, self.H, self.W, c.cg_iters)
+        elif c.coil_id is not None:
             raise ValueError('coil_id= needs coils=')
+
+    def _load(self, images, y, L_path, E_path, save_E):
+        """The ground truth (images=, or the files of testsets/<Set>: S4:62-94) and the measurements y=; where the results go."""
         self.names = None
         self.from_files = images is None and y is None
+        self.E_path = E_path
+        self.save_E = (True if save_E is None else save_E) if self.from_files else bool(save_E)
         if self.from_files:
             # S4:62-94: list testsets/<Set>, gray decode, modcrop(8), re-quantise
-            L_path = os.path.join(testsets, testset_name)
             paths = imageio.get_image_paths(L_path)
             self.names = [os.path.basename(p) for p in paths]
             imgs = [imageio.modcrop(imageio.imread_gray(p), 8) for p in paths]
@@ -215,11 +240,6 @@ class _Job:
                 if im.shape != (self.H, self.W):
                     raise ValueError('%s is %s, mask is %dx%d' % (p, im.shape, self.H, self.W))
             images = np.stack(imgs)
-            self.E_path = os.path.join(results, testset_name + '_dn_' + tag)
-            self.save_E = True if save_E is None else save_E
-        else:
-            self.E_path = os.path.join(results, testset_name + '_dn_' + tag)
-            self.save_E = bool(save_E)
         self.gt_u8 = None
         self.img_L = None
         if images is not None:
@@ -231,66 +251,70 @@ class _Job:
             self.gt_u8 = np.ascontiguousarray(images)
             self.img_L = imageio.requantise(self.gt_u8)                          # S4:91-94
         self.y = None if y is None else np.asarray(y)
-        if self.y is not None and self.y.ndim == (2 if coils is None else 3):
+        if self.y is not None and self.y.ndim == (2 if self.coils is None else 3):
             self.y = self.y[None]
         self.B = len(self.gt_u8) if self.gt_u8 is not None else len(self.y)
-        self.noises = None if noises is None else np.asarray(noises)
-        self.device = resolve_device(device)
-        self.ssim = True if ssim is None else ssim
+
+    def _open_log(self, log, name, L_path):
+        """the caller's logger, or -- when there are files to read or to write -- the reference's, in the results directory"""
         self.log = log
         if self.log is None and (self.from_files or self.save_E):
             os.makedirs(self.E_path, exist_ok=True)
-            name = testset_name + '_dn_' + tag
             self.log = logger_info(name, os.path.join(self.E_path, name + '.log'))
-            self.log.info(os.path.join(testsets, testset_name))
-        self.testset_name = testset_name
+            self.log.info(L_path)
 
-    def open_engine(self, stream=None, transform=None, levels=3, spin=None, spin_average=1):
-        """stream: HIP stream handle every engine call is ordered on (PnP: torch's current stream),
-        set BEFORE the first kernel so upload / synthesis / init and the loop share one queue.
-        transform / levels: Engine.set_sparsity (ADMM_L1 / ADMM_CNC); spin / spin_average: the table of spin_request and its group
-        size, Engine.set_spin."""
-        if self.mixing and self.estimate and self.coil_mix is None:  # y' = M y with ONE matrix for the batch; the maps come from y' below
-            self.y, _, self.coil_mix = coilmix.prepare(self.y, None, self.mask_bank, self.mask_id, None, self.virtual_coils, self.noise_cov,
-                                                       self.calib, self.precision, self.device)
-            if self.log is not None:
-                self.log.info(coilmix.describe(self.coil_mix))
-        elif self.mixing and self.coil_mix is None:                  # y' = M y, S' = M S: from here on the virtual coils are the coils
-            self.y, self.coils, self.coil_mix = coilmix.prepare(self.y, self.coils, self.mask_bank, self.mask_id, self.coil_id,
-                                                                self.virtual_coils, self.noise_cov, self.calib, self.precision, self.device)
-            if self.log is not None:
-                self.log.info(coilmix.describe(self.coil_mix))
-        eng = Engine(self.H, self.W, Bmax=self.B, device=self.device, precision=self.precision)
-        if transform is not None:
-            eng.set_sparsity(transform, levels)
-            if self.log is not None:
-                self.log.info('sparsity transform: {:s}, {:d} levels (periodic 2-D DWT; not in the reference scripts)'.format(
-                    transform, int(levels)))
-        if spin is not None:
-            eng.set_spin(spin, spin_average)
-            if self.log is not None:
-                self.log.info('cycle spinning: {:d} shifts, {:d} averaged per prox (not in the reference scripts)'.format(
-                    len(spin), int(spin_average)))
-        if stream is not None:
-            eng.set_stream(stream)
-        if self.estimate and self.coil_maps is None:                 # one coil set per slice, from the slice's own calibration region
+    def say(self, line, *args):
+        """one log line (line.format(*args)) where there is a logger"""
+        if self.log is not None:
+            self.log.info(line.format(*args) if args else line)
+
+    def _mix_coils(self):
+        """Coil mixing, once and before an engine exists: y' = M y and, for given maps, S' = M S -- from here on the virtual coils are
+        the coils.  With coils='estimate' ONE matrix for the batch; the maps come from y' in _set_coils."""
+        if not self.mixing or self.coil_mix is not None:
+            return
+        self.y, coils, self.coil_mix = coilmix.prepare(self.y, None if self.estimate else self.coils, self.mask_bank, self.mask_id,
+                                                       self.coil_id, self.virtual_coils, self.noise_cov, self.calib, self.precision,
+                                                       self.device)
+        if not self.estimate:
+            self.coils = coils
+        self.say(coilmix.describe(self.coil_mix))
+
+    def _set_coils(self, eng):
+        """The coil side of an open engine, in the order the library needs: estimate the maps (one coil set per slice, from the slice's
+        own calibration region), set_coils, then set_image_mode -- set_coils returns the engine to real mode."""
+        if self.estimate and self.coil_maps is None:
             self.coils, rank = coilmaps.estimate(self.y, self.mask_bank, self.mask_id, precision=self.precision, engine=eng, return_rank=True,
                                                  **self.maps_opts)
             self.coil_id = np.arange(self.B, dtype=np.int32)
             self.coil_maps = dict(self.maps_opts, support=coilmaps.support_share(self.coils))
             if rank is not None:
                 self.coil_maps['rank'] = [int(v) for v in rank]
-            if self.log is not None:
-                self.log.info(coilmaps.describe(self.coil_maps))
+            self.say(coilmaps.describe(self.coil_maps))
         if self.coils is not None:
             eng.set_coils(self.coils, self.cg_iters)
-            if self.log is not None:
-                self.log.info('multi-coil data consistency: {:d} coils, {:d} CG iterations per x-step (not in the reference scripts)'.format(
-                    eng.C, int(self.cg_iters)))
-        if self.image == 'complex':                                  # after set_coils, which returns the engine to real mode
+            self.say('multi-coil data consistency: {:d} coils, {:d} CG iterations per x-step (not in the reference scripts)',
+                     eng.C, int(self.cg_iters))
+        if self.image == 'complex':
             eng.set_image_mode('complex')
-            if self.log is not None:
-                self.log.info('complex-valued image: the phase is kept, the prox thresholds the modulus (not in the reference scripts)')
+            self.say('complex-valued image: the phase is kept, the prox thresholds the modulus (not in the reference scripts)')
+
+    def open_engine(self, stream=None, transform=None, levels=3, spin=None, spin_average=1):
+        """stream: HIP stream handle every engine call is ordered on (PnP: torch's current stream),
+        set BEFORE the first kernel so upload / synthesis / init and the loop share one queue.
+        transform / levels: Engine.set_sparsity (ADMM_L1 / ADMM_CNC); spin / spin_average: the table of spin_request and its group
+        size, Engine.set_spin."""
+        self._mix_coils()
+        eng = Engine(self.H, self.W, Bmax=self.B, device=self.device, precision=self.precision)
+        if transform is not None:
+            eng.set_sparsity(transform, levels)
+            self.say('sparsity transform: {:s}, {:d} levels (periodic 2-D DWT; not in the reference scripts)', transform, int(levels))
+        if spin is not None:
+            eng.set_spin(spin, spin_average)
+            self.say('cycle spinning: {:d} shifts, {:d} averaged per prox (not in the reference scripts)', len(spin), int(spin_average))
+        if stream is not None:
+            eng.set_stream(stream)
+        self._set_coils(eng)
         coil = {} if self.coils is None else {'coil_id': self.coil_id}
         if self.y is not None:
             eng.upload(self.y, self.mask_bank, self.mask_id, **coil)
@@ -333,14 +357,12 @@ class _Job:
                 info['ssim'] = list(map(float, eng.ssim(x_dev, self.gt_u8)))                  # device, double
             for n in range(self.B):
                 psnr1[n] = info['psnr'][n]
-                if self.log is not None and self.names is not None:
-                    self.log.info(('{:s} - PSNR: ' + self.psnr_fmt + ' dB; SSIM: {:.4f} ; RE: {:.4f}.').format(
-                        self.names[n], info['psnr'][n], info['ssim'][n] if self.ssim else float('nan'), info['re'][n]))
-            if self.log is not None:
-                ave = lambda v: sum(v) / len(v) if v else float('nan')
-                self.log.info('------> testset_name: ({}), {}Average PSNR:({:.3f})dB, Average ssim : ({:.3f}), '
-                              'Average re : ({:.3f}) )'.format(self.testset_name, extra, ave(info['psnr']),
-                                                               ave(info['ssim']), ave(info['re'])))
+                if self.names is not None:
+                    self.say('{:s} - PSNR: ' + self.psnr_fmt + ' dB; SSIM: {:.4f} ; RE: {:.4f}.',
+                             self.names[n], info['psnr'][n], info['ssim'][n] if self.ssim else float('nan'), info['re'][n])
+            ave = lambda v: sum(v) / len(v) if v else float('nan')
+            self.say('------> testset_name: ({}), {}Average PSNR:({:.3f})dB, Average ssim : ({:.3f}), Average re : ({:.3f}) )',
+                     self.testset_name, extra, ave(info['psnr']), ave(info['ssim']), ave(info['re']))
         if self.save_E:
             os.makedirs(self.E_path, exist_ok=True)
             for n in range(self.B):
@@ -385,9 +407,9 @@ def spin_request(spin, spin_average, spin_seed, transform, levels, iter_num):
 
 def log_early_stop(job, trace, iter_num, tol):
     """the one extra log line of a run that the stopping rule ended before iter_num"""
-    if trace is not None and tol is not None and trace['iters_done'] < iter_num and job.log is not None:
-        job.log.info('stopped after iteration {:d} of {:d}: max(r_pri, r_dual) <= {:g} * ||z|| for every slice'.format(
-            int(trace['iters_done']), int(iter_num), float(tol)))
+    if trace is not None and tol is not None and trace['iters_done'] < iter_num:
+        job.say('stopped after iteration {:d} of {:d}: max(r_pri, r_dual) <= {:g} * ||z|| for every slice',
+                int(trace['iters_done']), int(iter_num), float(tol))
 
 
 def _device_x(eng, job):
@@ -401,32 +423,37 @@ def _device_x(eng, job):
     return xt
 
 
+def _solve(c, tag, suffix, psnr_fmt, iter_num, run):
+    """ADMM_L1 / ADMM_CNC around the one call they differ in.  c: the entry point's keywords; run(eng, *trace_args): its whole loop on
+    the engine, with trace_args = (trace_every, tol, ground truth) for a traced call and none otherwise."""
+    traced = trace_request(c.trace_every, c.tol, c.return_info)
+    check_sparsity(c.transform, c.levels, *np.asarray(c.mask).shape[-2:])          # before an engine is opened
+    image_request(c.image, c.spin, c.trace_every, c.tol, c.transform, c.levels, c.precision)
+    shifts = spin_request(c.spin, c.spin_average, c.spin_seed, c.transform, c.levels, iter_num)
+    job = _Job(c.mask, c.noises, tag, suffix, coil_options(c), c.images, c.y, c.mask_id, c.testsets, c.testset_name, c.results, c.save_E,
+               c.device, psnr_fmt=psnr_fmt, precision=c.precision, image=c.image)
+    with job.open_engine(transform=c.transform, levels=c.levels, spin=shifts, spin_average=c.spin_average) as eng:
+        trace = run(eng, c.trace_every, c.tol, job.gt_u8) if traced else run(eng)
+        log_early_stop(job, trace, iter_num, c.tol)
+        x = _device_x(eng, job) if c.return_device else eng.x()      # iter_num = 0: the initial x = |ifft2(y)| (S4:103, 138)
+        out, _, info = job.finish(eng, x)
+        if traced:
+            info['trace'] = trace
+    return (out, info) if c.return_info else out
+
+
 def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
             results='results', save_E=None, device=None, return_info=False, precision='f32', return_device=False, trace_every=0, tol=None,
             transform=None, levels=3, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24,
             maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02,
-             maps_crop=0.9, spin=None, spin_average=1, spin_seed=0, image='real', **ADMM_L1_opts):
+            maps_crop=0.9, spin=None, spin_average=1, spin_seed=0, image='real', **ADMM_L1_opts):
     """ADMM with L1 prox on the MI355X engine.  Reference: "【1】ADMM_L1.py":29-169."""
+    call = SimpleNamespace(**locals())                   # the keywords above, by name: the first statement
     iter_num = ADMM_L1_opts.get('iter_num', 20)          # S1:35
     lambda1 = ADMM_L1_opts.get('lambda1', 0.04)          # S1:36
     reo = ADMM_L1_opts.get('reo', 0.04)                  # S1:37
-    traced = trace_request(trace_every, tol, return_info)
-    check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
-    image_request(image, spin, trace_every, tol, transform, levels, precision)
-    shifts = spin_request(spin, spin_average, spin_seed, transform, levels, iter_num)
-    job = _Job(mask, noises, 'ADMM_L1', '_PDG L1', images, y, mask_id, testsets, testset_name, results, save_E, device,
-               psnr_fmt='{:.2f}', precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters, virtual_coils=virtual_coils,
-               noise_cov=noise_cov, calib=calib, maps_radius=maps_radius, maps_power_iters=maps_power_iters, maps_thresh=maps_thresh,
-               maps_method=maps_method, maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop, image=image)   # S1:150
-    with job.open_engine(transform=transform, levels=levels, spin=shifts, spin_average=spin_average) as eng:
-        # S1:111-126, all slices, on device
-        trace = eng.admm_l1(iter_num, lambda1, reo, trace_every, tol, job.gt_u8) if traced else eng.admm_l1(iter_num, lambda1, reo)
-        log_early_stop(job, trace, iter_num, tol)
-        x = _device_x(eng, job) if return_device else eng.x()      # iter_num = 0: the initial x = |ifft2(y)| (S4:103, 138)
-        out, _, info = job.finish(eng, x)
-        if traced:
-            info['trace'] = trace
-    return (out, info) if return_info else out
+    return _solve(call, 'ADMM_L1', '_PDG L1', '{:.2f}', iter_num,                                       # PSNR format S1:150
+                  lambda eng, *trace: eng.admm_l1(iter_num, lambda1, reo, *trace))                      # S1:111-126, all slices, on device
 
 
 def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets', testset_name='Set1',
@@ -435,26 +462,11 @@ def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets
              maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02,
              maps_crop=0.9, spin=None, spin_average=1, spin_seed=0, image='real', **ADMM_CNC_opts):
     """ADMM with the convex-non-convex z-step.  Reference: "【4】ADMM_CNC .py":31-174."""
+    call = SimpleNamespace(**locals())                   # the keywords above, by name: the first statement
     iter_num = ADMM_CNC_opts.get('iter_num', 4)          # S4:37
     alpha = ADMM_CNC_opts.get('alpha', 0.4)              # S4:38
     lambda1 = ADMM_CNC_opts.get('lambda1', 0.04)         # S4:39
     reo = ADMM_CNC_opts.get('reo', 2.75)                 # S4:40  (reo is 1/beta of the paper)
     b = ADMM_CNC_opts.get('b', 1)                        # S4:41  (b is b^2 of the paper)
-    traced = trace_request(trace_every, tol, return_info)
-    check_sparsity(transform, levels, *np.asarray(mask).shape[-2:])          # before an engine is opened
-    image_request(image, spin, trace_every, tol, transform, levels, precision)
-    shifts = spin_request(spin, spin_average, spin_seed, transform, levels, iter_num)
-    job = _Job(mask, noises, 'ADMM_CNC', '_ADMM CNC', images, y, mask_id, testsets, testset_name, results, save_E, device,
-               precision=precision, coils=coils, coil_id=coil_id, cg_iters=cg_iters, virtual_coils=virtual_coils, noise_cov=noise_cov,
-               calib=calib, maps_radius=maps_radius, maps_power_iters=maps_power_iters, maps_thresh=maps_thresh,
-               maps_method=maps_method, maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop, image=image)
-    with job.open_engine(transform=transform, levels=levels, spin=shifts, spin_average=spin_average) as eng:
-        # S4:115-132
-        trace = (eng.admm_cnc(iter_num, alpha, lambda1, reo, b, trace_every, tol, job.gt_u8) if traced
-                 else eng.admm_cnc(iter_num, alpha, lambda1, reo, b))
-        log_early_stop(job, trace, iter_num, tol)
-        x = _device_x(eng, job) if return_device else eng.x()      # iter_num = 0: the initial x = |ifft2(y)| (S4:103, 138)
-        out, _, info = job.finish(eng, x)
-        if traced:
-            info['trace'] = trace
-    return (out, info) if return_info else out
+    return _solve(call, 'ADMM_CNC', '_ADMM CNC', '{:.4f}', iter_num,
+                  lambda eng, *trace: eng.admm_cnc(iter_num, alpha, lambda1, reo, b, *trace))           # S4:115-132

@@ -44,13 +44,14 @@ save_E=, device=, return_info=  as in solvers.py, plus
                             (the reference's one-slice calls: a forward is a train of short launches; FFDNet 0.50 -> see DESIGN.md 4.8)
 """
 import os
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import denoisers as D
 from . import utils_pnp as pnp
 from .engine import TRACE_FIELDS, trace_meets, trace_rows
-from .solvers import _Job, log_early_stop, resolve_device, trace_request
+from .solvers import _Job, coil_options, log_early_stop, resolve_device, trace_request
 
 PRESETS = {
     # PNP_ADMM_CNC_D(alpha, iter, lambda1, reo, b), S6:569-577
@@ -135,8 +136,9 @@ class _Tracer:
     also when the loop resumes at iter_start) reduces the tensors on the device when k is a checked iteration and says whether the
     stopping rule ends the loop there; result() is the trace of Engine._traced.  Off (`on` False): check() does nothing."""
 
-    def __init__(self, torch, eng, job, dev, trace_every, tol, return_info, iter_start, iter_num):
-        self.on = trace_request(trace_every, tol, return_info)
+    def __init__(self, torch, eng, job, dev, on, trace_every, tol, iter_start, iter_num):
+        """on: what trace_request made of the call"""
+        self.on = on
         self.tol, self.iter_num, self.done = tol, iter_num, iter_num if iter_num > iter_start else iter_start
         if not self.on:
             return
@@ -174,50 +176,74 @@ class _Tracer:
         return trace
 
 
+def _solve_pnp(c, nets, tag, suffix, psnr_fmt, iter_num, body, scratch, extra='', x8_for=(), keep_z=False):
+    """The three PnP solvers around their iteration.  c: the entry point's keywords; nets: [(model_name, model)], one per denoiser to
+    load; body(i, eng, dens, st, tracer) -> True to stop: iteration i on the loop's tensors st.x, st.z, st.w and the `scratch` ones
+    (names; each like z), with the loaded denoisers `dens`.  x8_for: the families that run in x8 mode; keep_z: the body updates z in
+    place, so a traced run gets st.z_prev for the z before a checked iteration (None otherwise).  extra: the front of the averages'
+    log line.  -> (out, psnr1, info)"""
+    import torch
+    traced = trace_request(c.trace_every, c.tol, c.return_info)
+    device = resolve_device(c.device)                                  # None: LOCAL_RANK under a process group, else 0
+    dev = torch.device('cuda', device)
+    x8 = bool(x8_for) and D.family(nets[0][0]) in x8_for
+    job = _Job(c.mask, c.noises, tag, suffix, coil_options(c), c.images, c.y, c.mask_id, c.testsets, c.testset_name, c.results, c.save_E,
+               device, psnr_fmt=psnr_fmt)
+    dens = [_load_model(name, model, c.model_zoo, iter_num, c.noises, x8, c.cnn_batch, dev, c.cnn_dtype, c.miopen_find, c.cnn_backend,
+                        c.cnn_graph, (job.H, job.W)) for name, model in nets]
+    iter_start = getattr(c, 'iter_start', 0)                           # PNP_ADMM_CNC_DnCNN has neither keyword
+    with torch.cuda.device(dev), torch.no_grad(), job.open_engine(torch.cuda.current_stream(dev).cuda_stream) as eng:
+        B, H, W = job.B, job.H, job.W
+        st = SimpleNamespace()
+        st.x, st.z, st.w = _device_state(torch, eng, B, H, W, dev)
+        _resume(torch, st.z, st.w, getattr(c, 'state0', None), dev)
+        for name in scratch:
+            setattr(st, name, torch.empty_like(st.z))
+        tracer = _Tracer(torch, eng, job, dev, traced, c.trace_every, c.tol, iter_start, iter_num)
+        st.z_prev = torch.empty_like(st.z) if keep_z and tracer.on else None
+        for i in range(iter_start, iter_num):                                 # S6:262, S6:491, S3:255
+            if body(i, eng, dens, st, tracer):
+                break
+        torch.cuda.current_stream(dev).synchronize()
+        trace = tracer.result() if tracer.on else None
+        out, psnr1, info = _finish_pnp(torch, job, eng, st.x, extra, c.return_device)
+        if c.return_info:
+            info['z'], info['w'] = st.z.reshape(B, H, W).cpu().numpy(), st.w.reshape(B, H, W).cpu().numpy()
+        if tracer.on:
+            info['trace'] = trace
+    return out, psnr1, info
+
+
+def _cnc_body(alpha, lambda1, reo, b, bank):
+    """-> the iteration PNP_ADMM_CNC_D (S6:262-308) and PNP_ADMM_CNC_DnCNN (S6:491-525) share: s = D1(z), t = their combination,
+    z = D2(t), with z and z_new swapped instead of copied.  One loaded denoiser is both D1 and D2; bank: switch its bank first (S6:289-298)."""
+    def body(i, eng, dens, st, tracer):
+        den1, den2 = dens[0], dens[-1]
+        eng.dc_step(st.z, st.w, st.x, reo)                                    # S6:266-271, S6:495-500
+        if bank:
+            den1.select_bank(i)                                               # S6:289-298
+        den1(st.z, i, out=st.s)                                               # S6:300, S6:517
+        eng.cnc_combine(st.z, st.x, st.w, st.s, st.t, alpha, lambda1, reo, b)    # S6:301, S6:518
+        den2(st.t, i, out=st.z_new)                                           # S6:302, S6:519
+        eng.dual_clamp(st.x, st.z_new, st.w)                                  # S6:305-308, S6:522-525
+        st.z, st.z_new = st.z_new, st.z
+        return tracer.check(i + 1, st.x, st.z, st.z_new, st.w)                # z_new now holds z of the iteration before
+    return body
+
+
 def PNP_ADMM_CNC_D(model_name, mask, noises, images=None, y=None, mask_id=None, testsets='testsets',
                    testset_name='Set1', results='results', save_E=None, device=None, return_info=False,
                    model_zoo='model_zoo', model=None, cnn_batch=None, cnn_dtype=None, miopen_find='auto', cnn_backend='auto', cnn_graph=False, return_device=False,
                    state0=None, iter_start=0, trace_every=0, tol=None, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24, maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02, maps_crop=0.9, **PNP_ADMM_CNC_D_opts):
     """CNC ADMM with a CNN denoiser in place of both soft-thresholds.  Reference: S6:79-351."""
-    import torch
+    call = SimpleNamespace(**locals())                     # the keywords above, by name: the first statement
     alpha = PNP_ADMM_CNC_D_opts.get('alpha', 0.4)          # S6:85-89
     iter_num = PNP_ADMM_CNC_D_opts.get('iter_num', 46)
     lambda1 = PNP_ADMM_CNC_D_opts.get('lambda1', 2.75)
     reo = PNP_ADMM_CNC_D_opts.get('reo', 1)
     b = PNP_ADMM_CNC_D_opts.get('b', 1)
-    device = resolve_device(device)                                    # None: LOCAL_RANK under a process group, else 0
-    dev = torch.device('cuda', device)
-    job = _Job(mask, noises, model_name, 'PNP_ADMM_CNC_D', images, y, mask_id, testsets, testset_name, results,
-               save_E, device, coils=coils, coil_id=coil_id, cg_iters=cg_iters,
-               virtual_coils=virtual_coils, noise_cov=noise_cov, calib=calib, maps_radius=maps_radius,
-               maps_power_iters=maps_power_iters, maps_thresh=maps_thresh, maps_method=maps_method,
-               maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop)
-    den = _load_model(model_name, model, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))   # x8 = False, S6:93
-    with torch.cuda.device(dev), torch.no_grad(), job.open_engine(torch.cuda.current_stream(dev).cuda_stream) as eng:
-        B, H, W = job.B, job.H, job.W
-        x, z, w = _device_state(torch, eng, B, H, W, dev)
-        _resume(torch, z, w, state0, dev)
-        s = torch.empty_like(z)
-        t = torch.empty_like(z)
-        z_new = torch.empty_like(z)
-        tracer = _Tracer(torch, eng, job, dev, trace_every, tol, return_info, iter_start, iter_num)
-        for i in range(iter_start, iter_num):                                 # S6:262
-            eng.dc_step(z, w, x, reo)                                         # S6:266-271
-            den.select_bank(i)                                                # S6:289-298
-            den(z, i, out=s)                                                  # S6:300
-            eng.cnc_combine(z, x, w, s, t, alpha, lambda1, reo, b)            # S6:301
-            den(t, i, out=z_new)                                              # S6:302
-            eng.dual_clamp(x, z_new, w)                                       # S6:305-308
-            z, z_new = z_new, z
-            if tracer.check(i + 1, x, z, z_new, w):                           # z_new now holds z of the iteration before
-                break
-        torch.cuda.current_stream(dev).synchronize()
-        trace = tracer.result() if tracer.on else None
-        out, psnr1, info = _finish_pnp(torch, job, eng, x, 'alpha: ({:.3f}), '.format(alpha), return_device)
-        if return_info:
-            info['z'], info['w'] = z.reshape(B, H, W).cpu().numpy(), w.reshape(B, H, W).cpu().numpy()
-        if tracer.on:
-            info['trace'] = trace
+    out, psnr1, info = _solve_pnp(call, [(model_name, model)], model_name, 'PNP_ADMM_CNC_D', '{:.4f}', iter_num,      # x8 = False, S6:93
+                                  _cnc_body(alpha, lambda1, reo, b, bank=True), ('s', 't', 'z_new'), 'alpha: ({:.3f}), '.format(alpha))
     return (out, psnr1, info) if return_info else (out, psnr1)
 
 
@@ -229,45 +255,16 @@ def PNP_ADMM_CNC_DnCNN(model_name1, model_name2, mask, noises, images=None, y=No
     """Two DnCNN-17 nets: s = D1(z), z = D2(t).  Reference: S6:372-567.
     `faithful_model2_path`: the reference loads model_path1 into BOTH nets (S6:435) although it logs
     path 2; True reproduces that, False loads model_name2's own weights."""
-    import torch
+    call = SimpleNamespace(**locals())                     # the keywords above, by name: the first statement
     alpha = opts.get('alpha', 0.4)
     iter_num = opts.get('iter_num', 46)
     lambda1 = opts.get('lambda1', 2.75)
     reo = opts.get('reo', 1)
     b = opts.get('b', 1)
-    device = resolve_device(device)                                    # None: LOCAL_RANK under a process group, else 0
-    dev = torch.device('cuda', device)
-    job = _Job(mask, noises, model_name1 + '_' + model_name2, 'PNP_ADMM_CNC_DnCNN', images, y, mask_id, testsets,
-               testset_name, results, save_E, device, coils=coils, coil_id=coil_id, cg_iters=cg_iters,
-               virtual_coils=virtual_coils, noise_cov=noise_cov, calib=calib, maps_radius=maps_radius,
-               maps_power_iters=maps_power_iters, maps_thresh=maps_thresh, maps_method=maps_method,
-               maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop)
-    den1 = _load_model(model_name1, model, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))
-    if faithful_model2_path and model2 is None:
-        den2 = _load_model(model_name1, model, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))
-    else:
-        den2 = _load_model(model_name2, model2, model_zoo, iter_num, noises, False, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))
-    with torch.cuda.device(dev), torch.no_grad(), job.open_engine(torch.cuda.current_stream(dev).cuda_stream) as eng:
-        B, H, W = job.B, job.H, job.W
-        x, z, w = _device_state(torch, eng, B, H, W, dev)
-        s, t, z_new = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
-        tracer = _Tracer(torch, eng, job, dev, trace_every, tol, return_info, 0, iter_num)
-        for i in range(iter_num):                                             # S6:491
-            eng.dc_step(z, w, x, reo)                                         # S6:495-500
-            den1(z, i, out=s)                                                 # S6:517
-            eng.cnc_combine(z, x, w, s, t, alpha, lambda1, reo, b)            # S6:518
-            den2(t, i, out=z_new)                                             # S6:519
-            eng.dual_clamp(x, z_new, w)                                       # S6:522-525
-            z, z_new = z_new, z
-            if tracer.check(i + 1, x, z, z_new, w):
-                break
-        torch.cuda.current_stream(dev).synchronize()
-        trace = tracer.result() if tracer.on else None
-        out, psnr1, info = _finish_pnp(torch, job, eng, x, 'alpha: ({:.3f}), '.format(alpha), return_device)
-        if return_info:
-            info['z'], info['w'] = z.reshape(B, H, W).cpu().numpy(), w.reshape(B, H, W).cpu().numpy()
-        if tracer.on:
-            info['trace'] = trace
+    second = (model_name1, model) if faithful_model2_path and model2 is None else (model_name2, model2)
+    out, psnr1, info = _solve_pnp(call, [(model_name1, model), second], model_name1 + '_' + model_name2, 'PNP_ADMM_CNC_DnCNN', '{:.4f}',
+                                  iter_num, _cnc_body(alpha, lambda1, reo, b, bank=False), ('s', 't', 'z_new'),
+                                  'alpha: ({:.3f}), '.format(alpha))
     return (out, psnr1, info) if return_info else (out, psnr1)
 
 
@@ -276,41 +273,21 @@ def PNP_ADMM_L1_D(model_name, mask, noises, images=None, y=None, mask_id=None, t
                   model_zoo='model_zoo', model=None, cnn_batch=None, cnn_dtype=None, miopen_find='auto', cnn_backend='auto', cnn_graph=False, return_device=False,
                   state0=None, iter_start=0, trace_every=0, tol=None, coils=None, coil_id=None, cg_iters=3, virtual_coils=None, noise_cov=None, calib=24, maps_radius=2, maps_power_iters=4, maps_thresh=0.05, maps_method='walsh', maps_kernel=4, maps_sigma=0.02, maps_crop=0.9, **PNP_ADMM_L1_D_opts):
     """L1-ADMM with the CNN as the prox: z = D(x + w).  Reference: S3:77-337."""
-    import torch
+    call = SimpleNamespace(**locals())                     # the keywords above, by name: the first statement
     iter_num = PNP_ADMM_L1_D_opts.get('iter_num', 20)      # S3:83-84
     reo = PNP_ADMM_L1_D_opts.get('reo', 0.04)
-    device = resolve_device(device)                                    # None: LOCAL_RANK under a process group, else 0
-    dev = torch.device('cuda', device)
-    fam = D.family(model_name)
-    x8 = fam in ('drunet', 'ffdnet')                       # x8 = True (S3:87) survives only there (S3:130,142,181)
-    job = _Job(mask, noises, model_name, '_' + model_name + '_PNP_ADMM_L1_D', images, y, mask_id, testsets,
-               testset_name, results, save_E, device, psnr_fmt='{:.2f}', coils=coils, coil_id=coil_id, cg_iters=cg_iters,
-               virtual_coils=virtual_coils, noise_cov=noise_cov, calib=calib, maps_radius=maps_radius,
-               maps_power_iters=maps_power_iters, maps_thresh=maps_thresh, maps_method=maps_method,
-               maps_kernel=maps_kernel, maps_sigma=maps_sigma, maps_crop=maps_crop)            # file name S3:308, PSNR format S3:320
-    den = _load_model(model_name, model, model_zoo, iter_num, noises, x8, cnn_batch, dev, cnn_dtype, miopen_find, cnn_backend, cnn_graph, (job.H, job.W))
-    with torch.cuda.device(dev), torch.no_grad(), job.open_engine(torch.cuda.current_stream(dev).cuda_stream) as eng:
-        B, H, W = job.B, job.H, job.W
-        x, z, w = _device_state(torch, eng, B, H, W, dev)
-        _resume(torch, z, w, state0, dev)
-        t = torch.empty_like(z)
-        tracer = _Tracer(torch, eng, job, dev, trace_every, tol, return_info, iter_start, iter_num)
-        z_prev = torch.empty_like(z) if tracer.on else None                   # this loop updates z in place: a checked iteration keeps the z before it
-        for i in range(iter_start, iter_num):                                 # S3:255
-            eng.dc_step(z, w, x, reo)                                         # S3:259-264
-            den.select_bank(i)
-            eng.add(x, w, t)                                                  # x + w
-            if tracer.wants(i + 1):
-                z_prev.copy_(z)
-            den(t, i, out=z)                                                  # S3:290
-            eng.dual_clamp(x, z, w)                                           # S3:293-296
-            if tracer.check(i + 1, x, z, z_prev, w):
-                break
-        torch.cuda.current_stream(dev).synchronize()
-        trace = tracer.result() if tracer.on else None
-        out, _, info = _finish_pnp(torch, job, eng, x, '', return_device)
-        if return_info:
-            info['z'], info['w'] = z.reshape(B, H, W).cpu().numpy(), w.reshape(B, H, W).cpu().numpy()
-        if tracer.on:
-            info['trace'] = trace
+
+    def body(i, eng, dens, st, tracer):
+        den, = dens
+        eng.dc_step(st.z, st.w, st.x, reo)                                    # S3:259-264
+        den.select_bank(i)
+        eng.add(st.x, st.w, st.t)                                             # x + w
+        if tracer.wants(i + 1):                                               # z is updated in place: a checked iteration keeps the z before it
+            st.z_prev.copy_(st.z)
+        den(st.t, i, out=st.z)                                                # S3:290
+        eng.dual_clamp(st.x, st.z, st.w)                                      # S3:293-296
+        return tracer.check(i + 1, st.x, st.z, st.z_prev, st.w)
+    out, _, info = _solve_pnp(call, [(model_name, model)], model_name, '_' + model_name + '_PNP_ADMM_L1_D', '{:.2f}',     # file name S3:308, PSNR format S3:320
+                              iter_num, body, ('t',), x8_for=('drunet', 'ffdnet'),      # x8 = True (S3:87) survives only there (S3:130,142,181)
+                              keep_z=True)
     return (out, info) if return_info else out

@@ -521,7 +521,9 @@ class Denoiser:
         # takes up to 256 slices of 256 x 256 (fewer for larger slices: the same pixel count): their 64-channel layers are short launches at
         # 64 slices (16 items per workgroup of the wide kernel), and 256 per call measured +5 % on config 3 (profiles/experiments/
         # ab_cnn_batch_r06.txt; DRUNet: +-0, its tensors are four times larger).  Results do not depend on it (bit-equal per slice on the HIP
-        # backends, tests/test_gpu_round2.py).
+        # backends, tests/test_gpu_round2.py) wherever libpnpmri.so runs every layer; DRUNet under 'hip' leaves its wider layers to MIOpen,
+        # whose default kernels do not even repeat bit for bit: float32 round-off apart there, bit-equal only with
+        # torch.backends.cudnn.deterministic set (100 x slower: the caller's choice; tests/test_gpu_denoiser_shapes.py).
         self._cnn_batch_auto = cnn_batch is None
         if cnn_batch is None:
             cnn_batch = 256 if (backend in HIP_BACKENDS and isinstance(model, _PlainStack)) else 64

@@ -435,6 +435,38 @@ int pnp_prox_cnc_dual_cx_f64(pnp_ctx* ctx, const double* x_dev, double* z_dev, d
                              double b);
 int pnp_A_cx(pnp_ctx* ctx, const float* x_dev, float* k_dev);
 
+/* ---- PnP denoisers on complex images (added after ABI 13, additive) -------------------------------
+ * NOT in the reference scripts.  The denoisers are real networks on [n][1][H][W] float planes; these four calls are the glue between
+ * them and the complex state of a context in complex image mode, so that the plug-and-play loops (solvers_pnp.py, image='complex')
+ * run on device pointers with no other elementwise launch.  Float only; B, H, W are the uploaded problem's, n = B H W.  Two ways to
+ * put a complex v through a real network D (mode):
+ *   PNP_CX_DENOISE_MODULUS  one plane of B slices, m = |v| (two rounded squares, a sum, a square root);  d = D(m);
+ *                           result (d / m) v where m != 0 -- one division, then two products; d may be negative and is not clamped --
+ *                           and (d, 0) where m == 0 (both signs of zero, components whose squares underflow).  Phase-equivariant; the
+ *                           network cost of the real loop.  `gain` is checked and not used.
+ *   PNP_CX_DENOISE_PARTS    two planes, plane-major [2 B][1][H][W]: P[0:B] = 0.5 + g Re v, P[B:2B] = 0.5 + g Im v (the second plane
+ *                           starts n floats behind the first);  Q = D(P) in one call on 2 B slices;  result ((Q[0:B] - 0.5) / g,
+ *                           (Q[B:2B] - 0.5) / g).  g = gain, finite and > 0 (also as a float).  The network's noise level acts on the
+ *                           planes, i.e. scaled by 1 / g on the image.  Not phase-equivariant.
+ * pnp_cx_den_in        v = a (+ b when b is not null) -> planes.
+ * pnp_cx_den_out       the network's planes q and the same a (+ b) -> complex z ('parts' does not read a, b; a must still be given).
+ * pnp_cx_den_out_dual  the same join, then w <- w + x - z from the unclipped values, left to right, and x, z, w <- their projection onto
+ *                      the unit disc (the complex counterpart of S6:305-308's clamp(0, 1)): x and w in place, z written.  a, b may be x, w.
+ * pnp_cnc_combine_cx   S6:301 component-wise on interleaved complex arrays, pnp_cnc_combine's expression and order on 2 n floats.
+ * Every operation is one correctly rounded float operation in the order given, no fma: results are bit-stable.
+ * Rules, the first broken one is named:  ctx or a required pointer null: PNP_E_ARG;  real image mode, an fp64 context or no uploaded
+ * problem: PNP_E_STATE;  mode not one of the two, gain not finite or <= 0: PNP_E_ARG;  a complex array or the plane base not 16-byte
+ * aligned: PNP_E_ARG (the kernels move 16 bytes per access; the SECOND plane of 'parts' may lie anywhere: n need not be a multiple of 4).
+ * The real pnp_cnc_combine / pnp_dual_clamp / pnp_add on a complex-mode context answer what they always did. */
+#define PNP_CX_DENOISE_MODULUS 0
+#define PNP_CX_DENOISE_PARTS   1
+int pnp_cx_den_in(pnp_ctx* ctx, const float* a_dev, const float* b_dev, float* planes_dev, int mode, double gain);
+int pnp_cx_den_out(pnp_ctx* ctx, const float* q_dev, const float* a_dev, const float* b_dev, float* z_dev, int mode, double gain);
+int pnp_cx_den_out_dual(pnp_ctx* ctx, const float* q_dev, const float* a_dev, const float* b_dev, float* x_dev, float* z_dev, float* w_dev,
+                        int mode, double gain);
+int pnp_cnc_combine_cx(pnp_ctx* ctx, const float* z_dev, const float* x_dev, const float* w_dev, const float* s_dev, float* t_dev,
+                       double alpha, double lambda1, double reo, double b);
+
 /* ---- coil mixing ahead of the multi-coil solve: noise prewhitening and coil compression (added after ABI 13, additive) ----
  * NOT in the reference scripts.  Array data has 32 to 128 channels, the solve above takes at most 32 and costs time linear in C.  Both
  * standard remedies are ONE operation: a C_out x C_in complex matrix M applied per k-space point to the measurements and per pixel to

@@ -145,6 +145,11 @@ SIGNATURES = {
     'pnp_prox_cnc_dual_cx': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double]),
     'pnp_prox_cnc_dual_cx_f64': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double]),
     'pnp_A_cx': (C.c_int, [ctx_p, _vp, _vp]),
+    # PnP denoisers on complex images (added after ABI 13, additive)
+    'pnp_cx_den_in': (C.c_int, [ctx_p, _vp, _vp, _vp, C.c_int, C.c_double]),
+    'pnp_cx_den_out': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, C.c_int, C.c_double]),
+    'pnp_cx_den_out_dual': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double]),
+    'pnp_cnc_combine_cx': (C.c_int, [ctx_p, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double]),
     # coil mixing ahead of the multi-coil solve: prewhitening and coil compression (added after ABI 13, additive)
     'pnp_coilmix_check': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'pnp_coil_mix': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_size_t]),

@@ -1967,6 +1967,58 @@ int pnp_A_cx(pnp_ctx* c, const float* x, float* k) {        // x: [B][H][W] comp
     return PNP_OK;
 }
 
+// ---- PnP denoisers on complex images: pnp_cx_ops.h, kernels_pnp_cx.hip.  The rules in the header's order: pointers, state, scalars, alignment ----
+
+static int cx_den_rules(pnp_ctx* c, const char* who, bool ptrs_ok, int mode, double gain) {
+    if (!ptrs_ok) return fail(PNP_E_ARG, "%s: null pointer", who);
+    if (!cx_mode(c)) return fail(PNP_E_STATE, "%s: needs complex image mode (pnp_set_image)", who);
+    if (c->f64) return fail(PNP_E_STATE, "%s: not available on an fp64 validation context", who);
+    if (c->B <= 0) return fail(PNP_E_STATE, "%s: no problem uploaded", who);
+    if (mode != PNP_CX_DENOISE_MODULUS && mode != PNP_CX_DENOISE_PARTS)
+        return fail(PNP_E_ARG, "%s: mode must be PNP_CX_DENOISE_MODULUS (0) or PNP_CX_DENOISE_PARTS (1) (got %d)", who, mode);
+    const float g = (float)gain;
+    if (!(gain > 0.0) || !std::isfinite(gain) || !(g > 0.0f) || !std::isfinite(g)) return fail(PNP_E_ARG, "%s: gain must be finite and > 0 (got %g)", who, gain);
+    return PNP_OK;
+}
+static int cx_den_aligned(const char* who, std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* q : ptrs) bits |= (uintptr_t)q;
+    if (bits & 15) return fail(PNP_E_ARG, "%s: the complex arrays and the plane base must be 16-byte aligned", who);
+    return PNP_OK;
+}
+
+int pnp_cx_den_in(pnp_ctx* c, const float* a, const float* b, float* planes, int mode, double gain) {
+    CTX(c);
+    if (int rc = cx_den_rules(c, __func__, a && planes, mode, gain)) return rc;
+    if (int rc = cx_den_aligned(__func__, { a, b, planes })) return rc;
+    HIPCHK(launch_cx_den_in(c->stream, mode, (const float2*)a, (const float2*)b, planes, (float)gain, (size_t)c->B * c->N));
+    return PNP_OK;
+}
+int pnp_cx_den_out(pnp_ctx* c, const float* q, const float* a, const float* b, float* z, int mode, double gain) {
+    CTX(c);
+    if (int rc = cx_den_rules(c, __func__, q && a && z, mode, gain)) return rc;
+    if (int rc = cx_den_aligned(__func__, { q, a, b, z })) return rc;
+    HIPCHK(launch_cx_den_out(c->stream, mode, q, (const float2*)a, (const float2*)b, (float2*)z, (float)gain, (size_t)c->B * c->N));
+    return PNP_OK;
+}
+int pnp_cx_den_out_dual(pnp_ctx* c, const float* q, const float* a, const float* b, float* x, float* z, float* w, int mode, double gain) {
+    CTX(c);
+    if (int rc = cx_den_rules(c, __func__, q && a && x && z && w, mode, gain)) return rc;
+    if (int rc = cx_den_aligned(__func__, { q, a, b, x, z, w })) return rc;
+    HIPCHK(launch_cx_den_out_dual(c->stream, mode, q, (const float2*)a, (const float2*)b, (float2*)x, (float2*)z, (float2*)w, (float)gain,
+                                  (size_t)c->B * c->N));
+    return PNP_OK;
+}
+int pnp_cnc_combine_cx(pnp_ctx* c, const float* z, const float* x, const float* w, const float* s, float* t, double alpha, double lambda1,
+                       double reo, double b) {
+    CTX(c);
+    if (int rc = cx_den_rules(c, __func__, z && x && w && s && t, PNP_CX_DENOISE_MODULUS, 1.0)) return rc;
+    if (int rc = cx_den_aligned(__func__, { z, x, w, s, t })) return rc;
+    HIPCHK(launch_combine(c->stream, z, x, w, s, t, (float)(1.0 - alpha), (float)alpha, (float)(alpha * reo * lambda1 * b),
+                          2 * (size_t)c->B * c->N));                  // component-wise: k_combine on 2 n floats
+    return PNP_OK;
+}
+
 // ---- coil mixing ahead of the multi-coil solve: coilmix_plan.h, kernels_coilmix.hip.  No context: caller-owned device arrays ----
 
 int pnp_coilmix_check(int C_in, int C_out, int Ks, int ncal, int H, int W) {

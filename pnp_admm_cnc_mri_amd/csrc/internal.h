@@ -141,6 +141,14 @@ hipError_t launch_wavelet_prox_cx(hipStream_t s, int wavelet, int levels, bool c
                                   typename CxOf<R>::type* w, typename CxOf<R>::type* coef, const ProxParamsT<R>& p, int B, int H, int W);
 bool wavelet_cx_fits(int wavelet, int levels, bool f64);
 
+// PnP denoisers on complex images (kernels_pnp_cx.hip, pnp_cx_ops.h): n complex floats, interleaved, and the real planes of a CNN -- one
+// plane of n floats (mode CXD_MODULUS) or two, the second n floats behind the first (CXD_PARTS).  a (+ b, or null) is the value the network
+// is asked about; every complex array and the plane base on 16 bytes (hipErrorInvalidValue otherwise)
+hipError_t launch_cx_den_in(hipStream_t s, int mode, const float2* a, const float2* b, float* planes, float g, size_t n);
+hipError_t launch_cx_den_out(hipStream_t s, int mode, const float* q, const float2* a, const float2* b, float2* z, float g, size_t n);
+hipError_t launch_cx_den_out_dual(hipStream_t s, int mode, const float* q, const float2* a, const float2* b, float2* x, float2* z, float2* w,
+                                  float g, size_t n);
+
 // coil mixing ahead of the multi-coil solve (kernels_coilmix.hip, coilmix_plan.h): interleaved complex arrays in R, no context.
 // out[b][j][p] = sum_c m[set_id[b]][j][c] in[b][c][p] (in [B][C_in][N], m [Ks][C_out][C_in], out [B][C_out][N]; set_id null: set 0), and
 // the per-slice Gram matrices of the calibration region, gram [B][C][C] complex double

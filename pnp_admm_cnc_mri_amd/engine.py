@@ -22,6 +22,20 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data)
 
 
+def _is_cx(a):
+    """a complex tensor or array?"""
+    return bool(getattr(getattr(a, 'dtype', None), 'is_complex', False)) or (isinstance(a, np.ndarray) and np.iscomplexobj(a))
+
+
+def _cx_denoise(mode):
+    """the PNP_CX_DENOISE_* code of 'modulus' / 'parts'; an integer goes through as it is (the library names a bad one)"""
+    if isinstance(mode, str):
+        if mode not in CX_DENOISE:
+            raise ValueError("cx_denoise must be 'modulus' or 'parts' (got %r)" % (mode,))
+        return CX_DENOISE[mode]
+    return int(mode)
+
+
 def _host(a, dtype):
     a = np.ascontiguousarray(a, dtype=dtype)
     return a
@@ -29,6 +43,7 @@ def _host(a, dtype):
 
 WAVELETS = {None: 0, 'haar': 1, 'db2': 2, 'db4': 3}                                    # PNP_WAVELET_* of include/pnp_mri.h
 IMAGE_MODES = {'real': 0, 'complex': 1}                                                # PNP_IMAGE_* of include/pnp_mri.h
+CX_DENOISE = {'modulus': 0, 'parts': 1}                                                # PNP_CX_DENOISE_* of include/pnp_mri.h
 
 
 def check_sparsity(wavelet, levels, H, W):
@@ -552,8 +567,22 @@ class Engine:
         _lib.check(fn(self._ctx, _ptr(x), _ptr(z), _ptr(w), float(alpha), float(lambda1), float(reo), float(b)))
 
     def cnc_combine(self, z, x, w, s, t, alpha, lambda1, reo, b):
-        _lib.check(self._L.pnp_cnc_combine(self._ctx, _ptr(z), _ptr(x), _ptr(w), _ptr(s), _ptr(t), float(alpha),
-                                           float(lambda1), float(reo), float(b)))
+        """S6:301; complex tensors: the same expression component-wise (pnp_cnc_combine_cx)"""
+        fn = self._L.pnp_cnc_combine_cx if _is_cx(z) else self._L.pnp_cnc_combine
+        _lib.check(fn(self._ctx, _ptr(z), _ptr(x), _ptr(w), _ptr(s), _ptr(t), float(alpha), float(lambda1), float(reo), float(b)))
+
+    # A real denoiser on a complex state (include/pnp_mri.h, "PnP denoisers on complex images"): complex64 device tensors [B,H,W] and the
+    # float32 planes of the network -- [B,1,H,W] for mode='modulus', plane-major [2B,1,H,W] for 'parts'.  a (+ b when given) is the value
+    # the network is asked about; gain: the g of 'parts'
+    def cx_den_in(self, a, b, planes, mode='modulus', gain=0.5):
+        _lib.check(self._L.pnp_cx_den_in(self._ctx, _ptr(a), _ptr(b), _ptr(planes), _cx_denoise(mode), float(gain)))
+
+    def cx_den_out(self, q, a, b, z, mode='modulus', gain=0.5):
+        _lib.check(self._L.pnp_cx_den_out(self._ctx, _ptr(q), _ptr(a), _ptr(b), _ptr(z), _cx_denoise(mode), float(gain)))
+
+    def cx_den_out_dual(self, q, a, b, x, z, w, mode='modulus', gain=0.5):
+        """the join of cx_den_out, then w <- w + x - z and the projection of x, z, w onto the unit disc: x, w in place, z written"""
+        _lib.check(self._L.pnp_cx_den_out_dual(self._ctx, _ptr(q), _ptr(a), _ptr(b), _ptr(x), _ptr(z), _ptr(w), _cx_denoise(mode), float(gain)))
 
     def add(self, a, b, out):
         _lib.check(self._L.pnp_add(self._ctx, _ptr(a), _ptr(b), _ptr(out)))

@@ -119,7 +119,10 @@ def solve_sharded(solver, mask, noises, images=None, y=None, mask_id=None, dst=0
     # hand back ONE [b,H,W] device tensor (no 22-slot list of host arrays), RCCL gathers it as it is, and the only device-to-host
     # copy of the job is the root's, of the gathered result (config 4: 128 MiB per rank stay off PCIe in both directions).
     tdt = torch.float64 if real is np.float64 else torch.float32
-    if kw.get('image') == 'complex':                      # ADMM_L1 / ADMM_CNC with image='complex': the gathered array is complex
+    if _bound(solver, 'image') == 'complex' and kw.get('image') != 'complex':        # known before anything runs
+        raise TypeError("solve_sharded: image='complex' is bound into the solver with functools.partial but is not among solve_sharded's "
+                        'keywords (every rank, also one with an empty shard, must know the dtype of the gather): pass it there')
+    if kw.get('image') == 'complex':                      # all five solvers with image='complex': the gathered array is complex
         real = np.complex128 if real is np.float64 else np.complex64
         tdt = torch.complex128 if real is np.complex128 else torch.complex64
     if hi > lo:
@@ -161,6 +164,16 @@ def collective_device(x_local, backend, device=None):
         return x_local.device
     from .solvers import resolve_device
     return torch.device('cuda', resolve_device(device))
+
+
+def _bound(fn, name):
+    """the value a chain of functools.partial binds to the keyword `name` (the outermost wins), None when none does"""
+    import functools
+    while isinstance(fn, functools.partial):
+        if name in fn.keywords:
+            return fn.keywords[name]
+        fn = fn.func
+    return None
 
 
 def _accepts(fn, name):

@@ -74,14 +74,14 @@ bypass the file system through the extra keyword arguments
               largest; maps_radius is not used.  C maps_kernel^2 <= 128 (of the MIXED channels: virtual_coils= first).  info['coil_maps']
               gains method, kernel, sigma, crop and rank (per slice).  The default, 'walsh', is bit for bit what it was
 
-    image='real'   (ADMM_L1 and ADMM_CNC only) 'complex': the reconstruction keeps the image phase (include/pnp_mri.h, "complex-valued
+    image='real'   (all five solvers) 'complex': the reconstruction keeps the image phase (include/pnp_mri.h, "complex-valued
               images"): x, z, w are complex, z0 = A^H y without the modulus, the x-step returns x^ itself instead of |Re x^|, and the prox
               thresholds the MODULUS of a pixel (or, with transform=, of a wavelet coefficient of the complex image).  Needs coils= (an
               array or 'estimate', with or without virtual_coils= / noise_cov=) and measured y=; spin=, trace_every= and tol= are refused
               with it (ValueError before an engine is opened).  `out` then holds complex128 [H,W] arrays (return_device=True: one complex
               tensor), PSNR / SSIM / RE are taken on |x| when images= is given, info['image'] = 'complex'.  NOT in the reference scripts,
               which reconstruct a real PNG; 'real' (the default) calls nothing new and is bit for bit what it was.  One extra log line.
-              The three PnP entry points do not have the keyword: their denoisers are real
+              The three PnP entry points put their real denoiser on the complex image by cx_denoise= / cx_gain= (solvers_pnp.py)
 
 The PnP entry points (PNP_ADMM_L1_D, PNP_ADMM_CNC_D, PNP_ADMM_CNC_DnCNN) live in solvers_pnp.py.
 """

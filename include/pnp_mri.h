@@ -435,6 +435,49 @@ int pnp_prox_cnc_dual_cx_f64(pnp_ctx* ctx, const double* x_dev, double* z_dev, d
                              double b);
 int pnp_A_cx(pnp_ctx* ctx, const float* x_dev, float* k_dev);
 
+/* ---- temporal sparsity (added after ABI 13, additive) ---------------------------------------------
+ * Everything above treats the slices of a batch as strangers.  A dynamic series (cine, perfusion) is a batch whose frames are nearly
+ * the same image; this regulariser penalises the coefficients of a unitary DFT along time of every pixel's series (k-t sparsity).  NOT in
+ * the reference scripts.  Opt-in per context (pnp_set_temporal); without the setting -- the default -- nothing here is called and every
+ * result is bit for bit what it was.
+ * The batch is S series of T = `frames` consecutive slices: slice b = s T + t.  For every series and pixel, with u = x + w:
+ *   U_k = T^(-1/2) sum_t u_t e^(-2 pi i k t / T);   the penalty is thr sum_k |U_k| over all T coefficients; with keep_dc (the default)
+ *   k = 0 carries none, as the LL band of the wavelet prox never does.
+ *   L1   Z_k = csoft(U_k, thr);   z+ = F^H Z,  z+_t = T^(-1/2) sum_k Z_k e^(+2 pi i k t / T);   w+ = u - z+.
+ *   CNC  z^ = F z;  t^_k = c1 z^_k + c2 U_k + c3 cclip(z^_k, ib), component-wise, each component fma(c1, z^, fma(c2, U, c3 * clip));
+ *        Z_k = csoft(t^_k, thr);  z+ and w+ as above.   thr, c1, c2, c3, ib are the scalars of the pixel-domain step.
+ *   An unpenalised coefficient is Z_0 = U_0 -- NOT t^_0.
+ * Real images: only k = 0 .. floor(T / 2) are formed and
+ *   z+_t = T^(-1/2) [Z_0 + 2 sum_{0<k<T/2} Re(Z_k e^(+2 pi i k t / T)) + (T even) Z_(T/2) (-1)^t],
+ *   so z stays exactly real; the real coefficients (0 and, T even, T / 2) take soft / clip on their real part.
+ * Complex images (pnp_set_image): the full complex spectrum, csoft / cclip as defined above.
+ * Arithmetic: direct sums, t ascending (analysis) and k ascending (synthesis); every product is one fma onto the running sum, which
+ *   starts at 0 -- analysis: re = fma(u, c, re), im = fma(-u, s, im) for real u, and re = fma(u.re, c, re), re = fma(u.im, s, re),
+ *   im = fma(u.im, c, im), im = fma(-u.re, s, im) for complex u; synthesis: re = fma(Z.re, c, re), re = fma(-Z.im, s, re) (and, complex
+ *   images, im = fma(Z.re, s, im), im = fma(Z.im, c, im)); real images end with v = fma(2, re, Z_0) [+- Z_(T/2)].  T^(-1/2), rounded
+ *   once to the context's precision, multiplies every finished sum once.  (c, s) = (cos, sin)(2 pi j / T), j = (k t) mod T, from a table
+ *   of T entries computed in double on the host and rounded once.  2 <= T <= 64, any T (primes included).
+ * One launch per prox, in both precisions, moving the pixel prox's bytes.  pnp_temporal_check: the argument rules without a context or
+ * a device -- frames outside 2..64: PNP_E_ARG ("temporal: frames must be 2..64 (got %d)"); B < 1 or not a multiple of frames:
+ * PNP_E_STATE ("temporal: the batch of %d slices is not a whole number of series of %d frames"). */
+int pnp_temporal_check(int frames, int B);
+/* frames = 0 clears the setting (keep_dc is not read); frames outside 2..64: PNP_E_ARG.  The setting excludes a wavelet and a spin table,
+ * in either order of setting: pnp_set_temporal on a context with a wavelet set, and pnp_set_sparsity (other than PNP_WAVELET_NONE) or
+ * pnp_set_spin on a context with frames set, return PNP_E_STATE.  It belongs to the context and survives uploads, pnp_set_coils and
+ * pnp_set_image.  With frames set
+ *   - pnp_admm_l1_run, pnp_admm_cnc_run and their _traced forms run, per iteration, the context's own data-consistency step (three
+ *     launches, as with a wavelet) and ONE prox launch: four launches per iteration, which pnp_get_plan / pnp_kernels_per_iteration
+ *     report.  The state stays in natural order, the slice-resident path is never taken (pnp_path_name never says "slice": it says
+ *     "fused", or "generic" where the shape has no two-launch engine), a run cut into
+ *     calls is bit-equal to one call.  On a coil context the x-step is followed by the same launch (5 + 5 cg_iters + 1), in real and in
+ *     complex image mode.
+ *   - pnp_prox_l1_dual, pnp_prox_cnc_dual and their _cx forms apply the temporal step to the uploaded problem's B slices (complex arrays
+ *     aligned to one complex value).
+ *   - a loop or prox call on a batch that is not a multiple of frames returns PNP_E_STATE with pnp_temporal_check's message. */
+int pnp_set_temporal(pnp_ctx* ctx, int frames, int keep_dc);
+/* frames = 0 without a setting (keep_dc then reads 1); either pointer may be null */
+int pnp_get_temporal(pnp_ctx* ctx, int* frames, int* keep_dc);
+
 /* ---- PnP denoisers on complex images (added after ABI 13, additive) -------------------------------
  * NOT in the reference scripts.  The denoisers are real networks on [n][1][H][W] float planes; these four calls are the glue between
  * them and the complex state of a context in complex image mode, so that the plug-and-play loops (solvers_pnp.py, image='complex')

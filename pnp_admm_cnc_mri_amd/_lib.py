@@ -115,6 +115,10 @@ SIGNATURES = {
     'pnp_set_spin': (C.c_int, [ctx_p, C.POINTER(C.c_int32), C.c_int, C.c_int]),
     'pnp_get_spin': (C.c_int, [ctx_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'pnp_set_spin_cursor': (C.c_int, [ctx_p, C.c_int]),
+    # temporal sparsity (added after ABI 13, additive)
+    'pnp_temporal_check': (C.c_int, [C.c_int, C.c_int]),
+    'pnp_set_temporal': (C.c_int, [ctx_p, C.c_int, C.c_int]),
+    'pnp_get_temporal': (C.c_int, [ctx_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'pnp_dwt2_shifted': (C.c_int, [ctx_p, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     'pnp_dwt2_shifted_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     # multi-coil (SENSE) data consistency (added after ABI 13, additive)

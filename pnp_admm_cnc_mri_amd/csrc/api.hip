@@ -3,6 +3,7 @@
 #include "../../include/pnp_mri.h"
 #include "internal.h"
 #include "wavelet_plan.h"
+#include "temporal_plan.h"
 #include "coil_plan.h"
 #include "coilmix_plan.h"
 #include "coilmaps_plan.h"
@@ -156,6 +157,9 @@ struct pnp_ctx {
     std::vector<int32_t> spin;        // pnp_set_spin: shifts[n][2] of the wavelet prox (empty: none) ...
     int spin_k = 1, spin_p = 0;       // ... per_prox of them a step, and the cursor: prox steps since it was last set
     void* wv_acc = nullptr;           // [Bmax][H][W] real: the sum of the shifts' z+ (by the first per_prox > 1)
+    int tp_frames = 0;                // pnp_set_temporal: the prox acts on the temporal DFT of series of this many slices (0: none) ...
+    bool tp_keep_dc = true;           // ... with coefficient 0 unpenalised
+    void* tp_tw = nullptr;            // the twiddle matrix of tp_frames in the context's precision (tp_twiddle_matrix), room for TP_MAX_FRAMES
     Coils coils;
     void* maps_scratch = nullptr;     // the coil-map estimators' array, laid out by the call that runs (coilmaps_scratch, espirit_scratch); on first use
     size_t maps_bytes = 0;
@@ -835,10 +839,16 @@ template <typename R> static int wavelet_prox_step(pnp_ctx* c, bool cnc, const R
 }
 
 // One z / w step of the loops and the step-wise calls, on real or (CX) complex arrays in natural order: the pixel prox (one launch) or the
-// wavelet prox of the context's sparsity setting (two; in real mode by the spin schedule).  Which launcher serves which type ends here.
+// wavelet prox of the context's sparsity setting (two; in real mode by the spin schedule), or the temporal prox of pnp_set_temporal (one).
+// Which launcher serves which type ends here.
 template <typename R, bool CX>
 static int prox_step(pnp_ctx* c, bool cnc, const CoilState<R, CX>* x, CoilState<R, CX>* z, CoilState<R, CX>* w, const ProxParamsT<R>& pp) {
     const size_t n = (size_t)c->B * c->N;
+    if (c->tp_frames) {
+        if (int rc = pnp_temporal_check(c->tp_frames, c->B)) return rc;
+        HIPCHK((launch_temporal_prox<R, CX>(c->stream, cnc, x, z, w, (const R*)c->tp_tw, pp, c->tp_frames, c->tp_keep_dc, c->B, c->N)));
+        return PNP_OK;
+    }
     if constexpr (CX) {
         if (c->wavelet == WV_NONE) {
             HIPCHK(launch_prox_cx<R>(c->stream, cnc, x, z, w, pp, n));
@@ -875,10 +885,12 @@ template <typename R> static int dwt2_any(pnp_ctx* c, const char* who, const R* 
     return PNP_OK;
 }
 
-// The loops with a wavelet set: per iteration the data-consistency step and the two prox launches, on the state in natural order.  Every
-// iteration stands alone -- nothing but x, z, w passes from one to the next -- so a run cut anywhere is bit-equal to the uncut run.
+// The loops with a wavelet or frames set (natural_loop): per iteration the data-consistency step and the prox step's launches, on the
+// state in natural order.  Every iteration stands alone -- nothing but x, z, w passes from one to the next -- so a run cut anywhere is
+// bit-equal to the uncut run.
+static bool natural_loop(const pnp_ctx* c) { return c->wavelet != WV_NONE || c->tp_frames != 0; }
 template <typename R>
-static int run_wavelet_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
+static int run_natural_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
     const Bufs<R> b = bufs<R>(c);
     if (int rc = state_order<R>(c, false)) return rc;
     const R cdc = dc_coeff<R>(reo);
@@ -903,18 +915,20 @@ template <typename R, bool CX> static int dc_step(pnp_ctx* c, const char* who, c
     }
     return coil_xstep<R, CX>(c, (const T*)z, (const T*)w, (T*)x, reo);
 }
-// pnp_prox_*_dual[_cx]: one prox step.  Complex arrays: 16-byte aligned for the pixel prox, 2 sizeof(R) for the wavelet prox; with a wavelet
+// pnp_prox_*_dual[_cx]: one prox step.  Complex arrays: 16-byte aligned for the pixel prox, 2 sizeof(R) for the wavelet and the temporal prox; with a wavelet
 // set the three arrays must not overlap.
 template <typename R, bool CX> static int prox_dual(pnp_ctx* c, const char* who, bool cnc, const R* x, R* z, R* w, const ProxParamsT<R>& pp) {
     using T = CoilState<R, CX>;
     if (!x || !z || !w) return fail(PNP_E_ARG, "%s: null pointer", who);
-    if constexpr (CX) if (int rc = cx_aligned<R>(who, x, z, w, c->wavelet == WV_NONE ? 16 : 2 * sizeof(R))) return rc;
+    if constexpr (CX) if (int rc = cx_aligned<R>(who, x, z, w, (c->wavelet == WV_NONE && !c->tp_frames) ? 16 : 2 * sizeof(R))) return rc;
     if (c->wavelet != WV_NONE) {
         const size_t bytes = (size_t)c->B * c->N * sizeof(T);
         const char *px = (const char*)x, *pz = (const char*)z, *pw = (const char*)w;
         if ((px < pz + bytes && pz < px + bytes) || (px < pw + bytes && pw < px + bytes) || (pz < pw + bytes && pw < pz + bytes))
             return fail(PNP_E_ARG, "%s: x, z and w must not overlap with a wavelet set (tiles read their neighbours' halo)", who);
     }
+    // no overlap rule with frames set: a workgroup of the temporal kernel loads its whole run of x, z, w before it stores z+ and w+, and runs
+    // are disjoint, so x, z, w that alias one another (the pixel prox's in-place use) are safe
     return prox_step<R, CX>(c, cnc, (const T*)x, (T*)z, (T*)w, pp);
 }
 
@@ -934,8 +948,9 @@ static int run_coil_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& 
 
 template <typename R>
 static int run_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
+    if (c->tp_frames) if (int rc = pnp_temporal_check(c->tp_frames, c->B)) return rc;      // before the first x-step
     if (c->coils.C > 0) return cx_mode(c) ? run_coil_loop<R, true>(c, iters, cnc, pp, reo) : run_coil_loop<R, false>(c, iters, cnc, pp, reo);
-    if (c->wavelet != WV_NONE && iters > 0) return run_wavelet_loop<R>(c, iters, cnc, pp, reo);
+    if (natural_loop(c) && iters > 0) return run_natural_loop<R>(c, iters, cnc, pp, reo);
     const Bufs<R> b = bufs<R>(c);
     const Path path = iters > 0 ? loop_path(c) : Path::generic;
     if (int rc = ensure_tables(c, path)) return rc;
@@ -1106,8 +1121,9 @@ static int run_traced(pnp_ctx* c, const char* who, int iters, bool cnc, const Pr
     }
     const TraceRun r{iters, every, checks, tol, gt};
     int done = 0, nrows = 0;
-    // with a wavelet set every iteration is a launch boundary with the state in natural order: the legs below, on run_loop's wavelet loop
-    const Path path = c->wavelet != WV_NONE ? Path::generic : loop_path(c);
+    // with a wavelet or frames set every iteration is a launch boundary with the state in natural order: the legs below, on run_loop's
+    // natural-order loop
+    const Path path = natural_loop(c) ? Path::generic : loop_path(c);
     if (path == Path::fused) {
         if (int rc = ensure_tables(c, Path::fused)) return rc;
         if (int rc = state_order<R>(c, false)) return rc;
@@ -1183,6 +1199,7 @@ static LoopPlan loop_plan(const pnp_ctx* c) {
     const int spin_extra = c->wavelet != WV_NONE ? 2 * (spin_per_prox(c) - 1) : 0;
     if (c->coils.C > 0) return {1, c->B, coil_iteration_launches(c->coils.cg_iters, c->wavelet != WV_NONE) + spin_extra, false, 1, c->B};
     if (c->wavelet != WV_NONE) return {1, c->B, 5 + spin_extra, false, 1, c->B};   // the data-consistency step (three launches on every path) + the prox launches
+    if (c->tp_frames) return {1, c->B, 4, false, 1, c->B};                         // ... + the one launch of the temporal prox
     switch (loop_path(c)) {
     case Path::generic: break;
     case Path::slice:   return plan_slice(c->B, c->sched);         // one launch per RUN: the iterations are a loop inside it
@@ -1394,7 +1411,7 @@ int pnp_ctx_destroy(pnp_ctx* c) {
     coils_free(c);
     anysize_destroy(c->any);
     void* ptrs[] = {c->y, c->work, c->z, c->w, c->x, c->mask_bank, c->mask_id, c->gt, c->acc, c->stage, c->ssim_part,
-                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc, c->wv_coef, c->wv_acc, c->maps_scratch};
+                    c->trace.partial, c->trace.counter, c->trace.rows, c->trace.zprev, c->trace.zc, c->trace.wc, c->wv_coef, c->wv_acc, c->tp_tw, c->maps_scratch};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1713,7 +1730,7 @@ const char* pnp_path_name(pnp_ctx* c) {
     if (c->coils.C > 0) return "coils";
     switch (loop_path(c)) {
     case Path::generic: return "generic";
-    case Path::slice:   return c->wavelet != WV_NONE ? "fused" : "slice";      // with a wavelet set the loops never run slice-resident
+    case Path::slice:   return natural_loop(c) ? "fused" : "slice";            // with a wavelet or frames set the loops never run slice-resident
     case Path::fused:   return "fused";
     }
     return "generic";
@@ -1734,6 +1751,8 @@ int pnp_sparsity_check(int wavelet, int levels, int H, int W) {
 int pnp_set_sparsity(pnp_ctx* c, int wavelet, int levels) {
     if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
     if (int rc = pnp_sparsity_check(wavelet, levels, c->H, c->W)) return rc;         // before any device work
+    if (wavelet != PNP_WAVELET_NONE && c->tp_frames)
+        return fail(PNP_E_STATE, "%s: a wavelet does not run with temporal sparsity (clear it with pnp_set_temporal(ctx, 0, 1))", __func__);
     if (cx_mode(c)) if (int rc = pnp_image_check(PNP_IMAGE_COMPLEX, wavelet, levels, c->f64)) return rc;
     CTX(c);
     if (wavelet != PNP_WAVELET_NONE) if (int rc = wavelet_scratch(c)) return rc;
@@ -1777,6 +1796,7 @@ int pnp_set_spin(pnp_ctx* c, const int32_t* shifts, int n, int per_prox) {
     if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
     if (n == 0) { c->spin.clear(); c->spin_k = 1; c->spin_p = 0; return PNP_OK; }
     NOT_IN_COMPLEX(c);
+    if (c->tp_frames) return fail(PNP_E_STATE, "%s: a spin table does not run with temporal sparsity (clear it with pnp_set_temporal(ctx, 0, 1))", __func__);
     if (c->wavelet == WV_NONE) return fail(PNP_E_STATE, "%s: no wavelet set (pnp_set_sparsity)", __func__);
     if (int rc = pnp_spin_check(c->wv_levels, shifts, n, per_prox)) return rc;          // before any device work
     CTX(c);
@@ -1800,6 +1820,46 @@ int pnp_set_spin_cursor(pnp_ctx* c, int cursor) {
     if (c->spin.empty()) return fail(PNP_E_STATE, "%s: no spin setting (pnp_set_spin)", __func__);
     if (cursor < 0) return fail(PNP_E_ARG, "%s: cursor must be >= 0 (got %d)", __func__, cursor);
     c->spin_p = cursor;
+    return PNP_OK;
+}
+
+// ---- temporal sparsity (temporal_plan.h, kernels_temporal.hip) ----
+
+int pnp_temporal_check(int frames, int B) {
+    switch (tp_check(frames, B)) {
+    case TP_OK:         return PNP_OK;
+    case TP_BAD_FRAMES: return fail(PNP_E_ARG, "temporal: frames must be %d..%d (got %d)", TP_MIN_FRAMES, TP_MAX_FRAMES, frames);
+    case TP_BAD_BATCH:  return fail(PNP_E_STATE, "temporal: the batch of %d slices is not a whole number of series of %d frames", B, frames);
+    }
+    return fail(PNP_E_ARG, "temporal: invalid setting");
+}
+
+int pnp_set_temporal(pnp_ctx* c, int frames, int keep_dc) {
+    CTX(c);
+    if (frames == 0) { c->tp_frames = 0; c->tp_keep_dc = true; return PNP_OK; }
+    if (int rc = pnp_temporal_check(frames, frames)) return rc;                       // the range alone, before any device work
+    if (c->wavelet != WV_NONE)
+        return fail(PNP_E_STATE, "%s: temporal sparsity does not run with a wavelet%s (clear it with pnp_set_sparsity(ctx, PNP_WAVELET_NONE, 0))",
+                    __func__, c->spin.empty() ? "" : " and its spin table");
+    const size_t real = c->f64 ? sizeof(double) : sizeof(float);
+    if (!c->tp_tw)
+        if (int rc = alloc_or_fail(&c->tp_tw, TP_MATRIX_MAX * real, __func__, "twiddle matrix", "frames=%d", frames)) return rc;
+    const size_t count = 2 * (size_t)frames * frames;
+    std::vector<double> tw64(c->f64 ? count : 0);
+    std::vector<float> tw32(c->f64 ? 0 : count);
+    if (c->f64) tp_twiddle_matrix<double>(frames, tw64.data()); else tp_twiddle_matrix<float>(frames, tw32.data());
+    c->tp_frames = 0;                                                                   // no setting if the copy fails
+    // copy_in of a host array synchronises, so the vectors may die at the end of this call
+    if (int rc = copy_in(c, c->tp_tw, c->f64 ? (const void*)tw64.data() : (const void*)tw32.data(), count * real, 0)) return rc;
+    c->tp_frames = frames;
+    c->tp_keep_dc = keep_dc != 0;
+    return PNP_OK;
+}
+
+int pnp_get_temporal(pnp_ctx* c, int* frames, int* keep_dc) {
+    CTX(c);
+    if (frames) *frames = c->tp_frames;
+    if (keep_dc) *keep_dc = c->tp_keep_dc ? 1 : 0;
     return PNP_OK;
 }
 

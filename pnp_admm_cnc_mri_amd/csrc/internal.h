@@ -207,6 +207,13 @@ template <typename R> hipError_t launch_wavelet_prox(hipStream_t s, int wavelet,
                                                      const ProxParamsT<R>& p, int B, int H, int W, const int* shifts = nullptr, int K = 1,
                                                      R* acc = nullptr);
 
+// temporal sparsity (kernels_temporal.hip, temporal_plan.h): the prox on the DFT along the frames of B / frames series of `frames` slices
+// of N values, real or (CX) complex, in place on z and w; one launch.  e: the context's twiddle matrix in R (tp_twiddle_matrix).
+// The accesses are as wide as N and the arrays' alignment allow (tp_group); an array not aligned to one value is hipErrorInvalidValue.
+template <typename R, bool CX>
+hipError_t launch_temporal_prox(hipStream_t s, bool cnc, const CoilState<R, CX>* x, CoilState<R, CX>* z, CoilState<R, CX>* w, const R* e,
+                                const ProxParamsT<R>& p, int frames, bool keep_dc, int B, size_t N);
+
 // calibration (pnp_calibrate_stream): the slice-resident loop's access shape without its arithmetic, `passes` passes over `slices` slices of 256 KiB
 hipError_t launch_calibrate_stream(hipStream_t s, float* z, float* w, const float* y, int slices, int passes);
 // The denoisers' conv layers.  Shape rules, tiles / items and the persistent grids of every launcher below: conv_plan.h -- a launcher

@@ -88,6 +88,17 @@ def check_spin(shifts, levels, per_prox=1):
     return t
 
 
+def check_temporal(frames, B=None):
+    """ValueError unless `frames` is a valid series length (2..64) and -- when B is given -- a batch of B slices is a whole number of
+    series (pnp_temporal_check: the library's own rule, no context and no device needed).  -> frames as an int."""
+    if isinstance(frames, bool) or int(frames) != frames:
+        raise ValueError('frames must be an integer (got %r)' % (frames,))
+    L = _lib.lib()
+    if L.pnp_temporal_check(int(frames), int(frames) if B is None else int(B)) != 0:
+        raise ValueError(L.pnp_last_error().decode('utf-8', 'replace'))
+    return int(frames)
+
+
 def spin_table(spin, levels, iters, average=1, seed=0):
     """The cycle-spinning table of a run of `iters` iterations that averages `average` shifts per prox (Engine.set_spin(table, average)):
     'random' -> np.random.default_rng(seed).integers(0, 2**levels, size=(iters * average, 2)); an array-like [n, 2] is passed through
@@ -244,6 +255,22 @@ class Engine:
     @spin_cursor.setter
     def spin_cursor(self, cursor):
         _lib.check(self._L.pnp_set_spin_cursor(self._ctx, int(cursor)))
+
+    def set_temporal(self, frames=None, keep_dc=True):
+        """Temporal sparsity (pnp_set_temporal): the batch is series of `frames` consecutive slices (2..64), and the penalty of admm_l1 /
+        admm_cnc / prox_*_dual acts on the coefficients of a unitary DFT along time of every pixel's series; keep_dc: coefficient 0
+        carries no penalty.  None clears.  Not together with set_sparsity / set_spin; survives set_coils and set_image_mode."""
+        if frames is None:
+            _lib.check(self._L.pnp_set_temporal(self._ctx, 0, 1))
+            return
+        _lib.check(self._L.pnp_set_temporal(self._ctx, check_temporal(frames), 1 if keep_dc else 0))
+
+    @property
+    def temporal(self):
+        """(frames, keep_dc) of set_temporal (pnp_get_temporal); (None, True) without one."""
+        f, k = C.c_int(0), C.c_int(0)
+        _lib.check(self._L.pnp_get_temporal(self._ctx, C.byref(f), C.byref(k)))
+        return (f.value or None), bool(k.value)
 
     def set_coils(self, sens, cg_iters=3):
         """Multi-coil (SENSE) data consistency (pnp_set_coils): sens [C,H,W] or a bank [Ks,C,H,W] of complex sensitivity maps (host array

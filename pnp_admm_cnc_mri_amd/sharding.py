@@ -98,6 +98,17 @@ def solve_sharded(solver, mask, noises, images=None, y=None, mask_id=None, dst=0
         raise ValueError('solve_sharded needs images= or y= (file-based inputs cannot be sharded by index)')
     B_total = len(src)
     grouped = dist.is_available() and dist.is_initialized()
+    frames = solver_kwargs.get('frames')
+    if frames is not None:
+        # temporal sparsity: a series is `frames` consecutive slices and the blocks below would cut one in two.  Every rank judges every
+        # shard -- its own or not, before any work -- so all of them raise the same error and none is left waiting in the gather
+        from .engine import check_temporal
+        check_temporal(frames)
+        sizes = shard_sizes(B_total, dist.get_world_size(group) if grouped else 1)
+        if any(n % int(frames) for n in sizes):
+            raise ValueError('solve_sharded: frames=%d does not divide the shards %s of %d slices over %d ranks: a series would be cut in two '
+                             '(series-aligned splitting is not built; choose a batch of ranks x k x frames slices)'
+                             % (int(frames), sizes, B_total, len(sizes)))
     if not grouped:
         lo, hi = 0, B_total
     else:

@@ -38,6 +38,12 @@ bypass the file system through the extra keyword arguments
               np.random.default_rng(spin_seed) (engine.spin_table); or an array [n, 2] of shifts, used in order and wrapping.
               spin_average = K (1..16): every prox averages K consecutive shifts of the table, at 2 K launches instead of 2.  NOT in
               the reference scripts; None (the default) calls nothing new.  One extra log line names the table and K
+    frames=None, temporal_keep_dc=True   (ADMM_L1 and ADMM_CNC only; taken by name from the options: not in the signatures, which are
+              pinned as they were) temporal sparsity for a dynamic series: the batch is series of `frames` consecutive slices (2..64, B a
+              multiple of it) and the penalty acts on the coefficients of a unitary DFT along time of every pixel's series, coefficient 0
+              unpenalised unless temporal_keep_dc=False (include/pnp_mri.h, "temporal sparsity").  One prox launch per iteration; with
+              coils= and image='complex' as well; not with transform= / spin=.  NOT in the reference scripts; None (the default) calls
+              nothing new.  One extra log line names the series length; info['frames'] is set
 
     coils=None, coil_id=None, cg_iters=3   (all five solvers) multi-coil (SENSE) data consistency: coils [C,H,W] complex sensitivity maps,
               or a bank [Ks,C,H,W] with coil_id [B] picking each slice's set.  The forward model becomes y_c = mask . fft2(S_c . x):
@@ -94,7 +100,7 @@ import numpy as np
 
 from . import coilmaps, coilmix, imageio
 from ._lib import PnpError
-from .engine import Engine, check_coils, check_image, check_sparsity, spin_table
+from .engine import Engine, check_coils, check_image, check_sparsity, check_temporal, spin_table
 
 # CLI presets of the reference scripts (positional order differs per script!)
 PRESETS = {
@@ -299,11 +305,11 @@ class _Job:
             eng.set_image_mode('complex')
             self.say('complex-valued image: the phase is kept, the prox thresholds the modulus (not in the reference scripts)')
 
-    def open_engine(self, stream=None, transform=None, levels=3, spin=None, spin_average=1):
+    def open_engine(self, stream=None, transform=None, levels=3, spin=None, spin_average=1, frames=None, keep_dc=True):
         """stream: HIP stream handle every engine call is ordered on (PnP: torch's current stream),
         set BEFORE the first kernel so upload / synthesis / init and the loop share one queue.
         transform / levels: Engine.set_sparsity (ADMM_L1 / ADMM_CNC); spin / spin_average: the table of spin_request and its group
-        size, Engine.set_spin."""
+        size, Engine.set_spin; frames / keep_dc: Engine.set_temporal."""
         self._mix_coils()
         eng = Engine(self.H, self.W, Bmax=self.B, device=self.device, precision=self.precision)
         if transform is not None:
@@ -312,6 +318,10 @@ class _Job:
         if spin is not None:
             eng.set_spin(spin, spin_average)
             self.say('cycle spinning: {:d} shifts, {:d} averaged per prox (not in the reference scripts)', len(spin), int(spin_average))
+        if frames is not None:
+            eng.set_temporal(frames, keep_dc)
+            self.say('temporal sparsity: series of {:d} frames, DFT along time{:s} (not in the reference scripts)', int(frames),
+                     ', coefficient 0 unpenalised' if keep_dc else '')
         if stream is not None:
             eng.set_stream(stream)
         self._set_coils(eng)
@@ -405,6 +415,23 @@ def spin_request(spin, spin_average, spin_seed, transform, levels, iter_num):
     return spin_table(spin, levels, iter_num, spin_average, spin_seed)
 
 
+def temporal_keywords(call, opts):
+    """frames= / temporal_keep_dc= of ADMM_L1 / ADMM_CNC: read BY NAME from the entry point's options and put beside its other keywords on
+    `call` (the signatures are pinned as they were, tests/test_solver_surface_cpu.py, so the two are not parameters)"""
+    call.frames = opts.get('frames')
+    call.temporal_keep_dc = opts.get('temporal_keep_dc', True)
+
+
+def temporal_request(frames, transform, spin, B=None):
+    """the rules of frames=; every one is a ValueError here, before an engine is opened.  B: the batch, once it is known"""
+    if frames is None:
+        return
+    if transform is not None or spin is not None:
+        raise ValueError('frames= (temporal sparsity) does not run with transform= / spin= (a spatial wavelet together with the temporal '
+                         'transform is not built)')
+    check_temporal(frames, B)
+
+
 def log_early_stop(job, trace, iter_num, tol):
     """the one extra log line of a run that the stopping rule ended before iter_num"""
     if trace is not None and tol is not None and trace['iters_done'] < iter_num:
@@ -430,15 +457,20 @@ def _solve(c, tag, suffix, psnr_fmt, iter_num, run):
     check_sparsity(c.transform, c.levels, *np.asarray(c.mask).shape[-2:])          # before an engine is opened
     image_request(c.image, c.spin, c.trace_every, c.tol, c.transform, c.levels, c.precision)
     shifts = spin_request(c.spin, c.spin_average, c.spin_seed, c.transform, c.levels, iter_num)
+    temporal_request(c.frames, c.transform, c.spin)
     job = _Job(c.mask, c.noises, tag, suffix, coil_options(c), c.images, c.y, c.mask_id, c.testsets, c.testset_name, c.results, c.save_E,
                c.device, psnr_fmt=psnr_fmt, precision=c.precision, image=c.image)
-    with job.open_engine(transform=c.transform, levels=c.levels, spin=shifts, spin_average=c.spin_average) as eng:
+    temporal_request(c.frames, c.transform, c.spin, job.B)
+    with job.open_engine(transform=c.transform, levels=c.levels, spin=shifts, spin_average=c.spin_average, frames=c.frames,
+                         keep_dc=c.temporal_keep_dc) as eng:
         trace = run(eng, c.trace_every, c.tol, job.gt_u8) if traced else run(eng)
         log_early_stop(job, trace, iter_num, c.tol)
         x = _device_x(eng, job) if c.return_device else eng.x()      # iter_num = 0: the initial x = |ifft2(y)| (S4:103, 138)
         out, _, info = job.finish(eng, x)
         if traced:
             info['trace'] = trace
+        if c.frames is not None:
+            info['frames'] = int(c.frames)
     return (out, info) if c.return_info else out
 
 
@@ -449,6 +481,7 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
             maps_crop=0.9, spin=None, spin_average=1, spin_seed=0, image='real', **ADMM_L1_opts):
     """ADMM with L1 prox on the MI355X engine.  Reference: "【1】ADMM_L1.py":29-169."""
     call = SimpleNamespace(**locals())                   # the keywords above, by name: the first statement
+    temporal_keywords(call, ADMM_L1_opts)
     iter_num = ADMM_L1_opts.get('iter_num', 20)          # S1:35
     lambda1 = ADMM_L1_opts.get('lambda1', 0.04)          # S1:36
     reo = ADMM_L1_opts.get('reo', 0.04)                  # S1:37
@@ -463,6 +496,7 @@ def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets
              maps_crop=0.9, spin=None, spin_average=1, spin_seed=0, image='real', **ADMM_CNC_opts):
     """ADMM with the convex-non-convex z-step.  Reference: "【4】ADMM_CNC .py":31-174."""
     call = SimpleNamespace(**locals())                   # the keywords above, by name: the first statement
+    temporal_keywords(call, ADMM_CNC_opts)
     iter_num = ADMM_CNC_opts.get('iter_num', 4)          # S4:37
     alpha = ADMM_CNC_opts.get('alpha', 0.4)              # S4:38
     lambda1 = ADMM_CNC_opts.get('lambda1', 0.04)         # S4:39

@@ -18,6 +18,9 @@ ENV = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPT
 CODE = {'haar': 1, 'db2': 2, 'db4': 3}
 TAPS = {'haar': 2, 'db2': 4, 'db4': 8}
 SHAPES = [(128, 128), (128, 160), (256, 192), (256, 256), (512, 512)]          # the shapes of tests/test_gpu_wavelet.py
+# the partial-tile sizes of tests/test_gpu_wavelet_edges.py and their transposes: every valid L runs, the table's own L is the largest
+EDGE_SHAPES = [hw for _, H, W in O.EDGE_CASES for hw in ((H, W), (W, H))]
+EDGE_PROX = [(name, L, H, W) for L, H, W in O.EDGE_CASES for name in O.NAMES]
 
 
 def valid(name, L, H, W):
@@ -105,7 +108,7 @@ def test_plan_fits_the_lds(exe):
         assert 0 < lds_fwd <= 160 * 1024 and 0 < lds_inv <= 160 * 1024, (wv, L, lds_fwd, lds_inv)
 
 
-@pytest.mark.parametrize('H,W', SHAPES)
+@pytest.mark.parametrize('H,W', SHAPES + EDGE_SHAPES)
 @pytest.mark.parametrize('name', O.NAMES)
 def test_tiled_transform_matches_oracle(exe, tmp_path, name, H, W):
     """Analysis and synthesis tile by tile through wavelet_plan.h's item functions reproduce the whole-image oracle (double: 1e-12; any
@@ -125,7 +128,7 @@ def test_tiled_transform_matches_oracle(exe, tmp_path, name, H, W):
         assert rel_l2(back, v) <= 1e-12, (L, rel_l2(back, v))
 
 
-@pytest.mark.parametrize('name,L,H,W', [('db4', 4, 128, 128), ('db2', 3, 128, 160), ('haar', 2, 256, 192), ('db4', 2, 144, 176)])
+@pytest.mark.parametrize('name,L,H,W', [('db4', 4, 128, 128), ('db2', 3, 128, 160), ('haar', 2, 256, 192), ('db4', 2, 144, 176)] + EDGE_PROX)
 @pytest.mark.parametrize('f64', [True, False])
 def test_tiled_prox_matches_oracle(exe, tmp_path, name, L, H, W, f64):
     """Both prox steps tile by tile (CNC: z first, then x + w through the same arrays) against the oracle; 144 x 176 is no multiple of the
@@ -146,6 +149,63 @@ def test_tiled_prox_matches_oracle(exe, tmp_path, name, L, H, W, f64):
     got = emulate(exe, tmp_path, name, L, 3, [x, z, w], p, f64)
     assert np.isfinite(got).all()
     assert rel_l2(got[0], zc) <= bar and rel_l2(got[1], wc) <= bar, (rel_l2(got[0], zc), rel_l2(got[1], wc))
+
+
+# ---- the per-element bars of tests/test_gpu_wavelet_edges.py ------------------------------------------------------------------------
+
+@pytest.mark.parametrize('name,L,H,W', EDGE_PROX)
+def test_the_edge_bars_see_one_pixel_of_the_thinnest_tile(name, L, H, W):
+    """What the per-element bars are for, shown on the oracle itself on the inputs of the GPU prox test: one pixel of the bottom-right tile
+    -- partial on both axes, on one of them 2^L pixels thin or one 2^L short -- moved by 1e-5 of the array's scale is beyond the float bar
+    (4 x the float32 restatement's distance, floor 2e-6, never above 5e-6) and is reported as the worst element, in a partial tile; the
+    whole-image rel-L2 of the sibling GPU files, at 4 x the restatement's rel-L2, lets the same array pass."""
+    x, z, w = O.edge_prox_inputs(H, W)
+    assert len(x) == O.EDGE_B and (O.FREEDOM, O.FLOOR, O.F64_BAR, O.F32_CAP) == (4.0, 2e-6, 1e-12, 5e-6)
+    t = O.tile(name, L)
+    ty, tx = O.last_tile_origin(H, W, name, L)
+    part = O.partial_tile_mask(H, W, name, L)
+    assert 0 < H - ty < t and 0 < W - tx < t                                                   # both axes partial
+    if t == 32 or (L, H, W) == O.EDGE_TILE64:
+        assert (H + t - 1) // t != (W + t - 1) // t                                            # tiles_x != tiles_y
+    assert sorted((H - ty, W - tx)) == sorted((1 << L, t - (1 << L)))          # one deepest-level coefficient; one short of a full tile
+    assert part[ty:, :].all() and part[:, tx:].all() and not part[:ty, :tx].any()
+    assert part.sum() == O.partial_tile_mask(H, W, name, L, coef=True).sum()                    # as many coefficients as pixels
+    assert np.array_equal(O.partial_tile_mask(H, W, name, L, shifts=((3, 1),)), np.roll(part, (3, 1), (0, 1)))
+    p = O.PROX_CNC
+    for kind, r64, r32 in (('l1', O.prox_l1(x, z, w, O.PROX_L1_THR, name, L), O.prox_l1(x, z, w, O.PROX_L1_THR, name, L, np.float32)),
+                           ('cnc', O.prox_cnc(x, z, w, name=name, levels=L, **p), O.prox_cnc(x, z, w, name=name, levels=L, dtype=np.float32, **p))):
+        for k in (0, 1):
+            bar = O.float_bar(r32[k], r64[k])                                                   # asserts bar <= F32_CAP
+            assert (bar >= O.FLOOR).all() and O.worst(r32[k], r64[k], bar, part)['ratio'] <= 1.0 / O.FREEDOM
+            wrong = r64[k].copy()
+            wrong[1, ty, tx] += 1e-5 * np.abs(r64[k][1]).max()
+            r = O.worst(wrong, r64[k], bar, part)
+            assert r['ratio'] >= 2.0 and r['pos'] == (1, ty, tx) and r['partial'] and r['outside'] == 0.0, (kind, k, r)
+            assert not (O.distance(wrong, r64[k]) <= bar).all()
+            assert rel_l2(wrong, r64[k]) <= 4 * rel_l2(r32[k], r64[k]), (kind, k)               # the whole-image bar does not see it
+
+
+@pytest.mark.parametrize('H,W,name,L', [(136, 184, 'db4', 3), (144, 176, 'db2', 4)])
+def test_the_edge_points_leave_the_branches_they_name_empty(H, W, name, L):
+    """wavelet_oracle.edge_points on the inputs of the GPU test: alpha in {0, 1}, b in {0.5, 1e4}, lambda1 = 0 and an L1 threshold of 0 are
+    all there, every branch a point names holds < 0.1 % of the detail coefficients, every other one >= 2 %, and no float bar of z+ or
+    w+ exceeds 5e-6 (w+ at threshold 0 is ~ 0 and judged against max |x + w|)."""
+    x, z, w = O.edge_prox_inputs(H, W)
+    pts = O.edge_points()
+    cnc = [p for kind, p, _ in pts if kind == 'cnc']
+    assert {0.0, 1.0} <= {p[0] for p in cnc} and {0.5, 1e4} <= {p[3] for p in cnc} and 0.0 in {p[1] for p in cnc}
+    assert [p[0] * p[1] for kind, p, _ in pts if kind == 'l1'] == [0.0]
+    for kind, params, off in pts:
+        share = O.check_branches(kind, params, off, x, z, w, name, L)
+        assert abs(share['zero'] + share['pass'] - 1.0) <= 1e-12
+        if kind == 'l1':
+            r64, r32 = (O.prox_l1(x, z, w, params[0] * params[1], name, L, dt) for dt in (np.float64, np.float32))
+            scale = np.abs(x.astype(np.float64) + w).reshape(len(x), -1).max(axis=1)
+            assert np.abs(r64[1]).max() <= 1e-13 * scale.max()
+        else:
+            r64, r32 = (O.prox_cnc(x, z, w, *params, name, L, dt) for dt in (np.float64, np.float32))
+            scale = None
+        assert (O.float_bar(r32[0], r64[0]) <= O.F32_CAP).all() and (O.float_bar(r32[1], r64[1], scale) <= O.F32_CAP).all()
 
 
 # ---- arguments and binding ------------------------------------------------------------------------------------------------------

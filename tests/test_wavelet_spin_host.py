@@ -21,6 +21,9 @@ SAN = ['-O1', '-g', '-std=c++17', '-fsanitize=address,undefined', '-fno-sanitize
 ENV = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
 CODE = {'haar': 1, 'db2': 2, 'db4': 3}
 SHAPES = [(128, 128), (128, 160), (256, 192)]
+# the partial-tile sizes of tests/test_gpu_wavelet_edges.py that take L = 3 and L = 4: shifts_of(L) holds (2^L - 1, 2^L - 1)
+EDGE_SHAPES = [O.EDGE_SIZES[3], O.EDGE_SIZES[4]]
+EDGE_PROX = [(name, L) + O.EDGE_SIZES[L] for L in (3, 4) for name in O.NAMES]
 L1_THR = 0.4
 CNC = dict(alpha=0.45, lambda1=0.5, reo=1.0, b=4.0)
 CNC_P = (CNC['alpha'] * CNC['reo'] * CNC['lambda1'], 1 - CNC['alpha'], CNC['alpha'], CNC['alpha'] * CNC['reo'] * CNC['lambda1'] * CNC['b'],
@@ -76,7 +79,7 @@ def emulate_unshifted(exe, tmp_path, name, L, mode, arrays, params=(0, 0, 0, 0, 
 
 # ---- the shifted index maps against the rolled oracle ---------------------------------------------------------------------------
 
-@pytest.mark.parametrize('H,W', SHAPES)
+@pytest.mark.parametrize('H,W', SHAPES + EDGE_SHAPES)
 @pytest.mark.parametrize('name', O.NAMES)
 def test_shifted_transform_matches_rolled_oracle(exe, exe_unshifted, tmp_path, name, H, W):
     """Psi_s and Psi_s^T tile by tile through wavelet_plan.h's item functions, every valid L = 1..4 and the five shifts, against the oracle
@@ -100,7 +103,7 @@ def test_shifted_transform_matches_rolled_oracle(exe, exe_unshifted, tmp_path, n
                 assert not np.array_equal(got, plain[0]), (L, s)
 
 
-@pytest.mark.parametrize('name,L,H,W', [('db4', 4, 128, 128), ('db2', 3, 128, 160), ('haar', 2, 256, 192), ('db4', 1, 128, 160), ('haar', 4, 128, 128)])
+@pytest.mark.parametrize('name,L,H,W', [('db4', 4, 128, 128), ('db2', 3, 128, 160), ('haar', 2, 256, 192), ('db4', 1, 128, 160), ('haar', 4, 128, 128)] + EDGE_PROX)
 def test_shifted_prox_matches_rolled_oracle(exe, exe_unshifted, tmp_path, name, L, H, W):
     """Both prox steps in the five shifted frames (CNC: z first, then x + w through the same arrays) against the rolled oracle to 1e-12 in
     double; s = (0, 0) equals the unshifted emulation bit for bit."""

@@ -256,6 +256,146 @@ def problem(B, H, W, seed=0):
     return y, mask, gt
 
 
+# ---- the partial-tile cases of tests/test_gpu_wavelet_edges.py: sizes, inputs, the per-element distance and where the partial tiles lie ---
+# Helpers only: no arithmetic of the transform or the prox is added here.
+
+# levels: (H, W).  Every length is >= 128 and a multiple of 2^L; at the tile of every filter (tile()) both axes end in a partial tile: one
+# in a tile with a single coefficient of the deepest level (2^L pixels), the other in a tile one such coefficient short of full -- at L = 4
+# with tile 32 both end in half a tile.  tiles_x != tiles_y where the tile is 32 (5 x 6 tiles); at tile 64 these sizes are 3 x 3 tiles
+# (2 . 64 + 2^L and 3 . 64 - 2^L), so EDGE_TILE64 adds one size of 3 x 4 tiles of 64 (2 . 64 + 8, 4 . 64 - 8; 5 x 8 tiles of 32).
+EDGE_SIZES = {1: (130, 190), 2: (132, 188), 3: (136, 184), 4: (144, 176)}
+EDGE_TILE64 = (3, 136, 248)                  # (L, H, W)
+EDGE_CASES = tuple((L,) + hw for L, hw in sorted(EDGE_SIZES.items())) + (EDGE_TILE64,)          # (L, H, W)
+EDGE_B = 2                                   # slices of every edge case, on contexts of Bmax = 3
+FREEDOM, FLOOR, F64_BAR = 4.0, 2e-6, 1e-12   # tests/param_space_oracle.py: 4 x the float32 restatement's distance, floor 2e-6; 1e-12 in double
+F32_CAP = 5e-6                               # no float bar of a single step may exceed this (asserted where the bar is formed)
+
+
+def tile(name, levels):
+    """the tile edge of csrc/wavelet_plan.h (wv_tile): 64 while the analysis halo (T - 2)(2^L - 1) is at most 16 pixels, else 32"""
+    return 64 if (TAPS[name] - 2) * ((1 << levels) - 1) <= 16 else 32
+
+
+def edge_prox_inputs(H, W):
+    """the first EDGE_B slices of prox_inputs(H, W)"""
+    return tuple(a[:EDGE_B] for a in prox_inputs(H, W))
+
+
+def edge_points():
+    """The points of the partial-tile tests that change the branch structure of the prox: (kind, parameters, the branches the point
+    leaves empty) -- 'lo', 'mid', 'hi' of the inner clip, 'zero', 'pass' of the soft threshold (tests/param_space_oracle.py, whose points
+    these are wherever it names one).  kind 'cnc': (alpha, lambda1, reo, b); 'l1': (lambda1, reo)."""
+    import param_space_oracle as PS
+    return (
+        ('cnc', PS.params('cnc', 2), ('zero',)),             # alpha = 0: thr = 0, c2 = c3 = 0, the coefficients of z pass through
+        # alpha = 1 (c1 = 0).  Not the grid's point 3 (reo = 0.05, thr = 0.025): there w+ = u - z+ is small against u, the float32
+        # restatement's distance is 6.1e-6 of max |w+| on these inputs, and 4 x that is beyond F32_CAP.  thr = 0.3, c3 = 1.2:
+        ('cnc', (1.0, 0.3, 1.0, 4.0), ()),
+        ('cnc', PS.params('cnc', 5), ('zero',)),             # lambda1 = 0: thr = 0, c3 = 0
+        ('cnc', PS.params('cnc', 6), ('lo', 'hi')),          # b = 0.5: the clip never acts
+        ('cnc', PS.params('cnc', 7), ('mid', 'zero')),       # b = 1e4: the clip acts everywhere, thr = 4.5e-5
+        ('l1', PS.params('l1', 1), ('zero',)),               # lambda1 = 0: thr = 0, z+ = Psi^T Psi (x + w), w+ ~ 0
+    )
+
+
+BRANCH_ON, BRANCH_OFF = 0.02, 0.001          # a populated branch holds >= 2 % of the detail coefficients (test_gpu_wavelet), an empty one < 0.1 %
+
+
+def prox_branches(kind, params, x, z, w, name, levels):
+    """Share of the detail coefficients in each branch of one prox step, counted in float64: {'zero', 'pass'} and for CNC
+    {'lo', 'mid', 'hi'}."""
+    det = detail_mask(*np.shape(x)[-2:], levels)
+    cu = fwd(np.asarray(x, np.float64) + np.asarray(w, np.float64), name, levels)[..., det]
+    if kind == 'cnc':
+        alpha, lambda1, reo, b = params
+        cz = fwd(z, name, levels)[..., det]
+        thr = alpha * reo * lambda1
+        t = (1 - alpha) * cz + alpha * cu + thr * b * np.clip(cz, -1 / b, 1 / b)
+        out = {'lo': np.mean(cz < -1 / b), 'mid': np.mean(np.abs(cz) <= 1 / b), 'hi': np.mean(cz > 1 / b)}
+    else:
+        lambda1, reo = params
+        t, thr, out = cu, reo * lambda1, {}
+    out.update(zero=np.mean(np.abs(t) <= thr), **{'pass': np.mean(np.abs(t) > thr)})
+    return {k: float(v) for k, v in out.items()}
+
+
+def check_branches(kind, params, off, x, z, w, name, levels):
+    """assert that the branches in `off` are empty and every other one is populated -> the shares"""
+    share = prox_branches(kind, params, x, z, w, name, levels)
+    for k, v in share.items():
+        assert (v < BRANCH_OFF) if k in off else (v >= BRANCH_ON), (kind, params, k, v, share)
+    return share
+
+
+def _axis_level(n, levels):
+    """level of the Mallat band each index of an axis of length n falls in when the other axis lies in an approximation part"""
+    idx = np.arange(n)
+    lv = np.full(n, levels)
+    for l in range(levels, 0, -1):
+        lv[idx >= (n >> l)] = l
+    return lv
+
+
+def partial_tile_mask(H, W, name, levels, coef=False, shifts=((0, 0),)):
+    """-> bool [H, W]: the elements a workgroup with a partial tile writes -- a tile that the image ends inside, on either axis.
+    coef=False: pixels; with cycle spinning the synthesis emits pixel (i, j) of a tile to (i + sy, j + sx), so the strip moves with every
+    shift of `shifts` (their union).  coef=True: coefficients in Mallat layout -- a band of level l is cut into tiles of tile >> l, in the
+    frame of the shift, so `shifts` does not move them."""
+    t = tile(name, levels)
+    if not coef:
+        m = np.zeros((H, W), bool)
+        if H % t:
+            m[H - H % t:, :] = True
+        if W % t:
+            m[:, W - W % t:] = True
+        out = np.zeros((H, W), bool)
+        for sy, sx in shifts:
+            out |= np.roll(m, (int(sy), int(sx)), (0, 1))
+        return out
+    lv = np.minimum(_axis_level(H, levels)[:, None], _axis_level(W, levels)[None, :])
+    yy, xx = np.mgrid[:H, :W]
+    py = np.where(yy >= (H >> lv), yy - (H >> lv), yy)
+    px = np.where(xx >= (W >> lv), xx - (W >> lv), xx)
+    return ((H % t != 0) & (py // (t >> lv) == H // t)) | ((W % t != 0) & (px // (t >> lv) == W // t))
+
+
+def last_tile_origin(H, W, name, levels):
+    """first pixel of the bottom-right tile: partial on both axes at every EDGE_SIZES case"""
+    t = tile(name, levels)
+    return (H - 1) // t * t, (W - 1) // t * t
+
+
+def distance(got, ref, scale=None):
+    """max |got - ref| / max |ref| per slice, [B]; scale [B]: in place of max |ref|, where the reference itself is ~ 0"""
+    ref = np.asarray(ref)
+    d = np.abs(np.asarray(got).astype(ref.dtype) - ref).reshape(ref.shape[0], -1).max(axis=1)
+    s = np.abs(ref).reshape(ref.shape[0], -1).max(axis=1) if scale is None else np.asarray(scale, np.float64)
+    return d / s
+
+
+def float_bar(r32, r64, scale=None, cap=True):
+    """The bar of a float kernel, per slice [B], as a multiple of max |ref| (or `scale`): FREEDOM x the distance of the float32
+    restatement r32 from the float64 oracle r64 on the same case, floor FLOOR.  cap: a bar beyond F32_CAP is an error of the case."""
+    bar = np.maximum(FREEDOM * distance(r32, r64, scale), FLOOR)
+    assert not cap or (bar <= F32_CAP).all(), bar
+    return bar
+
+
+def worst(got, ref, bar, part, scale=None):
+    """Per-element comparison of got with ref [B, H, W] at bar [B] (or a number) -> dict: 'ratio' the worst max |got - ref| / (bar x
+    max |ref|) over the slices, 'pos' (slice, row, column) of the worst element, 'partial' whether it lies in `part` (bool [H, W]: the
+    partial tiles), 'inside' / 'outside' the worst ratio over the elements in / not in `part`."""
+    ref = np.asarray(ref)
+    got = np.asarray(got)
+    assert got.shape == ref.shape and np.isfinite(got.view(got.real.dtype)).all(), (got.shape, ref.shape)
+    s = np.abs(ref).reshape(ref.shape[0], -1).max(axis=1) if scale is None else np.asarray(scale, np.float64)
+    r = np.abs(got.astype(ref.dtype) - ref) / (np.broadcast_to(np.asarray(bar, np.float64), s.shape) * s)[:, None, None]
+    pos = tuple(int(v) for v in np.unravel_index(int(np.argmax(r)), r.shape))
+    inside = float(r[:, part].max()) if part.any() else 0.0
+    outside = float(r[:, ~part].max()) if not part.all() else 0.0
+    return {'ratio': float(r.max()), 'pos': pos, 'partial': bool(part[pos[1], pos[2]]), 'inside': inside, 'outside': outside}
+
+
 def _rel(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return float(np.linalg.norm(a - b) / np.linalg.norm(b))

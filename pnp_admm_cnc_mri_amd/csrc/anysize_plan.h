@@ -14,6 +14,7 @@
 #pragma once
 #include <math.h>
 #include <vector>
+#include "c2c_roles.h"
 
 #if defined(__HIPCC__)
 #define PNP_HD __host__ __device__
@@ -98,17 +99,9 @@ inline void chirp(int n, std::vector<double>& re, std::vector<double>& im) {
     for (int j = 0; j < n; ++j) unit_root(((long long)j * j) % (2LL * n), 2LL * n, re[j], im[j]);
 }
 
-// ---- butterflies, shared by the host emulation and the kernels (C: float2 / double2 or any struct with x, y) ----
-
-PNP_HD inline float  fma_a(float a, float b, float c)    { return fmaf(a, b, c); }
-PNP_HD inline double fma_a(double a, double b, double c) { return fma(a, b, c); }
-
-template <typename C, typename R> PNP_HD inline C mkc(R x, R y) { C r; r.x = x; r.y = y; return r; }
-template <typename C> PNP_HD inline C cmul(C a, C b)  { return mkc<C>(fma_a(a.x, b.x, -(a.y * b.y)), fma_a(a.x, b.y, a.y * b.x)); }
-template <typename C> PNP_HD inline C cmulc(C a, C b) { return mkc<C>(fma_a(a.x, b.x, a.y * b.y), fma_a(a.y, b.x, -(a.x * b.y))); }   // a * conj(b)
-template <typename C> PNP_HD inline C cadd(C a, C b)  { return mkc<C>(a.x + b.x, a.y + b.y); }
-template <typename C> PNP_HD inline C csub(C a, C b)  { return mkc<C>(a.x - b.x, a.y - b.y); }
-template <typename C> PNP_HD inline C cconj(C a)      { return mkc<C>(a.x, -a.y); }
+// ---- butterflies, shared by the host emulation and the kernels (C: float2 / double2 or any struct with x, y).  The complex
+// helpers are those of c2c_roles.h, named here too for callers that open this namespace alone ----
+using pnp::mkc; using pnp::cmul; using pnp::cmulc; using pnp::cadd; using pnp::csub; using pnp::cconj;
 
 // in-register DFT of length RAD; roots W_RAD^p = tw[p * (L / RAD)] (conjugated for the inverse)
 template <int RAD, bool INV, typename C>

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include "loop_schedule.h"
 #include "prox_params.h"
+#include "c2c_roles.h"
 #include "trace_plan.h"
 
 namespace pnp {
@@ -23,7 +24,6 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // complex / real types per precision: float2 for the production path, double2 for the fp64
 // validation context (pnp_ctx_create_f64)
-template <typename R> struct CxOf;
 template <> struct CxOf<float>  { using type = float2; };
 template <> struct CxOf<double> { using type = double2; };
 
@@ -41,38 +41,8 @@ inline hipError_t lds_opt_in(const void* fn, std::atomic<bool>* done, size_t lds
     return e;
 }
 
-enum RowIn  { IN_COMPLEX = 0, IN_REAL = 1, IN_REAL_DIFF = 2 };
-enum RowEpi { EPI_COMPLEX = 0, EPI_ABS_REAL = 1, EPI_ABS_COMPLEX = 2, EPI_L1 = 3, EPI_CNC = 4 };
-enum ColMid { MID_NONE = 0, MID_BLEND = 1, MID_MASK = 2, MID_RESID = 3, MID_MASK_ADD = 4 };
-
-template <typename R>
-struct RowArgsT {
-    using C = typename CxOf<R>::type;
-    const C* cin;      // IN_COMPLEX
-    const R* rin0;     // IN_REAL / IN_REAL_DIFF (minuend)
-    const R* rin1;     // IN_REAL_DIFF (subtrahend)
-    C*       cout;     // EPI_COMPLEX
-    R*       x_out;    // EPI_ABS_* (required) / EPI_L1, EPI_CNC (optional, may be null)
-    R*       z;        // EPI_L1 / EPI_CNC: read old, write new
-    R*       w;
-    R        scale;    // applied to the transform output
-    ProxParamsT<R> prox;
-    int      nrows;    // B*H
-};
+// the roles of a row / column launch, their argument structs and element forms: c2c_roles.h
 using RowArgs = RowArgsT<float>;
-
-template <typename R>
-struct ColArgsT {
-    using C = typename CxOf<R>::type;
-    const C*       in;
-    C*             out;        // may alias in
-    const C*       y;          // MID_BLEND / MID_RESID: measurements; MID_MASK_ADD: noise
-    const uint8_t* mask_bank;  // [K][H][W]
-    const int32_t* mask_id;    // [B] or null
-    R              c;          // MID_BLEND: 1/(1+La2)
-    int            y_per_slice;// MID_MASK_ADD: 0 = one [H][W] noise array for all slices
-    int            B;
-};
 using ColArgs = ColArgsT<float>;
 
 // generic path (kernels_generic.hip); H, W in {256, 512}; R = float | double

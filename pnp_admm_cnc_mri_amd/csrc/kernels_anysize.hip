@@ -1,7 +1,7 @@
 // Any-size c2c kernels of libpnpmri.so for gfx950: H, W in [128, 1024], float and double.
 //
-// The same row / column roles as launch_rows / launch_cols (kernels_generic.hip), with the same RowIn / RowEpi / ColMid
-// epilogues, for every slice shape outside {256, 512}^2: the generic loop body of api.hip drives them unchanged.  Plan,
+// The row / column roles of c2c_roles.h (RowIn / RowEpi / ColMid element forms and legal triples, shared with kernels_generic.hip)
+// for every slice shape outside {256, 512}^2: the generic loop body of api.hip drives them unchanged.  Plan,
 // tables and butterflies: anysize_plan.h (7-smooth lengths: mixed-radix Stockham; others: Bluestein over a power of two).
 //
 //   rows   : G rows per 256-thread workgroup, each row a line of LDS (pitch m + 1), both ping-pong buffers in LDS
@@ -16,7 +16,6 @@
 #include "internal.h"
 #include "anysize_plan.h"
 #include "coil_plan.h"
-#include "prox_ops.h"
 #include <string.h>
 #include <atomic>
 #include <vector>
@@ -74,7 +73,6 @@ __device__ __forceinline__ C* stockham_lines(C* a, C* b, int G, int pitch, const
 template <bool INV, typename R>
 __device__ __forceinline__ typename CxOf<R>::type* line_fft(typename CxOf<R>::type* a, typename CxOf<R>::type* b, const AxisT<R>& t) {
     using C = typename CxOf<R>::type;
-    using anysize::mkc;
     const int G = t.lines, pitch = t.pitch, n = t.plan.n, m = t.plan.m;
     if (!t.plan.bluestein) return stockham_lines<INV>(a, b, G, pitch, t.plan, t.tw);
     for (int i = threadIdx.x; i < G * m; i += ANY_THREADS) {
@@ -82,8 +80,8 @@ __device__ __forceinline__ typename CxOf<R>::type* line_fft(typename CxOf<R>::ty
         C v = mkc<C>(R(0), R(0));
         if (j < n) {
             v = a[g * pitch + j];
-            if (INV) v = anysize::cconj(v);
-            v = anysize::cmul(v, t.chirp[j]);
+            if (INV) v = cconj(v);
+            v = cmul(v, t.chirp[j]);
         }
         a[g * pitch + j] = v;
     }
@@ -92,14 +90,14 @@ __device__ __forceinline__ typename CxOf<R>::type* line_fft(typename CxOf<R>::ty
     C* o = (r == a) ? b : a;
     for (int i = threadIdx.x; i < G * m; i += ANY_THREADS) {
         const int g = i / m, j = i - g * m;
-        r[g * pitch + j] = anysize::cmul(r[g * pitch + j], t.kern[j]);
+        r[g * pitch + j] = cmul(r[g * pitch + j], t.kern[j]);
     }
     __syncthreads();
     r = stockham_lines<true>(r, o, G, pitch, t.plan, t.tw);
     for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) {
         const int g = i / n, j = i - g * n;
-        C v = anysize::cmul(r[g * pitch + j], t.chirp[j]);
-        if (INV) v = anysize::cconj(v);
+        C v = cmul(r[g * pitch + j], t.chirp[j]);
+        if (INV) v = cconj(v);
         r[g * pitch + j] = v;
     }
     __syncthreads();
@@ -107,12 +105,11 @@ __device__ __forceinline__ typename CxOf<R>::type* line_fft(typename CxOf<R>::ty
 }
 
 // ------------------------------------------------------------------------------------------
-// rows: the epilogues of k_rows (kernels_generic.hip)
+// rows: row_load / row_store of c2c_roles.h around the line transform
 // ------------------------------------------------------------------------------------------
 template <int IN, bool INV, int EPI, typename R>
 __global__ __launch_bounds__(ANY_THREADS) void k_any_rows(RowArgsT<R> p, AxisT<R> t) {
     using C = typename CxOf<R>::type;
-    using anysize::mkc;
     extern __shared__ __attribute__((aligned(16))) unsigned char any_smem[];
     C* sA = reinterpret_cast<C*>(any_smem);
     C* sB = sA + t.lines * t.pitch;
@@ -121,35 +118,14 @@ __global__ __launch_bounds__(ANY_THREADS) void k_any_rows(RowArgsT<R> p, AxisT<R
     for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) {
         const int g = i / n, k = i - g * n, row = row0 + g;
         C v = mkc<C>(R(0), R(0));
-        if (row < p.nrows) {
-            const size_t e = (size_t)row * n + k;
-            if (IN == IN_COMPLEX) v = p.cin[e];
-            else if (IN == IN_REAL) v = mkc<C>(p.rin0[e], R(0));
-            else v = mkc<C>(p.rin0[e] - p.rin1[e], R(0));
-        }
+        if (row < p.nrows) v = row_load<IN>(p, (size_t)row * n + k);
         sA[g * pitch + k] = v;
     }
     __syncthreads();
     const C* r = line_fft<INV, R>(sA, sB, t);
     for (int i = threadIdx.x; i < G * n; i += ANY_THREADS) {
         const int g = i / n, k = i - g * n, row = row0 + g;
-        if (row >= p.nrows) continue;
-        const size_t e = (size_t)row * n + k;
-        const C v = r[g * pitch + k];
-        if (EPI == EPI_COMPLEX) {
-            p.cout[e] = mkc<C>(v.x * p.scale, v.y * p.scale);
-        } else if (EPI == EPI_ABS_REAL) {
-            p.x_out[e] = fabs(v.x * p.scale);
-        } else if (EPI == EPI_ABS_COMPLEX) {
-            p.x_out[e] = sqrt(v.x * v.x + v.y * v.y) * p.scale;
-        } else {
-            const R x = fabs(v.x * p.scale);
-            R z = p.z[e], w = p.w[e];
-            if (EPI == EPI_L1) prox_l1(x, z, w, p.prox); else prox_cnc(x, z, w, p.prox);
-            p.z[e] = z;
-            p.w[e] = w;
-            if (p.x_out) p.x_out[e] = x;
-        }
+        if (row < p.nrows) row_store<EPI>(p, (size_t)row * n + k, r[g * pitch + k]);
     }
 }
 
@@ -185,7 +161,6 @@ template <typename R> static AxisT<R> coil_axis(AxisT<R> t) {
 template <bool REAL, typename R>
 __global__ __launch_bounds__(ANY_THREADS) void k_any_rows_coil_in(CoilRowArgsT<R> p, AxisT<R> t) {
     using C = typename CxOf<R>::type;
-    using anysize::mkc;
     extern __shared__ __attribute__((aligned(16))) unsigned char any_smem[];
     C* sA = reinterpret_cast<C*>(any_smem);
     C* sB = sA + t.lines * t.pitch;
@@ -207,7 +182,7 @@ __global__ __launch_bounds__(ANY_THREADS) void k_any_rows_coil_in(CoilRowArgsT<R
             C v = mkc<C>(R(0), R(0));
             if (row < p.nrows) {
                 const int b = coil_row_slice(row, H), h = coil_row_line(row, H);
-                v = anysize::cmul(sP[i], p.maps[coil_map_index(coil_set_of(p.coil_id, b), c, p.ncoils, h, k, H, n)]);
+                v = cmul(sP[i], p.maps[coil_map_index(coil_set_of(p.coil_id, b), c, p.ncoils, h, k, H, n)]);
             }
             sA[g * pitch + k] = v;
         }
@@ -227,7 +202,6 @@ __global__ __launch_bounds__(ANY_THREADS) void k_any_rows_coil_in(CoilRowArgsT<R
 template <typename R>
 __global__ __launch_bounds__(ANY_THREADS) void k_any_rows_coil_epi(CoilRowArgsT<R> p, AxisT<R> t) {
     using C = typename CxOf<R>::type;
-    using anysize::mkc;
     extern __shared__ __attribute__((aligned(16))) unsigned char any_smem[];
     C* sA = reinterpret_cast<C*>(any_smem);
     C* sB = sA + t.lines * t.pitch;
@@ -250,7 +224,7 @@ __global__ __launch_bounds__(ANY_THREADS) void k_any_rows_coil_epi(CoilRowArgsT<
             const int b = coil_row_slice(row, H), h = coil_row_line(row, H);
             const C v = r[g * pitch + k];
             const C sv = mkc<C>(v.x * p.scale, v.y * p.scale);
-            sAcc[i] = anysize::cadd(sAcc[i], anysize::cmulc(sv, p.maps[coil_map_index(coil_set_of(p.coil_id, b), c, p.ncoils, h, k, H, n)]));
+            sAcc[i] = cadd(sAcc[i], cmulc(sv, p.maps[coil_map_index(coil_set_of(p.coil_id, b), c, p.ncoils, h, k, H, n)]));
         }
         __syncthreads();
     }
@@ -313,12 +287,11 @@ template hipError_t anysize_coil_rows_epi<float>(const AnySize*, hipStream_t, co
 template hipError_t anysize_coil_rows_epi<double>(const AnySize*, hipStream_t, const CoilRowArgsT<double>&);
 
 // ------------------------------------------------------------------------------------------
-// columns: [optional forward] -> pointwise k-space op -> [optional inverse], the pointwise pass of k_cols
+// columns: [optional forward] -> col_mid of c2c_roles.h -> [optional inverse]
 // ------------------------------------------------------------------------------------------
 template <bool PRE, int MID, bool POST, typename R>
 __global__ __launch_bounds__(ANY_THREADS) void k_any_cols(ColArgsT<R> p, AxisT<R> t, int W) {
     using C = typename CxOf<R>::type;
-    using anysize::mkc;
     extern __shared__ __attribute__((aligned(16))) unsigned char any_smem[];
     C* sA = reinterpret_cast<C*>(any_smem);
     C* sB = sA + t.lines * t.pitch;
@@ -347,20 +320,7 @@ __global__ __launch_bounds__(ANY_THREADS) void k_any_cols(ColArgsT<R> p, AxisT<R
             const int r = idx / G, c = idx - r * G;
             if (c >= gc) continue;
             const size_t g = (size_t)r * W + k0 + c;
-            C X = cur[c * pitch + r];
-            const bool m = mask[g] != 0;
-            // an unsampled measurement is SELECTED away, never multiplied: a NaN there cannot reach the result
-            if (MID == MID_BLEND) {
-                if (m) { const C yv = yb[g]; X.x = fma_r(yv.x - X.x, p.c, X.x); X.y = fma_r(yv.y - X.y, p.c, X.y); }
-            } else if (MID == MID_MASK) {
-                if (!m) X = mkc<C>(R(0), R(0));
-            } else if (MID == MID_RESID) {
-                if (m) { const C yv = yb[g]; X.x -= yv.x; X.y -= yv.y; } else X = mkc<C>(R(0), R(0));
-            } else if (MID == MID_MASK_ADD) {
-                const C nv = yb[g];
-                X = m ? anysize::cadd(X, nv) : nv;
-            }
-            cur[c * pitch + r] = X;
+            cur[c * pitch + r] = col_mid<MID>(cur[c * pitch + r], mask[g] != 0, &yb[g], p.c);
         }
         __syncthreads();
     }
@@ -411,14 +371,14 @@ template <typename C>
 static hipError_t upload_axis(const Plan& p, void** out) {
     std::vector<double> tre, tim, cre, cim;
     anysize::twiddles(p.m, tre, tim);
-    std::vector<C> h((size_t)2 * p.m + p.n, anysize::mkc<C>(0.0, 0.0));
-    for (int i = 0; i < p.m; ++i) h[i] = anysize::mkc<C>(tre[i], tim[i]);
+    std::vector<C> h((size_t)2 * p.m + p.n, mkc<C>(0.0, 0.0));
+    for (int i = 0; i < p.m; ++i) h[i] = mkc<C>(tre[i], tim[i]);
     if (p.bluestein) {
         anysize::chirp(p.n, cre, cim);
         std::vector<double2> kd;
         anysize::bluestein_kernel<double2>(p, cre, cim, kd);
-        for (int j = 0; j < p.n; ++j) h[p.m + j] = anysize::mkc<C>(cre[j], cim[j]);
-        for (int i = 0; i < p.m; ++i) h[p.m + p.n + i] = anysize::mkc<C>(kd[i].x, kd[i].y);
+        for (int j = 0; j < p.n; ++j) h[p.m + j] = mkc<C>(cre[j], cim[j]);
+        for (int i = 0; i < p.m; ++i) h[p.m + p.n + i] = mkc<C>(kd[i].x, kd[i].y);
     }
     hipError_t e = hipMalloc(out, h.size() * sizeof(C));
     if (e == hipSuccess) e = hipMemcpy(*out, h.data(), h.size() * sizeof(C), hipMemcpyHostToDevice);
@@ -463,21 +423,8 @@ template <typename R>
 hipError_t anysize_rows(const AnySize* A, hipStream_t s, RowIn in, bool inv, RowEpi epi, const RowArgsT<R>& a) {
     if (!A || A->f64 != std::is_same<R, double>::value) return hipErrorInvalidValue;
     const AxisT<R> t = axis<R>(A, 0);
-    if (!inv && epi == EPI_COMPLEX) {
-        if (in == IN_COMPLEX)   return any_rows_t<IN_COMPLEX, false, EPI_COMPLEX>(s, t, a);
-        if (in == IN_REAL)      return any_rows_t<IN_REAL, false, EPI_COMPLEX>(s, t, a);
-        if (in == IN_REAL_DIFF) return any_rows_t<IN_REAL_DIFF, false, EPI_COMPLEX>(s, t, a);
-    }
-    if (inv && in == IN_COMPLEX) {
-        switch (epi) {
-            case EPI_COMPLEX:     return any_rows_t<IN_COMPLEX, true, EPI_COMPLEX>(s, t, a);
-            case EPI_ABS_REAL:    return any_rows_t<IN_COMPLEX, true, EPI_ABS_REAL>(s, t, a);
-            case EPI_ABS_COMPLEX: return any_rows_t<IN_COMPLEX, true, EPI_ABS_COMPLEX>(s, t, a);
-            case EPI_L1:          return any_rows_t<IN_COMPLEX, true, EPI_L1>(s, t, a);
-            case EPI_CNC:         return any_rows_t<IN_COMPLEX, true, EPI_CNC>(s, t, a);
-        }
-    }
-    return hipErrorInvalidValue;
+    return row_roles(in, inv, epi, hipErrorInvalidValue,
+                     [&](auto IN, auto INV, auto EPI) { return any_rows_t<IN(), INV(), EPI()>(s, t, a); });
 }
 template hipError_t anysize_rows<float>(const AnySize*, hipStream_t, RowIn, bool, RowEpi, const RowArgsT<float>&);
 template hipError_t anysize_rows<double>(const AnySize*, hipStream_t, RowIn, bool, RowEpi, const RowArgsT<double>&);
@@ -487,15 +434,8 @@ hipError_t anysize_cols(const AnySize* A, hipStream_t s, bool pre, ColMid mid, b
     if (!A || A->f64 != std::is_same<R, double>::value) return hipErrorInvalidValue;
     const AxisT<R> t = axis<R>(A, 1);
     const int W = A->plan[0].n;
-    if (pre && !post && mid == MID_NONE)      return any_cols_t<true, MID_NONE, false>(s, t, W, a);
-    if (!pre && post && mid == MID_NONE)      return any_cols_t<false, MID_NONE, true>(s, t, W, a);
-    if (pre && post && mid == MID_BLEND)      return any_cols_t<true, MID_BLEND, true>(s, t, W, a);
-    if (pre && !post && mid == MID_MASK)      return any_cols_t<true, MID_MASK, false>(s, t, W, a);
-    if (pre && post && mid == MID_MASK)       return any_cols_t<true, MID_MASK, true>(s, t, W, a);      // the coil columns of G
-    if (!pre && post && mid == MID_MASK)      return any_cols_t<false, MID_MASK, true>(s, t, W, a);
-    if (pre && post && mid == MID_RESID)      return any_cols_t<true, MID_RESID, true>(s, t, W, a);
-    if (pre && !post && mid == MID_MASK_ADD)  return any_cols_t<true, MID_MASK_ADD, false>(s, t, W, a);
-    return hipErrorInvalidValue;
+    return col_roles(pre, mid, post, hipErrorInvalidValue,
+                     [&](auto PRE, auto MID, auto POST) { return any_cols_t<PRE(), MID(), POST()>(s, t, W, a); });
 }
 template hipError_t anysize_cols<float>(const AnySize*, hipStream_t, bool, ColMid, bool, const ColArgsT<float>&);
 template hipError_t anysize_cols<double>(const AnySize*, hipStream_t, bool, ColMid, bool, const ColArgsT<double>&);

@@ -11,9 +11,10 @@
 //   columns: a tile of 16 columns x N rows per workgroup, transposed into LDS on load so the
 //            same row routine runs on it (16 lanes per column); global accesses are 128-B row
 //            segments; the LDS pitch N+1 keeps the transposing writes conflict-free.
+// What a row launch (RowIn, inverse, RowEpi) and a column launch (pre, ColMid, post) read, compute per element and write, the legal
+// triples and the complex helpers: c2c_roles.h, shared with kernels_anysize.hip.
 #include "internal.h"
 #include "fft16.h"
-#include "prox_ops.h"
 #include <math.h>
 #include <stdint.h>
 #include <initializer_list>
@@ -48,17 +49,6 @@ template <typename R> struct Tw;
 template <> struct Tw<float>  { __device__ static const float2*  get(int N) { return N == 256 ? g_tw256 : g_tw512; } };
 template <> struct Tw<double> { __device__ static const double2* get(int N) { return N == 256 ? g_tw256d : g_tw512d; } };
 
-__device__ __forceinline__ float2  mkc(float x, float y)   { return make_float2(x, y); }
-__device__ __forceinline__ double2 mkc(double x, double y) { return make_double2(x, y); }
-template <typename C> __device__ __forceinline__ C cmul(C a, C b) {
-    return mkc(fma_r(a.x, b.x, -(a.y * b.y)), fma_r(a.x, b.y, a.y * b.x));
-}
-template <typename C> __device__ __forceinline__ C cmulc(C a, C b) {   // a * conj(b)
-    return mkc(fma_r(a.x, b.x, a.y * b.y), fma_r(a.y, b.x, -(a.x * b.y)));
-}
-template <typename C> __device__ __forceinline__ C cadd(C a, C b) { return mkc(a.x + b.x, a.y + b.y); }
-template <typename C> __device__ __forceinline__ C csub(C a, C b) { return mkc(a.x - b.x, a.y - b.y); }
-
 // The T threads of one transform are lanes of ONE wavefront (T <= 64, groups aligned to T): a wave's LDS instructions
 // execute in order, so the stages need no workgroup barrier -- only the compiler has to keep the order.  (Until round 3
 // every stage ended in __syncthreads(): 9-10 workgroup barriers per transform held every column of a tile to the pace of
@@ -90,7 +80,7 @@ __device__ __forceinline__ C* fft_lds(C* a, C* b, const C* tw, int t) {
             }
             const C t0 = cadd(v0, v2), t1 = csub(v0, v2), t2 = cadd(v1, v3);
             const C d = csub(v1, v3);
-            const C t3 = INV ? mkc(-d.y, d.x) : mkc(d.y, -d.x);   // (+/-) i * d
+            const C t3 = INV ? mkc<C>(-d.y, d.x) : mkc<C>(d.y, -d.x);   // (+/-) i * d
             const int j0 = ((j - k) << 2) + k;
             b[j0] = cadd(t0, t2);
             b[j0 + Ns] = cadd(t1, t3);
@@ -138,32 +128,14 @@ __global__ __launch_bounds__(256) void k_rows(RowArgsT<R> p) {
 #pragma unroll
     for (int i = 0; i < N / T; ++i) {
         const int n = lane + i * T;
-        C v;
-        if (IN == IN_COMPLEX) v = p.cin[base + n];
-        else if (IN == IN_REAL) v = mkc(p.rin0[base + n], R(0));
-        else v = mkc(p.rin0[base + n] - p.rin1[base + n], R(0));
-        a[n] = v;
+        a[n] = row_load<IN>(p, base + n);
     }
     __syncthreads();
     C* r = fft_lds<N, T, INV>(a, b, sTw, lane);
 #pragma unroll
     for (int i = 0; i < N / T; ++i) {
         const int n = lane + i * T;
-        const C v = r[n];
-        if (EPI == EPI_COMPLEX) {
-            p.cout[base + n] = mkc(v.x * p.scale, v.y * p.scale);
-        } else if (EPI == EPI_ABS_REAL) {
-            p.x_out[base + n] = fabs(v.x * p.scale);
-        } else if (EPI == EPI_ABS_COMPLEX) {
-            p.x_out[base + n] = sqrt(v.x * v.x + v.y * v.y) * p.scale;
-        } else {
-            const R x = fabs(v.x * p.scale);
-            R z = p.z[base + n], w = p.w[base + n];
-            if (EPI == EPI_L1) prox_l1(x, z, w, p.prox); else prox_cnc(x, z, w, p.prox);
-            p.z[base + n] = z;
-            p.w[base + n] = w;
-            if (p.x_out) p.x_out[base + n] = x;
-        }
+        row_store<EPI>(p, base + n, r[n]);
     }
 }
 
@@ -176,21 +148,8 @@ static hipError_t launch_rows_t(hipStream_t s, const RowArgsT<R>& a) {
 
 template <int N, typename R>
 static hipError_t launch_rows_n(hipStream_t s, RowIn in, bool inv, RowEpi epi, const RowArgsT<R>& a) {
-    if (!inv && epi == EPI_COMPLEX) {
-        if (in == IN_COMPLEX)   return launch_rows_t<N, IN_COMPLEX, false, EPI_COMPLEX>(s, a);
-        if (in == IN_REAL)      return launch_rows_t<N, IN_REAL, false, EPI_COMPLEX>(s, a);
-        if (in == IN_REAL_DIFF) return launch_rows_t<N, IN_REAL_DIFF, false, EPI_COMPLEX>(s, a);
-    }
-    if (inv && in == IN_COMPLEX) {
-        switch (epi) {
-            case EPI_COMPLEX:     return launch_rows_t<N, IN_COMPLEX, true, EPI_COMPLEX>(s, a);
-            case EPI_ABS_REAL:    return launch_rows_t<N, IN_COMPLEX, true, EPI_ABS_REAL>(s, a);
-            case EPI_ABS_COMPLEX: return launch_rows_t<N, IN_COMPLEX, true, EPI_ABS_COMPLEX>(s, a);
-            case EPI_L1:          return launch_rows_t<N, IN_COMPLEX, true, EPI_L1>(s, a);
-            case EPI_CNC:         return launch_rows_t<N, IN_COMPLEX, true, EPI_CNC>(s, a);
-        }
-    }
-    return hipErrorInvalidValue;
+    return row_roles(in, inv, epi, hipErrorInvalidValue,
+                     [&](auto IN, auto INV, auto EPI) { return launch_rows_t<N, IN(), INV(), EPI()>(s, a); });
 }
 
 template <typename R>
@@ -244,19 +203,7 @@ __global__ __launch_bounds__(256) void k_cols(ColArgsT<R> p, int W) {
         for (int idx = tid; idx < N * COLS; idx += 256) {
             const int r = idx / COLS, c = idx % COLS;
             const size_t g = (size_t)r * W + k0 + c;
-            C X = cur[c * P + r];
-            const bool m = mask[g] != 0;
-            if (MID == MID_BLEND) {
-                if (m) { const C yv = yb[g]; X.x = fma_r(yv.x - X.x, p.c, X.x); X.y = fma_r(yv.y - X.y, p.c, X.y); }
-            } else if (MID == MID_MASK) {
-                if (!m) X = mkc(R(0), R(0));
-            } else if (MID == MID_RESID) {
-                if (m) { const C yv = yb[g]; X.x -= yv.x; X.y -= yv.y; } else X = mkc(R(0), R(0));
-            } else if (MID == MID_MASK_ADD) {
-                const C nv = yb[g];
-                X = m ? cadd(X, nv) : nv;
-            }
-            cur[c * P + r] = X;
+            cur[c * P + r] = col_mid<MID>(cur[c * P + r], mask[g] != 0, &yb[g], p.c);
         }
         __syncthreads();
     }
@@ -284,16 +231,9 @@ static hipError_t launch_cols_t(hipStream_t s, int W, const ColArgsT<R>& a) {
 
 template <int N, typename R>
 static hipError_t launch_cols_n(hipStream_t s, int W, bool pre, ColMid mid, bool post, const ColArgsT<R>& a) {
-    if (pre && !post && mid == MID_NONE)      return launch_cols_t<N, true, MID_NONE, false>(s, W, a);
-    if (!pre && post && mid == MID_NONE)      return launch_cols_t<N, false, MID_NONE, true>(s, W, a);
-    if (pre && post && mid == MID_BLEND)      return launch_cols_t<N, true, MID_BLEND, true>(s, W, a);
-    if (pre && !post && mid == MID_MASK)      return launch_cols_t<N, true, MID_MASK, false>(s, W, a);
-    if (!pre && post && mid == MID_MASK)      return launch_cols_t<N, false, MID_MASK, true>(s, W, a);
-    if (pre && post && mid == MID_RESID)      return launch_cols_t<N, true, MID_RESID, true>(s, W, a);
-    if (pre && !post && mid == MID_MASK_ADD)  return launch_cols_t<N, true, MID_MASK_ADD, false>(s, W, a);
-    return hipErrorInvalidValue;
+    return col_roles(pre, mid, post, hipErrorInvalidValue,
+                     [&](auto PRE, auto MID, auto POST) { return launch_cols_t<N, PRE(), MID(), POST()>(s, W, a); });
 }
-
 
 // ------------------------------------------------------------------------------------------
 // columns of 256-row float arrays: the register transform of fft16.h (16 lanes x 16 points, ONE exchange through LDS)
@@ -353,7 +293,7 @@ __global__ __launch_bounds__(256, (MID != MID_NONE ? 3 : 4)) void k_cols16(ColAr
         tin[i] = in[sbase + (size_t)r * W + k0 + c];
     }
     uint32_t mq[4];
-    c32 yv[16];
+    c32 yv[16] = {};                                  // MID_MASK never fills it; col_mid takes its element by value
     if (MID != MID_NONE) {
         const int mid = p.mask_id ? p.mask_id[b] : 0;
         const uint32_t* mask4 = reinterpret_cast<const uint32_t*>(p.mask_bank + (size_t)mid * 256 * W + k0);   // k0 % 16 == 0: aligned
@@ -396,20 +336,7 @@ __global__ __launch_bounds__(256, (MID != MID_NONE ? 3 : 4)) void k_cols16(ColAr
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int idx = tid + 256 * i, r = idx >> 4, cc = idx & 15;
-            c32 X = tile[cc * C16_P + r];
-            const bool m = mbytes[16 * r + cc] != 0;
-            // an unsampled measurement is SELECTED away, never multiplied: a NaN there cannot reach the result
-            if (MID == MID_BLEND) {
-                if (m) { const c32 yy = yv[i]; X.x = fmaf(yy.x - X.x, p.c, X.x); X.y = fmaf(yy.y - X.y, p.c, X.y); }
-            } else if (MID == MID_MASK) {
-                if (!m) X = mk<float>(0.f, 0.f);
-            } else if (MID == MID_RESID) {
-                if (m) { const c32 yy = yv[i]; X.x -= yy.x; X.y -= yy.y; } else X = mk<float>(0.f, 0.f);
-            } else if (MID == MID_MASK_ADD) {
-                const c32 nv = yv[i];
-                X = m ? X + nv : nv;
-            }
-            tile[cc * C16_P + r] = X;
+            tile[cc * C16_P + r] = col_mid<MID>(tile[cc * C16_P + r], mbytes[16 * r + cc] != 0, yv[i], p.c);
         }
         __syncthreads();
 #pragma unroll
@@ -433,14 +360,8 @@ static hipError_t launch_cols16(hipStream_t s, int W, const ColArgsT<float>& a) 
     return hipGetLastError();
 }
 static hipError_t launch_cols16_any(hipStream_t s, int W, bool pre, ColMid mid, bool post, const ColArgsT<float>& a) {
-    if (pre && !post && mid == MID_NONE)      return launch_cols16<true, MID_NONE, false>(s, W, a);
-    if (!pre && post && mid == MID_NONE)      return launch_cols16<false, MID_NONE, true>(s, W, a);
-    if (pre && post && mid == MID_BLEND)      return launch_cols16<true, MID_BLEND, true>(s, W, a);
-    if (pre && !post && mid == MID_MASK)      return launch_cols16<true, MID_MASK, false>(s, W, a);
-    if (!pre && post && mid == MID_MASK)      return launch_cols16<false, MID_MASK, true>(s, W, a);
-    if (pre && post && mid == MID_RESID)      return launch_cols16<true, MID_RESID, true>(s, W, a);
-    if (pre && !post && mid == MID_MASK_ADD)  return launch_cols16<true, MID_MASK_ADD, false>(s, W, a);
-    return hipErrorInvalidValue;
+    return col_roles(pre, mid, post, hipErrorInvalidValue,
+                     [&](auto PRE, auto MID, auto POST) { return launch_cols16<PRE(), MID(), POST()>(s, W, a); });
 }
 // ------------------------------------------------------------------------------------------
 // the same for 512-row float arrays: 32 lanes x 16 points per column (fft16.h: structure A forward, t-layout -> k-layout;
@@ -527,19 +448,7 @@ __global__ __launch_bounds__(512, 4) void k_cols32(ColArgsT<float> p, int W) {  
         for (int i = 0; i < 16; ++i) {
             const int idx = tid + 512 * i, r = idx >> 4, cc = idx & 15;
             const size_t g = (size_t)r * W + k0 + cc;
-            c32 X = tile[cc * C32_P + r];
-            const bool m = mask[g] != 0;
-            if (MID == MID_BLEND) {
-                if (m) { const c32 yv = yb[g]; X.x = fmaf(yv.x - X.x, p.c, X.x); X.y = fmaf(yv.y - X.y, p.c, X.y); }
-            } else if (MID == MID_MASK) {
-                if (!m) X = mk<float>(0.f, 0.f);
-            } else if (MID == MID_RESID) {
-                if (m) { const c32 yv = yb[g]; X.x -= yv.x; X.y -= yv.y; } else X = mk<float>(0.f, 0.f);
-            } else if (MID == MID_MASK_ADD) {
-                const c32 nv = yb[g];
-                X = m ? X + nv : nv;
-            }
-            tile[cc * C32_P + r] = X;
+            tile[cc * C32_P + r] = col_mid<MID>(tile[cc * C32_P + r], mask[g] != 0, &yb[g], p.c);
         }
         __syncthreads();
 #pragma unroll
@@ -572,14 +481,8 @@ static hipError_t launch_cols32(hipStream_t s, int W, const ColArgsT<float>& a) 
     return hipGetLastError();
 }
 static hipError_t launch_cols32_any(hipStream_t s, int W, bool pre, ColMid mid, bool post, const ColArgsT<float>& a) {
-    if (pre && !post && mid == MID_NONE)      return launch_cols32<true, MID_NONE, false>(s, W, a);
-    if (!pre && post && mid == MID_NONE)      return launch_cols32<false, MID_NONE, true>(s, W, a);
-    if (pre && post && mid == MID_BLEND)      return launch_cols32<true, MID_BLEND, true>(s, W, a);
-    if (pre && !post && mid == MID_MASK)      return launch_cols32<true, MID_MASK, false>(s, W, a);
-    if (!pre && post && mid == MID_MASK)      return launch_cols32<false, MID_MASK, true>(s, W, a);
-    if (pre && post && mid == MID_RESID)      return launch_cols32<true, MID_RESID, true>(s, W, a);
-    if (pre && !post && mid == MID_MASK_ADD)  return launch_cols32<true, MID_MASK_ADD, false>(s, W, a);
-    return hipErrorInvalidValue;
+    return col_roles(pre, mid, post, hipErrorInvalidValue,
+                     [&](auto PRE, auto MID, auto POST) { return launch_cols32<PRE(), MID(), POST()>(s, W, a); });
 }
 // A/B knob of experiment builds (-DPNP_EXPERIMENT_KNOBS): PNP_GENERIC_STOCKHAM selects the four-stage LDS kernel for float too
 static inline bool generic_stockham() {
@@ -590,29 +493,20 @@ static inline bool generic_stockham() {
     return false;
 #endif
 }
-template <typename R> static hipError_t cols32_or_stockham(hipStream_t s, int W, bool pre, ColMid mid, bool post, const ColArgsT<R>& a);
-template <> hipError_t cols32_or_stockham<float>(hipStream_t s, int W, bool pre, ColMid mid, bool post, const ColArgsT<float>& a) {
-    const bool stockham = generic_stockham();
-    return stockham ? launch_cols_n<512>(s, W, pre, mid, post, a) : launch_cols32_any(s, W, pre, mid, post, a);
-}
-template <> hipError_t cols32_or_stockham<double>(hipStream_t s, int W, bool pre, ColMid mid, bool post, const ColArgsT<double>& a) {
-    return launch_cols_n<512>(s, W, pre, mid, post, a);
-}
-
-template <typename R> static hipError_t cols16_or_stockham(hipStream_t s, int W, bool pre, ColMid mid, bool post, const ColArgsT<R>& a);
-template <> hipError_t cols16_or_stockham<float>(hipStream_t s, int W, bool pre, ColMid mid, bool post, const ColArgsT<float>& a) {
-    const bool stockham = generic_stockham();
-    return stockham ? launch_cols_n<256>(s, W, pre, mid, post, a) : launch_cols16_any(s, W, pre, mid, post, a);
-}
-template <> hipError_t cols16_or_stockham<double>(hipStream_t s, int W, bool pre, ColMid mid, bool post, const ColArgsT<double>& a) {
-    return launch_cols_n<256>(s, W, pre, mid, post, a);
+// float columns take the register transforms (k_cols16 / k_cols32); double, and float under the knob, the four-stage LDS kernel
+template <int N, typename R>
+static hipError_t cols_reg_or_stockham(hipStream_t s, int W, bool pre, ColMid mid, bool post, const ColArgsT<R>& a) {
+    if constexpr (std::is_same<R, float>::value) {
+        if (!generic_stockham()) return N == 256 ? launch_cols16_any(s, W, pre, mid, post, a) : launch_cols32_any(s, W, pre, mid, post, a);
+    }
+    return launch_cols_n<N>(s, W, pre, mid, post, a);
 }
 
 template <typename R>
 hipError_t launch_cols(hipStream_t s, int H, int W, bool pre, ColMid mid, bool post, const ColArgsT<R>& a) {
     if (W % 16) return hipErrorInvalidValue;
-    if (H == 256) return cols16_or_stockham<R>(s, W, pre, mid, post, a);
-    if (H == 512) return cols32_or_stockham<R>(s, W, pre, mid, post, a);
+    if (H == 256) return cols_reg_or_stockham<256>(s, W, pre, mid, post, a);
+    if (H == 512) return cols_reg_or_stockham<512>(s, W, pre, mid, post, a);
     return hipErrorInvalidValue;
 }
 template hipError_t launch_cols<float>(hipStream_t, int, int, bool, ColMid, bool, const ColArgsT<float>&);

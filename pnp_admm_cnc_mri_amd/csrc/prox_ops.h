@@ -1,40 +1,39 @@
-// The z / w update of the generic iteration (S1:123-126 / S4:127-132), shared by the row epilogues of kernels_generic.hip and
-// kernels_anysize.hip -- and its complex form (include/pnp_mri.h, "complex-valued images"): csoft, cclip and the two steps on a complex
-// state, host- and device-callable without HIP, so tests/host/complex_emulation.cpp runs the same text under g++ and the sanitizers.
+// The z / w update of the generic iteration (S1:123-126 / S4:127-132), applied by the row epilogues of c2c_roles.h -- and its complex form
+// (include/pnp_mri.h, "complex-valued images"): csoft, cclip and the two steps on a complex state.  Host- and device-callable without
+// HIP, so tests/host/c2c_roles_emulation.cpp and tests/host/complex_emulation.cpp run the same text under g++ and the sanitizers.
 #pragma once
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#include "internal.h"
-#define PROX_HD __host__ __device__
-#else
 #include <math.h>
 #include "prox_params.h"
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define PROX_HD __host__ __device__
+#else
 #define PROX_HD
 #endif
 
 namespace pnp {
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-__device__ __forceinline__ float  fma_r(float a, float b, float c)    { return fmaf(a, b, c); }
-__device__ __forceinline__ double fma_r(double a, double b, double c) { return fma(a, b, c); }
+// the fused multiply-add of the c2c roles, the real prox, the coil and the wavelet kernels (-ffp-contract=off: only such calls fuse);
+// the complex and temporal code below keeps its own name for the same call, cpx_fma
+PROX_HD inline float  fma_r(float a, float b, float c)    { return fmaf(a, b, c); }
+PROX_HD inline double fma_r(double a, double b, double c) { return fma(a, b, c); }
 
-template <typename R> __device__ __forceinline__ R soft(R a, R c) {
+template <typename R> PROX_HD inline R soft(R a, R c) {
     const R m = fabs(a) - c;
     const R r = m > R(0) ? m : R(0);
     return a < R(0) ? -r : r;
 }
-template <typename R> __device__ __forceinline__ void prox_l1(R x, R& z, R& w, const ProxParamsT<R>& p) {
+template <typename R> PROX_HD inline void prox_l1(R x, R& z, R& w, const ProxParamsT<R>& p) {
     const R u = x + w;
     z = soft(u, p.thr);
     w = u - z;
 }
-template <typename R> __device__ __forceinline__ void prox_cnc(R x, R& z, R& w, const ProxParamsT<R>& p) {
+template <typename R> PROX_HD inline void prox_cnc(R x, R& z, R& w, const ProxParamsT<R>& p) {
     const R u = x + w;
     const R clipz = z < -p.ib ? -p.ib : (z > p.ib ? p.ib : z);          // z - soft(z, 1/b)
     const R t = fma_r(p.c1, z, fma_r(p.c2, u, p.c3 * clipz));
     z = soft(t, p.thr);
     w = u - z;
 }
-#endif
 
 // ---- complex state: a value is two components of S (float | double) --------------------------------------------------------------
 template <typename S> struct alignas(2 * sizeof(S)) Cpx {

@@ -121,6 +121,20 @@ def test_coil_maps_against_the_oracle(Cn, r, n, H, W, ncal, precision):
     compare(got, lam, o64, o32, precision, 'C=%d r=%d n=%d %dx%d ncal=%d' % (Cn, r, n, H, W, ncal))
 
 
+def test_coil_maps_on_a_fixed_size_double_context():
+    """256 x 256 in double: the calibration's inverse transform is the one double entry point that runs the fixed-size row kernel with a
+    complex input and a complex output (k_rows<256, IN_COMPLEX, inverse, EPI_COMPLEX, double>, then the Stockham k_cols<256, double>);
+    every other shape of this file is an any-size one.  The rules and the double bar (1e-12) of the cases above."""
+    from pnp_admm_cnc_mri_amd import Engine
+    Cn, r, n, H, W, ncal = 2, 1, 2, 256, 256, 5
+    masks, _, _, y = scene(Cn, H, W, ncal)
+    o64, o32 = oracle(Cn, r, n, H, W, ncal)
+    with Engine(H, W, Bmax=7, precision='f64') as eng:
+        assert eng.ctx_path != 'anysize' and eng.fft_plan(0) == 'fixed 256' and eng.fft_plan(1) == 'fixed 256'
+        got, lam = raw_maps(y, masks, MID, ncal, r, n, 'f64', eng=eng)
+    compare(got, lam, o64, o32, 'f64', 'C=%d r=%d n=%d %dx%d ncal=%d (fixed-size kernels)' % (Cn, r, n, H, W, ncal))
+
+
 # ---- 2. exact statements ----------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize('precision', ['f32', 'f64'])

@@ -122,6 +122,30 @@ def test_dc_step_teacher_forced(env, H, W):
         assert e <= 5e-7, (b, e)
 
 
+@pytest.mark.parametrize('H, W', SHAPES)
+def test_dc_step_double_through_a_wavelet_iteration(env, H, W):
+    """EPI_ABS_REAL rows in double (k_rows<W, IN_COMPLEX, inverse, EPI_ABS_REAL, double>): there is no double pnp_dc_step, and the plain
+    double loops take x from the prox epilogues, so the one way in is a loop with a wavelet set, whose iteration is the x-step on the
+    context's kernels and then the prox.  x of the first iteration is dc(z0, 0) whatever the prox does to z and w.  Per slice against
+    O.dc_step on the y the device holds; bar 1e-12, the double bar of this file for one application of an operator (synthesis, z0)."""
+    P = env['P']
+    masks, _, ys, _, _ = _problem(H, W)
+    with P.Engine(H, W, Bmax=BMAX, precision='f64') as eng:
+        eng.set_sparsity('haar', 1)
+        eng.upload(ys, masks, MID)
+        _assert_fixed_generic(_path(eng), H, W)
+        eng.init_state()
+        z0, w0 = eng.get_state()
+        eng.admm_l1(1, 0.1, 0.05)
+        x = eng.x()
+    assert x.dtype == np.float64 and not w0.any()
+    for b in range(B):
+        ref = O.dc_step(z0[b], w0[b], ys[b], masks[MID[b]], 0.05)
+        e = rel_l2(x[b], ref)
+        print('%dx%d double slice %d: dc_step %.2e (<= 1e-12)' % (H, W, b, e))
+        assert e <= 1e-12, (b, e)
+
+
 @pytest.mark.parametrize('per_slice', [False, True], ids=['shared_noise', 'per_slice_noise'])
 @pytest.mark.parametrize('precision, bar', [('f32', 2e-6), ('f64', 1e-12)])
 @pytest.mark.parametrize('H, W', SHAPES)

@@ -478,6 +478,61 @@ int pnp_set_temporal(pnp_ctx* ctx, int frames, int keep_dc);
 /* frames = 0 without a setting (keep_dc then reads 1); either pointer may be null */
 int pnp_get_temporal(pnp_ctx* ctx, int* frames, int* keep_dc);
 
+/* ---- low-rank: the locally low-rank prox of a dynamic series (added after ABI 13, additive) ---------
+ * The temporal DFT above fits periodic motion.  A contrast that changes without a period (uptake, relaxation, perfusion) is not sparse
+ * under it; the regulariser for that case is LOCALLY LOW-RANK: the image is cut into block x block patches, a patch across the T frames
+ * of its series is a P x T (Casorati) matrix, the penalty is its nuclear norm, the prox singular-value thresholding.  NOT in the
+ * reference scripts.  Opt-in per context (pnp_set_lowrank, on a context with pnp_set_temporal's series length); without the setting
+ * nothing here is called and every result is bit for bit what it was.  Real images only.
+ * Convention.  The grid is anchored at a shift (sy, sx), 0 <= sy, sx < b = block: patch (i, j) holds the pixels in rows
+ *   (sy + i b + r) mod H and columns (sx + j b + c) mod W, r, c < b.  Where b does not divide H or W the last patch row or column is
+ *   partial (H mod b rows, W mod b columns); it does not wrap onto the first patch, so the patches partition the image exactly.
+ *   X is the P x T matrix of one patch (P <= b^2 pixels, T frames), X = U diag(sigma) V^T, and for a function g on singular values
+ *   S_g(X) = X V diag(g(sigma)) V^T.  With thr, c1, c2, c3, ib the scalars of the pixel-domain step and s = `scale`:
+ *   thr <- s thr, ib <- s ib (each product formed in double from the rounded scalar and rounded once), c1, c2, c3 as they are -- which is
+ *   lambda <- s lambda, b_cnc <- b_cnc / s, so the clipped term still stays below the threshold.
+ *   L1    z+ = S_shrink(u), u = x + w, shrink(sigma) = max(1 - thr / sigma, 0): exactly 0 for sigma <= thr and for sigma = 0.
+ *   CNC   t = c1 z + c2 u + c3 S_clip(z) [fma(c1, z, fma(c2, u, c3 * S_clip(z)))], clip(sigma) = min(1, ib / sigma), clip(0) = 1;
+ *         z+ = S_shrink(t).
+ *   both  w+ = u - z+.
+ *   There is no keep_dc notion here (pnp_set_temporal's keep_dc is not read), and both maps are continuous in X.
+ * Arithmetic.  G = X^T X (T x T; every entry one chain of fma over the pixels p = r pw + c ascending, pw the patch's width) is
+ *   diagonalised by cyclic Jacobi in the round-robin ordering (an odd T padded by an index whose pairs are skipped), a sweep = T' - 1
+ *   rounds of T' / 2 disjoint rotations, T' = T rounded up to even; before every sweep the off-diagonal sum of squares is tested against
+ *   (eps ||G||_F)^2, eps = the precision's machine epsilon / 64, under a cap of 20 sweeps, so the result depends on the patch alone.  The
+ *   vectors V and the rotations are held in double in both precisions (V stays orthogonal; G turns in the context's precision).
+ *   Negative eigenvalues are clamped to 0, sigma = sqrt(lambda), M = V diag(g(sigma)) V^T (summed in double, rounded once), and
+ *   S_g(X) = X M row by row.  CNC solves twice, for z and for t.  One launch per prox in both precisions; z+ and w+ are written once.
+ * Limits: 2 <= frames <= 64 as for pnp_set_temporal; 2 <= block <= 32 and block <= min(H, W); a (frames, block, precision, L1 / CNC)
+ *   whose patch does not fit the LDS one workgroup may declare (160 KiB) is refused.  Admitted at least: block <= 8 at every frames <= 64
+ *   and block = 16 at every frames <= 16, in both precisions, for L1 and CNC.
+ * pnp_lowrank_check: the argument rules without a context or a device, in this order -- frames outside 2..64: PNP_E_ARG with
+ *   pnp_temporal_check's message; block outside 2..32: PNP_E_ARG ("lowrank: block must be 2..32 (got %d)"); block > H or W: PNP_E_ARG
+ *   ("lowrank: block %d exceeds the image (%d x %d)"); LDS: PNP_E_ARG ("lowrank: a patch of %d x %d pixels over %d frames does not fit
+ *   the LDS of a workgroup in float|double (L1|CNC)"); B < 1 or not a multiple of frames: PNP_E_STATE with pnp_temporal_check's message. */
+int pnp_lowrank_check(int frames, int block, int H, int W, int B, int f64, int cnc);
+/* block = 0 clears the setting (nothing else is read).  Needs pnp_set_temporal first (PNP_E_STATE otherwise) and is checked against that
+ * series length for the L1 step (a CNC loop or prox call whose patch does not fit is refused where it is made, PNP_E_ARG).  scale > 0.
+ * shifts: a table of n_shifts >= 1 pairs (sy, sx), each in [0, block) (PNP_E_ARG otherwise; at most 65536 pairs); it is copied.  The
+ * table is walked one entry per prox step by a cursor: prox step p since the cursor was last set uses entry p mod n_shifts.  The cursor
+ * is 0 after pnp_set_lowrank and after pnp_init_state; pnp_set_state keeps it, so a run cut into calls is bit-equal to one call.
+ * With a block set
+ *   - the prox step of pnp_admm_l1_run, pnp_admm_cnc_run, their _traced forms, the coil loop in real image mode and pnp_prox_l1_dual /
+ *     pnp_prox_cnc_dual is the low-rank step instead of the temporal DFT step: the same four launches per iteration (5 + 5 cg_iters + 1
+ *     with coils), which pnp_get_plan / pnp_kernels_per_iteration report;
+ *   - complex image mode is refused in either order: pnp_set_lowrank on a context in complex mode, and pnp_set_image(PNP_IMAGE_COMPLEX)
+ *     on a context with a block set, return PNP_E_STATE;
+ *   - a wavelet and a spin table are refused as with pnp_set_temporal alone (its rules hold: the block needs the series length);
+ *   - a batch that is not a whole number of series is PNP_E_STATE with pnp_temporal_check's message;
+ *   - pnp_set_temporal(ctx, 0, ..) clears the block too; pnp_set_temporal with another length keeps it if the patch still fits
+ *     (PNP_E_ARG and no change otherwise).
+ * The step-wise real prox calls exist in float only, as before. */
+int pnp_set_lowrank(pnp_ctx* ctx, int block, double scale, const int32_t* shifts, int n_shifts);
+/* block = 0 without a setting (scale then reads 1, n_shifts and cursor 0); any pointer may be null */
+int pnp_get_lowrank(pnp_ctx* ctx, int* block, double* scale, int* n_shifts, int* cursor);
+/* cursor >= 0; PNP_E_STATE without a block */
+int pnp_set_lowrank_cursor(pnp_ctx* ctx, int cursor);
+
 /* ---- PnP denoisers on complex images (added after ABI 13, additive) -------------------------------
  * NOT in the reference scripts.  The denoisers are real networks on [n][1][H][W] float planes; these four calls are the glue between
  * them and the complex state of a context in complex image mode, so that the plug-and-play loops (solvers_pnp.py, image='complex')

@@ -119,6 +119,11 @@ SIGNATURES = {
     'pnp_temporal_check': (C.c_int, [C.c_int, C.c_int]),
     'pnp_set_temporal': (C.c_int, [ctx_p, C.c_int, C.c_int]),
     'pnp_get_temporal': (C.c_int, [ctx_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    # locally low-rank prox (added after ABI 13, additive)
+    'pnp_lowrank_check': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'pnp_set_lowrank': (C.c_int, [ctx_p, C.c_int, C.c_double, C.POINTER(C.c_int32), C.c_int]),
+    'pnp_get_lowrank': (C.c_int, [ctx_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'pnp_set_lowrank_cursor': (C.c_int, [ctx_p, C.c_int]),
     'pnp_dwt2_shifted': (C.c_int, [ctx_p, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     'pnp_dwt2_shifted_f64': (C.c_int, [ctx_p, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     # multi-coil (SENSE) data consistency (added after ABI 13, additive)

@@ -4,6 +4,7 @@
 #include "internal.h"
 #include "wavelet_plan.h"
 #include "temporal_plan.h"
+#include "lowrank_plan.h"
 #include "coil_plan.h"
 #include "coilmix_plan.h"
 #include "coilmaps_plan.h"
@@ -160,6 +161,10 @@ struct pnp_ctx {
     int tp_frames = 0;                // pnp_set_temporal: the prox acts on the temporal DFT of series of this many slices (0: none) ...
     bool tp_keep_dc = true;           // ... with coefficient 0 unpenalised
     void* tp_tw = nullptr;            // the twiddle matrix of tp_frames in the context's precision (tp_twiddle_matrix), room for TP_MAX_FRAMES
+    int lr_block = 0;                 // pnp_set_lowrank: with tp_frames set, the prox thresholds the singular values of patches of this side (0: none) ...
+    double lr_scale = 1.0;            // ... with thr and ib times this ...
+    std::vector<int32_t> lr_shifts;   // ... on the grid anchored at shifts[n][2], one entry per prox step ...
+    int lr_p = 0;                     // ... by the cursor: prox steps since it was last set
     Coils coils;
     void* maps_scratch = nullptr;     // the coil-map estimators' array, laid out by the call that runs (coilmaps_scratch, espirit_scratch); on first use
     size_t maps_bytes = 0;
@@ -838,12 +843,31 @@ template <typename R> static int wavelet_prox_step(pnp_ctx* c, bool cnc, const R
     return PNP_OK;
 }
 
+// One low-rank prox of the context, wherever one runs (the loops, the coil loop, pnp_prox_*_dual): thr and ib scaled, on the grid anchored
+// at the shift table's current entry, and the cursor moves on.
+template <typename R> static int lowrank_prox_step(pnp_ctx* c, bool cnc, const R* x, R* z, R* w, const ProxParamsT<R>& pp) {
+    if (int rc = pnp_lowrank_check(c->tp_frames, c->lr_block, c->H, c->W, c->B, c->f64 ? 1 : 0, cnc ? 1 : 0)) return rc;
+    const int n = (int)(c->lr_shifts.size() / 2);
+    const int32_t* s = c->lr_shifts.data() + 2 * (size_t)lr_shift_entry(c->lr_p, n);
+    ProxParamsT<R> q = pp;
+    q.thr = (R)((double)pp.thr * c->lr_scale);
+    q.ib = (R)((double)pp.ib * c->lr_scale);
+    HIPCHK(launch_lowrank_prox<R>(c->stream, cnc, x, z, w, q, c->tp_frames, c->lr_block, s[0], s[1], c->B, c->H, c->W));
+    c->lr_p = c->lr_p == INT_MAX ? INT_MAX % n + 1 : c->lr_p + 1;                      // the same entries, within int
+    return PNP_OK;
+}
+
 // One z / w step of the loops and the step-wise calls, on real or (CX) complex arrays in natural order: the pixel prox (one launch) or the
-// wavelet prox of the context's sparsity setting (two; in real mode by the spin schedule), or the temporal prox of pnp_set_temporal (one).
+// wavelet prox of the context's sparsity setting (two; in real mode by the spin schedule), or the temporal prox of pnp_set_temporal (one),
+// or -- ahead of it -- the low-rank prox of pnp_set_lowrank (one; real images).
 // Which launcher serves which type ends here.
 template <typename R, bool CX>
 static int prox_step(pnp_ctx* c, bool cnc, const CoilState<R, CX>* x, CoilState<R, CX>* z, CoilState<R, CX>* w, const ProxParamsT<R>& pp) {
     const size_t n = (size_t)c->B * c->N;
+    if (c->lr_block) {
+        if constexpr (CX) return fail(PNP_E_STATE, "lowrank: not available in complex image mode (pnp_set_image)");
+        else return lowrank_prox_step<R>(c, cnc, x, z, w, pp);
+    }
     if (c->tp_frames) {
         if (int rc = pnp_temporal_check(c->tp_frames, c->B)) return rc;
         HIPCHK((launch_temporal_prox<R, CX>(c->stream, cnc, x, z, w, (const R*)c->tp_tw, pp, c->tp_frames, c->tp_keep_dc, c->B, c->N)));
@@ -949,6 +973,7 @@ static int run_coil_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& 
 template <typename R>
 static int run_loop(pnp_ctx* c, int iters, bool cnc, const ProxParamsT<R>& pp, double reo) {
     if (c->tp_frames) if (int rc = pnp_temporal_check(c->tp_frames, c->B)) return rc;      // before the first x-step
+    if (c->lr_block) if (int rc = pnp_lowrank_check(c->tp_frames, c->lr_block, c->H, c->W, c->B, c->f64 ? 1 : 0, cnc ? 1 : 0)) return rc;
     if (c->coils.C > 0) return cx_mode(c) ? run_coil_loop<R, true>(c, iters, cnc, pp, reo) : run_coil_loop<R, false>(c, iters, cnc, pp, reo);
     if (natural_loop(c) && iters > 0) return run_natural_loop<R>(c, iters, cnc, pp, reo);
     const Bufs<R> b = bufs<R>(c);
@@ -1460,6 +1485,7 @@ int pnp_download_y_f64(pnp_ctx* c, double* y, int on_device) { CTX(c); F64_ONLY(
 int pnp_init_state(pnp_ctx* c) {
     CTX(c); NEED_PROBLEM(c);
     c->spin_p = 0;                    // a fresh run starts the spin schedule over (pnp_set_state does not)
+    c->lr_p = 0;                      // ... and the low-rank shift table
     return c->f64 ? init_state<double>(c) : init_state<float>(c);
 }
 
@@ -1825,6 +1851,8 @@ int pnp_set_spin_cursor(pnp_ctx* c, int cursor) {
 
 // ---- temporal sparsity (temporal_plan.h, kernels_temporal.hip) ----
 
+static void lowrank_clear(pnp_ctx* c) { c->lr_block = 0; c->lr_scale = 1.0; c->lr_shifts.clear(); c->lr_p = 0; }
+
 int pnp_temporal_check(int frames, int B) {
     switch (tp_check(frames, B)) {
     case TP_OK:         return PNP_OK;
@@ -1836,8 +1864,9 @@ int pnp_temporal_check(int frames, int B) {
 
 int pnp_set_temporal(pnp_ctx* c, int frames, int keep_dc) {
     CTX(c);
-    if (frames == 0) { c->tp_frames = 0; c->tp_keep_dc = true; return PNP_OK; }
+    if (frames == 0) { c->tp_frames = 0; c->tp_keep_dc = true; lowrank_clear(c); return PNP_OK; }
     if (int rc = pnp_temporal_check(frames, frames)) return rc;                       // the range alone, before any device work
+    if (c->lr_block) if (int rc = pnp_lowrank_check(frames, c->lr_block, c->H, c->W, frames, c->f64 ? 1 : 0, 0)) return rc;   // the block must fit the new length
     if (c->wavelet != WV_NONE)
         return fail(PNP_E_STATE, "%s: temporal sparsity does not run with a wavelet%s (clear it with pnp_set_sparsity(ctx, PNP_WAVELET_NONE, 0))",
                     __func__, c->spin.empty() ? "" : " and its spin table");
@@ -1860,6 +1889,57 @@ int pnp_get_temporal(pnp_ctx* c, int* frames, int* keep_dc) {
     CTX(c);
     if (frames) *frames = c->tp_frames;
     if (keep_dc) *keep_dc = c->tp_keep_dc ? 1 : 0;
+    return PNP_OK;
+}
+
+// ---- locally low-rank prox (lowrank_plan.h, kernels_lowrank.hip) ----
+
+int pnp_lowrank_check(int frames, int block, int H, int W, int B, int f64, int cnc) {
+    switch (lr_check(frames, block, H, W, B, f64 ? sizeof(double) : sizeof(float), cnc != 0)) {
+    case LR_OK:         return PNP_OK;
+    case LR_BAD_FRAMES: return pnp_temporal_check(frames, frames);
+    case LR_BAD_BLOCK:  return fail(PNP_E_ARG, "lowrank: block must be %d..%d (got %d)", LR_MIN_BLOCK, LR_MAX_BLOCK, block);
+    case LR_BAD_SHAPE:  return fail(PNP_E_ARG, "lowrank: block %d exceeds the image (%d x %d)", block, H, W);
+    case LR_BAD_LDS:    return fail(PNP_E_ARG, "lowrank: a patch of %d x %d pixels over %d frames does not fit the LDS of a workgroup in %s (%s)",
+                                    block, block, frames, f64 ? "double" : "float", cnc ? "CNC" : "L1");
+    case LR_BAD_BATCH:  return pnp_temporal_check(frames, B);
+    }
+    return fail(PNP_E_ARG, "lowrank: invalid setting");
+}
+
+int pnp_set_lowrank(pnp_ctx* c, int block, double scale, const int32_t* shifts, int n_shifts) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
+    if (block == 0) { lowrank_clear(c); return PNP_OK; }
+    NOT_IN_COMPLEX(c);
+    if (!c->tp_frames) return fail(PNP_E_STATE, "%s: no series length set (pnp_set_temporal)", __func__);
+    if (int rc = pnp_lowrank_check(c->tp_frames, block, c->H, c->W, c->tp_frames, c->f64 ? 1 : 0, 0)) return rc;
+    if (!(scale > 0.0) || !(scale <= 1e30)) return fail(PNP_E_ARG, "%s: scale must be a positive number (got %g)", __func__, scale);
+    if (!shifts || n_shifts < 1 || n_shifts > LR_MAX_SHIFTS)
+        return fail(PNP_E_ARG, "%s: shifts must be a table of 1..%d pairs (got %d%s)", __func__, LR_MAX_SHIFTS, n_shifts, shifts ? "" : ", null");
+    for (int i = 0; i < n_shifts; ++i)
+        if (!lr_shift_ok(block, shifts[2 * i], shifts[2 * i + 1]))
+            return fail(PNP_E_ARG, "%s: shift %d = (%d, %d) out of range [0, %d)", __func__, i, shifts[2 * i], shifts[2 * i + 1], block);
+    c->lr_block = block;
+    c->lr_scale = scale;
+    c->lr_shifts.assign(shifts, shifts + 2 * (size_t)n_shifts);
+    c->lr_p = 0;
+    return PNP_OK;
+}
+
+int pnp_get_lowrank(pnp_ctx* c, int* block, double* scale, int* n_shifts, int* cursor) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
+    if (block) *block = c->lr_block;
+    if (scale) *scale = c->lr_scale;
+    if (n_shifts) *n_shifts = (int)(c->lr_shifts.size() / 2);
+    if (cursor) *cursor = c->lr_p;
+    return PNP_OK;
+}
+
+int pnp_set_lowrank_cursor(pnp_ctx* c, int cursor) {
+    if (!c) return fail(PNP_E_ARG, "%s: ctx is null", __func__);
+    if (!c->lr_block) return fail(PNP_E_STATE, "%s: no low-rank setting (pnp_set_lowrank)", __func__);
+    if (cursor < 0) return fail(PNP_E_ARG, "%s: cursor must be >= 0 (got %d)", __func__, cursor);
+    c->lr_p = cursor;
     return PNP_OK;
 }
 
@@ -1948,6 +2028,7 @@ int pnp_set_image(pnp_ctx* c, int mode) {
     if (mode == PNP_IMAGE_COMPLEX) {
         if (c->coils.C == 0) return fail(PNP_E_STATE, "%s: complex images need a context with coils (pnp_set_coils)", __func__);
         if (!c->spin.empty()) return fail(PNP_E_STATE, "%s: complex images do not run with a spin table (clear it with pnp_set_spin(ctx, NULL, 0, 1))", __func__);
+        if (c->lr_block) return fail(PNP_E_STATE, "%s: complex images do not run with a low-rank block (clear it with pnp_set_lowrank(ctx, 0, 0, NULL, 0))", __func__);
         if (int rc = pnp_image_check(mode, c->wavelet, c->wv_levels, c->f64)) return rc;
     }
     HIPCHK(hipSetDevice(c->device));

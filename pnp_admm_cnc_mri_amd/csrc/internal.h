@@ -184,6 +184,13 @@ template <typename R, bool CX>
 hipError_t launch_temporal_prox(hipStream_t s, bool cnc, const CoilState<R, CX>* x, CoilState<R, CX>* z, CoilState<R, CX>* w, const R* e,
                                 const ProxParamsT<R>& p, int frames, bool keep_dc, int B, size_t N);
 
+// locally low-rank prox (kernels_lowrank.hip, lowrank_plan.h): singular-value thresholding of the block x block patches, anchored at the
+// shift (sy, sx), of B / frames series of `frames` real slices of H x W, in place on z and w; one launch.  p: thr and ib already scaled.
+// A setting lr_check refuses, a shift outside [0, block) or an array not aligned to one value is hipErrorInvalidValue.
+template <typename R>
+hipError_t launch_lowrank_prox(hipStream_t s, bool cnc, const R* x, R* z, R* w, const ProxParamsT<R>& p, int frames, int block, int sy, int sx,
+                               int B, int H, int W);
+
 // calibration (pnp_calibrate_stream): the slice-resident loop's access shape without its arithmetic, `passes` passes over `slices` slices of 256 KiB
 hipError_t launch_calibrate_stream(hipStream_t s, float* z, float* w, const float* y, int slices, int passes);
 // The denoisers' conv layers.  Shape rules, tiles / items and the persistent grids of every launcher below: conv_plan.h -- a launcher

@@ -99,6 +99,41 @@ def check_temporal(frames, B=None):
     return int(frames)
 
 
+LOWRANK_TABLE = 64                                                                      # entries of the 'random' shift table
+
+
+def check_lowrank(frames, block, H, W, B=None, precision='f32', cnc=False):
+    """ValueError unless `block` is a valid patch side for series of `frames` slices of H x W in this precision and for this step (L1, or
+    CNC with cnc=True) and -- when B is given -- the batch is a whole number of series (pnp_lowrank_check: the library's own rule, no
+    context and no device needed).  -> block as an int."""
+    frames = check_temporal(frames)
+    if isinstance(block, bool) or int(block) != block:
+        raise ValueError('lowrank must be an integer (got %r)' % (block,))
+    L = _lib.lib()
+    if L.pnp_lowrank_check(frames, int(block), int(H), int(W), frames if B is None else int(B), 1 if precision == 'f64' else 0, 1 if cnc else 0) != 0:
+        raise ValueError(L.pnp_last_error().decode('utf-8', 'replace'))
+    return int(block)
+
+
+def lowrank_table(shift, block, seed=0):
+    """The shift table of the low-rank prox (Engine.set_lowrank), one entry per prox step, wrapping: 'random' -> 64 entries of
+    np.random.default_rng(seed).integers(0, block, size=(64, 2)), made here on the host; None -> the single entry (0, 0); an array-like
+    [n, 2] of (sy, sx) in [0, block) is passed through after checking.  Always int32."""
+    if shift is None:
+        return np.zeros((1, 2), np.int32)
+    if isinstance(shift, str):
+        if shift != 'random':
+            raise ValueError("lowrank_shift must be 'random', None or an array [n, 2] of shifts (got %r)" % (shift,))
+        return np.random.default_rng(seed).integers(0, int(block), size=(LOWRANK_TABLE, 2)).astype(np.int32)
+    a = np.asarray(shift)
+    if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError('lowrank_shift must be an integer array [n, 2] of (sy, sx), n >= 1 (got shape %s, dtype %s)' % (a.shape, a.dtype))
+    for i, (sy, sx) in enumerate(a.tolist()):
+        if not (0 <= sy < int(block) and 0 <= sx < int(block)):
+            raise ValueError('lowrank_shift: entry %d = (%d, %d) out of range [0, %d)' % (i, sy, sx, int(block)))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 def spin_table(spin, levels, iters, average=1, seed=0):
     """The cycle-spinning table of a run of `iters` iterations that averages `average` shifts per prox (Engine.set_spin(table, average)):
     'random' -> np.random.default_rng(seed).integers(0, 2**levels, size=(iters * average, 2)); an array-like [n, 2] is passed through
@@ -271,6 +306,40 @@ class Engine:
         f, k = C.c_int(0), C.c_int(0)
         _lib.check(self._L.pnp_get_temporal(self._ctx, C.byref(f), C.byref(k)))
         return (f.value or None), bool(k.value)
+
+    def set_lowrank(self, block=None, scale=None, shifts=None):
+        """Locally low-rank prox (pnp_set_lowrank), on an engine with set_temporal's series length: the prox of admm_l1 / admm_cnc /
+        prox_*_dual thresholds the singular values of the block x block patches of every series across its frames, thr and ib times
+        `scale` (default block / 2), on the grid anchored at `shifts` ([n, 2] of (sy, sx) in [0, block), default the single entry
+        (0, 0)), one entry per prox step (lowrank_cursor).  None or 0 clears.  Real images only."""
+        if not block:
+            _lib.check(self._L.pnp_set_lowrank(self._ctx, 0, 0.0, None, 0))
+            return
+        if isinstance(block, bool) or int(block) != block:
+            raise ValueError('lowrank must be an integer (got %r)' % (block,))
+        t = lowrank_table(shifts, block)
+        _lib.check(self._L.pnp_set_lowrank(self._ctx, int(block), float(block) / 2.0 if scale is None else float(scale),
+                                           t.ctypes.data_as(C.POINTER(C.c_int32)), int(t.shape[0])))
+
+    def _lowrank(self):
+        b, s, n, p = C.c_int(0), C.c_double(0), C.c_int(0), C.c_int(0)
+        _lib.check(self._L.pnp_get_lowrank(self._ctx, C.byref(b), C.byref(s), C.byref(n), C.byref(p)))
+        return b.value, s.value, n.value, p.value
+
+    @property
+    def lowrank(self):
+        """(block, scale, entries of the shift table) of set_lowrank (pnp_get_lowrank); None without one."""
+        b, s, n, _ = self._lowrank()
+        return (b, s, n) if b else None
+
+    @property
+    def lowrank_cursor(self):
+        """prox steps since the cursor was last set (set_lowrank and init_state set it to 0): the next step uses entry cursor mod n"""
+        return self._lowrank()[3]
+
+    @lowrank_cursor.setter
+    def lowrank_cursor(self, cursor):
+        _lib.check(self._L.pnp_set_lowrank_cursor(self._ctx, int(cursor)))
 
     def set_coils(self, sens, cg_iters=3):
         """Multi-coil (SENSE) data consistency (pnp_set_coils): sens [C,H,W] or a bank [Ks,C,H,W] of complex sensitivity maps (host array

@@ -44,6 +44,19 @@ bypass the file system through the extra keyword arguments
               unpenalised unless temporal_keep_dc=False (include/pnp_mri.h, "temporal sparsity").  One prox launch per iteration; with
               coils= and image='complex' as well; not with transform= / spin=.  NOT in the reference scripts; None (the default) calls
               nothing new.  One extra log line names the series length; info['frames'] is set
+    lowrank=None, lowrank_scale=None, lowrank_shift='random', lowrank_seed=0   (ADMM_L1 and ADMM_CNC only, with frames=; taken by name
+              from the options like frames=) the LOCALLY LOW-RANK prox for a dynamic series whose contrast changes without a period:
+              lowrank = b (2..32, at most min(H, W)) cuts every frame into b x b patches, a patch across the `frames` slices of its series
+              is a b^2 x frames matrix, and the prox thresholds its singular values instead of the temporal DFT's coefficients
+              (include/pnp_mri.h, "low-rank"): L1 soft-thresholds them, CNC clips those of z and soft-thresholds those of the
+              combination.  lowrank_scale (default b / 2) multiplies the threshold and the clip level.  lowrank_shift moves the patch
+              grid from one prox step to the next so that no pixel stays at a patch border: 'random' (the default) is a table of 64
+              shifts np.random.default_rng(lowrank_seed).integers(0, b, size=(64, 2)), made on the host (engine.lowrank_table); None
+              keeps the grid at (0, 0); an array [n, 2] of (sy, sx) in [0, b) is used in order, wrapping.  One prox launch per
+              iteration; with coils= as well; real images only (not with image='complex'), not with transform= / spin=, and
+              temporal_keep_dc=False does not apply.  A (frames, b, precision, solver) whose patch does not fit the LDS is a
+              ValueError.  NOT in the reference scripts; None (the default) calls nothing new.  One extra log line;
+              info['lowrank'] = {block, scale, shifts}
 
     coils=None, coil_id=None, cg_iters=3   (all five solvers) multi-coil (SENSE) data consistency: coils [C,H,W] complex sensitivity maps,
               or a bank [Ks,C,H,W] with coil_id [B] picking each slice's set.  The forward model becomes y_c = mask . fft2(S_c . x):
@@ -100,7 +113,7 @@ import numpy as np
 
 from . import coilmaps, coilmix, imageio
 from ._lib import PnpError
-from .engine import Engine, check_coils, check_image, check_sparsity, check_temporal, spin_table
+from .engine import Engine, check_coils, check_image, check_lowrank, check_sparsity, check_temporal, lowrank_table, spin_table
 
 # CLI presets of the reference scripts (positional order differs per script!)
 PRESETS = {
@@ -305,11 +318,11 @@ class _Job:
             eng.set_image_mode('complex')
             self.say('complex-valued image: the phase is kept, the prox thresholds the modulus (not in the reference scripts)')
 
-    def open_engine(self, stream=None, transform=None, levels=3, spin=None, spin_average=1, frames=None, keep_dc=True):
+    def open_engine(self, stream=None, transform=None, levels=3, spin=None, spin_average=1, frames=None, keep_dc=True, lowrank=None):
         """stream: HIP stream handle every engine call is ordered on (PnP: torch's current stream),
         set BEFORE the first kernel so upload / synthesis / init and the loop share one queue.
         transform / levels: Engine.set_sparsity (ADMM_L1 / ADMM_CNC); spin / spin_average: the table of spin_request and its group
-        size, Engine.set_spin; frames / keep_dc: Engine.set_temporal."""
+        size, Engine.set_spin; frames / keep_dc: Engine.set_temporal; lowrank: the dict of lowrank_request, Engine.set_lowrank."""
         self._mix_coils()
         eng = Engine(self.H, self.W, Bmax=self.B, device=self.device, precision=self.precision)
         if transform is not None:
@@ -322,6 +335,10 @@ class _Job:
             eng.set_temporal(frames, keep_dc)
             self.say('temporal sparsity: series of {:d} frames, DFT along time{:s} (not in the reference scripts)', int(frames),
                      ', coefficient 0 unpenalised' if keep_dc else '')
+        if lowrank is not None:
+            eng.set_lowrank(lowrank['block'], lowrank['scale'], lowrank['shifts'])
+            self.say('locally low-rank prox: {:d} x {:d} patches across the frames, thresholds x {:g}, {:d} grid shifts (not in the '
+                     'reference scripts)', lowrank['block'], lowrank['block'], lowrank['scale'], len(lowrank['shifts']))
         if stream is not None:
             eng.set_stream(stream)
         self._set_coils(eng)
@@ -432,6 +449,35 @@ def temporal_request(frames, transform, spin, B=None):
     check_temporal(frames, B)
 
 
+def lowrank_keywords(call, opts):
+    """lowrank= / lowrank_scale= / lowrank_shift= / lowrank_seed= of ADMM_L1 / ADMM_CNC: read BY NAME from the entry point's options, as
+    temporal_keywords does"""
+    call.lowrank = opts.get('lowrank')
+    call.lowrank_scale = opts.get('lowrank_scale')
+    call.lowrank_shift = opts.get('lowrank_shift', 'random')
+    call.lowrank_seed = opts.get('lowrank_seed', 0)
+
+
+def lowrank_request(c, cnc):
+    """-> dict(block, scale, shifts [n, 2] int32) of lowrank= and its companions, or None; every rule is a ValueError here, before an
+    engine is opened"""
+    if c.lowrank is None:
+        return None
+    if c.frames is None:
+        raise ValueError('lowrank= (locally low-rank prox) needs frames= (the series length)')
+    temporal_request(c.frames, c.transform, c.spin)
+    if c.image != 'real':
+        raise ValueError("lowrank= does not run with image='complex' (real images only)")
+    if not c.temporal_keep_dc:
+        raise ValueError('lowrank= has no unpenalised coefficient: temporal_keep_dc=False does not apply')
+    H, W = np.asarray(c.mask).shape[-2:]
+    block = check_lowrank(c.frames, c.lowrank, H, W, None, c.precision, cnc)
+    scale = block / 2.0 if c.lowrank_scale is None else c.lowrank_scale
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not 0 < scale < float('inf'):
+        raise ValueError('lowrank_scale must be a positive number (got %r)' % (c.lowrank_scale,))
+    return dict(block=block, scale=float(scale), shifts=lowrank_table(c.lowrank_shift, block, c.lowrank_seed))
+
+
 def log_early_stop(job, trace, iter_num, tol):
     """the one extra log line of a run that the stopping rule ended before iter_num"""
     if trace is not None and tol is not None and trace['iters_done'] < iter_num:
@@ -454,6 +500,7 @@ def _solve(c, tag, suffix, psnr_fmt, iter_num, run):
     """ADMM_L1 / ADMM_CNC around the one call they differ in.  c: the entry point's keywords; run(eng, *trace_args): its whole loop on
     the engine, with trace_args = (trace_every, tol, ground truth) for a traced call and none otherwise."""
     traced = trace_request(c.trace_every, c.tol, c.return_info)
+    lowrank = lowrank_request(c, tag == 'ADMM_CNC')
     check_sparsity(c.transform, c.levels, *np.asarray(c.mask).shape[-2:])          # before an engine is opened
     image_request(c.image, c.spin, c.trace_every, c.tol, c.transform, c.levels, c.precision)
     shifts = spin_request(c.spin, c.spin_average, c.spin_seed, c.transform, c.levels, iter_num)
@@ -462,7 +509,7 @@ def _solve(c, tag, suffix, psnr_fmt, iter_num, run):
                c.device, psnr_fmt=psnr_fmt, precision=c.precision, image=c.image)
     temporal_request(c.frames, c.transform, c.spin, job.B)
     with job.open_engine(transform=c.transform, levels=c.levels, spin=shifts, spin_average=c.spin_average, frames=c.frames,
-                         keep_dc=c.temporal_keep_dc) as eng:
+                         keep_dc=c.temporal_keep_dc, lowrank=lowrank) as eng:
         trace = run(eng, c.trace_every, c.tol, job.gt_u8) if traced else run(eng)
         log_early_stop(job, trace, iter_num, c.tol)
         x = _device_x(eng, job) if c.return_device else eng.x()      # iter_num = 0: the initial x = |ifft2(y)| (S4:103, 138)
@@ -471,6 +518,8 @@ def _solve(c, tag, suffix, psnr_fmt, iter_num, run):
             info['trace'] = trace
         if c.frames is not None:
             info['frames'] = int(c.frames)
+        if lowrank is not None:
+            info['lowrank'] = lowrank
     return (out, info) if c.return_info else out
 
 
@@ -482,6 +531,7 @@ def ADMM_L1(mask, noises, images=None, y=None, mask_id=None, testsets='testsets'
     """ADMM with L1 prox on the MI355X engine.  Reference: "【1】ADMM_L1.py":29-169."""
     call = SimpleNamespace(**locals())                   # the keywords above, by name: the first statement
     temporal_keywords(call, ADMM_L1_opts)
+    lowrank_keywords(call, ADMM_L1_opts)
     iter_num = ADMM_L1_opts.get('iter_num', 20)          # S1:35
     lambda1 = ADMM_L1_opts.get('lambda1', 0.04)          # S1:36
     reo = ADMM_L1_opts.get('reo', 0.04)                  # S1:37
@@ -497,6 +547,7 @@ def ADMM_CNC(mask, noises, images=None, y=None, mask_id=None, testsets='testsets
     """ADMM with the convex-non-convex z-step.  Reference: "【4】ADMM_CNC .py":31-174."""
     call = SimpleNamespace(**locals())                   # the keywords above, by name: the first statement
     temporal_keywords(call, ADMM_CNC_opts)
+    lowrank_keywords(call, ADMM_CNC_opts)
     iter_num = ADMM_CNC_opts.get('iter_num', 4)          # S4:37
     alpha = ADMM_CNC_opts.get('alpha', 0.4)              # S4:38
     lambda1 = ADMM_CNC_opts.get('lambda1', 0.04)         # S4:39
